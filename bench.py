@@ -14,7 +14,8 @@ Goldilocks, 2^20 trace rows, blowup 8, 20 security bits — independent proofs o
 every rank (weak scaling: the path partitions over proofs; no data-path
 collective).
 
-Rank 0 prints ONE JSON line.  Besides the headline it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`); with
+--dump-outputs DIR it first writes the proofs of the last timed step under DIR (dump_outputs).  With --full the line carries besides the headline
   roofline       per-kernel HIP-event timing of the dominant NTT pass kernel vs its algorithmic bytes
   roofline_valu  the SHA-256 kernels (59 % of the kernel time) against the VALU issue roofline
   sharded        N > 1 only: ONE 2^24-row proof (BASELINE configs[3]) computed by all ranks together (ms_set_shard_rccl:
@@ -124,9 +125,9 @@ def launch_ranks(args, argv):
         sys.exit(rc or 1)
     out = json.loads(js[-1])
     out["launcher"] = "bench.py (self-launched ranks; no torchrun)"
-    if args.mode == "replicas" and not args.no_shard_leg:
+    if args.mode == "replicas" and args.full and not args.no_shard_leg:
         sargv = ["--gpus", str(world), "--mode", "shard", "--log-rows", str(args.shard_log_rows), "--steps", str(args.shard_steps), "--warmup", "1", "--backend", args.backend,
-                 "--field", str(args.field), "--blowup", str(args.blowup), "--no-cpu-baseline", "--no-extras"] + (["--emu"] if args.emu else [])
+                 "--field", str(args.field), "--blowup", str(args.blowup), "--no-cpu-baseline", "--no-extras", "--full"] + (["--emu"] if args.emu else [])
         # the sliced digest exchange (hashing overlapped with the all-to-all on a second stream) has never run on more than one GPU: try it first, and if that
         # wave fails or disagrees with the unsharded proof, run the plain exchange in a fresh wave and say which one the numbers come from
         rc2, lines2, failed2 = _run_wave(sargv, world, timeout=args.shard_timeout, extra_env={"MS_SHARD_SLICES": os.environ.get("MS_SHARD_SLICES", "4")})
@@ -283,46 +284,49 @@ def sharded_leg(args, grp, local_rank, log_rows, steps, warmup):
     grp.barrier()
     el = grp.max_over_ranks(time.perf_counter() - t0)
     mine = hs.last_proof(read_fri_proof=False)
+    if args.dump_outputs and grp.rank == 0:   # ms_shard_proof_on_root: rank 0 holds the whole FRI proof
+        dump_outputs(args.dump_outputs, [mine], [ctx.fri_proof_read()])
     roots = grp.all_gather_bytes(mine.fri_roots[-1])
     calls = dict(xchg.calls)     # (a snapshot: the profiled proof below goes through the same exchange)
     nbytes = xchg.bytes
     dist_rounds = sum(1 for i in range(cfg.rounds) if ctx.L.ms_shard_round_is_distributed(ctx.h, C.c_int(i)) == 1)
-    # one more (untimed) proof with every launch bracketed by HIP events: kernel time of this rank's PART of the proof vs kernel time REPLICATED on every rank
-    buf = C.create_string_buffer(1 << 15)
-    ctx.check(ctx.L.ms_profile_begin(ctx.h))
-    prove(1)
-    ctx.check(ctx.L.ms_profile_end(ctx.h, buf, C.c_size_t(len(buf))))
-    shard_prof = json.loads(buf.value.decode()).get("shard", {})
-    # ... and one more through the stage functions one by one (fixed challenges, every rank the same calls): host-visible milliseconds per stage of the sharded proof,
-    # what a first real multi-GPU run needs to see where the time goes (collectives included)
-    stage_ms = {}
-    try:
-        from mini_stark_amd.synthetic import SplitMix64
-        P, e = (2**64 - 2**32 + 1, 2) if args.field == 0 else (2013265921, 4)
-        rng = SplitMix64(99)
+    shard_prof, stage_ms = {}, {}
+    if args.full:
+        # one more (untimed) proof with every launch bracketed by HIP events: kernel time of this rank's PART of the proof vs kernel time REPLICATED on every rank
+        buf = C.create_string_buffer(1 << 15)
+        ctx.check(ctx.L.ms_profile_begin(ctx.h))
+        prove(1)
+        ctx.check(ctx.L.ms_profile_end(ctx.h, buf, C.c_size_t(len(buf))))
+        shard_prof = json.loads(buf.value.decode()).get("shard", {})
+        # ... and one more through the stage functions one by one (fixed challenges, every rank the same calls): host-visible milliseconds per stage of the sharded proof,
+        # what a first real multi-GPU run needs to see where the time goes (collectives included)
+        try:
+            from mini_stark_amd.synthetic import SplitMix64
+            P, e = (2**64 - 2**32 + 1, 2) if args.field == 0 else (2013265921, 4)
+            rng = SplitMix64(99)
 
-        def st(name, fn):
-            t = time.perf_counter(); r = fn(); stage_ms[name] = stage_ms.get(name, 0.0) + (time.perf_counter() - t) * 1e3
-            return r
-        ctx.check(st("trace_commit", lambda: ctx.trace_commit_device(d_trace.data_ptr(), N, 3, tt.constrain_number()))[0])
-        ctx.check(st("interpolate", ctx.interpolate))
-        for sc, idx in tt.transitions:
-            ctx.check(st("polys_lincomb", lambda: ctx.polys_lincomb(sc, idx)))
-        ctx.check(st("lde_commit", lambda: ctx.lde_commit(args.blowup, rng.next() % P or 3, tt.constrain_number()))[0])
-        ctx.check(st("mix", lambda: ctx.mix(rng.next() % P)))
-        ctx.check(st("eval_ext", lambda: ctx.eval_ext(np.array([rng.next() % P for _ in range(e)], dtype=np.uint64)))[0])
-        ctx.check(st("fri_begin", lambda: ctx.fri_begin(args.blowup, cfg.rounds))[0])
-        for _ in range(1, cfg.rounds):
-            ctx.check(st("fri_deep", lambda: ctx.fri_deep([rng.next() % P for _ in range(e)]))[0])
-            ctx.check(st("fri_fold_commit", lambda: ctx.fri_fold_commit([rng.next() % P for _ in range(e)]))[0])
-        ctx.check(st("fri_query", lambda: ctx.fri_query([rng.next() for _ in range(cfg.fri_queries)], read=False))[0])
-        stage_ms = {k: round(v, 3) for k, v in stage_ms.items()}
-    except Exception as ex:  # noqa: BLE001 - a diagnostic must not take the leg down
-        stage_ms = {"error": f"{type(ex).__name__}: {ex}"}
+            def st(name, fn):
+                t = time.perf_counter(); r = fn(); stage_ms[name] = stage_ms.get(name, 0.0) + (time.perf_counter() - t) * 1e3
+                return r
+            ctx.check(st("trace_commit", lambda: ctx.trace_commit_device(d_trace.data_ptr(), N, 3, tt.constrain_number()))[0])
+            ctx.check(st("interpolate", ctx.interpolate))
+            for sc, idx in tt.transitions:
+                ctx.check(st("polys_lincomb", lambda: ctx.polys_lincomb(sc, idx)))
+            ctx.check(st("lde_commit", lambda: ctx.lde_commit(args.blowup, rng.next() % P or 3, tt.constrain_number()))[0])
+            ctx.check(st("mix", lambda: ctx.mix(rng.next() % P)))
+            ctx.check(st("eval_ext", lambda: ctx.eval_ext(np.array([rng.next() % P for _ in range(e)], dtype=np.uint64)))[0])
+            ctx.check(st("fri_begin", lambda: ctx.fri_begin(args.blowup, cfg.rounds))[0])
+            for _ in range(1, cfg.rounds):
+                ctx.check(st("fri_deep", lambda: ctx.fri_deep([rng.next() % P for _ in range(e)]))[0])
+                ctx.check(st("fri_fold_commit", lambda: ctx.fri_fold_commit([rng.next() % P for _ in range(e)]))[0])
+            ctx.check(st("fri_query", lambda: ctx.fri_query([rng.next() for _ in range(cfg.fri_queries)], read=False))[0])
+            stage_ms = {k: round(v, 3) for k, v in stage_ms.items()}
+        except Exception as ex:  # noqa: BLE001 - a diagnostic must not take the leg down
+            stage_ms = {"error": f"{type(ex).__name__}: {ex}"}
     # the same trace proved UNSHARDED by rank 0 on a second context: pins the exchange path (a symmetric error - wrong chunk order in the
     # all-to-all, a mistake in the in-place all-reduce - gives every rank the same wrong root and would pass `all_ranks_same_final_root`)
     matches = None
-    if grp.rank == 0 and not args.no_shard_check:
+    if grp.rank == 0 and args.full and not args.no_shard_check:
         c1 = ms.Context(args.field, device=local_rank, lib_path=lib)
         h1 = HostStark(c1, 20, args.blowup, N - 1, tt.constrain_number())
         c1.check(h1.prove_raw(tt, trace_device_ptr=d_trace.data_ptr(), read_fri_proof=False))
@@ -351,6 +355,46 @@ def sharded_leg(args, grp, local_rank, log_rows, steps, warmup):
     xchg.close()
     ctx.close()
     return res, cfg
+
+
+FRI_SAMPLE_WORDS = 1 << 18   # u32 words of each FRI proof kept by --dump-outputs (2 MiB per proof as float64; 8 proofs in flight: 16 MiB)
+
+
+def dump_outputs(out_dir, proofs, blobs):
+    """--dump-outputs: what the timed path returned in its last step, one row per proof (the lanes in order), as float64 .npy files that hold every
+    value exactly: digests, roots and the transcript as bytes (0..255), field elements as their two u32 halves (low half first).  A FRI proof (MSFP,
+    ~64 MiB at 2^20 rows) is kept as its SHA-256, its length and a fixed sample of its u32 words (seeded; the same positions in every proof).
+    `blobs` yields the FRI proofs in lane order; one is held in host memory at a time."""
+    import hashlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def u8(bs):
+        return np.stack([np.frombuffer(b, dtype=np.uint8) for b in bs]).astype(np.float64)
+
+    def u64_halves(a):
+        a = np.asarray(a, dtype=np.uint64)
+        return np.stack([a & np.uint64(0xFFFFFFFF), a >> np.uint64(32)], axis=-1).astype(np.float64)
+    sha, nbytes, sample, idx = [], [], [], None
+    for b in blobs:
+        w = np.frombuffer(b, dtype="<u4", count=len(b) // 4)   # (a tail of < 4 bytes is covered by the digest)
+        if idx is None:
+            idx = np.sort(np.random.default_rng(0).choice(len(w), size=min(FRI_SAMPLE_WORDS, len(w)), replace=False))
+        sha.append(hashlib.sha256(b).digest())
+        nbytes.append(len(b))
+        sample.append(w[idx])
+    arrays = {"trace_commit": u8([p.trace_commit for p in proofs]),
+              "constrain_trace_commit": u8([p.constrain_trace_commit for p in proofs]),
+              "fri_roots": np.stack([u8(p.fri_roots) for p in proofs]),
+              "constrain_queries": u64_halves(np.stack([p.constrain_queries for p in proofs])),
+              "validity_queries": u64_halves(np.stack([p.validity_queries for p in proofs])),
+              "transcript": u8([p.arthur for p in proofs]),
+              "fri_proof_sha256": u8(sha),
+              "fri_proof_bytes": np.array(nbytes, dtype=np.float64),
+              "fri_proof_sample": np.stack(sample).astype(np.float64),
+              "fri_proof_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def profile_is_current(round_tag):
@@ -408,7 +452,12 @@ def main():
                                                     "instead of HBM, backend gloo; exercises the launcher, the rank plumbing and the sharded leg's exchange without a GPU.  Timings are meaningless")
     ap.add_argument("--no-shard-check", action="store_true", help="sharded leg: skip rank 0's unsharded proof of the same trace (matches_unsharded)")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="time limit of the self-launched ranks (--gpus N > 1 without torchrun), seconds")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: roofline (one profiled proof), the N = 1 extras, the CPU baseline and, "
+                                                     "with N > 1, the sharded proof (--mode shard: its profiled, per-stage and unsharded proofs).  Without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the proofs of the last step (rank 0) as DIR/<name>.npy, float64: see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.emu:
         args.backend = "gloo"
     # --gpus N > 1 started as a plain `python bench.py` (no torchrun, WORLD_SIZE unset): this process becomes the launcher of N ranks
@@ -456,6 +505,8 @@ def main():
     elapsed = lanes.timed(grp, args.steps, args.warmup)
     final_roots = grp.all_gather_bytes(lanes.last[0].fri_roots[-1])  # every rank finished a proof (outside the timed region)
     assert len(final_roots) == world
+    if args.dump_outputs and rank == 0:   # the FRI proofs were left in HBM by the timed proofs: read back here, outside the timed region
+        dump_outputs(args.dump_outputs, lanes.last, (c.fri_proof_read() for c in lanes.ctxs))
     out = {
         "metric": "stark_proofs_per_s", "value": world * args.steps * C_IN / elapsed, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -470,7 +521,7 @@ def main():
     # (subprocess timeout) nor a crash of it may take the headline down.
     if args.emu:
         out["emulation"] = "REHEARSAL: CPU emulation build of the kernel source, host memory, gloo - exercises launcher / rank plumbing / exchange only; timings are meaningless"
-    if world > 1 and not args.no_shard_leg and not launched:
+    if world > 1 and args.full and not args.no_shard_leg and not launched:
         import subprocess
         lanes.close()
         lanes = None
@@ -483,7 +534,7 @@ def main():
         env["MASTER_PORT"] = str(int(os.environ.get("MASTER_PORT", "29500")) + 1)
         env.pop("TORCHELASTIC_USE_AGENT_STORE", None)   # torchrun's workers use the agent's store on MASTER_PORT; the children host their own on the next port
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--mode", "shard", "--log-rows", str(args.shard_log_rows), "--steps", str(args.shard_steps),
-               "--warmup", "1", "--backend", args.backend, "--field", str(args.field), "--blowup", str(args.blowup), "--no-cpu-baseline", "--no-extras"] + (["--emu"] if args.emu else [])
+               "--warmup", "1", "--backend", args.backend, "--field", str(args.field), "--blowup", str(args.blowup), "--no-cpu-baseline", "--no-extras", "--full"] + (["--emu"] if args.emu else [])
         try:
             cp = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.shard_timeout)
             lines = [l for l in cp.stdout.splitlines() if l.startswith("{")]
@@ -499,7 +550,7 @@ def main():
             if rank == 0:
                 out["sharded"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and args.emu:
+    if rank == 0 and (args.emu or not args.full):
         print(json.dumps(out), flush=True)
     elif rank == 0:
         if lanes is None:
@@ -862,6 +913,8 @@ def main():
                 except Exception as e:  # noqa: BLE001 - a reported baseline must not take the line down
                     out["cpu_baseline"]["at_2p24"] = {"error": f"{type(e).__name__}: {e}"}
         print(json.dumps(out), flush=True)
+    if lanes is not None:   # the contexts go before the process does (a second close of the same lanes is a no-op)
+        lanes.close()
     grp.close()
 
 

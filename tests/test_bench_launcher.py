@@ -37,7 +37,7 @@ def check(res, world):
     assert sh["distributed_rounds"] >= 2 and sh["replicated_ms_estimate"] is not None and sh["partitioned_ms_estimate"] is not None
 
 
-ARGV = ["--emu", "--log-rows", "7", "--steps", "1", "--warmup", "1", "--inflight", "1", "--shard-log-rows", "9", "--shard-steps", "1"]
+ARGV = ["--full", "--emu", "--log-rows", "7", "--steps", "1", "--warmup", "1", "--inflight", "1", "--shard-log-rows", "9", "--shard-steps", "1"]
 
 
 def test_self_launched_two_ranks():
@@ -54,8 +54,26 @@ def test_under_torchrun_two_ranks():
 
 def test_self_launched_eight_ranks():
     """world 8 - the target configuration - end to end: 8 replica ranks, then ONE 2^10-row proof sharded over 8 ranks vs the unsharded proof."""
-    res = run_bench(["--gpus", "8", "--emu", "--log-rows", "6", "--steps", "1", "--warmup", "0", "--inflight", "1", "--shard-log-rows", "10", "--shard-steps", "1"], timeout=1200)
+    res = run_bench(["--gpus", "8", "--full", "--emu", "--log-rows", "6", "--steps", "1", "--warmup", "0", "--inflight", "1", "--shard-log-rows", "10", "--shard-steps", "1"], timeout=1200)
     check(res, 8)
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full a run times the headline alone (no sharded leg with 2 ranks); --dump-outputs writes rank 0's proofs of the last step as float
+    .npy files, the same whatever --steps, --warmup and the rank count (rank 0 proves the traces of a 1-GPU run)."""
+    import numpy as np
+    a = run_bench(["--gpus", "2", "--emu", "--log-rows", "6", "--steps", "2", "--warmup", "1", "--inflight", "2", "--dump-outputs", str(tmp_path / "a")])
+    b = run_bench(["--gpus", "1", "--emu", "--log-rows", "6", "--steps", "1", "--warmup", "0", "--inflight", "2", "--dump-outputs", str(tmp_path / "b")])
+    assert "sharded" not in a and a["steps"] == 2 and a["ms_per_step"] > 0 and b["steps"] == 1
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "fri_proof_sha256.npy" in names and "transcript.npy" in names
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "trace_commit.npy").shape == (2, 32)
 
 
 def test_failing_rank_fails_the_launcher():

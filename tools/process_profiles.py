@@ -65,7 +65,7 @@ fwd = [n for n in variants if ", false," in n]
 first = [n for n in fwd if n.rstrip(">").rstrip().endswith(", 3")] or [n for n in fwd if n.rstrip(">").rstrip().endswith(", 2")]   # the 3-column LDE's first pass: the shared-table instance since r03
 lde_traffic = sum(big(n) for n in first[:1] + [n for n in fwd if n.rstrip(">").rstrip().endswith(", 1")][:1])
 json.dump(dict(kernel=roof, round=R, launches=rv["launches"], hbm_bytes_per_launch=rv["hbm_bytes_per_launch"],
-               method="rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate runs of `python3 bench.py --steps 1 --warmup 0 --inflight 1 --no-cpu-baseline --no-extras` "
+               method="rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in two separate runs of `python3 bench.py --full --steps 1 --warmup 0 --inflight 1 --no-cpu-baseline --no-extras` "
                       "(2 proofs: per proof one 3-column LDE and one 1-column FRI round-0 transform, each two launches; plus the 3-column INTT). Counter unit KB (x1024). "
                       "FETCH_SIZE calibration (MI355X_MICROARCH.md: a 128-byte request is tallied as 64 bytes; other patterns to be calibrated on a known byte count): a plain or later pass "
                       "(modes 0, 1) reads exactly the bytes it writes (WRITE_SIZE is exact), so fetch_correction = 2 where the raw count is half of that - the later passes since the "
