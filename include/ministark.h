@@ -15,7 +15,9 @@
  *    limb for both fields, src/field.rs:47,76).  Extension elements are E
  *    consecutive limbs: Goldilocks Fp2 = (c0, c1); BabyBear Fp4 =
  *    (c0.c0, c0.c1, c1.c0, c1.c1)  (src/field.rs:50-109).
- *  - Digests are 32 raw SHA-256 bytes (`Hash<Sha256>`, src/lib.rs:13).
+ *  - Digests are 32 raw bytes of the context's `D` (`Hash<D>`, src/lib.rs:13): SHA-256 (MS_DIGEST_SHA256, `D = Sha256`, the
+ *    default) or BLAKE2s-256 (MS_DIGEST_BLAKE2S256, `D = Blake2s256`, with MS_FLAG_DIGEST_BLAKE2S).  Every digest the library
+ *    handles is 32 bytes, so roots, nodes, Merkle paths and the proof layouts are the same for both.
  *  - Every function returns MS_OK or a negative ms_status; nothing unwinds.
  *    Conditions on which the reference panics/asserts map to MS_ERR_SHAPE
  *    (src/merkle.rs:93-104, src/air.rs:23-26,53-54, src/starks.rs:317-320);
@@ -59,13 +61,18 @@ typedef enum {
                                          * (4-5 us less per transcript round trip, 44 of them per proof; a stage longer than 2 ms falls back to the blocking wait).
                                          * With several contexts in flight it costs throughput (the side streams compete for HIP's few hardware queues: -15 % at
                                          * 8 in flight; every proving thread burns a core while it waits): leave it off there. */
+#define MS_FLAG_DIGEST_BLAKE2S 0x8u      /* every commitment of the context (trace, LDE, FRI rounds, the Merkle entry points) hashes with BLAKE2s-256 (RFC 7693, unkeyed:
+                                         * RustCrypto `blake2::Blake2s256`) instead of SHA-256: the reference's `D` type argument.  One proof sharded over ranks stays
+                                         * SHA-256 only: ms_set_shard / ms_set_shard_rccl return MS_ERR_ARG on such a context. */
 #define MS_FLAGS_DEFAULT MS_FLAG_ZERO_DISPLAY_EMPTY
+typedef enum { MS_DIGEST_SHA256 = 0, MS_DIGEST_BLAKE2S256 = 1 } ms_digest_id;
 
 /* ---- context ------------------------------------------------------------ */
 int ms_create(ms_ctx** out, int device, ms_field field, uint32_t flags);
 void ms_destroy(ms_ctx* ctx);
 const char* ms_last_error(const ms_ctx* ctx);
 int ms_ext_degree(const ms_ctx* ctx);             /* 2 (Goldilocks) / 4 (BabyBear): StarkField::Extension */
+int ms_digest(const ms_ctx* ctx);                 /* ms_digest_id: what the context commits with */
 int ms_set_stream(ms_ctx* ctx, void* hip_stream); /* run on a caller-owned hipStream_t (NULL: back to the ctx's own) */
 int ms_synchronize(ms_ctx* ctx);
 /* page-locked host memory for the boundary's bulk transfers (the trace going in, the FRI proof coming out): copies to and from

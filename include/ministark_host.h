@@ -9,7 +9,7 @@
  *   trace_commit[32] | constrain_trace_commit[32]
  *   constrain_queries q*c*E u64 | validity_queries q*E u64                     (StarkProof.constrain_queries / validity_query)
  *   fri_roots rounds*32   (round 0 first; not in the reference's StarkProof: round 0's root never reaches its transcript)
- *   arthur bytes          (the prover's transcript, StarkProof.arthur; build-defined SHA-256 chain, NOT nimue's bytes)
+ *   arthur bytes          (the prover's transcript, StarkProof.arthur; build-defined hash chain over the context's digest, NOT nimue's bytes)
  *   FriProof in the MSFP layout of ministark.h
  * The Python mirror writes the same bytes (mini_stark_amd.stark.StarkProof.to_bytes). */
 #ifndef MINISTARK_HOST_H

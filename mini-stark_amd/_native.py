@@ -15,6 +15,8 @@ GOLDILOCKS, BABYBEAR = 0, 1
 FLAG_ZERO_DISPLAY_EMPTY = 1
 FLAG_TRACE_MONT64 = 2
 FLAG_LATENCY = 4   # the context proves alone on its GPU: independent chains of a stage on two streams (costs throughput with several contexts in flight)
+FLAG_DIGEST_BLAKE2S = 8   # D = Blake2s256 for every commitment of the context (default: SHA-256)
+DIGEST_SHA256, DIGEST_BLAKE2S256 = 0, 1   # ms_digest_id
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -84,6 +86,11 @@ class Context:
             raise MsError(rc, "ms_create failed (no usable GPU / HIP runtime?)")
         self.h = h
         self.e = self.L.ms_ext_degree(self.h)
+        # what the context commits with (ms_digest).  A library built before the symbol existed (MS_LIB_PATH naming an older build) knows SHA-256 only
+        self.digest = int(self.L.ms_digest(self.h)) if hasattr(self.L, "ms_digest") else DIGEST_SHA256
+        if (flags & FLAG_DIGEST_BLAKE2S) and self.digest != DIGEST_BLAKE2S256:
+            self.close()
+            raise MsError(ERR_ARG, "FLAG_DIGEST_BLAKE2S: this build of the library has no BLAKE2s-256 kernels")
         self.N = self.w = self.Lsize = 0
 
     def close(self):

@@ -59,6 +59,7 @@ int ms_create(ms_ctx** out, int device, ms_field field, uint32_t flags) {
 void ms_destroy(ms_ctx* ctx) { if (ctx) { try { B(ctx)->bind_device(); delete B(ctx); } catch (...) {} } }
 const char* ms_last_error(const ms_ctx* ctx) { return ctx ? B(ctx)->err.c_str() : "null context"; }
 int ms_ext_degree(const ms_ctx* ctx) { return ctx ? B(ctx)->ext_degree() : MS_ERR_ARG; }
+int ms_digest(const ms_ctx* ctx) { return ctx ? B(ctx)->digest : MS_ERR_ARG; }
 int ms_set_stream(ms_ctx* ctx, void* s) { MS_ENTRY(ctx, B(ctx)->set_stream(s)); }
 int ms_set_shard(ms_ctx* ctx, int rank, int world, void* d_send, void* d_recv, size_t cap, ms_exchange_fn fn, void* user) {
   MS_ENTRY(ctx, B(ctx)->set_shard(rank, world, d_send, d_recv, cap, fn, user));

@@ -69,6 +69,7 @@ struct CtxBase {
   // entry point returns MS_ERR_STATE; only ms_destroy is valid, and it waits for the transfer WITHOUT limit before it frees anything.
   bool poisoned = false;
   virtual ~CtxBase() {}
+  int digest = MS_DIGEST_SHA256;   // ms_digest_id: the D of every commitment of this context (MS_FLAG_DIGEST_BLAKE2S at ms_create)
   virtual int ext_degree() const = 0;
   virtual void bind_device() const = 0;  // HIP's current device is per host thread: every entry point binds the context's device
   virtual int set_stream(void* s) = 0;
@@ -307,7 +308,7 @@ template <class F> struct Ctx : CtxBase {
   struct TreeShape { size_t leaf_num = 0, lpn = 0, ic = 0, levels = 0, nodes = 0, local_nodes = 0, Mloc = 0; bool sharded = false; };
   // src/merkle.rs:89-118 (shape checks and node count)
   int tree_shape(size_t leaf_num, size_t lpn, size_t ic, TreeShape* ts);
-  // leaf-group digests of `ngroups` groups into `out`: LeafHashKernel + the compacted pad-only blocks it deferred
+  // leaf-group digests of `ngroups` groups into `out`: LeafHashKernel + (SHA-256) the compacted pad-only blocks it deferred; by the context's digest
   template <int EL>
   int leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
                 size_t g_first = 0, u32 run_len = 0, u32 run_stride = 0, const msmerkle::LinColSpec* lin = nullptr, size_t out_g0 = 0);
@@ -320,6 +321,7 @@ template <class F> struct Ctx : CtxBase {
   bool root_on_host = false;
   unsigned long long* pending_aux = nullptr; bool aux_on_host = false;   // a device word the tree's final launch forwards to pinned[0] (the degree result)
   int inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels = true, u8* rec_out = nullptr);
+  int inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip);
   // Sharded MerkleTree::new over a binary tree of M = leaf_num/lpn leaf groups, of which this rank hashes the groups
   // j = rank + W*i found at local group index i of the view (base, strides): digest all-to-all, subtree, root all-gather, top.
   template <int EL>
@@ -554,6 +556,7 @@ template <class F> struct Ctx : CtxBase {
   struct StreamScope { Ctx* c; msrt::Stream* keep; StreamScope(Ctx* c_, msrt::Stream* s) : c(c_), keep(c_->stream) { c->stream = s; } ~StreamScope() { c->stream = keep; } };
   int join_side() { if (side_pending) { side_pending = false; CK(msrt::stream_wait_event(stream, ev_side)); } return 0; }   // the context's stream goes on only behind the side stream's work
   int fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done);
+  template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: msmerkle::Sha256Kernels / Blake2sKernels, by `digest`
   int fri_round_info(int r, u64* ncoef, u64* D) override;
   int fri_round_poly_read(int r, u64* out) override;
   int fri_round_codeword_read(int r, u64* out) override;

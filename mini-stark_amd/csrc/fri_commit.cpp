@@ -310,14 +310,18 @@ int Ctx<F>::fold_dist(Round* pr, Round* nr, const XE& a, size_t* nq_coef_out) {
 // level, root and length word into page-locked memory.  *done = false: the round does not qualify (the caller takes the launch-per-step path).
 template <class F>
 int Ctx<F>::fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done) {
+  return digest == MS_DIGEST_BLAKE2S256 ? fri_tail_round_t<msmerkle::Blake2sKernels>(pr, nr, a, done) : fri_tail_round_t<msmerkle::Sha256Kernels>(pr, nr, a, done);
+}
+template <class F> template <class DG>
+int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {
   *done = false;
   const size_t n = pr->ncoef, m = (n + 1) / 2, Dn = nr->D, M = Dn / 2;
   bool z_outside_base = false;
   for (int l = 1; l < E; l++) z_outside_base = z_outside_base || cur_z.c[l] != 0;
   // replicated rounds only (a sharded proof's tail is replicated on every rank); the pointwise codeword needs y - z != 0 on the base-field domain; one scan block
   if (!fri_tail_max || pr->D > fri_tail_max || pr->dist || pr->ts.sharded || shardable(M) || !fri_pointwise || !z_outside_base || m > (size_t)mspoly::SH_BS || M < 1) return 0;
-  typedef msfri::FriTailKernel<F, E> TK;
-  if (M > (size_t)TK::WG_GROUPS << msmerkle::InnerSubtreeKernel::MAX_LEVELS) return 0;
+  typedef msfri::FriTailKernel<F, E, DG> TK;
+  if (M > (size_t)TK::WG_GROUPS << TK::TreeK::MAX_LEVELS) return 0;
   if (ctz64(Dn) > F::TWO_ADICITY) return fail(MS_ERR_SHAPE, "FRI domain larger than the field's two-adicity");
   RQ(tree_shape(Dn, 2, 2, &nr->ts));
   nr->m = 0;

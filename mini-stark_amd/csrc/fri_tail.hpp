@@ -17,12 +17,13 @@
 // stand-alone kernel (mspoly::FoldKernel, SuffixHornerKernel, DegreeKernel, FriFoldEvalKernel, msmerkle::LeafHashKernel, InnerSubtreeKernel): same
 // arithmetic, same bytes - the parity suite runs with the fused round forced on and off (MS_FRI_TAIL_MAX).
 #pragma once
-#include "merkle.hpp"
+#include "blake2s.hpp"
 #include "poly.hpp"
 
 namespace msfri {
 
-template <class F, int E> struct FriTailKernel {
+// DG: the digest's kernel family (msmerkle::Sha256Kernels / Blake2sKernels): the leaf and subtree steps are its kernels' device code.
+template <class F, int E, class DG = msmerkle::Sha256Kernels> struct FriTailKernel {
   typedef typename F::T T;
   static constexpr int THREADS = 256;
   static constexpr int WG_GROUPS = 256;                 // leaf groups per evaluation-side workgroup (one per thread; 8 tree levels per workgroup)
@@ -30,8 +31,8 @@ template <class F, int E> struct FriTailKernel {
   typedef mspoly::SuffixHornerKernel<F, E> ScanK;
   typedef mspoly::DegreeKernel<F, E> DegK;
   typedef mspoly::FriFoldEvalKernel<F, E, 2> EvalK;      // two outputs per thread: a workgroup's 512 outputs = its 256 leaf groups
-  typedef msmerkle::LeafHashKernel<F, E> LeafK;
-  typedef msmerkle::InnerSubtreeKernel TreeK;
+  typedef msmerkle::LeafHashKernel<F, E, false, DG> LeafK;
+  typedef typename DG::Subtree TreeK;
   static_assert(FoldK::THREADS == THREADS && ScanK::THREADS == THREADS && DegK::THREADS == THREADS && EvalK::THREADS == THREADS && LeafK::THREADS == THREADS &&
                 TreeK::THREADS == THREADS, "one workgroup shape for every step");
   struct Params {

@@ -1,4 +1,4 @@
-// merkle.hpp — SHA-256 Merkle commitment kernels.
+// merkle.hpp — Merkle commitment kernels: the digest-independent message assembly and the SHA-256 family (BLAKE2s-256: blake2s.hpp).
 //
 // Replaces MerkleTree::new (src/merkle.rs:81-148):
 //   leaf pass  : one digest per group of `leafs_per_node` field elements,
@@ -215,24 +215,20 @@ MS_HD u32 drop_bytes(u32 hi, u32 lo, u32 l, u32 sel) {
 #endif
 }
 
-// byte stream -> SHA-256.  The not-yet-compressed tail of the message (< 64 bytes between appends) lives as
+// byte stream -> digest.  The not-yet-compressed tail of the message (< 64 bytes between appends) lives as
 // big-endian words in a per-thread buffer of NWORDS words in LDS, word-interleaved across the workgroup
 // (word i of thread t at buf[i*NT + t]: conflict free); buf[0] is always the first word of the next block.
 // Appends are whole-register operations: a string of NW packed words is shifted into place by one funnel
 // shift per word and stored at compile-time offsets from the write pointer; the word that holds the
 // stream's tail is always stored with zero fill, so LDS is a valid image of the pending bytes at any time.
-// `drain` is the only compression site (the 64-round compression is instantiated ONCE per kernel: inlining
-// it at every append made the kernel I-cache bound); after a block is compressed the leftover words move
-// down to the buffer start.  Between two drains at most 4*(NWORDS-17)-3 bytes may be appended.
-template <int NWORDS, int NT, int MAXW, bool LAZY> struct ShaStream {
-  static_assert(NWORDS >= 16 + MAXW + 1 && NWORDS <= 48, "buffer = one or two blocks + room for one element");
-  Sha256 h;
+// PackStream is the digest-independent half (the buffer and the appends); ShaStream below and B2Stream (blake2s.hpp) add the state and `drain`.
+template <int NWORDS, int NT> struct PackStream {
   u32* buf;    // this thread's word 0
   u32 acc;     // the last four bytes appended (low byte = most recent)
   u32 total;   // bytes appended
   u32 done;    // words compressed (multiple of 16); before the final drain it is the stream index of buf[0]
   u32 fbase;   // `done` when the final drain began (buf[0] stays put from then on)
-  MS_HD void init(u32* lds_words, int tid_) { h.init(); buf = lds_words + tid_; acc = 0; total = 0; done = 0; fbase = 0; }
+  MS_HD void init_buf(u32* lds_words, int tid_) { buf = lds_words + tid_; acc = 0; total = 0; done = 0; fbase = 0; }
   // append the first nbytes (1 <= nbytes <= 4*NW) bytes of W (big-endian, zero beyond nbytes);
   // last4 = the last four bytes of the stream after the append (only its low min(4, bytes so far) bytes matter)
   template <int NW> MS_HD void append_words(const u32 (&W)[NW], u32 nbytes, u32 last4) {
@@ -252,13 +248,34 @@ template <int NWORDS, int NT, int MAXW, bool LAZY> struct ShaStream {
     append_words<1>(W, nbytes, l4);
   }
   MS_HD void begin_final() { fbase = done; }
+};
+// byte stream -> SHA-256.
+// `drain` is the only compression site (the 64-round compression is instantiated ONCE per kernel: inlining
+// it at every append made the kernel I-cache bound); after a block is compressed the leftover words move
+// down to the buffer start.  Between two drains at most 4*(NWORDS-17)-3 bytes may be appended.
+template <int NWORDS, int NT, int MAXW, bool LAZY> struct ShaStream : PackStream<NWORDS, NT> {
+  static_assert(NWORDS >= 16 + MAXW + 1 && NWORDS <= 48, "buffer = one or two blocks + room for one element");
+  typedef PackStream<NWORDS, NT> Base;
+  using Base::buf; using Base::total; using Base::done; using Base::fbase;
+  Sha256 h;
+  MS_HD void init(u32* lds_words, int tid_) { h.init(); Base::init_buf(lds_words, tid_); }
+  // the message is complete: the 0x80 byte of the FIPS 180-4 padding goes in behind it; returns the message length in bytes
+  MS_HD u32 end_message() { const u32 n = total; Base::append_small(0x80000000u, 1); Base::begin_final(); return n; }
+  // digest to 8 words of global memory, standard byte order
+  MS_HD void store_digest(u32* dst) const {
+    uint4_t* out = reinterpret_cast<uint4_t*>(dst);
+    uint4_t o0, o1;
+    o0.x = bswap32(h.st[0]); o0.y = bswap32(h.st[1]); o0.z = bswap32(h.st[2]); o0.w = bswap32(h.st[3]);
+    o1.x = bswap32(h.st[4]); o1.y = bswap32(h.st[5]); o1.z = bswap32(h.st[6]); o1.w = bswap32(h.st[7]);
+    out[0] = o0; out[1] = o1;
+  }
   // Compresses at most ONE block per call (the only compression site of the kernel).
   // Before the final drain: the block at buf[0..16) once it is complete, after which the leftover moves down.  LAZY buffers
   // hold two blocks and compress only when some lane of the wave runs out of room: the lanes of a wave cross block
   // boundaries within an element or two of each other, and compressing "whenever any lane has a block" ran the 64 rounds
   // ~1.4 times per block on wide rows (lpn = 128), mostly masked off.
-  // Final drain (uniform over the workgroup; the caller has appended the 0x80 byte of a msg_bytes-byte message and called
-  // begin_final): called until it stops returning MORE; the FIPS 180-4 padding is applied on the fly — words past the 0x80
+  // Final drain (uniform over the workgroup; the caller has called end_message() on a msg_bytes-byte message):
+  // called until it stops returning MORE; the FIPS 180-4 padding is applied on the fly — words past the 0x80
   // byte read as zero, the last block carries the bit length.  When the length does not fit behind the message, the message
   // ends with one more block that holds NO message bytes (zeros + length).  Few lanes of a wave need it (0.9 % of the
   // Fibonacci LDE rows, but 44 % of its waves), so it is not compressed here: DEFER tells the caller to hand the state to
@@ -428,7 +445,9 @@ template <> struct Affix<4> {
 // LDE columns (transition polynomials that ms_polys_lincomb defined, starks.rs:80-91 by linearity) are only ever hashed, so they need not exist in HBM.
 constexpr int LIN_MAXT = 4;
 struct LinColSpec { u32 n /* 0: a stored column */; u32 src[LIN_MAXT]; u64 s[LIN_MAXT]; };
-template <class F, int E, bool LAZY = false> struct LeafHashKernel {
+// DG: the digest's kernel family (Sha256Kernels below, Blake2sKernels in blake2s.hpp): its message stream and whether final blocks without message bytes exist.
+struct Sha256Kernels;
+template <class F, int E, bool LAZY = false, class DG = Sha256Kernels> struct LeafHashKernel {
   typedef typename F::T T;
   static constexpr int THREADS = msmerkle::THREADS;
   struct Params {
@@ -445,8 +464,8 @@ template <class F, int E, bool LAZY = false> struct LeafHashKernel {
   };
   static constexpr int MAX_BYTES = F::MAX_DIGITS + Affix<E>::MAX_BYTES;  // appended between two drains
   static constexpr int MAXW = (3 + MAX_BYTES + 3) / 4 + 1;               // words one iteration can touch past the write position
-  static constexpr int NWORDS = (LAZY ? 32 : 16) + MAXW + 1;
-  typedef ShaStream<NWORDS, THREADS, MAXW, LAZY> Stream;
+  static constexpr int NWORDS = (LAZY ? 32 : 16) + MAXW + 1 + DG::EXTRA_WORDS;
+  typedef typename DG::template Stream<NWORDS, THREADS, MAXW, LAZY> Stream;
   static MS_HD int nphases(const Params&) { return 1; }
   static MS_HD size_t lds_bytes() { return (size_t)NWORDS * THREADS * sizeof(u32); }
   static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int nthreads, unsigned char* lds) {
@@ -479,38 +498,35 @@ template <class F, int E, bool LAZY = false> struct LeafHashKernel {
         Affix<E>::after(s, k);
         if (k == (u32)(E - 1) && ++col == p.width) { col = 0; row++; }
       } else if (j == nlimbs) {
-        msg_bytes = s.total;
-        s.append_small(0x80000000u, 1);
-        s.begin_final();
+        msg_bytes = s.end_message();
       }
       const int st = s.drain(j >= nlimbs, msg_bytes);  // the only compression site
       if constexpr (LAZY) { if (j >= nlimbs && st != Stream::MORE) { deferred = st == Stream::DEFER; break; } }
       else deferred = st == Stream::DEFER;
     }
-    if (deferred && !p.ovf) {   // no deferred-block lists (the fused FRI round, fri_tail.hpp: a launch of a few waves has nothing to compact): the pad-only block right here
-      u32 w[16];
+    if constexpr (!DG::DEFERS) { s.store_digest(p.nodes + (g - p.out_g0) * 8); }   // (no block without message bytes: nothing to hand on, p.ovf* unused)
+    else {
+      if (deferred && !p.ovf) {   // no deferred-block lists (the fused FRI round, fri_tail.hpp: a launch of a few waves has nothing to compact): the pad-only block right here
+        u32 w[16];
 #pragma unroll
-      for (int i = 0; i < 15; i++) w[i] = 0;
-      w[15] = msg_bytes * 8u;
-      s.h.compress(w);
-      deferred = false;
-    }
-    const u32 list = (u32)bx % (u32)OVF_LISTS;
-    const u32 slot = msrt::wave_alloc_slot(p.ovf_count + list, deferred);
-    const size_t go = g - p.out_g0;   // digest slot
-    if (deferred) {
-      u32* e = p.ovf + ((size_t)list * p.ovf_cap + slot) * OVF_WORDS;
-      e[0] = (u32)go; e[1] = msg_bytes * 8u;
-      u32* st = p.nodes + go * 8;  // the state is parked in the digest slot
+        for (int i = 0; i < 15; i++) w[i] = 0;
+        w[15] = msg_bytes * 8u;
+        s.h.compress(w);
+        deferred = false;
+      }
+      const u32 list = (u32)bx % (u32)OVF_LISTS;
+      const u32 slot = msrt::wave_alloc_slot(p.ovf_count + list, deferred);
+      const size_t go = g - p.out_g0;   // digest slot
+      if (deferred) {
+        u32* e = p.ovf + ((size_t)list * p.ovf_cap + slot) * OVF_WORDS;
+        e[0] = (u32)go; e[1] = msg_bytes * 8u;
+        u32* st = p.nodes + go * 8;  // the state is parked in the digest slot
 #pragma unroll
-      for (int i = 0; i < 8; i++) st[i] = s.h.st[i];
-      return;
+        for (int i = 0; i < 8; i++) st[i] = s.h.st[i];
+        return;
+      }
+      s.store_digest(p.nodes + go * 8);
     }
-    uint4_t* out = reinterpret_cast<uint4_t*>(p.nodes + go * 8);
-    uint4_t o0, o1;
-    o0.x = bswap32(s.h.st[0]); o0.y = bswap32(s.h.st[1]); o0.z = bswap32(s.h.st[2]); o0.w = bswap32(s.h.st[3]);
-    o1.x = bswap32(s.h.st[4]); o1.y = bswap32(s.h.st[5]); o1.z = bswap32(s.h.st[6]); o1.w = bswap32(s.h.st[7]);
-    out[0] = o0; out[1] = o1;
   }
 };
 // The last block of the messages LeafHashKernel deferred: zeros + bit length, one compacted lane per entry.
@@ -704,6 +720,14 @@ struct InnerSubtreeKernel {
       child_off += nchildren; nchildren = nparents;
     }
   }
+};
+
+// The SHA-256 kernel family (the default DG of LeafHashKernel and of msfri::FriTailKernel).
+struct Sha256Kernels {
+  template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = ShaStream<NWORDS, NT, MAXW, LAZY>;
+  static constexpr int EXTRA_WORDS = 0;
+  static constexpr bool DEFERS = true;   // a final block may hold no message bytes: PadOnlyBlockKernel (or, without lists, in place)
+  typedef InnerSubtreeKernel Subtree;
 };
 
 // MerklePath extraction (src/merkle.rs:216-288), one thread per opened leaf.  Each job names a

@@ -1,6 +1,7 @@
-// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and
+// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp or, by the context's digest, the BLAKE2s-256 kernels of blake2s.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and
 // sharded by contiguous range; ms_merkle_commit.
 #include "ctx.hpp"
+#include "blake2s.hpp"
 
 namespace msctx {
 
@@ -25,6 +26,21 @@ template <class F> template <int EL>
 int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
               size_t g_first, u32 run_len, u32 run_stride, const msmerkle::LinColSpec* lin, size_t out_g0) {
   if (ngroups >> 32) return fail(MS_ERR_SHAPE, "more than 2^32 leaf groups");
+  if (digest == MS_DIGEST_BLAKE2S256) {   // one launch: no block without message bytes, so no lists, no zeroed counters, no follow-up kernel
+    auto launch = [&](auto kernel) -> int {
+      typedef decltype(kernel) LK;
+      typename LK::Params lp;
+      lp.base = base; lp.col_stride = col_stride; lp.row_stride = row_stride; lp.limb_stride = limb_stride;
+      lp.width = width; lp.lpn = (u32)lpn; lp.zero_as_empty = zae; lp.ngroups = ngroups; lp.nodes = out;
+      lp.ovf_count = nullptr; lp.ovf = nullptr; lp.ovf_cap = 0;
+      lp.g_first = g_first; lp.run_len = run_len; lp.run_stride = run_stride; lp.lin = lin; lp.out_g0 = out_g0;
+      next_bytes = (double)ngroups * (lpn * EL * sizeof(T) + 32);
+      CK(run<LK>(K_LEAF_HASH, grid1(ngroups, msmerkle::THREADS), 1, msmerkle::THREADS, LK::lds_bytes(), lp));
+      return 0;
+    };
+    if (lpn * EL >= (size_t)leaf_lazy_min) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake2sKernels>());
+    return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake2sKernels>());
+  }
   // deferred pad-only blocks: OVF_LISTS lists, list l fed by the workgroups bx = l (mod OVF_LISTS); capacity = all their threads
   const size_t nwg = grid1(ngroups, msmerkle::THREADS), lists = msmerkle::OVF_LISTS;
   const size_t cap = ((nwg + lists - 1) / lists) * msmerkle::THREADS;
@@ -61,6 +77,19 @@ int Ctx<F>::tree_build(const T* base, size_t col_stride, size_t row_stride, size
   return 0;
 }
 
+// `grid` workgroups of the level kernel of the context's digest (ic == 2: the binary tree's instance)
+template <class F>
+int Ctx<F>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip) {
+  if (digest == MS_DIGEST_BLAKE2S256) {
+    if (ip.ic == 2) CK(run<msmerkle::B2InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    else CK(run<msmerkle::B2InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+  } else {
+    if (ip.ic == 2) CK(run<msmerkle::InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    else CK(run<msmerkle::InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+  }
+  return 0;
+}
+
 template <class F>
 int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels, u8* rec_out) {
   size_t child_off = 0;
@@ -73,6 +102,7 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
     if (shard_aux) { ip.aux_src = shard_aux; ip.aux_dst = reinterpret_cast<unsigned long long*>(rec_out + 32); }
     rec_done = true;
   };
+  const bool b2 = digest == MS_DIGEST_BLAKE2S256;
   while (nchildren > 1) {
     msmerkle::InnerHashKernel::Params ip;
     ip.nodes = nodes; ip.child_off = child_off; ip.nchildren = nchildren; ip.ic = (u32)ic; ip.host_root = nullptr; ip.aux_src = nullptr; ip.aux_dst = nullptr; ip.flag = msrt::HostFlag{nullptr, 0};
@@ -89,7 +119,8 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       } else if (rec_out && left == 1) to_rec(ip);
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
-      CK(run_coop<SK>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      if (b2) CK(run_coop<msmerkle::B2InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      else CK(run_coop<SK>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       for (u32 l = 0; l < nl; l++) { child_off += nchildren; nchildren >>= 1; }
       continue;
     }
@@ -103,14 +134,12 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       u32 nl = 0; for (size_t m = nchildren; m > 1; m /= ic) nl++;
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
-      if (ic == 2) CK(run<msmerkle::InnerHashKernel2>(K_INNER_HASH, 1, 1, msmerkle::THREADS, 0, ip));
-      else CK(run<msmerkle::InnerHashKernel>(K_INNER_HASH, 1, 1, msmerkle::THREADS, 0, ip));
+      RQ(inner_launch(1, ip));
       break;
     }
     ip.nlevels = 1;
     next_bytes = (double)nparents * (ic * 32 + 32);
-    if (ic == 2) CK(run<msmerkle::InnerHashKernel2>(K_INNER_HASH, (unsigned)((nparents + msmerkle::THREADS - 1) / msmerkle::THREADS), 1, msmerkle::THREADS, 0, ip));
-    else CK(run<msmerkle::InnerHashKernel>(K_INNER_HASH, (unsigned)((nparents + msmerkle::THREADS - 1) / msmerkle::THREADS), 1, msmerkle::THREADS, 0, ip));
+    RQ(inner_launch((unsigned)((nparents + msmerkle::THREADS - 1) / msmerkle::THREADS), ip));
     child_off += nchildren; nchildren = nparents;
   }
   if (rec_out && !rec_done) {   // no launch took the record along (a one-digest "subtree"): by copies
@@ -228,6 +257,7 @@ int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn
 // the members this unit defines, for both fields (the other units see declarations only)
 #define MS_INSTANTIATE(FF) \
   template int Ctx<FF>::tree_shape(size_t leaf_num, size_t lpn, size_t ic, Ctx<FF>::TreeShape* ts); \
+  template int Ctx<FF>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip); \
   template int Ctx<FF>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels, u8* rec_out); \
   template int Ctx<FF>::finish_sharded_tree(Ctx<FF>::TreeShape& ts, DevBuf& nodes, size_t Mloc); \
   template int Ctx<FF>::read_root(const DevBuf& nodes, const Ctx<FF>::TreeShape& ts, u8* root); \
