@@ -16,8 +16,9 @@
  *    consecutive limbs: Goldilocks Fp2 = (c0, c1); BabyBear Fp4 =
  *    (c0.c0, c0.c1, c1.c0, c1.c1)  (src/field.rs:50-109).
  *  - Digests are 32 raw bytes of the context's `D` (`Hash<D>`, src/lib.rs:13): SHA-256 (MS_DIGEST_SHA256, `D = Sha256`, the
- *    default) or BLAKE2s-256 (MS_DIGEST_BLAKE2S256, `D = Blake2s256`, with MS_FLAG_DIGEST_BLAKE2S).  Every digest the library
- *    handles is 32 bytes, so roots, nodes, Merkle paths and the proof layouts are the same for both.
+ *    default), BLAKE2s-256 (MS_DIGEST_BLAKE2S256, `D = Blake2s256`, with MS_FLAG_DIGEST_BLAKE2S) or BLAKE3 (MS_DIGEST_BLAKE3,
+ *    `D = blake3::Hasher`, with MS_FLAG_DIGEST_BLAKE3).  Every digest the library handles is 32 bytes, so roots, nodes, Merkle
+ *    paths and the proof layouts are the same for all of them.
  *  - Every function returns MS_OK or a negative ms_status; nothing unwinds.
  *    Conditions on which the reference panics/asserts map to MS_ERR_SHAPE
  *    (src/merkle.rs:93-104, src/air.rs:23-26,53-54, src/starks.rs:317-320);
@@ -64,8 +65,12 @@ typedef enum {
 #define MS_FLAG_DIGEST_BLAKE2S 0x8u      /* every commitment of the context (trace, LDE, FRI rounds, the Merkle entry points) hashes with BLAKE2s-256 (RFC 7693, unkeyed:
                                          * RustCrypto `blake2::Blake2s256`) instead of SHA-256: the reference's `D` type argument.  One proof sharded over ranks stays
                                          * SHA-256 only: ms_set_shard / ms_set_shard_rccl return MS_ERR_ARG on such a context. */
+#define MS_FLAG_DIGEST_BLAKE3 0x10u      /* the same with BLAKE3 (unkeyed hash mode, 32-byte output: the `blake3` crate's `Hasher`, which implements the `digest` traits behind its
+                                         * `traits-preview` feature).  Excludes MS_FLAG_DIGEST_BLAKE2S: ms_create returns MS_ERR_ARG when both are set.  A hashed message
+                                         * (a leaf group's decimal text, or the children of an inner node) may be at most 16 KiB under this digest: a commitment whose
+                                         * shape allows more returns MS_ERR_ARG.  Sharded proofs: as for BLAKE2s, MS_ERR_ARG from ms_set_shard / ms_set_shard_rccl. */
 #define MS_FLAGS_DEFAULT MS_FLAG_ZERO_DISPLAY_EMPTY
-typedef enum { MS_DIGEST_SHA256 = 0, MS_DIGEST_BLAKE2S256 = 1 } ms_digest_id;
+typedef enum { MS_DIGEST_SHA256 = 0, MS_DIGEST_BLAKE2S256 = 1, MS_DIGEST_BLAKE3 = 2 } ms_digest_id;
 
 /* ---- context ------------------------------------------------------------ */
 int ms_create(ms_ctx** out, int device, ms_field field, uint32_t flags);

@@ -16,7 +16,8 @@ FLAG_ZERO_DISPLAY_EMPTY = 1
 FLAG_TRACE_MONT64 = 2
 FLAG_LATENCY = 4   # the context proves alone on its GPU: independent chains of a stage on two streams (costs throughput with several contexts in flight)
 FLAG_DIGEST_BLAKE2S = 8   # D = Blake2s256 for every commitment of the context (default: SHA-256)
-DIGEST_SHA256, DIGEST_BLAKE2S256 = 0, 1   # ms_digest_id
+FLAG_DIGEST_BLAKE3 = 0x10   # D = BLAKE3 (excludes FLAG_DIGEST_BLAKE2S)
+DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3 = 0, 1, 2   # ms_digest_id
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +92,9 @@ class Context:
         if (flags & FLAG_DIGEST_BLAKE2S) and self.digest != DIGEST_BLAKE2S256:
             self.close()
             raise MsError(ERR_ARG, "FLAG_DIGEST_BLAKE2S: this build of the library has no BLAKE2s-256 kernels")
+        if (flags & FLAG_DIGEST_BLAKE3) and self.digest != DIGEST_BLAKE3:
+            self.close()
+            raise MsError(ERR_ARG, "FLAG_DIGEST_BLAKE3: this build of the library has no BLAKE3 kernels")
         self.N = self.w = self.Lsize = 0
 
     def close(self):

@@ -1,7 +1,8 @@
-// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp or, by the context's digest, the BLAKE2s-256 kernels of blake2s.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and
-// sharded by contiguous range; ms_merkle_commit.
+// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp or, by the context's digest, the BLAKE2s-256 kernels of blake2s.hpp
+// or the BLAKE3 kernels of blake3.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
 #include "ctx.hpp"
 #include "blake2s.hpp"
+#include "blake3.hpp"
 
 namespace msctx {
 
@@ -26,7 +27,7 @@ template <class F> template <int EL>
 int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
               size_t g_first, u32 run_len, u32 run_stride, const msmerkle::LinColSpec* lin, size_t out_g0) {
   if (ngroups >> 32) return fail(MS_ERR_SHAPE, "more than 2^32 leaf groups");
-  if (digest == MS_DIGEST_BLAKE2S256) {   // one launch: no block without message bytes, so no lists, no zeroed counters, no follow-up kernel
+  if (digest != MS_DIGEST_SHA256) {   // BLAKE2s-256 / BLAKE3: one launch - no block without message bytes, so no lists, no zeroed counters, no follow-up kernel
     auto launch = [&](auto kernel) -> int {
       typedef decltype(kernel) LK;
       typename LK::Params lp;
@@ -38,7 +39,21 @@ int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_
       CK(run<LK>(K_LEAF_HASH, grid1(ngroups, msmerkle::THREADS), 1, msmerkle::THREADS, LK::lds_bytes(), lp));
       return 0;
     };
-    if (lpn * EL >= (size_t)leaf_lazy_min) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake2sKernels>());
+    const bool lazy = lpn * EL >= (size_t)leaf_lazy_min;
+    if (digest == MS_DIGEST_BLAKE3) {
+      // an upper bound of a leaf group's message: every limb at its longest, with its share of the extension's affixes.  Up to one chunk: the kernels without
+      // a chunk tree; up to B3_MAX_BYTES: the multi-chunk instances; beyond: refused (never a wrong digest)
+      const size_t bound = lpn * EL * (size_t)msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3Kernels>::MAX_BYTES;
+      if (lpn > msmerkle::B3_MAX_BYTES || bound > msmerkle::B3_MAX_BYTES)
+        return fail(MS_ERR_ARG, "BLAKE3: a leaf group's message may exceed 16384 bytes (leafs_per_node x limbs x longest decimal): not supported by the BLAKE3 kernels");
+      if (bound > msmerkle::B3_CHUNK_BYTES) {
+        if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake3MultiKernels>());
+        return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3MultiKernels>());
+      }
+      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake3Kernels>());
+      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3Kernels>());
+    }
+    if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake2sKernels>());
     return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake2sKernels>());
   }
   // deferred pad-only blocks: OVF_LISTS lists, list l fed by the workgroups bx = l (mod OVF_LISTS); capacity = all their threads
@@ -80,7 +95,12 @@ int Ctx<F>::tree_build(const T* base, size_t col_stride, size_t row_stride, size
 // `grid` workgroups of the level kernel of the context's digest (ic == 2: the binary tree's instance)
 template <class F>
 int Ctx<F>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip) {
-  if (digest == MS_DIGEST_BLAKE2S256) {
+  if (digest == MS_DIGEST_BLAKE3) {
+    if (ip.ic > msmerkle::B3InnerHashMultiKernel::MAX_IC) return fail(MS_ERR_ARG, "BLAKE3: inner nodes of more than 512 children (16384 bytes) are not supported by the BLAKE3 kernels");
+    if (ip.ic == 2) CK(run<msmerkle::B3InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    else if (ip.ic <= msmerkle::B3InnerHashKernel::MAX_IC) CK(run<msmerkle::B3InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    else CK(run<msmerkle::B3InnerHashMultiKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, msmerkle::B3InnerHashMultiKernel::lds_bytes(), ip));   // more than one chunk: the chunk tree, chaining values in LDS
+  } else if (digest == MS_DIGEST_BLAKE2S256) {
     if (ip.ic == 2) CK(run<msmerkle::B2InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
     else CK(run<msmerkle::B2InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
   } else {
@@ -102,7 +122,6 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
     if (shard_aux) { ip.aux_src = shard_aux; ip.aux_dst = reinterpret_cast<unsigned long long*>(rec_out + 32); }
     rec_done = true;
   };
-  const bool b2 = digest == MS_DIGEST_BLAKE2S256;
   while (nchildren > 1) {
     msmerkle::InnerHashKernel::Params ip;
     ip.nodes = nodes; ip.child_off = child_off; ip.nchildren = nchildren; ip.ic = (u32)ic; ip.host_root = nullptr; ip.aux_src = nullptr; ip.aux_dst = nullptr; ip.flag = msrt::HostFlag{nullptr, 0};
@@ -119,7 +138,8 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       } else if (rec_out && left == 1) to_rec(ip);
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
-      if (b2) CK(run_coop<msmerkle::B2InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      if (digest == MS_DIGEST_BLAKE3) CK(run_coop<msmerkle::B3InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      else if (digest == MS_DIGEST_BLAKE2S256) CK(run_coop<msmerkle::B2InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       else CK(run_coop<SK>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       for (u32 l = 0; l < nl; l++) { child_off += nchildren; nchildren >>= 1; }
       continue;

@@ -44,8 +44,18 @@ def _host():
             getattr(L, n).restype = C.c_size_t
         L.msh_proof_blob_checksum.restype = C.c_uint64
         L.msh_proof_blob_sample.restype = C.c_uint64
+        L.msh_hash.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p]
+        L.msh_hash.restype = C.c_int
         _HOST = L
     return _HOST
+
+
+def hash_bytes(digest_id: int, data: bytes) -> bytes:
+    """D(data) for an ms_digest_id by the C++ mirror's own host hashes (msh_hash): SHA-256, BLAKE2s-256, BLAKE3 (any length)."""
+    out = C.create_string_buffer(32)
+    if _host().msh_hash(int(digest_id), bytes(data), len(data), out) != 0:
+        raise MsError(-5, f"msh_hash: unknown digest id {digest_id}")
+    return out.raw
 
 
 class HostStark:

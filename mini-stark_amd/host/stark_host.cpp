@@ -7,7 +7,7 @@
 //                               Fri::commit_phase/query_phase src/fri.rs:64-189 (inlined: same call order)
 //   ministark::Stark::verify <- Stark::verify / Fri::verify / MerkleRoot::check_proof   src/starks.rs:171-235, src/fri.rs:191-290,
 //                               src/merkle.rs:312-338 — on the CPU, as in the reference
-//   ministark::Transcript    <- nimue Merlin                  BUILD-DEFINED stand-in: a hash chain over the context's digest (SHA-256 / BLAKE2s-256) with the
+//   ministark::Transcript    <- nimue Merlin                  BUILD-DEFINED stand-in: a hash chain over the context's digest (SHA-256 / BLAKE2s-256 / BLAKE3) with the
 //                                                             message ORDER of src/fiatshamir.rs:48-64,100-116;
 //                                                             not nimue's bytes (its source is unavailable).
 // Every field operation of the PROVER happens on the GPU inside libministark.so; prove() only moves challenges and
@@ -106,12 +106,66 @@ struct Blake2s {
   }
 };
 
+// ---- BLAKE3 (unkeyed hash mode, 32-byte output), the whole specification: chunks of 1024 bytes, the binary tree of chunk chaining values -----------
+struct Blake3 {
+  enum { CHUNK_START = 1, CHUNK_END = 2, PARENT = 4, ROOT = 8 };
+  u32 cv[8]; u8 buf[64]; size_t nb = 0; u32 blocks = 0 /* compressed in the current chunk */; u64 chunk = 0; u32 stack[64][8]; int sp = 0;
+  Blake3() { memcpy(cv, Blake2s::iv(), 32); memset(buf, 0, 64); }
+  static u32 rotr(u32 x, int n) { return (x >> n) | (x << (32 - n)); }
+  // cv = the first 8 words of the compression of the 64-byte block p (little-endian words) under chaining value `in`
+  static void compress(const u32 in[8], const u8* p, u64 counter, u32 len, u32 flags, u32 out[8]) {
+    static const u8 PERM[16] = {2, 6, 3, 10, 7, 0, 4, 13, 1, 11, 12, 5, 9, 14, 15, 8};
+    u32 m[16], v[16];
+    for (int i = 0; i < 16; i++) m[i] = (u32)p[4 * i] | ((u32)p[4 * i + 1] << 8) | ((u32)p[4 * i + 2] << 16) | ((u32)p[4 * i + 3] << 24);
+    for (int i = 0; i < 8; i++) v[i] = in[i];
+    for (int i = 0; i < 4; i++) v[8 + i] = Blake2s::iv()[i];
+    v[12] = (u32)counter; v[13] = (u32)(counter >> 32); v[14] = len; v[15] = flags;
+    auto G = [&](int a, int b, int c, int d, u32 x, u32 y) {
+      v[a] = v[a] + v[b] + x; v[d] = rotr(v[d] ^ v[a], 16); v[c] = v[c] + v[d]; v[b] = rotr(v[b] ^ v[c], 12);
+      v[a] = v[a] + v[b] + y; v[d] = rotr(v[d] ^ v[a], 8); v[c] = v[c] + v[d]; v[b] = rotr(v[b] ^ v[c], 7);
+    };
+    for (int r = 0; r < 7; r++) {
+      G(0, 4, 8, 12, m[0], m[1]); G(1, 5, 9, 13, m[2], m[3]); G(2, 6, 10, 14, m[4], m[5]); G(3, 7, 11, 15, m[6], m[7]);
+      G(0, 5, 10, 15, m[8], m[9]); G(1, 6, 11, 12, m[10], m[11]); G(2, 7, 8, 13, m[12], m[13]); G(3, 4, 9, 14, m[14], m[15]);
+      u32 t[16]; for (int i = 0; i < 16; i++) t[i] = m[PERM[i]];
+      memcpy(m, t, 64);
+    }
+    for (int i = 0; i < 8; i++) out[i] = v[i] ^ v[i + 8];
+  }
+  void parent(const u32 left[8], u32 flags) {   // cv = PARENT(left, cv)
+    u8 blk[64]; memcpy(blk, left, 32); memcpy(blk + 32, cv, 32);   // (little-endian host, as everywhere in this file)
+    compress(Blake2s::iv(), blk, 0, 64, PARENT | flags, cv);
+  }
+  // a full buffer is compressed only once more bytes arrive: a chunk's (and the message's) last block carries its flags
+  void update(const void* data, size_t n) {
+    const u8* p = (const u8*)data;
+    while (n) {
+      if (nb == 64) {
+        compress(cv, buf, chunk, 64, (blocks == 0 ? CHUNK_START : 0) | (blocks == 15 ? CHUNK_END : 0), cv);
+        if (blocks == 15) {   // the chunk is complete and more follows: merge the subtrees it completes (one per trailing zero bit of the chunk count), wait
+          u64 tot = ++chunk;
+          while ((tot & 1) == 0) { parent(stack[--sp], 0); tot >>= 1; }
+          memcpy(stack[sp++], cv, 32); memcpy(cv, Blake2s::iv(), 32); blocks = 0;
+        } else blocks++;
+        nb = 0;
+      }
+      size_t k = 64 - nb < n ? 64 - nb : n; memcpy(buf + nb, p, k); nb += k; p += k; n -= k;
+    }
+  }
+  void finish(u8 out[32]) {
+    memset(buf + nb, 0, 64 - nb);
+    compress(cv, buf, chunk, (u32)nb, (blocks == 0 ? CHUNK_START : 0) | CHUNK_END | (sp == 0 ? ROOT : 0), cv);
+    while (sp) { --sp; parent(stack[sp], sp == 0 ? ROOT : 0); }
+    for (int k = 0; k < 8; k++) { out[4 * k] = cv[k]; out[4 * k + 1] = cv[k] >> 8; out[4 * k + 2] = cv[k] >> 16; out[4 * k + 3] = cv[k] >> 24; }
+  }
+};
+
 // the `D` of the handle's context (ms_digest): one streaming hash by ms_digest_id
 struct Hasher {
-  int id; Sha256 s; Blake2s b;
+  int id; Sha256 s; Blake2s b; Blake3 b3;
   explicit Hasher(int digest) : id(digest) {}
-  void update(const void* d, size_t n) { if (id == MS_DIGEST_BLAKE2S256) b.update(d, n); else s.update(d, n); }
-  void finish(u8 out[32]) { if (id == MS_DIGEST_BLAKE2S256) b.finish(out); else s.finish(out); }
+  void update(const void* d, size_t n) { if (id == MS_DIGEST_BLAKE3) b3.update(d, n); else if (id == MS_DIGEST_BLAKE2S256) b.update(d, n); else s.update(d, n); }
+  void finish(u8 out[32]) { if (id == MS_DIGEST_BLAKE3) b3.finish(out); else if (id == MS_DIGEST_BLAKE2S256) b.finish(out); else s.finish(out); }
 };
 
 // Build-defined Fiat–Shamir hash chain (byte-identical to mini-stark_amd/stark.py::Transcript): the stand-in for `DigestBridge<D>`, over the context's digest.
@@ -628,6 +682,12 @@ int msh_cubic_rows(u64 p, size_t length, size_t w, u64 seed, u64* out, u64* scal
     const u64* a = out + (i - 1) * w; u64* b = out + i * w;
     for (size_t j = 0; j < w; j++) b[j] = (u64)(((unsigned __int128)mm(mm(a[j], a[(j + 1) % w]), a[(j + 2) % w]) + mm(scalars[j], a[(j + 3) % w])) % p);
   }
+  return 0;
+}
+// D(data) for an ms_digest_id, by the hashes of this mirror (the Python mirror has no BLAKE3 of its own and calls this one): 0, or -1 for an unknown id
+int msh_hash(int digest_id, const u8* data, size_t len, u8 out[32]) {
+  if (digest_id < MS_DIGEST_SHA256 || digest_id > MS_DIGEST_BLAKE3 || !out || (!data && len)) return -1;
+  ministark::Hasher h(digest_id); if (len) h.update(data, len); h.finish(out);
   return 0;
 }
 // the synthetic Fibonacci-AIR trace of the benchmark workload (tests/e2e_goldilocks.rs:20-63 rows + SplitMix64 padding; = mini_stark_amd.synthetic.fibonacci_rows)

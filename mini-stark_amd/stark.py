@@ -11,7 +11,7 @@ transcript and the library.
 
 Transcript: the reference uses nimue (`IOPattern`/`Merlin` over
 `DigestBridge<Sha256>`, src/fiatshamir.rs) whose source is not available here,
-so `Transcript` below is a BUILD-DEFINED hash chain (over the context's digest: SHA-256 or BLAKE2s-256) that follows the
+so `Transcript` below is a BUILD-DEFINED hash chain (over the context's digest: SHA-256, BLAKE2s-256 or BLAKE3) that follows the
 same message ORDER (src/fiatshamir.rs:48-64,100-116) but not nimue's bytes.
 A Rust caller keeps nimue and passes the challenges in.
 """
@@ -22,7 +22,7 @@ from typing import List
 
 import numpy as np
 
-from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, DIGEST_SHA256, DIGEST_BLAKE2S256
+from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
 
@@ -31,12 +31,33 @@ def _blake2s256(data=b""):
     return hashlib.blake2s(data, digest_size=32)
 
 
+class _Blake3:
+    """hashlib has no BLAKE3: a hashlib-shaped object over the C++ host mirror's implementation (msh_hash of libministark_host.so, the whole specification)."""
+    name, digest_size, block_size = "blake3", 32, 64
+
+    def __init__(self, data=b""):
+        self._data = bytearray(data)
+
+    def update(self, data):
+        self._data += data
+
+    def copy(self):
+        return _Blake3(self._data)
+
+    def digest(self):
+        from .host import hash_bytes   # (host.py imports this module)
+        return hash_bytes(DIGEST_BLAKE3, bytes(self._data))
+
+    def hexdigest(self):
+        return self.digest().hex()
+
+
 # ms_digest_id -> hash constructor: the D of `DigestBridge<D>` (fiatshamir.rs:23-46) is the D of the commitments
-DIGEST_HASH = {DIGEST_SHA256: hashlib.sha256, DIGEST_BLAKE2S256: _blake2s256}
+DIGEST_HASH = {DIGEST_SHA256: hashlib.sha256, DIGEST_BLAKE2S256: _blake2s256, DIGEST_BLAKE3: _Blake3}
 
 
 class Transcript:
-    """Build-defined Fiat–Shamir sponge (NOT nimue): state' = D(state || tag || data), D = SHA-256 unless `digest` (an ms_digest_id) says BLAKE2s-256."""
+    """Build-defined Fiat–Shamir sponge (NOT nimue): state' = D(state || tag || data), D = SHA-256 unless `digest` (an ms_digest_id) says BLAKE2s-256 or BLAKE3."""
 
     def __init__(self, domsep: str, digest: int = DIGEST_SHA256):
         self.hash = DIGEST_HASH[digest]

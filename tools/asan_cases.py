@@ -58,6 +58,25 @@ for field in (0, 1):
 os.environ["MS_FRI_TAIL_MAX"] = "1048576"
 pc.case_prove(lambda f, fresh=False: mk(f, fresh=True), 0, 10, 8)
 del os.environ["MS_FRI_TAIL_MAX"]
+# BLAKE3 contexts (MS_FLAG_DIGEST_BLAKE3): the single-chunk and the multi-chunk leaf kernels (both buffers), inner nodes above one chunk, the refusal above 16 KiB, a whole proof
+import blake3_cases as bc
+def mk3(field, flags, env=None):
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        return ms.Context(field, flags=flags, lib_path=EMU)
+    finally:
+        for k, v in old.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+for field in (0, 1):
+    b3 = mk3(field, bc.ZAE | bc.B3)
+    for shape in bc.MERKLE_SHAPES:
+        bc.case_every_node(b3, field, *shape, True)
+    bc.case_too_long_is_refused(b3, field)
+    for lazy in (False, True):
+        bc.case_length_edges(mk3, field, (6, 16) if field == 0 else (6, 24), lazy)
+    bc.case_whole_proof(mk3, field, 10, 8, variants=[("fused tail", bc.ZAE | bc.B3, {"MS_FRI_TAIL_MAX": "65536"}), ("latency", bc.ZAE | bc.B3 | bc.LATENCY, None)])
 from mini_stark_amd.host import build_host_library
 build_host_library()
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
