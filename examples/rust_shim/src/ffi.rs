@@ -16,10 +16,14 @@ pub const MS_FLAG_TRACE_MONT64: u32 = 2; // ms_trace_commit* reads arkworks memo
 pub const MS_FLAG_LATENCY: u32 = 4; // one proof alone on the GPU: independent chains of a stage on two streams, the calling thread spins for a stage's results
 pub const MS_FLAG_DIGEST_BLAKE2S: u32 = 8; // D = Blake2s256: every commitment of the context hashes with BLAKE2s-256 instead of SHA-256
 pub const MS_FLAG_DIGEST_BLAKE3: u32 = 0x10; // D = blake3::Hasher (the crate's `traits-preview` feature); excludes MS_FLAG_DIGEST_BLAKE2S (MS_ERR_ARG from ms_create)
+pub const MS_FLAG_DIGEST_KECCAK256: u32 = 0x20; // D = sha3::Keccak256 (the original Keccak padding: Ethereum's hash); a context takes at most one MS_FLAG_DIGEST_* flag
+pub const MS_FLAG_DIGEST_SHA3_256: u32 = 0x40; // D = sha3::Sha3_256 (FIPS 202)
 pub const MS_FLAGS_DEFAULT: u32 = MS_FLAG_ZERO_DISPLAY_EMPTY;
 pub const MS_DIGEST_SHA256: c_int = 0; // ms_digest_id
 pub const MS_DIGEST_BLAKE2S256: c_int = 1;
 pub const MS_DIGEST_BLAKE3: c_int = 2;
+pub const MS_DIGEST_KECCAK256: c_int = 4; // (3 is unassigned)
+pub const MS_DIGEST_SHA3_256: c_int = 5;
 pub type ms_exchange_fn = Option<unsafe extern "C" fn(user: *mut c_void, op: c_int, bytes: usize) -> c_int>;
 
 extern "C" {

@@ -16,9 +16,11 @@
  *    consecutive limbs: Goldilocks Fp2 = (c0, c1); BabyBear Fp4 =
  *    (c0.c0, c0.c1, c1.c0, c1.c1)  (src/field.rs:50-109).
  *  - Digests are 32 raw bytes of the context's `D` (`Hash<D>`, src/lib.rs:13): SHA-256 (MS_DIGEST_SHA256, `D = Sha256`, the
- *    default), BLAKE2s-256 (MS_DIGEST_BLAKE2S256, `D = Blake2s256`, with MS_FLAG_DIGEST_BLAKE2S) or BLAKE3 (MS_DIGEST_BLAKE3,
- *    `D = blake3::Hasher`, with MS_FLAG_DIGEST_BLAKE3).  Every digest the library handles is 32 bytes, so roots, nodes, Merkle
- *    paths and the proof layouts are the same for all of them.
+ *    default), BLAKE2s-256 (MS_DIGEST_BLAKE2S256, `D = Blake2s256`, with MS_FLAG_DIGEST_BLAKE2S), BLAKE3 (MS_DIGEST_BLAKE3,
+ *    `D = blake3::Hasher`, with MS_FLAG_DIGEST_BLAKE3), Keccak-256 (MS_DIGEST_KECCAK256, `D = sha3::Keccak256`, with
+ *    MS_FLAG_DIGEST_KECCAK256: the hash the EVM has as an opcode) or SHA3-256 (MS_DIGEST_SHA3_256, `D = sha3::Sha3_256`, with
+ *    MS_FLAG_DIGEST_SHA3_256).  Every digest the library handles is 32 bytes, so roots, nodes, Merkle paths and the proof layouts
+ *    are the same for all of them.
  *  - Every function returns MS_OK or a negative ms_status; nothing unwinds.
  *    Conditions on which the reference panics/asserts map to MS_ERR_SHAPE
  *    (src/merkle.rs:93-104, src/air.rs:23-26,53-54, src/starks.rs:317-320);
@@ -69,8 +71,13 @@ typedef enum {
                                          * `traits-preview` feature).  Excludes MS_FLAG_DIGEST_BLAKE2S: ms_create returns MS_ERR_ARG when both are set.  A hashed message
                                          * (a leaf group's decimal text, or the children of an inner node) may be at most 16 KiB under this digest: a commitment whose
                                          * shape allows more returns MS_ERR_ARG.  Sharded proofs: as for BLAKE2s, MS_ERR_ARG from ms_set_shard / ms_set_shard_rccl. */
+#define MS_FLAG_DIGEST_KECCAK256 0x20u   /* the same with Keccak-256: the Keccak-f[1600] sponge, rate 136 bytes, with the ORIGINAL Keccak padding (domain byte 0x01) as Ethereum
+                                         * uses it (`sha3::Keccak256`).  A sponge has no message-length limit.  Sharded proofs: MS_ERR_ARG, as for the BLAKE digests. */
+#define MS_FLAG_DIGEST_SHA3_256 0x40u    /* the same sponge with the FIPS 202 padding (domain byte 0x06): SHA3-256 (`sha3::Sha3_256`).
+                                         * A context has ONE digest: ms_create returns MS_ERR_ARG when more than one of the four MS_FLAG_DIGEST_* flags is set. */
 #define MS_FLAGS_DEFAULT MS_FLAG_ZERO_DISPLAY_EMPTY
-typedef enum { MS_DIGEST_SHA256 = 0, MS_DIGEST_BLAKE2S256 = 1, MS_DIGEST_BLAKE3 = 2 } ms_digest_id;
+/* Id 3 is unassigned on purpose and stays so: ms_digest never returns it and msh_hash refuses it (the Keccak family starts at 4). */
+typedef enum { MS_DIGEST_SHA256 = 0, MS_DIGEST_BLAKE2S256 = 1, MS_DIGEST_BLAKE3 = 2, MS_DIGEST_KECCAK256 = 4, MS_DIGEST_SHA3_256 = 5 } ms_digest_id;
 
 /* ---- context ------------------------------------------------------------ */
 int ms_create(ms_ctx** out, int device, ms_field field, uint32_t flags);

@@ -17,7 +17,10 @@ FLAG_TRACE_MONT64 = 2
 FLAG_LATENCY = 4   # the context proves alone on its GPU: independent chains of a stage on two streams (costs throughput with several contexts in flight)
 FLAG_DIGEST_BLAKE2S = 8   # D = Blake2s256 for every commitment of the context (default: SHA-256)
 FLAG_DIGEST_BLAKE3 = 0x10   # D = BLAKE3 (excludes FLAG_DIGEST_BLAKE2S)
+FLAG_DIGEST_KECCAK256 = 0x20   # D = Keccak-256 (original padding: Ethereum's); a context takes at most one FLAG_DIGEST_* flag
+FLAG_DIGEST_SHA3_256 = 0x40   # D = SHA3-256 (FIPS 202)
 DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3 = 0, 1, 2   # ms_digest_id
+DIGEST_KECCAK256, DIGEST_SHA3_256 = 4, 5   # (3 is unassigned)
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -95,6 +98,10 @@ class Context:
         if (flags & FLAG_DIGEST_BLAKE3) and self.digest != DIGEST_BLAKE3:
             self.close()
             raise MsError(ERR_ARG, "FLAG_DIGEST_BLAKE3: this build of the library has no BLAKE3 kernels")
+        for flag, want, name in ((FLAG_DIGEST_KECCAK256, DIGEST_KECCAK256, "KECCAK256"), (FLAG_DIGEST_SHA3_256, DIGEST_SHA3_256, "SHA3_256")):
+            if (flags & flag) and self.digest != want:
+                self.close()
+                raise MsError(ERR_ARG, f"FLAG_DIGEST_{name}: this build of the library has no Keccak kernels")
         self.N = self.w = self.Lsize = 0
 
     def close(self):

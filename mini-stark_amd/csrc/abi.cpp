@@ -46,7 +46,7 @@ int ms_create(ms_ctx** out, int device, ms_field field, uint32_t flags) {
   if (!out) return MS_ERR_ARG;
   *out = nullptr;
   if (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) return MS_ERR_ARG;
-  if ((flags & MS_FLAG_DIGEST_BLAKE2S) && (flags & MS_FLAG_DIGEST_BLAKE3)) return MS_ERR_ARG;   // a context has one D
+  { const uint32_t d = flags & (MS_FLAG_DIGEST_BLAKE2S | MS_FLAG_DIGEST_BLAKE3 | MS_FLAG_DIGEST_KECCAK256 | MS_FLAG_DIGEST_SHA3_256); if (d & (d - 1)) return MS_ERR_ARG; }   // a context has one D
   CtxBase* c = nullptr;
   try {
     int rc;

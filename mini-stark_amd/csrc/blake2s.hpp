@@ -189,6 +189,7 @@ struct B2InnerSubtreeKernel {
 // The BLAKE2s-256 kernel family (DG of LeafHashKernel and msfri::FriTailKernel).
 struct Blake2sKernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B2Stream<NWORDS, NT, MAXW, LAZY>;
+  static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
   static constexpr int EXTRA_WORDS = 1;
   static constexpr bool DEFERS = false;
   typedef B2InnerSubtreeKernel Subtree;

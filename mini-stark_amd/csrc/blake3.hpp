@@ -293,12 +293,14 @@ struct B3InnerSubtreeKernel {
 // The BLAKE3 kernel families (DG of LeafHashKernel and msfri::FriTailKernel): messages of at most one chunk, and (leaf hashing only) of up to B3_MAX_BYTES.
 struct Blake3Kernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B3StreamT<NWORDS, NT, MAXW, LAZY, false>;
+  static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
   static constexpr int EXTRA_WORDS = 1;
   static constexpr bool DEFERS = false;
   typedef B3InnerSubtreeKernel Subtree;
 };
 struct Blake3MultiKernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B3StreamT<NWORDS, NT, MAXW, LAZY, true>;
+  static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
   static constexpr int EXTRA_WORDS = 1 + B3CvStack<THREADS>::WORDS;
   static constexpr bool DEFERS = false;
   typedef B3InnerSubtreeKernel Subtree;

@@ -69,7 +69,7 @@ struct CtxBase {
   // entry point returns MS_ERR_STATE; only ms_destroy is valid, and it waits for the transfer WITHOUT limit before it frees anything.
   bool poisoned = false;
   virtual ~CtxBase() {}
-  int digest = MS_DIGEST_SHA256;   // ms_digest_id: the D of every commitment of this context (MS_FLAG_DIGEST_BLAKE2S / MS_FLAG_DIGEST_BLAKE3 at ms_create)
+  int digest = MS_DIGEST_SHA256;   // ms_digest_id: the D of every commitment of this context (the MS_FLAG_DIGEST_* flag at ms_create)
   virtual int ext_degree() const = 0;
   virtual void bind_device() const = 0;  // HIP's current device is per host thread: every entry point binds the context's device
   virtual int set_stream(void* s) = 0;
@@ -556,7 +556,7 @@ template <class F> struct Ctx : CtxBase {
   struct StreamScope { Ctx* c; msrt::Stream* keep; StreamScope(Ctx* c_, msrt::Stream* s) : c(c_), keep(c_->stream) { c->stream = s; } ~StreamScope() { c->stream = keep; } };
   int join_side() { if (side_pending) { side_pending = false; CK(msrt::stream_wait_event(stream, ev_side)); } return 0; }   // the context's stream goes on only behind the side stream's work
   int fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done);
-  template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: msmerkle::Sha256Kernels / Blake2sKernels / Blake3Kernels, by `digest`
+  template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: msmerkle::Sha256Kernels / Blake2sKernels / Blake3Kernels / KeccakKernels<SUFFIX>, by `digest`
   int fri_round_info(int r, u64* ncoef, u64* D) override;
   int fri_round_poly_read(int r, u64* out) override;
   int fri_round_codeword_read(int r, u64* out) override;

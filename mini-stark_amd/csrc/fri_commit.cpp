@@ -310,6 +310,8 @@ int Ctx<F>::fold_dist(Round* pr, Round* nr, const XE& a, size_t* nq_coef_out) {
 // level, root and length word into page-locked memory.  *done = false: the round does not qualify (the caller takes the launch-per-step path).
 template <class F>
 int Ctx<F>::fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done) {
+  if (digest == MS_DIGEST_KECCAK256) return fri_tail_round_t<msmerkle::Keccak256Kernels>(pr, nr, a, done);
+  if (digest == MS_DIGEST_SHA3_256) return fri_tail_round_t<msmerkle::Sha3_256Kernels>(pr, nr, a, done);
   if (digest == MS_DIGEST_BLAKE3) return fri_tail_round_t<msmerkle::Blake3Kernels>(pr, nr, a, done);   // (a round's leaf group is 2 extension elements: far below one chunk)
   return digest == MS_DIGEST_BLAKE2S256 ? fri_tail_round_t<msmerkle::Blake2sKernels>(pr, nr, a, done) : fri_tail_round_t<msmerkle::Sha256Kernels>(pr, nr, a, done);
 }

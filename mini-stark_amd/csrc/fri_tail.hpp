@@ -19,11 +19,12 @@
 #pragma once
 #include "blake2s.hpp"
 #include "blake3.hpp"
+#include "keccak.hpp"
 #include "poly.hpp"
 
 namespace msfri {
 
-// DG: the digest's kernel family (msmerkle::Sha256Kernels / Blake2sKernels / Blake3Kernels): the leaf and subtree steps are its kernels' device code.
+// DG: the digest's kernel family (msmerkle::Sha256Kernels / Blake2sKernels / Blake3Kernels / KeccakKernels<SUFFIX>): the leaf and subtree steps are its kernels' device code.
 template <class F, int E, class DG = msmerkle::Sha256Kernels> struct FriTailKernel {
   typedef typename F::T T;
   static constexpr int THREADS = 256;

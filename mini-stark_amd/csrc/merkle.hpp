@@ -445,7 +445,8 @@ template <> struct Affix<4> {
 // LDE columns (transition polynomials that ms_polys_lincomb defined, starks.rs:80-91 by linearity) are only ever hashed, so they need not exist in HBM.
 constexpr int LIN_MAXT = 4;
 struct LinColSpec { u32 n /* 0: a stored column */; u32 src[LIN_MAXT]; u64 s[LIN_MAXT]; };
-// DG: the digest's kernel family (Sha256Kernels below, Blake2sKernels in blake2s.hpp): its message stream and whether final blocks without message bytes exist.
+// DG: the digest's kernel family (Sha256Kernels below, Blake2sKernels in blake2s.hpp, Blake3Kernels in blake3.hpp, KeccakKernels in keccak.hpp): its message stream, the
+// stream's block size and whether final blocks without message bytes exist.
 struct Sha256Kernels;
 template <class F, int E, bool LAZY = false, class DG = Sha256Kernels> struct LeafHashKernel {
   typedef typename F::T T;
@@ -464,7 +465,7 @@ template <class F, int E, bool LAZY = false, class DG = Sha256Kernels> struct Le
   };
   static constexpr int MAX_BYTES = F::MAX_DIGITS + Affix<E>::MAX_BYTES;  // appended between two drains
   static constexpr int MAXW = (3 + MAX_BYTES + 3) / 4 + 1;               // words one iteration can touch past the write position
-  static constexpr int NWORDS = (LAZY ? 32 : 16) + MAXW + 1 + DG::EXTRA_WORDS;
+  static constexpr int NWORDS = DG::BLOCK_WORDS * (LAZY ? DG::LAZY_BLOCKS : 1) + MAXW + 1 + DG::EXTRA_WORDS;   // blocks of the digest's stream + room for one element
   typedef typename DG::template Stream<NWORDS, THREADS, MAXW, LAZY> Stream;
   static MS_HD int nphases(const Params&) { return 1; }
   static MS_HD size_t lds_bytes() { return (size_t)NWORDS * THREADS * sizeof(u32); }
@@ -725,6 +726,8 @@ struct InnerSubtreeKernel {
 // The SHA-256 kernel family (the default DG of LeafHashKernel and of msfri::FriTailKernel).
 struct Sha256Kernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = ShaStream<NWORDS, NT, MAXW, LAZY>;
+  static constexpr int BLOCK_WORDS = 16;   // words the stream compresses at a time
+  static constexpr int LAZY_BLOCKS = 2;    // blocks a LAZY buffer holds
   static constexpr int EXTRA_WORDS = 0;
   static constexpr bool DEFERS = true;   // a final block may hold no message bytes: PadOnlyBlockKernel (or, without lists, in place)
   typedef InnerSubtreeKernel Subtree;

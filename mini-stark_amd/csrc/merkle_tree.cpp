@@ -1,8 +1,9 @@
 // merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp or, by the context's digest, the BLAKE2s-256 kernels of blake2s.hpp
-// or the BLAKE3 kernels of blake3.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
+// or the BLAKE3 kernels of blake3.hpp or the Keccak-256 / SHA3-256 kernels of keccak.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
 #include "ctx.hpp"
 #include "blake2s.hpp"
 #include "blake3.hpp"
+#include "keccak.hpp"
 
 namespace msctx {
 
@@ -27,7 +28,7 @@ template <class F> template <int EL>
 int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
               size_t g_first, u32 run_len, u32 run_stride, const msmerkle::LinColSpec* lin, size_t out_g0) {
   if (ngroups >> 32) return fail(MS_ERR_SHAPE, "more than 2^32 leaf groups");
-  if (digest != MS_DIGEST_SHA256) {   // BLAKE2s-256 / BLAKE3: one launch - no block without message bytes, so no lists, no zeroed counters, no follow-up kernel
+  if (digest != MS_DIGEST_SHA256) {   // BLAKE2s-256 / BLAKE3: one launch - no block without message bytes, so no lists, no zeroed counters, no follow-up kernel.  Keccak-256 / SHA3-256: one launch - a block of padding only is absorbed in place
     auto launch = [&](auto kernel) -> int {
       typedef decltype(kernel) LK;
       typename LK::Params lp;
@@ -52,6 +53,14 @@ int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_
       }
       if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake3Kernels>());
       return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3Kernels>());
+    }
+    if (digest == MS_DIGEST_KECCAK256) {   // a sponge: any length
+      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Keccak256Kernels>());
+      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Keccak256Kernels>());
+    }
+    if (digest == MS_DIGEST_SHA3_256) {
+      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Sha3_256Kernels>());
+      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Sha3_256Kernels>());
     }
     if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake2sKernels>());
     return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake2sKernels>());
@@ -95,7 +104,15 @@ int Ctx<F>::tree_build(const T* base, size_t col_stride, size_t row_stride, size
 // `grid` workgroups of the level kernel of the context's digest (ic == 2: the binary tree's instance)
 template <class F>
 int Ctx<F>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip) {
-  if (digest == MS_DIGEST_BLAKE3) {
+  if (digest == MS_DIGEST_KECCAK256 || digest == MS_DIGEST_SHA3_256) {
+    auto launch = [&](auto family) -> int {
+      typedef decltype(family) DG;
+      if (ip.ic == 2) CK(run<typename DG::Inner2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+      else CK(run<typename DG::Inner>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+      return 0;
+    };
+    return digest == MS_DIGEST_KECCAK256 ? launch(msmerkle::Keccak256Kernels()) : launch(msmerkle::Sha3_256Kernels());
+  } else if (digest == MS_DIGEST_BLAKE3) {
     if (ip.ic > msmerkle::B3InnerHashMultiKernel::MAX_IC) return fail(MS_ERR_ARG, "BLAKE3: inner nodes of more than 512 children (16384 bytes) are not supported by the BLAKE3 kernels");
     if (ip.ic == 2) CK(run<msmerkle::B3InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
     else if (ip.ic <= msmerkle::B3InnerHashKernel::MAX_IC) CK(run<msmerkle::B3InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
@@ -138,7 +155,9 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       } else if (rec_out && left == 1) to_rec(ip);
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
-      if (digest == MS_DIGEST_BLAKE3) CK(run_coop<msmerkle::B3InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      if (digest == MS_DIGEST_KECCAK256) CK(run_coop<msmerkle::Keccak256Kernels::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      else if (digest == MS_DIGEST_SHA3_256) CK(run_coop<msmerkle::Sha3_256Kernels::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      else if (digest == MS_DIGEST_BLAKE3) CK(run_coop<msmerkle::B3InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       else if (digest == MS_DIGEST_BLAKE2S256) CK(run_coop<msmerkle::B2InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       else CK(run_coop<SK>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
       for (u32 l = 0; l < nl; l++) { child_off += nchildren; nchildren >>= 1; }

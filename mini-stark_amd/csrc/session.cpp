@@ -94,7 +94,9 @@ template <class F>
 int Ctx<F>::init(int dev, u32 flags) {
   device = dev; zae = (flags & MS_FLAG_ZERO_DISPLAY_EMPTY) ? 1 : 0; trace_mont = (flags & MS_FLAG_TRACE_MONT64) ? 1 : 0; fri_overlap = (flags & MS_FLAG_LATENCY) ? 1 : 0; poll_sync = fri_overlap;
   if ((flags & MS_FLAG_DIGEST_BLAKE2S) && (flags & MS_FLAG_DIGEST_BLAKE3)) return fail(MS_ERR_ARG, "ms_create: MS_FLAG_DIGEST_BLAKE2S and MS_FLAG_DIGEST_BLAKE3 exclude each other");
-  digest = (flags & MS_FLAG_DIGEST_BLAKE3) ? MS_DIGEST_BLAKE3 : (flags & MS_FLAG_DIGEST_BLAKE2S) ? MS_DIGEST_BLAKE2S256 : MS_DIGEST_SHA256;
+  { const u32 d = flags & (MS_FLAG_DIGEST_BLAKE2S | MS_FLAG_DIGEST_BLAKE3 | MS_FLAG_DIGEST_KECCAK256 | MS_FLAG_DIGEST_SHA3_256); if (d & (d - 1)) return fail(MS_ERR_ARG, "ms_create: the MS_FLAG_DIGEST_* flags exclude each other"); }
+  digest = (flags & MS_FLAG_DIGEST_KECCAK256) ? MS_DIGEST_KECCAK256 : (flags & MS_FLAG_DIGEST_SHA3_256) ? MS_DIGEST_SHA3_256
+         : (flags & MS_FLAG_DIGEST_BLAKE3) ? MS_DIGEST_BLAKE3 : (flags & MS_FLAG_DIGEST_BLAKE2S) ? MS_DIGEST_BLAKE2S256 : MS_DIGEST_SHA256;
   if (const char* e = getenv("MS_NTT_KMAX")) { int v = atoi(e); if (v >= 5 && v <= msntt::MAX_LOG_R) ntt_kmax = v; }
   if (const char* e = getenv("MS_NTT_FAST")) ntt_fast = atoi(e);
   if (const char* e = getenv("MS_NTT_V2")) ntt_v2 = atoi(e);

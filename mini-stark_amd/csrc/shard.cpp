@@ -102,7 +102,7 @@ void Ctx<F>::drop_rccl() {
 
 template <class F>
 int Ctx<F>::set_shard_rccl(int rank, int world, const u8* unique_id, size_t cap) {
-  if (digest != MS_DIGEST_SHA256) return fail(MS_ERR_ARG, "set_shard_rccl: sharded proofs commit with SHA-256 only (this context was created with MS_FLAG_DIGEST_BLAKE2S or MS_FLAG_DIGEST_BLAKE3)");
+  if (digest != MS_DIGEST_SHA256) return fail(MS_ERR_ARG, "set_shard_rccl: sharded proofs commit with SHA-256 only (this context was created with one of the MS_FLAG_DIGEST_* flags)");
   if (world < 1 || !is_pow2((u64)world) || rank < 0 || rank >= world) return fail(MS_ERR_ARG, "set_shard_rccl: world must be a power of two and 0 <= rank < world");
   // the old communicator and buffers go first; until the new ones are complete the context is UNSHARDED, so that a failure below
   // (no unique id, librccl missing, out of memory, ncclCommInitRank) cannot leave sh_world > 1 over freed buffers / a null callback
@@ -188,7 +188,7 @@ int Ctx<F>::rccl_selftest() {
 
 template <class F>
 int Ctx<F>::set_shard(int rank, int world, void* d_send, void* d_recv, size_t cap, ms_exchange_fn fn, void* user) {
-  if (digest != MS_DIGEST_SHA256) return fail(MS_ERR_ARG, "set_shard: sharded proofs commit with SHA-256 only (this context was created with MS_FLAG_DIGEST_BLAKE2S or MS_FLAG_DIGEST_BLAKE3)");
+  if (digest != MS_DIGEST_SHA256) return fail(MS_ERR_ARG, "set_shard: sharded proofs commit with SHA-256 only (this context was created with one of the MS_FLAG_DIGEST_* flags)");
   if (world < 1 || !is_pow2((u64)world) || rank < 0 || rank >= world) return fail(MS_ERR_ARG, "set_shard: world must be a power of two and 0 <= rank < world");
   if (world > 1 && (!d_send || !d_recv || (!fn && !shard_stub) || cap < 4096)) return fail(MS_ERR_ARG, "set_shard: exchange buffers / callback missing");
   drop_rccl();

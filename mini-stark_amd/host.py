@@ -51,7 +51,7 @@ def _host():
 
 
 def hash_bytes(digest_id: int, data: bytes) -> bytes:
-    """D(data) for an ms_digest_id by the C++ mirror's own host hashes (msh_hash): SHA-256, BLAKE2s-256, BLAKE3 (any length)."""
+    """D(data) for an ms_digest_id by the C++ mirror's own host hashes (msh_hash): SHA-256, BLAKE2s-256, BLAKE3, Keccak-256, SHA3-256 (any length)."""
     out = C.create_string_buffer(32)
     if _host().msh_hash(int(digest_id), bytes(data), len(data), out) != 0:
         raise MsError(-5, f"msh_hash: unknown digest id {digest_id}")

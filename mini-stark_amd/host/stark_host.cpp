@@ -7,7 +7,7 @@
 //                               Fri::commit_phase/query_phase src/fri.rs:64-189 (inlined: same call order)
 //   ministark::Stark::verify <- Stark::verify / Fri::verify / MerkleRoot::check_proof   src/starks.rs:171-235, src/fri.rs:191-290,
 //                               src/merkle.rs:312-338 — on the CPU, as in the reference
-//   ministark::Transcript    <- nimue Merlin                  BUILD-DEFINED stand-in: a hash chain over the context's digest (SHA-256 / BLAKE2s-256 / BLAKE3) with the
+//   ministark::Transcript    <- nimue Merlin                  BUILD-DEFINED stand-in: a hash chain over the context's digest (SHA-256 / BLAKE2s-256 / BLAKE3 / Keccak-256 / SHA3-256) with the
 //                                                             message ORDER of src/fiatshamir.rs:48-64,100-116;
 //                                                             not nimue's bytes (its source is unavailable).
 // Every field operation of the PROVER happens on the GPU inside libministark.so; prove() only moves challenges and
@@ -160,12 +160,44 @@ struct Blake3 {
   }
 };
 
+// ---- Keccak-f[1600] sponge, rate 136 bytes, 32 bytes out: Keccak-256 (domain suffix 0x01, the original padding) and SHA3-256 (0x06, FIPS 202) ------------
+struct Keccak {
+  u64 a[25]; size_t nb = 0; u8 suffix;
+  explicit Keccak(u8 suffix_ = 0x01) : suffix(suffix_) { memset(a, 0, sizeof a); }
+  static u64 rol(u64 x, int n) { return n ? (x << n) | (x >> (64 - n)) : x; }
+  void permute() {
+    static const u64 RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull, 0x000000000000808Bull, 0x0000000080000001ull,
+                               0x8000000080008081ull, 0x8000000000008009ull, 0x000000000000008Aull, 0x0000000000000088ull, 0x0000000080008009ull, 0x000000008000000Aull,
+                               0x000000008000808Bull, 0x800000000000008Bull, 0x8000000000008089ull, 0x8000000000008003ull, 0x8000000000008002ull, 0x8000000000000080ull,
+                               0x000000000000800Aull, 0x800000008000000Aull, 0x8000000080008081ull, 0x8000000000008080ull, 0x0000000080000001ull, 0x8000000080008008ull};
+    static const int RHO[25] = {0, 1, 62, 28, 27, 36, 44, 6, 55, 20, 3, 10, 43, 25, 39, 41, 45, 15, 21, 8, 18, 2, 61, 56, 14};   // lane x + 5 y
+    for (int r = 0; r < 24; r++) {
+      u64 c[5], b[25];
+      for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
+      for (int x = 0; x < 5; x++) { const u64 d = c[(x + 4) % 5] ^ rol(c[(x + 1) % 5], 1); for (int y = 0; y < 5; y++) a[x + 5 * y] ^= d; }
+      for (int y = 0; y < 5; y++) for (int x = 0; x < 5; x++) b[y + 5 * ((2 * x + 3 * y) % 5)] = rol(a[x + 5 * y], RHO[x + 5 * y]);
+      for (int y = 0; y < 5; y++) for (int x = 0; x < 5; x++) a[x + 5 * y] = b[x + 5 * y] ^ (~b[(x + 1) % 5 + 5 * y] & b[(x + 2) % 5 + 5 * y]);
+      a[0] ^= RC[r];
+    }
+  }
+  void xor_byte(size_t pos, u8 v) { a[pos >> 3] ^= (u64)v << (8 * (pos & 7)); }   // lanes are little-endian
+  void update(const void* data, size_t n) {
+    const u8* p = (const u8*)data;
+    for (size_t i = 0; i < n; i++) { xor_byte(nb++, p[i]); if (nb == 136) { permute(); nb = 0; } }
+  }
+  void finish(u8 out[32]) {   // pad10*1: the suffix behind the message, 0x80 into the block's last byte
+    xor_byte(nb, suffix); xor_byte(135, 0x80); permute();
+    for (int k = 0; k < 32; k++) out[k] = (u8)(a[k >> 3] >> (8 * (k & 7)));
+  }
+};
+
 // the `D` of the handle's context (ms_digest): one streaming hash by ms_digest_id
 struct Hasher {
-  int id; Sha256 s; Blake2s b; Blake3 b3;
-  explicit Hasher(int digest) : id(digest) {}
-  void update(const void* d, size_t n) { if (id == MS_DIGEST_BLAKE3) b3.update(d, n); else if (id == MS_DIGEST_BLAKE2S256) b.update(d, n); else s.update(d, n); }
-  void finish(u8 out[32]) { if (id == MS_DIGEST_BLAKE3) b3.finish(out); else if (id == MS_DIGEST_BLAKE2S256) b.finish(out); else s.finish(out); }
+  int id; Sha256 s; Blake2s b; Blake3 b3; Keccak k;
+  explicit Hasher(int digest) : id(digest), k(digest == MS_DIGEST_SHA3_256 ? 0x06 : 0x01) {}
+  bool keccak() const { return id == MS_DIGEST_KECCAK256 || id == MS_DIGEST_SHA3_256; }
+  void update(const void* d, size_t n) { if (keccak()) k.update(d, n); else if (id == MS_DIGEST_BLAKE3) b3.update(d, n); else if (id == MS_DIGEST_BLAKE2S256) b.update(d, n); else s.update(d, n); }
+  void finish(u8 out[32]) { if (keccak()) k.finish(out); else if (id == MS_DIGEST_BLAKE3) b3.finish(out); else if (id == MS_DIGEST_BLAKE2S256) b.finish(out); else s.finish(out); }
 };
 
 // Build-defined Fiat–Shamir hash chain (byte-identical to mini-stark_amd/stark.py::Transcript): the stand-in for `DigestBridge<D>`, over the context's digest.
@@ -686,7 +718,8 @@ int msh_cubic_rows(u64 p, size_t length, size_t w, u64 seed, u64* out, u64* scal
 }
 // D(data) for an ms_digest_id, by the hashes of this mirror (the Python mirror has no BLAKE3 of its own and calls this one): 0, or -1 for an unknown id
 int msh_hash(int digest_id, const u8* data, size_t len, u8 out[32]) {
-  if (digest_id < MS_DIGEST_SHA256 || digest_id > MS_DIGEST_BLAKE3 || !out || (!data && len)) return -1;
+  const bool known = (digest_id >= MS_DIGEST_SHA256 && digest_id <= MS_DIGEST_BLAKE3) || digest_id == MS_DIGEST_KECCAK256 || digest_id == MS_DIGEST_SHA3_256;   // (3 is unassigned)
+  if (!known || !out || (!data && len)) return -1;
   ministark::Hasher h(digest_id); if (len) h.update(data, len); h.finish(out);
   return 0;
 }

@@ -11,7 +11,7 @@ transcript and the library.
 
 Transcript: the reference uses nimue (`IOPattern`/`Merlin` over
 `DigestBridge<Sha256>`, src/fiatshamir.rs) whose source is not available here,
-so `Transcript` below is a BUILD-DEFINED hash chain (over the context's digest: SHA-256, BLAKE2s-256 or BLAKE3) that follows the
+so `Transcript` below is a BUILD-DEFINED hash chain (over the context's digest: SHA-256, BLAKE2s-256, BLAKE3, Keccak-256 or SHA3-256) that follows the
 same message ORDER (src/fiatshamir.rs:48-64,100-116) but not nimue's bytes.
 A Rust caller keeps nimue and passes the challenges in.
 """
@@ -22,7 +22,7 @@ from typing import List
 
 import numpy as np
 
-from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3
+from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
 
@@ -52,12 +52,24 @@ class _Blake3:
         return self.digest().hex()
 
 
+class _Keccak256(_Blake3):
+    """hashlib's sha3_256 is FIPS 202; Keccak-256 with the original padding (Ethereum's) is not in hashlib: the same stand-in over msh_hash."""
+    name, digest_size, block_size = "keccak256", 32, 136
+
+    def copy(self):
+        return _Keccak256(self._data)
+
+    def digest(self):
+        from .host import hash_bytes
+        return hash_bytes(DIGEST_KECCAK256, bytes(self._data))
+
+
 # ms_digest_id -> hash constructor: the D of `DigestBridge<D>` (fiatshamir.rs:23-46) is the D of the commitments
-DIGEST_HASH = {DIGEST_SHA256: hashlib.sha256, DIGEST_BLAKE2S256: _blake2s256, DIGEST_BLAKE3: _Blake3}
+DIGEST_HASH = {DIGEST_SHA256: hashlib.sha256, DIGEST_BLAKE2S256: _blake2s256, DIGEST_BLAKE3: _Blake3, DIGEST_KECCAK256: _Keccak256, DIGEST_SHA3_256: hashlib.sha3_256}
 
 
 class Transcript:
-    """Build-defined Fiat–Shamir sponge (NOT nimue): state' = D(state || tag || data), D = SHA-256 unless `digest` (an ms_digest_id) says BLAKE2s-256 or BLAKE3."""
+    """Build-defined Fiat–Shamir sponge (NOT nimue): state' = D(state || tag || data), D = SHA-256 unless `digest` (an ms_digest_id) says BLAKE2s-256, BLAKE3, Keccak-256 or SHA3-256."""
 
     def __init__(self, domsep: str, digest: int = DIGEST_SHA256):
         self.hash = DIGEST_HASH[digest]

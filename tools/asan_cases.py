@@ -77,6 +77,17 @@ for field in (0, 1):
     for lazy in (False, True):
         bc.case_length_edges(mk3, field, (6, 16) if field == 0 else (6, 24), lazy)
     bc.case_whole_proof(mk3, field, 10, 8, variants=[("fused tail", bc.ZAE | bc.B3, {"MS_FRI_TAIL_MAX": "65536"}), ("latency", bc.ZAE | bc.B3 | bc.LATENCY, None)])
+# Keccak-256 / SHA3-256 contexts (MS_FLAG_DIGEST_KECCAK256 / MS_FLAG_DIGEST_SHA3_256): every tree shape (inner nodes of many rate blocks, the wide leaf group), the message
+# lengths around the 136-byte rate through both leaf buffers, a whole proof through the fused tail and in latency mode
+import keccak_cases as kc
+for field in (0, 1):
+    for d in kc.DIGESTS:
+        k = mk3(field, kc.ZAE | kc.FLAG[d])
+        for shape in kc.MERKLE_SHAPES:
+            kc.case_every_node(k, d, field, *shape, True)
+    for lazy in (False, True):
+        kc.case_length_edges(mk3, 4, field, (6, 16) if field == 0 else (6, 28), lazy)
+    kc.case_whole_proof(mk3, 4, field, 8, 8, variants=kc.tail_variants(4)[::2])
 from mini_stark_amd.host import build_host_library
 build_host_library()
 sys.path.insert(0, os.path.join(ROOT, 'tests'))

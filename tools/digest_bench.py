@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""SHA-256 against BLAKE2s-256 (MS_FLAG_DIGEST_BLAKE2S) against BLAKE3 (MS_FLAG_DIGEST_BLAKE3) on the headline shape, in ONE process on one GPU: 2^20-row
-Goldilocks Fibonacci AIR, blowup 8, traces resident in HBM, 8 proofs in flight (bench.py's Lanes), the legs alternated SHA-256 / BLAKE2s / BLAKE3 / SHA-256 / ... -
+"""SHA-256 against BLAKE2s-256 (MS_FLAG_DIGEST_BLAKE2S), BLAKE3 (MS_FLAG_DIGEST_BLAKE3), Keccak-256 (MS_FLAG_DIGEST_KECCAK256) and SHA3-256
+(MS_FLAG_DIGEST_SHA3_256) on the headline shape, in ONE process on one GPU: 2^20-row Goldilocks Fibonacci AIR, blowup 8, traces resident in HBM, 8 proofs in
+flight (bench.py's Lanes), the legs alternated SHA-256 / BLAKE2s / BLAKE3 / Keccak-256 / SHA3-256 / SHA-256 / ... -
 box-to-box spread is larger than the differences may be, so only the paired rates of one run mean anything.  Then one proof alone with MS_FLAG_LATENCY for each digest, and one more
 (untimed) proof per digest with every launch bracketed by HIP events (ms_profile_begin / ms_profile_end): kernel milliseconds per proof by class.
 Prints one JSON line.
@@ -34,8 +35,9 @@ def main():
     import mini_stark_amd as ms
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    names = {"sha256": ms.FLAG_ZERO_DISPLAY_EMPTY, "blake2s": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_BLAKE2S, "blake3": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_BLAKE3}
-    ids = {"sha256": ms.DIGEST_SHA256, "blake2s": ms.DIGEST_BLAKE2S256, "blake3": ms.DIGEST_BLAKE3}
+    names = {"sha256": ms.FLAG_ZERO_DISPLAY_EMPTY, "blake2s": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_BLAKE2S, "blake3": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_BLAKE3,
+             "keccak256": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_KECCAK256, "sha3_256": ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_DIGEST_SHA3_256}
+    ids = {"sha256": ms.DIGEST_SHA256, "blake2s": ms.DIGEST_BLAKE2S256, "blake3": ms.DIGEST_BLAKE3, "keccak256": ms.DIGEST_KECCAK256, "sha3_256": ms.DIGEST_SHA3_256}
     grp = OneRank()
     lanes = {k: bench.Lanes(0, args.log_rows, args.blowup, args.inflight, 0, dev, flags=f) for k, f in names.items()}
     for k, ln in lanes.items():
@@ -65,8 +67,10 @@ def main():
         kernel_ms[k]["total"] = round(sum(v for n, v in kernel_ms[k].items() if n != "launches"), 4)
         ln.close()
     print(json.dumps({"metric": "digest_bench", "workload": f"Fibonacci AIR, Goldilocks, 2^{args.log_rows} rows, blowup {args.blowup}, traces resident, {args.inflight} proofs in flight, "
-                      f"{args.steps} steps per leg, legs alternated sha256 / blake2s / blake3 x {args.passes}", "unit": "proofs/s",
-                      "sha256": mean["sha256"], "blake2s": mean["blake2s"], "blake3": mean["blake3"], "ratio_blake2s_over_sha256": mean["blake2s"] / mean["sha256"],
+                      f"{args.steps} steps per leg, legs alternated sha256 / blake2s / blake3 / keccak256 / sha3_256 x {args.passes}", "unit": "proofs/s",
+                      "sha256": mean["sha256"], "blake2s": mean["blake2s"], "blake3": mean["blake3"], "keccak256": mean["keccak256"], "sha3_256": mean["sha3_256"],
+                      "ratio_keccak256_over_sha256": mean["keccak256"] / mean["sha256"], "ratio_sha3_256_over_sha256": mean["sha3_256"] / mean["sha256"],
+                      "single_proof_ratio_keccak256_over_sha256": single["keccak256"] / single["sha256"], "ratio_blake2s_over_sha256": mean["blake2s"] / mean["sha256"],
                       "ratio_blake3_over_sha256": mean["blake3"] / mean["sha256"], "ratio_blake3_over_blake2s": mean["blake3"] / mean["blake2s"], "passes": rates,
                       "ms_single_proof_latency_flag": single, "single_proof_ratio_sha256_over_blake2s": single["sha256"] / single["blake2s"],
                       "single_proof_ratio_sha256_over_blake3": single["sha256"] / single["blake3"], "single_proof_ratio_blake2s_over_blake3": single["blake2s"] / single["blake3"],
