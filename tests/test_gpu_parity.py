@@ -217,7 +217,8 @@ def test_merkle_prove_by_value(mk, field, ext, lpn, n):
     pc.case_merkle_prove(mk, field, n, ext, lpn)
 
 
-@pytest.mark.parametrize("world,field,log_n,mode", [(2, 0, 12, "gpu"), (4, 1, 11, "gpu"), (2, 0, 16, "gpu"), (4, 0, 15, "gpu,root-only"), (2, 1, 13, "gpu,base-z")])
+@pytest.mark.parametrize("world,field,log_n,mode", [(2, 0, 12, "gpu"), (4, 1, 11, "gpu"), (2, 0, 16, "gpu"), (4, 0, 15, "gpu,root-only"), (2, 1, 13, "gpu,base-z"),
+                                                   (2, 0, 12, "gpu,low-degree")])   # trace columns of degree N/2 + 2: half-empty coefficient ranges
 def test_sharded_proof_on_gpu(world, field, log_n, mode):
     """ms_set_shard on the real HIP kernels: `world` ranks share this box's GPU (gloo, payloads staged through host
     memory), each proves its share of ONE proof; every rank checks all outputs against the oracle (tests/shard_worker.py)."""

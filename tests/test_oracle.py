@@ -184,11 +184,14 @@ def test_intt_property_air_rs_306():
             assert acc == int(t[i, c])
 
 
-def run_both(field, N, blowup, nq_fri, seed, zae=1):
-    """Drives oracle Session and PyProver with identical inputs; returns per-stage outputs."""
+def run_both(field, N, blowup, nq_fri, seed, zae=1, trace=None, challenges=None, rounds=None):
+    """Drives oracle Session and PyProver with identical inputs; returns per-stage outputs.  `trace`: another N x 3 trace than the Fibonacci one; `challenges`:
+    explicit values (structured_cases.random_challenges' keys: shift, r, ood, per-round z and alpha, betas) instead of the draws from SplitMix64(seed); `rounds`:
+    another FRI round count than the config's."""
     p, e = MODULUS[field], EXT[field]
     rng = SplitMix64(seed)
-    t = fibonacci_trace(field, N)
+    ch = challenges or {}
+    t = fibonacci_trace(field, N) if trace is None else trace
     omega = orc.root_of_unity(field, N)
     cl = fibonacci_closures(field, N, omega)
     o = orc.Session(field, zae)
@@ -205,29 +208,37 @@ def run_both(field, N, blowup, nq_fri, seed, zae=1):
     for i in range(6):
         out.append((list(map(int, o.poly_read(i))), y.polys[i]))
     shift = rng.nonzero(p)
+    shift = ch.get("shift", shift)
     rc, root = o.lde_commit(blowup, shift, 6)
     assert rc == 0
     out.append((root, y.lde_commit(blowup, shift, 6)))
     out.append((o.lde_read().tolist(), y.lde))
     r = rng.field(p)
+    r = ch.get("r", r)
     assert o.mix(r) == 0
     y.mix(r)
     out.append((list(map(int, o.validity_read())), y.validity))
     zs = [[rng.field(p) for _ in range(e)] for _ in range(2)]
+    zs = ch.get("ood", zs)
     rc, ev = o.eval_ext(np.array(zs, dtype=np.uint64))
     assert rc == 0
     out.append((ev.tolist(), [[list(v) for v in row] for row in y.eval_ext(zs)]))
-    rounds = int(L.or_ceil_log2_k(C.c_uint64((N - 1) * blowup + 1), C.c_uint64(2)))
+    if rounds is None:
+        rounds = int(L.or_ceil_log2_k(C.c_uint64((N - 1) * blowup + 1), C.c_uint64(2)))
     rc, root = o.fri_begin(blowup, rounds)
     assert rc == 0
     out.append((root, y.fri_begin(blowup, rounds)))
-    for _ in range(1, rounds):
+    for i in range(1, rounds):
         z = [rng.field(p) for _ in range(e)]
+        if "z" in ch:
+            z = ch["z"][(i - 1) % len(ch["z"])]
         rc, B = o.fri_deep(z)
         assert rc == 0
         By = y.fri_deep(z)
         out.append((B.reshape(2, e).tolist(), [list(b) for b in By]))
         al = [rng.field(p) for _ in range(e)]
+        if "alpha" in ch:
+            al = ch["alpha"][(i - 1) % len(ch["alpha"])]
         rc, root = o.fri_fold_commit(al)
         assert rc == 0
         out.append((root, y.fri_fold_commit(al)))
@@ -235,6 +246,7 @@ def run_both(field, N, blowup, nq_fri, seed, zae=1):
         out.append((o.fri_round_poly(i).tolist(), [list(c) for c in y.rounds[i]["poly"]]))
         out.append((o.fri_round_info(i)[1], y.rounds[i]["D"]))
     betas = [rng.next() for _ in range(nq_fri)] + [3, 2 * N * blowup]  # small + wrap-around cases (Q6)
+    betas = ch.get("betas", betas)
     rc, proof = o.fri_query(betas)
     assert rc == 0
     out.append((proof, y.serialise_fri(y.fri_query(betas))))
@@ -245,6 +257,22 @@ def run_both(field, N, blowup, nq_fri, seed, zae=1):
 def test_prove_oracle_vs_bigint(field, N, blowup):
     for i, (a, b) in enumerate(run_both(field, N, blowup, 2, seed=1234 + N)):
         assert a == b, f"stage output {i} differs"
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("name", ["zero", "const", "deg1", "len5", "half+3", "even", "odd", "mono_top", "gap"])
+def test_prove_oracle_vs_bigint_structured(field, name):
+    """The oracle against the big-integer restatement where the validity polynomial is low-degree, sparse or zero (tests/structured_cases.py) - trimmed lengths,
+    the domain sizes they give, ragged even / odd halves, a fold that vanishes, equal values under two leaves - with random alpha, alpha = 0 and base-field z."""
+    import structured_cases as sc
+    N, blowup = 16, 4
+    trace = sc.trace_from_support(field, N, sc.SUPPORTS[name](N), seed=50 + field)
+    for mode in sc.MODES:
+        ch = sc.random_challenges(field, seed=60 + sc.MODES.index(mode), mode=mode)
+        _, D0 = sc.oracle_round0(field, trace, blowup, ch["r"])
+        ch["betas"] = ch["betas"][:1] + [0, 3, D0 // 2 + 1, D0, 2 * N * blowup]
+        for i, (a, b) in enumerate(run_both(field, N, blowup, 0, seed=1, trace=trace, challenges=ch, rounds=D0.bit_length() - 1)):
+            assert a == b, f"{mode}: stage output {i} differs"
 
 
 def test_fri_roundtrip_fri_rs_426():
