@@ -68,6 +68,8 @@ extern "C" {
     pub fn ms_mix(ctx: *mut ms_ctx, r: u64) -> c_int;
     pub fn ms_validity_read(ctx: *mut ms_ctx, out: *mut u64) -> c_int;
     pub fn ms_mix_cubic(ctx: *mut ms_ctx, r: u64, spec: *const c_int, s: *const u64, ncons: c_int) -> c_int;
+    pub fn ms_mix_terms(ctx: *mut ms_ctx, r: u64, ncons: c_int, term_begin: *const u32, coef: *const u64, fac_begin: *const u32, fac_poly: *const u32,
+                        fac_row: *const u32, nexempt: c_int) -> c_int;
     pub fn ms_validity_len(ctx: *const ms_ctx) -> usize;
     pub fn ms_eval_ext(ctx: *mut ms_ctx, z: *const u64, q: c_int, out: *mut u64) -> c_int;
     // ---- Fri::prove stages (src/fri.rs:53-189)

@@ -72,6 +72,28 @@ impl Gpu {
     }
     /// starks.rs:108-119: validity = sum_i r^i f_i
     pub fn mix(&mut self, r: u64) -> Result<(), GpuError> { self.check(unsafe { ms_mix(self.ctx, r) }) }
+    /// BUILD-DEFINED (no reference counterpart): polynomial constraints of any degree in place of `mix`, with the true quotient by x^N - 1.
+    /// `constraints[t]` = the terms of constraint t, each `(coef, [(poly, row), ..])`: coef * prod P_poly(w^row x); the last `nexempt` rows are exempt.
+    /// Returns the length of the validity polynomial (ms_validity_len: N * next_pow2(max(1, d - 1)) for nexempt <= d - 1).
+    pub fn mix_terms(&mut self, r: u64, constraints: &[Vec<(u64, Vec<(u32, u32)>)>], nexempt: usize) -> Result<usize, GpuError> {
+        let (mut term_begin, mut coef, mut fac_begin, mut fac_poly, mut fac_row) = (vec![0u32], Vec::new(), vec![0u32], Vec::new(), Vec::new());
+        for terms in constraints {
+            for (c, factors) in terms {
+                coef.push(*c);
+                for (poly, row) in factors {
+                    fac_poly.push(*poly);
+                    fac_row.push(*row);
+                }
+                fac_begin.push(fac_poly.len() as u32);
+            }
+            term_begin.push(coef.len() as u32);
+        }
+        // (an empty Vec's pointer is dangling but non-null, which is all the library asks of an array it reads nothing from)
+        self.check(unsafe {
+            ms_mix_terms(self.ctx, r, constraints.len() as i32, term_begin.as_ptr(), coef.as_ptr(), fac_begin.as_ptr(), fac_poly.as_ptr(), fac_row.as_ptr(), nexempt as i32)
+        })?;
+        Ok(unsafe { ms_validity_len(self.ctx) })
+    }
     /// starks.rs:124-151: out[t] = (f_0(z_t), .., f_{c-1}(z_t), validity(z_t)), E limbs each
     pub fn eval_ext(&mut self, z_limbs: &[u64], c: usize) -> Result<Vec<u64>, GpuError> {
         let q = z_limbs.len() / self.ext;

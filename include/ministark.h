@@ -182,7 +182,7 @@ int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_
 int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c */);
 /* 1.3  validity = sum_i r^i f_i (remainder of divide_by_vanishing_poly; quirk Q1).  starks.rs:108-119. */
 int ms_mix(ms_ctx* ctx, uint64_t r);
-int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, or 2N after ms_mix_cubic */);
+int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms */);
 /* BUILD-DEFINED, no reference counterpart (BASELINE configs[4] "degree-3 constraints"; the reference cannot express them: its validity polynomial is the
  * remainder of divide_by_vanishing_poly, starks.rs:118-119, quirk Q1).  In place of ms_mix, with the TRUE quotient:
  *   C_t(x) = P_j(w x) - P_a(x) P_b(x) P_c(x) - s_t P_d(x)         spec[t] = {j, a, b, c, d} (polynomial indices), w = the trace domain's generator
@@ -190,6 +190,31 @@ int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, or 2
  * Evaluated on the LDE domain of the preceding ms_lde_commit (blowup >= 4), interpolated back.  ms_eval_ext / ms_validity_read / ms_fri_begin then work on the
  * 2N-coefficient validity polynomial.  Checked against a big-integer restatement in the tests; self-verified at full size. */
 int ms_mix_cubic(ms_ctx* ctx, uint64_t r, const int* spec /* [ncons][5] */, const uint64_t* s /* [ncons] */, int ncons);
+/* BUILD-DEFINED, no reference counterpart: polynomial transition constraints of ANY degree, in place of ms_mix / ms_mix_cubic, with the TRUE quotient.  The
+ * constraint system is a sum of monomials over the polynomials the context holds (trace columns and whatever ms_polys_lincomb / ms_polys_append added: indices
+ * < ms_polys_count), each factor at a row offset; w = the trace domain's generator:
+ *   C_t(x)      = sum_{m in terms(t)} coef_m * prod_{f in factors(m)} P_{poly_f}(w^{row_f} x)          (a term without factors is the constant coef_m)
+ *   validity(x) = (sum_t r^t C_t(x)) * prod_{k=1..nexempt} (x - w^(N-k)) / (x^N - 1)
+ * i.e. every constraint must hold on the rows 0 .. N-1-nexempt; the last `nexempt` rows are exempt for ALL constraints.  Boundary constraints and per-constraint
+ * exemptions are not part of this stage.  The program is passed as CSR arrays: the terms of constraint t are term_begin[t] .. term_begin[t+1]-1, the factors of
+ * term m are fac_begin[m] .. fac_begin[m+1]-1 (both arrays start at 0 and do not decrease).
+ * With d = the most factors of any term, VL = N * next_pow2(max(1, d - 1)) - or, when nexempt > d - 1, next_pow2 of the ceil(((d - 1) N - d + nexempt + 1) / N)
+ * slots the quotient's (d - 1) N - d + nexempt + 1 coefficients then need: afterwards ms_validity_len is VL, the validity polynomial has VL coefficients (zero
+ * above its degree) and ms_validity_read / ms_eval_ext / ms_fri_begin .. ms_fri_query work on it as after ms_mix_cubic.  Evaluated pointwise on the LDE domain of
+ * the preceding ms_lde_commit (L = blowup * N points), interpolated back.
+ *   MS_ERR_STATE  called before ms_lde_commit; the LDE of the context is sharded over ranks.
+ *   MS_ERR_ARG    a null array; ncons outside 1..4096; more than 65536 terms; a term with more than 8 factors; no term with a factor (d = 0); term_begin / fac_begin
+ *                 not starting at 0 or decreasing; a polynomial index >= ms_polys_count; a row offset >= N; a coefficient or r >= p; nexempt outside 0..16.
+ *   MS_ERR_SHAPE  the LDE domain cannot decide exactness: needs d (N - 1) + nexempt < L and VL + N <= L (for d = 3, nexempt = 1: blowup >= 4);
+ *                 the LDE coset meets the trace domain (shift^N is a blowup-th root of unity);
+ *                 the division is not exact: a constraint does not hold on a non-exempt row.
+ * Everything but the last is decided before anything is launched; after any refusal the context is usable as if the call had not been made (a validity
+ * polynomial of an earlier ms_mix on the same LDE may have to be recomputed).  Checked against a big-integer restatement of this definition, bit for bit
+ * against ms_mix_cubic on the specs that entry can express, and by the DEEP-ALI identity at out-of-domain points (tests/test_terms_*.py);
+ * msh_terms_expected_validity (ministark_host.h) is the verifying side's evaluation of the same program. */
+int ms_mix_terms(ms_ctx* ctx, uint64_t r, int ncons, const uint32_t* term_begin /* ncons + 1 */, const uint64_t* coef /* nterms, canonical */,
+                 const uint32_t* fac_begin /* nterms + 1 */, const uint32_t* fac_poly /* nfacs: polynomial index */,
+                 const uint32_t* fac_row /* nfacs: row offset, 0 <= row < N */, int nexempt /* 0..16 */);
 size_t ms_validity_len(const ms_ctx* ctx);
 /* 2.   DEEP-ALI: out[t][i] = f_i(z_t) for the c constraint polys, out[t][c] = validity(z_t);
  *      z: q*E limbs, out: q*(c+1)*E limbs.  starks.rs:124-151, field.rs:23-32. */

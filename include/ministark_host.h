@@ -76,6 +76,15 @@ int msh_stark_verify_mssp(const msh_stark* h, const uint64_t* constrains, size_t
 int msh_fri_proof_parse(const uint8_t* blob, size_t len, uint32_t e, uint32_t windows, uint32_t nq, msh_fri_query_view* out, size_t cap);
 /* D(data) by this library's own host implementation of an ms_digest_id (SHA-256, BLAKE2s-256, BLAKE3 with its chunk tree, Keccak-256, SHA3-256: any length): 0, -1 for an unknown id (3 is unassigned) */
 int msh_hash(int digest_id, const uint8_t* data, size_t len, uint8_t out[32]);
+/* The verifying side of ms_mix_terms (ministark.h; build-defined, no reference counterpart): the value validity(z) must have at an extension point z (E limbs),
+ *   (sum_t r^t C_t(z)) * prod_{k=1..nexempt} (z - w^(N-k)) / (z^N - 1),  C_t(z) = sum_m coef_m * prod_f opened[k(row_f)][poly_f],
+ * from the same CSR program and the opened values opened[k][j] = P_j(w^rows[k] z): E limbs each, row k at opened + k * row_stride (u64 words), polynomial j at
+ * + j * E - with rows[k] the offsets the program touches, the output of ms_eval_ext at the points w^rows[k] z is this layout with row_stride = (c + 1) * E.
+ * Writes E limbs to out.  MS_OK; MS_ERR_ARG for a null argument, a malformed program (the conditions of ms_mix_terms; a polynomial index >= npolys) or a
+ * non-canonical element; MS_ERR_OUT_OF_RANGE when the program uses a row that `rows` does not list; MS_ERR_SHAPE when z^N = 1. */
+int msh_terms_expected_validity(int field, uint64_t r, int ncons, const uint32_t* term_begin, const uint64_t* coef, const uint32_t* fac_begin, const uint32_t* fac_poly,
+                                const uint32_t* fac_row, int nexempt, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows, const uint64_t* opened,
+                                size_t row_stride, uint32_t npolys, uint64_t* out);
 /* synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic): col_j[i+1] = col_j[i] col_{j+1}[i] col_{j+2}[i] + s_j col_{j+3}[i]; length x w row-major, w scalars */
 int msh_cubic_rows(uint64_t p, size_t length, size_t w, uint64_t seed, uint64_t* out, uint64_t* scalars);
 /* synthetic Fibonacci-AIR trace of the benchmark workload (N x 3 row-major) */

@@ -78,6 +78,27 @@ def _u64(a):
     return a, a.ctypes.data_as(_u64p)
 
 
+def flatten_terms(constraints):
+    """The CSR arrays of ms_mix_terms from `constraints` = [[(coef, [(poly, row), ...]), ...], ...] (one list of terms per constraint; a term with an empty
+    factor list is a constant): (term_begin, coef, fac_begin, fac_poly, fac_row) as contiguous numpy arrays."""
+    term_begin, coef, fac_begin, fac_poly, fac_row = [0], [], [0], [], []
+    for terms in constraints:
+        for c, factors in terms:
+            coef.append(int(c))
+            for poly, row in factors:
+                fac_poly.append(int(poly))
+                fac_row.append(int(row))
+            fac_begin.append(len(fac_poly))
+        term_begin.append(len(coef))
+    return (np.array(term_begin, dtype=np.uint32), np.array(coef, dtype=np.uint64), np.array(fac_begin, dtype=np.uint32),
+            np.array(fac_poly, dtype=np.uint32), np.array(fac_row, dtype=np.uint32))
+
+
+def terms_rows(constraints):
+    """The row offsets a term program touches, ascending: the verifier needs P_j(w^k z) for every such k, i.e. ms_eval_ext at the points w^k z."""
+    return sorted({int(row) for terms in constraints for _, factors in terms for _, row in factors})
+
+
 class Context:
     """One ms_ctx: a prover session on one GPU (include/ministark.h)."""
 
@@ -261,6 +282,16 @@ class Context:
         sp = np.ascontiguousarray(spec, dtype=np.int32).reshape(-1, 5)
         sc, scp = _u64(scalars)
         return self.L.ms_mix_cubic(self.h, C.c_uint64(r), sp.ctypes.data_as(C.POINTER(C.c_int)), scp, C.c_int(len(sp)))
+
+    def mix_terms(self, r, constraints, nexempt):
+        """ms_mix_terms (BUILD-DEFINED composition of any degree with the true quotient; include/ministark.h): constraints = [[(coef, [(poly, row), ...]), ...], ...],
+        or the CSR arrays themselves (the 5-tuple flatten_terms returns)."""
+        csr = constraints if isinstance(constraints, tuple) and len(constraints) == 5 and isinstance(constraints[0], np.ndarray) else flatten_terms(constraints)
+        tb, cf, fb, fp, fr = csr
+        u32p = C.POINTER(C.c_uint32)
+        # (an empty numpy array still has a valid, non-null data pointer)
+        return self.L.ms_mix_terms(self.h, C.c_uint64(r), C.c_int(len(tb) - 1), tb.ctypes.data_as(u32p), cf.ctypes.data_as(_u64p), fb.ctypes.data_as(u32p),
+                                   fp.ctypes.data_as(u32p), fr.ctypes.data_as(u32p), C.c_int(nexempt))
 
     def validity_read(self):
         self.L.ms_validity_len.restype = C.c_size_t

@@ -1,5 +1,5 @@
 // air_stages.cpp — constraint columns by linear provenance, coset LDE + commitment (starks.rs:80-95), constraint mixing (starks.rs:108-119; build-defined
-// ms_mix_cubic), DEEP-ALI evaluations (starks.rs:124-151).
+// ms_mix_cubic and ms_mix_terms), DEEP-ALI evaluations (starks.rs:124-151).
 #include "ctx.hpp"
 
 namespace msctx {
@@ -268,6 +268,94 @@ int Ctx<F>::mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) {
   return MS_OK;
 }
 
+// Build-defined composition of any degree (include/ministark.h): the constraints as sums of monomials over the polynomials, factors at row offsets, with the true
+// quotient by x^N - 1.  Same sequence as mix_cubic with 2N replaced by VL = N * next_pow2(slots), slots = max(1, d - 1) (one more when nexempt > d - 1), d = the most factors of any term.  Everything that can be
+// refused is refused before the first launch, except the exactness of the division, which only the interpolant shows; nothing of the session changes before that.
+template <class F>
+int Ctx<F>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) {
+  if (!have_lde) return fail(MS_ERR_STATE, "mix_terms before lde_commit");
+  if (lde_ts.sharded) return fail(MS_ERR_STATE, "mix_terms: the LDE of a sharded proof is distributed over the ranks");
+  if (!term_begin || !coef || !fac_begin || !fac_poly || !fac_row) return fail(MS_ERR_ARG, "mix_terms: null array");
+  if (ncons < 1 || ncons > 4096 || r >= F::P || nexempt < 0 || nexempt > mspoly::TERMS_MAX_EXEMPT) return fail(MS_ERR_ARG, "mix_terms arguments");
+  if (term_begin[0] != 0) return fail(MS_ERR_ARG, "mix_terms: term_begin[0] must be 0");
+  for (int t = 0; t < ncons; t++) if (term_begin[t + 1] < term_begin[t] || term_begin[t + 1] > 65536) return fail(MS_ERR_ARG, "mix_terms: term_begin not monotone, or more than 65536 terms");
+  const u32 nterms = term_begin[ncons];
+  if (fac_begin[0] != 0) return fail(MS_ERR_ARG, "mix_terms: fac_begin[0] must be 0");
+  u32 d = 0;
+  for (u32 m = 0; m < nterms; m++) {
+    if (fac_begin[m + 1] < fac_begin[m]) return fail(MS_ERR_ARG, "mix_terms: fac_begin not monotone");
+    const u32 nf = fac_begin[m + 1] - fac_begin[m];
+    if (nf > (u32)mspoly::TERMS_MAX_FACTORS) return fail(MS_ERR_ARG, "mix_terms: a term with more than 8 factors");
+    if (coef[m] >= F::P) return fail(MS_ERR_ARG, "mix_terms: coefficient not canonical");
+    if (nf > d) d = nf;
+  }
+  if (d == 0) return fail(MS_ERR_ARG, "mix_terms: no term has a factor (d = 0)");
+  const u32 nfacs = fac_begin[nterms];
+  const size_t c = lde_c;
+  for (u32 f = 0; f < nfacs; f++) if ((size_t)fac_poly[f] >= c || (size_t)fac_row[f] >= N) return fail(MS_ERR_ARG, "mix_terms: polynomial index or row offset out of range");
+  // the quotient has at most (d - 1) N - d + nexempt + 1 coefficients: d - 1 slots of N, one more when nexempt > d - 1
+  const size_t need = (size_t)(d - 1) * N + (size_t)nexempt + 1 - d, need_slots = (need + N - 1) / N;
+  size_t slots = d > 1 ? d - 1 : 1; if (need_slots > slots) slots = need_slots;
+  size_t vmul = 1; while (vmul < slots) vmul <<= 1;
+  const size_t VL = N * vmul;
+  // the size-L interpolant I of the pointwise quotient satisfies I (x^N - 1) = numerator on L points: with both sides of degree < L, "I has at most VL coefficients"
+  // is "the division is exact"
+  if (!((size_t)d * (N - 1) + (size_t)nexempt < L) || VL + N > L) return fail(MS_ERR_SHAPE, "mix_terms: the LDE domain is too small to decide exactness (need d (N - 1) + nexempt < L and VL + N <= L)");
+  typedef mspoly::TermRec<F> TR;
+  typedef mspoly::TermFac TF;
+  typedef mspoly::ComposeTermsKernel<F> CK_;
+  const int logL = ctz64(L), logN = ctz64(N);
+  const T gL = f_root_of_unity<F>(logL), wN = f_root_of_unity<F>(logN), sh = F::from_u64(lde_shift);
+  // x^N - 1 on the coset: shift^N * zeta^(i mod blowup) - 1, zeta = g_L^N
+  const T shN = f_pow<F>(sh, (u64)N), zeta = f_pow<F>(gL, (u64)N);
+  std::vector<T> dinv(blowup);
+  { T z = F::from_u64(1);
+    for (size_t k = 0; k < blowup; k++) { const T den = F::sub(F::mul(shN, z), F::from_u64(1)); if (den == 0) return fail(MS_ERR_SHAPE, "mix_terms: the LDE coset meets the trace domain (shift^N is a blowup-th root of unity)"); dinv[k] = f_inv<F>(den); z = F::mul(z, zeta); } }
+  // the device table: [terms | factors | exemption roots | den_inv], r^t folded into the coefficients of constraint t's terms
+  const size_t off_f = ((size_t)nterms * sizeof(TR) + 15) & ~(size_t)15, off_x = (off_f + (size_t)nfacs * sizeof(TF) + 15) & ~(size_t)15;
+  const size_t off_d = off_x + mspoly::TERMS_MAX_EXEMPT * sizeof(T), tab_bytes = off_d + dinv.size() * sizeof(T);
+  std::vector<u8> tab(tab_bytes, 0);
+  { TR* ht = reinterpret_cast<TR*>(tab.data()); TF* hf = reinterpret_cast<TF*>(tab.data() + off_f); T* hx = reinterpret_cast<T*>(tab.data() + off_x);
+    T rp = F::from_u64(1);
+    for (int t = 0; t < ncons; t++) {
+      for (u32 m = term_begin[t]; m < term_begin[t + 1]; m++) { ht[m].coef = F::mul(rp, F::from_u64(coef[m])); ht[m].nfac = fac_begin[m + 1] - fac_begin[m]; }
+      rp = F::mul(rp, F::from_u64(r));
+    }
+    for (u32 f = 0; f < nfacs; f++) { hf[f].poly = fac_poly[f]; hf[f].rowoff = (u32)((size_t)fac_row[f] * blowup); }
+    T wk = f_inv<F>(wN), wi = wk;                                // w^(N-k) = w^-k
+    for (int k = 0; k < nexempt; k++) { hx[k] = wk; wk = F::mul(wk, wi); }
+    memcpy(tab.data() + off_d, dinv.data(), dinv.size() * sizeof(T)); }
+  if (lde_cols_virtual) { RQ(lincomb_linear_columns(d_lde.as<T>(), lde_col_stride, lde_col_len)); lde_cols_virtual = false; }
+  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(tab_bytes + 64)) return fail(MS_ERR_NOMEM, "mix_terms buffers");
+  u8* ht;
+  RQ(tabs_host(tab_bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
+  memcpy(ht, tab.data(), tab_bytes);
+  CK(msrt::h2d(d_tabs.p, ht, tab_bytes, stream));
+  typename CK_::Params cp;
+  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.nterms = nterms; cp.nexempt = (u32)nexempt;
+  cp.terms = d_tabs.as<TR>(); cp.facs = reinterpret_cast<const TF*>(d_tabs.as<u8>() + off_f);
+  cp.ex_roots = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_x); cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_d);
+  cp.shift = sh; cp.gL = gL; cp.gL_step = f_pow<F>(gL, (u64)CK_::THREADS); cp.out = d_cubic.as<T>();
+  next_bytes = (double)(nfacs + 1) * L * sizeof(T);
+  CK(run<CK_>(K_MIX_TERMS, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
+  // evaluations on shift * <g_L>  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k
+  T* cf = d_cubic.as<T>() + L;
+  RQ(ntt_run(logL, true, d_cubic.as<T>(), L, L, cf, L, 1));
+  if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
+  RQ(ensure_polys(npolys + VL / N));
+  unsigned long long* dres;
+  RQ(degree_launch1(cf, L, &dres));
+  CK(msrt::d2h(pinned, dres, 8, stream));
+  CK(msrt::sync(stream));
+  if (*reinterpret_cast<unsigned long long*>(pinned) > VL) return fail(MS_ERR_SHAPE, "mix_terms: the constraints do not vanish on the non-exempt rows (the quotient by x^N - 1 is not a polynomial of VL coefficients)");
+  const size_t ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
+  const T shi = f_inv<F>(sh);
+  RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, shi, 1));
+  validity_ncoef = ncoef; validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
+  have_validity = true; validity_len = VL; nrounds_done = 0;
+  return MS_OK;
+}
+
 // trimmed length of a base-field coefficient vector
 template <class F>
 int Ctx<F>::degree_launch1(const T* poly, size_t n, unsigned long long** dres_out) {
@@ -433,6 +521,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   template int Ctx<FF>::lde_read(u64* out); \
   template int Ctx<FF>::mix(u64 r); \
   template int Ctx<FF>::mix_cubic(u64 r, const int* spec, const u64* sc, int ncons); \
+  template int Ctx<FF>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt); \
   template int Ctx<FF>::degree_launch1(const Ctx<FF>::T* poly, size_t n, unsigned long long** dres_out); \
   template int Ctx<FF>::validity_read(u64* out); \
   template int Ctx<FF>::shard_combine_launch(size_t off, size_t rank_stride, u32 n, const Ctx<FF>::XE& zstep, Ctx<FF>::T* out); \

@@ -796,6 +796,64 @@ template <class F> struct CubicComposeKernel {
   }
 };
 
+// ---------------------------------------------------------------- build-defined composition of ANY degree (ms_mix_terms)
+// The constraint system as a sum of monomials over the context's polynomials, factors at row offsets (include/ministark.h):
+//   validity(x) = (sum_m c'_m prod_f P_poly_f(w^row_f x)) prod_{k=1..nexempt} (x - w^(N-k)) / (x^N - 1),   c'_m = r^t coef_m for a term of constraint t
+// on the committed LDE domain, like CubicComposeKernel: P(w^row x_i) is the value row * blowup rows further on (mod L), x^N - 1 comes from the table of `blowup` inverses.
+// The program is ONE device table, the same for every lane: terms (c', number of factors) in order, their factors (poly, row * blowup) in the same order.  A thread
+// owns ITEMS strided points and walks the program ONCE for all of them - a term's coefficient and factor records are read once per ITEMS points, the ITEMS
+// column loads of a factor are independent and in flight together - and stores only behind the walk: no store can precede a program read, the loop counters
+// are uniform, so the program reads are scalar loads.  Column loads are coalesced along i; the index is masked by L - 1 (a power of two), so it is in
+// bounds even for the points past L of a domain shorter than a workgroup's share, which are computed and dropped.  No LDS, no atomics, no cross-workgroup traffic.
+template <class F> struct TermRec { typename F::T coef; u32 nfac; };
+struct TermFac { u32 poly, rowoff; };
+constexpr int TERMS_MAX_EXEMPT = 16, TERMS_MAX_FACTORS = 8;
+template <class F> struct ComposeTermsKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int ITEMS = 8;
+  struct Params { const T* lde; size_t L; u32 blowup, nterms, nexempt; const TermRec<F>* terms; const TermFac* facs; const T* ex_roots /* w^(N-k), k = 1 .. nexempt */;
+                  const T* den_inv; T shift, gL, gL_step /* gL^THREADS */; T* out; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
+    const size_t i0 = (size_t)bx * (THREADS * ITEMS) + tid;
+    if (i0 >= p.L) return;
+    const size_t mask = p.L - 1;
+    T acc[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) acc[it] = 0;
+    u32 f = 0;
+    for (u32 m = 0; m < p.nterms; m++) {
+      const TermRec<F> tr = p.terms[m];
+      T v[ITEMS];
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) v[it] = tr.coef;
+      for (u32 k = 0; k < tr.nfac; k++, f++) {
+        const TermFac fc = p.facs[f];
+        const T* col = p.lde + (size_t)fc.poly * p.L;
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) v[it] = F::mul(v[it], col[(i0 + (size_t)it * THREADS + fc.rowoff) & mask]);
+      }
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) acc[it] = F::add(acc[it], v[it]);
+    }
+    T x[ITEMS];
+    x[0] = F::mul(p.shift, f_pow<F>(p.gL, i0));
+#pragma unroll
+    for (int it = 1; it < ITEMS; it++) x[it] = F::mul(x[it - 1], p.gL_step);
+    for (u32 k = 0; k < p.nexempt; k++) {
+      const T root = p.ex_roots[k];
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) acc[it] = F::mul(acc[it], F::sub(x[it], root));
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+      const size_t i = i0 + (size_t)it * THREADS;
+      if (i < p.L) p.out[i] = F::mul(acc[it], p.den_inv[i & (size_t)(p.blowup - 1)]);   // (blowup is a power of two: ms_lde_commit)
+    }
+  }
+};
+
 // ms_arith_selftest: one operation of the NTT tiles' arithmetic class per element (A = GLM for Goldilocks: inline asm with hand-managed
 // gfx950 wait states, which only a run on the device can check; BB for BabyBear).  Ops: include/ministark.h.
 template <int S> struct ArithShift { template <class A> static MS_DEV u64 run(u64 x, int s) { return s == S ? msntt::gl_mul_pow2<S, A>(x) : ArithShift<S - 1>::template run<A>(x, s); } };

@@ -524,6 +524,48 @@ template <class F, int E> struct Verifier {
 // ---- C entry points for the Python test / bench harness ---------------------------------------
 using namespace ministark;
 struct msh_stark { Stark s; };
+// The verifying side of ms_mix_terms: the value validity(z) must have, from the opened values opened[k][j] = P_j(w^rows[k] z) - the same program in the extension field,
+//   (sum_t r^t C_t(z)) prod_{k=1..nexempt} (z - w^(N-k)) / (z^N - 1),   C_t(z) = sum_m coef_m prod_f opened[row_f][poly_f]
+template <class F, int E> static int terms_expected(u64 r, int ncons, const u32* tb, const u64* coef, const u32* fb, const u32* fp, const u32* fr, int nexempt, u64 N,
+                                                    const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  if (r >= F::P || !V::canon(z, E)) return MS_ERR_ARG;
+  if (tb[0] != 0 || fb[0] != 0) return MS_ERR_ARG;
+  for (int t = 0; t < ncons; t++) if (tb[t + 1] < tb[t] || tb[t + 1] > 65536) return MS_ERR_ARG;
+  const u32 nterms = tb[ncons];
+  for (u32 m = 0; m < nterms; m++) if (fb[m + 1] < fb[m] || fb[m + 1] - fb[m] > 8 || coef[m] >= F::P) return MS_ERR_ARG;
+  std::vector<int> slot(fb[nterms], -1);
+  for (u32 f = 0; f < fb[nterms]; f++) {
+    if (fp[f] >= npolys || (u64)fr[f] >= N) return MS_ERR_ARG;
+    for (int k = 0; k < nrows; k++) if (rows[k] == fr[f]) { slot[f] = k; break; }
+    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;                       // a row the program uses was not opened
+    if (!V::canon(opened + (size_t)slot[f] * row_stride + (size_t)fp[f] * E, E)) return MS_ERR_ARG;
+  }
+  const X zz = V::load(z);
+  X acc = e_zero<F, E>();
+  typename F::T rp = F::from_u64(1);
+  for (int t = 0; t < ncons; t++) {
+    X ct = e_zero<F, E>();
+    for (u32 m = tb[t]; m < tb[t + 1]; m++) {
+      X v = e_from_base<F, E>(F::from_u64(coef[m]));
+      for (u32 f = fb[m]; f < fb[m + 1]; f++) v = e_mul<F>(v, V::load(opened + (size_t)slot[f] * row_stride + (size_t)fp[f] * E));
+      ct = e_add<F, E>(ct, v);
+    }
+    acc = e_add<F, E>(acc, e_mul_base<F, E>(ct, rp));
+    rp = F::mul(rp, F::from_u64(r));
+  }
+  int lg = 0; while (((u64)1 << lg) < N) lg++;
+  const typename F::T wi = f_inv<F>(f_root_of_unity<F>(lg));
+  typename F::T wk = wi;                                                // w^(N-k) = w^-k
+  for (int k = 0; k < nexempt; k++) { acc = e_mul<F>(acc, e_sub<F, E>(zz, e_from_base<F, E>(wk))); wk = F::mul(wk, wi); }
+  const X den = e_sub<F, E>(e_pow<F, E>(zz, N), e_one<F, E>());
+  bool zero = true; for (int l = 0; l < E; l++) zero = zero && den.c[l] == 0;
+  if (zero) return MS_ERR_SHAPE;                                        // z lies in the trace domain
+  acc = e_mul<F>(acc, e_inv<F>(den));
+  for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
+  return MS_OK;
+}
 static size_t copy_out(const void* src, size_t n, void* dst, size_t cap) { if (dst && cap >= n && n) memcpy(dst, src, n); return n; }
 
 extern "C" {
@@ -700,6 +742,15 @@ int msh_fri_proof_parse(const u8* blob, size_t len, u32 e, u32 windows, u32 nq, 
       if (out && n < cap) out[n] = q;
     }
   return left == 0 ? (int)n : -1;
+}
+int msh_terms_expected_validity(int field, u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row,
+                                int nexempt, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+  if (!term_begin || !coef || !fac_begin || !fac_poly || !fac_row || !z || !opened || !out || (nrows && !rows)) return MS_ERR_ARG;
+  if ((field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) || ncons < 1 || ncons > 4096 || nexempt < 0 || nexempt > 16 || nrows < 0 || !N || (N & (N - 1))) return MS_ERR_ARG;
+  try {
+    if (field == MS_FIELD_GOLDILOCKS) return N > ((u64)1 << GL::TWO_ADICITY) ? MS_ERR_ARG : terms_expected<GL, 2>(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt, N, z, nrows, rows, opened, row_stride, npolys, out);
+    return N > ((u64)1 << BB::TWO_ADICITY) ? MS_ERR_ARG : terms_expected<BB, 4>(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt, N, z, nrows, rows, opened, row_stride, npolys, out);
+  } catch (...) { return MS_ERR_NOMEM; }   // nothing unwinds through the C boundary
 }
 // synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic; BASELINE configs[4]): row 0 and the w scalars from SplitMix64(seed), then
 // col_j[i+1] = col_j[i] * col_{j+1}[i] * col_{j+2}[i] + s_j * col_{j+3}[i]  (column indices mod w) - the same values as tests/parity_cases.py:cubic_trace
