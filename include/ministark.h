@@ -294,7 +294,8 @@ int ms_bench_lde(ms_ctx* ctx, size_t blowup, uint64_t shift);
  * inline-asm class GLM, whose gfx950 wait states are managed by hand and which no CPU build can execute; BabyBear: BB) - so that a
  * test can compare every operation with big-integer arithmetic on directed edge values.  a, b canonical.  op: 0 add, 1 sub, 2 mul,
  * 3 mul by the table form of b (mul_tw(a, to_tw(b))), 4 a * 2^32, 5 a * 2^64, 6 a * 2^(b mod 96) through the compile-time shift
- * chains of the butterflies (Goldilocks only), 7 fold: a + (b mod 2^31) * 2^64 mod p (Goldilocks only).  No reference counterpart. */
+ * chains of the butterflies (Goldilocks only), 7 fold: a + (b mod 2^31) * 2^64 mod p (Goldilocks only), 8 / 9 / 10 a * 2^24 / 2^48 / 2^72 and
+ * 11 a * 2^(12 (b mod 8)): the multiplier-free products by 8th and 16th roots of unity of the FRI fold (GL::mul_pow2; Goldilocks only).  No reference counterpart. */
 int ms_arith_selftest(ms_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int ms_profile_begin(ms_ctx* ctx);
 int ms_profile_end(ms_ctx* ctx, char* json_out, size_t cap);

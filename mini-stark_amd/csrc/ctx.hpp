@@ -259,6 +259,7 @@ template <class F> struct Ctx : CtxBase {
     bool regp[4] = {false, false, false, false};                                                 // pass runs on msntt::RegPassKernel (last pass, radix <= 32, registers only)
     DevBuf tw_lo, tw_hi, w_r[4], vtw, w0;
     T n_inv = 0;
+    T root = 0;   // w_n the tables hold the powers of (host copy: the FRI fold's octet table is derived from it)
   };
   std::map<int, Plan*> plans;  // key = (log_n*4 + log_pad)*2 + inverse
   DevBuf ntt_scratch;
@@ -363,7 +364,8 @@ template <class F> struct Ctx : CtxBase {
   // Round 0 keeps the whole (replicated) validity polynomial in `poly` and every rank uses its range of it; later rounds hold only their own S coefficients
   // (local_store: limb l of coefficient k*S + i at poly[l*S + i]).
   struct Round { DevBuf poly, cw, nodes; size_t cap = 0, ncoef = 0, D = 0; TreeShape ts; size_t m = 0; /* sharded: local codeword = limbs x 2 cosets x m */
-                 bool dist = false, local_store = false; size_t S = 0; };
+                 bool dist = false, local_store = false; size_t S = 0;
+                 bool base_cw = false; /* the codeword's limbs >= 1 are identically zero (round 0: transform of a base-field polynomial) */ };
   size_t shard_gather_chunk = 0;
   int shard_dist = 1;          // MS_SHARD_DIST=0: the coefficient-domain work of a sharded proof stays replicated on every rank (r03 behaviour; A/B and tests)
   int proof_root_only = 0;     // ms_shard_proof_on_root: the FRI proof blob is assembled on rank 0 only
@@ -501,7 +503,7 @@ template <class F> struct Ctx : CtxBase {
   // codeword + tree of rounds[i] from its coefficient limbs (ncoef_in valid coefficients)
   // `nonzero_limbs`: limbs >= this are identically zero (round 0: extend_poly embeds base coefficients), so their
   // transform is all zeros and is not computed
-  // `prev` != nullptr: the codeword is folded out of prev's codeword in the evaluation domain (FriFoldEvalKernel) instead of
+  // `prev` != nullptr: the codeword is folded out of prev's codeword in the evaluation domain (FriFoldEvalKernel / FriFoldWgKernel) instead of
   // transforming the round polynomial — same values, a quarter of the arithmetic
   int round_commit(Round* r, size_t ncoef_in, int nonzero_limbs = E, const Round* prev = nullptr, const XE* alpha = nullptr);
   // trimmed length of a round polynomial (DegreeKernel) into a zeroed device word

@@ -60,6 +60,29 @@ struct GL {
     const u64 p11 = (u64)a1 * b1 + (p01 >> 32) + (p10 >> 32);
     return reduce128((p10 << 32) | (u32)p00, p11);
   }
+  // x * 2^S for a compile-time 0 <= S < 96, canonical: no multiplier.  With b = S mod 32 the 96-bit x << b = (t0, t1, t2) starts at word S / 32 of the product:
+  //   word 0: t0 + t1 2^32 + t2 2^64, word 1: t0 2^32 + t1 2^64 + t2 2^96 (both through reduce128), word 2: t0 2^64 + t1 2^96 + t2 2^128 = t0 EPS - (t1 + t2 2^32)
+  // (2^96 == -1, 2^128 == -2^32; t2 < 2^31 and t0 EPS <= (2^32 - 1)^2 are both < p, so the last form is one modular subtraction).
+  // 2 has order 192: these are the products by the 2^k-th roots of unity up to k = 6 (w_8 = 2^24 or an odd power of it, w_16 = 2^12 ...; the FRI fold's octets).
+  // (ntt.hpp has two older forms for its butterflies, gl_mul_pow2_v1 and gl_mul_pow2<S, A>: the first folds S >= 64 as the difference of two shifted 128-bit copies, the
+  // second chains fold_small / mul_x32 / mul_x64 of the sign-bit classes GLT / GLM.  The NTT tiles stay on them instruction for instruction; this one is the compare-and-
+  // select class's, one reduction whatever S, for kernels that compute in GL.)
+  template <int S> static MS_HD T mul_pow2(T x) {
+    static_assert(S >= 0 && S < 96, "shift out of range");
+    if constexpr (S == 0) return x;
+    else {
+      constexpr int b = S & 31, w = S >> 5;
+      const u64 l = x << b;
+      u32 t2 = 0;
+      if constexpr (b != 0) t2 = (u32)(x >> (64 - b));
+      if constexpr (w == 0) return reduce128(l, t2);
+      else if constexpr (w == 1) return reduce128((u64)lo(l) << 32, mk(hi(l), t2));
+      else return sub(((u64)lo(l) << 32) - lo(l), mk(hi(l), t2));
+    }
+  }
+  static MS_HD T mul_2p24(T x) { return mul_pow2<24>(x); }   // x * w_8  (for the root with w_8 = 2^24)
+  static MS_HD T mul_2p48(T x) { return mul_pow2<48>(x); }   // x * w_4
+  static MS_HD T mul_2p72(T x) { return mul_pow2<72>(x); }   // x * w_8^3;  2^96 == -1 closes the cycle
   static MS_HD T from_u64(u64 v) { return v; }
   static MS_HD u64 to_u64(T v) { return v; }
   // twiddle tables hold to_tw(w); mul_tw(a, to_tw(w)) == a * w.  Nothing to gain for Goldilocks: identity.

@@ -8,13 +8,14 @@ namespace msctx {
 // codeword + tree of rounds[i] from its coefficient limbs (ncoef_in valid coefficients)
 // `nonzero_limbs`: limbs >= this are identically zero (round 0: extend_poly embeds base coefficients), so their
 // transform is all zeros and is not computed
-// `prev` != nullptr: the codeword is folded out of prev's codeword in the evaluation domain (FriFoldEvalKernel) instead of
+// `prev` != nullptr: the codeword is folded out of prev's codeword in the evaluation domain (FriFoldEvalKernel / FriFoldWgKernel) instead of
 // transforming the round polynomial — same values, a quarter of the arithmetic
 template <class F>
 int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Round* prev, const XE* alpha) {
   if (ctz64(r->D) > F::TWO_ADICITY) return fail(MS_ERR_SHAPE, "FRI domain larger than the field's two-adicity");
   RQ(tree_shape(r->D, 2, 2, &r->ts));  // starks.rs:290-295: leafs_per_node 2, inner_children 2
   r->m = 0;
+  r->base_cw = false;
   {
     const bool shard_next = shardable(r->D / 2);
     bool z_outside_base = false;   // then y - z != 0 on the whole (base-field) domain
@@ -22,7 +23,7 @@ int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Rou
     if (prev && fri_pointwise && z_outside_base && prev->D == 2 * r->D && prev->ts.sharded == shard_next) {
       Plan* pl;
       RQ(get_plan(ctz64(prev->D), 0, false, &pl));   // w_D^e tables of the previous domain
-      // one output per thread in the late rounds (at most MS_FOLD_SMALL_MAX outputs: their launches are latency, not throughput), eight otherwise
+      // one output per thread in the late rounds (at most MS_FOLD_SMALL_MAX outputs: their launches are latency, not throughput), eight otherwise (FriFoldWgKernel)
       const size_t W = (size_t)sh_world;
       const size_t m_out = shard_next ? r->D / (2 * W) : r->D;
       const size_t local = shard_next ? 2 * m_out : r->D;       // elements per limb held here
@@ -30,9 +31,7 @@ int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Rou
       if (r->cw.ensure(local * E * sizeof(T))) return fail(MS_ERR_NOMEM, "codeword");
       const size_t total = m_out * (shard_next ? 2 : 1);
       const XE c = e_add<F, E>(cur_B[0], e_mul<F>(cur_B[1], *alpha));   // B(alpha), fri.rs:99
-      auto fold_launch = [&](auto* kernel) {
-        typedef typename std::remove_pointer<decltype(kernel)>::type FK;
-        typename FK::Params fp;
+      auto fold_params = [&](auto& fp) {
         fp.src = prev->cw.template as<T>(); fp.src_limb_stride = shard_next ? 2 * prev->m : prev->D;
         fp.dst = r->cw.template as<T>(); fp.dst_limb_stride = local;
         fp.m_out = m_out; fp.log_m = (u32)ctz64(m_out); fp.groups = shard_next ? 2 : 1; fp.shard_W = shard_next ? (u32)W : 0; fp.shard_k = (u32)sh_rank;
@@ -41,10 +40,45 @@ int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Rou
         fp.c2 = e_add<F, E>(c, c);
         fp.z = cur_z;
         fp.inv2 = f_inv<F>(F::from_u64(2));
+      };
+      auto fold_launch = [&](auto* kernel) {   // the latency form: one output per thread
+        typedef typename std::remove_pointer<decltype(kernel)>::type FK;
+        typename FK::Params fp;
+        fold_params(fp);
         return run<FK>(K_FOLD, grid1(total, FK::THREADS * FK::ITEMS), 1, FK::THREADS, 0, fp);
       };
-      next_bytes = (double)total * E * sizeof(T) * 3;   // two inputs read, one output written per element
-      { PartScopeIf part(this, shard_next); CK(total <= fold_small_max ? fold_launch((mspoly::FriFoldEvalKernel<F, E, 1>*)nullptr) : fold_launch((mspoly::FriFoldEvalKernel<F, E, 8>*)nullptr)); }
+      // Octet layout of the throughput form (Goldilocks): the plan's w_D^(D/16) is a primitive 16th root of unity, so it is (2^12)^mm for ONE odd mm (2 has order 192);
+      // item k of a thread then wants the position e = k / mm (mod 16) of its sixteen points x0 w_16^e, i.e. output e mod 8 with f(x) and f(-x) swapped if e >= 8
+      // (w_16^8 = -1), and 2^(-12 k) = -2^(96 - 12 k) for k > 0 flips the sign once more.  No mm found (another field, a root that is no power of 2): item layout.
+      u32 oct_q[8] = {0, 0, 0, 0, 0, 0, 0, 0}, oct_neg = 0;
+      bool oct = false;
+      if constexpr (F::ID == 0) {
+        if (!shard_next && m_out >= 8 && (m_out & (m_out - 1)) == 0) {
+          const T w16 = f_pow<F>(pl->root, (u64)(prev->D / 16));
+          for (u32 mm = 1; mm < 16 && !oct; mm += 2) {
+            if (f_pow<F>(F::from_u64((u64)1 << 12), mm) != w16) continue;
+            u32 minv = 1; while ((mm * minv) % 16 != 1) minv += 2;
+            for (u32 k = 0; k < 8; k++) { const u32 e = (k * minv) % 16; oct_q[k] = e % 8; if ((e >= 8) != (k > 0)) oct_neg |= 1u << k; }
+            oct = true;
+          }
+        }
+      }
+      auto wg_launch = [&](auto* kernel) {     // the throughput form: eight outputs per thread, one inversion per workgroup
+        typedef typename std::remove_pointer<decltype(kernel)>::type FK;
+        typename FK::Params wp;
+        fold_params(wp.f);
+        for (int k = 0; k < 8; k++) wp.oct_q[k] = oct_q[k];
+        wp.oct_neg = oct_neg;
+        return run_coop<FK>(K_FOLD, grid1(FK::grid_items(wp), FK::THREADS), FK::THREADS, FK::lds_bytes(), wp);
+      };
+      const bool src1 = prev->base_cw;          // round 0 -> 1: f(x) +- f(-x) are base elements
+      next_bytes = (double)total * (E + 2 * (src1 ? 1 : E)) * sizeof(T);   // two inputs read, one output written per element
+      { PartScopeIf part(this, shard_next);
+        if (total <= fold_small_max) CK(fold_launch((mspoly::FriFoldEvalKernel<F, E, 1>*)nullptr));
+        else if constexpr (F::ID == 0) {
+          if (oct) CK(src1 ? wg_launch((mspoly::FriFoldWgKernel<F, E, 1, true>*)nullptr) : wg_launch((mspoly::FriFoldWgKernel<F, E, E, true>*)nullptr));
+          else CK(src1 ? wg_launch((mspoly::FriFoldWgKernel<F, E, 1, false>*)nullptr) : wg_launch((mspoly::FriFoldWgKernel<F, E, E, false>*)nullptr));
+        } else CK(src1 ? wg_launch((mspoly::FriFoldWgKernel<F, E, 1, false>*)nullptr) : wg_launch((mspoly::FriFoldWgKernel<F, E, E, false>*)nullptr)); }
       if (shard_next) RQ((tree_build_sharded<E>(r->cw.template as<T>(), m_out, 1, 2 * m_out, 2, r->ts, r->nodes)));
       else RQ((tree_build<E>(r->cw.template as<T>(), 0, 1, r->D, 1, r->ts, r->nodes)));
       return 0;
@@ -64,12 +98,14 @@ int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Rou
     }
     { PartScope part(this); RQ(coset_eval(coef, coef_stride, ncoef_in, ctz64(r->D), F::from_u64(1), 2, r->cw.template as<T>(), 2 * m, (size_t)nonzero_limbs)); }
     if (nonzero_limbs < E) CK(msrt::memset_dev(r->cw.template as<T>() + (size_t)nonzero_limbs * 2 * m, 0, (size_t)(E - nonzero_limbs) * 2 * m * sizeof(T), stream));
+    r->base_cw = nonzero_limbs == 1;
     RQ((tree_build_sharded<E>(r->cw.template as<T>(), m, 1, 2 * m, 2, r->ts, r->nodes)));
     return 0;
   }
   if (r->cw.ensure(r->D * E * sizeof(T))) return fail(MS_ERR_NOMEM, "codeword");
   RQ(ntt_run(ctz64(r->D), false, r->poly.template as<T>(), r->cap, ncoef_in, r->cw.template as<T>(), r->D, (size_t)nonzero_limbs));  // fri.rs:350
   if (nonzero_limbs < E) CK(msrt::memset_dev(r->cw.template as<T>() + (size_t)nonzero_limbs * r->D, 0, (size_t)(E - nonzero_limbs) * r->D * sizeof(T), stream));
+  r->base_cw = nonzero_limbs == 1;
   RQ((tree_build<E>(r->cw.template as<T>(), 0, 1, r->D, 1, r->ts, r->nodes)));                                       // fri.rs:351
   return 0;
 }
@@ -327,7 +363,7 @@ int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {
   if (M > (size_t)TK::WG_GROUPS << TK::TreeK::MAX_LEVELS) return 0;
   if (ctz64(Dn) > F::TWO_ADICITY) return fail(MS_ERR_SHAPE, "FRI domain larger than the field's two-adicity");
   RQ(tree_shape(Dn, 2, 2, &nr->ts));
-  nr->m = 0;
+  nr->m = 0; nr->base_cw = false;
   if (nr->poly.ensure(nr->cap * E * sizeof(T)) || d_folded.ensure((m + 1) * E * sizeof(T)) || nr->cw.ensure(Dn * E * sizeof(T)) || nr->nodes.ensure(nr->ts.nodes * 32) ||
       d_sh.ensure(sh_scratch_elems(m) * sizeof(T)))
     return fail(MS_ERR_NOMEM, "fused FRI round");

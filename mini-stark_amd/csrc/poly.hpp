@@ -501,9 +501,10 @@ template <class F, int E> struct SuffixHornerKernel {
 // r = i (replicated round) or 2*(rank + W*i) + t (sharded round: this rank's two cosets).
 template <class F> MS_HD typename F::T fold_base_inv(typename F::T x) { return f_inv<F>(x); }
 template <> MS_HD u64 fold_base_inv<GL>(u64 x) { return gl_inv_chain(x); }
-// ITEMS_: outputs per thread.  8 amortises the field inversion over eight norms (the throughput choice); 1 is the LATENCY choice for the small late rounds, where a
-// launch is one wave deep anyway and eight serial outputs per thread only stretch it (with 8 a launch took 22 us whatever its size; one proof alone on the GPU:
-// 118.6 -> 120.4 proofs/s, eight in flight: neutral - profiles/r04_small_round_kernels_ab.log).
+// ITEMS_: outputs per thread, one field inversion per thread (Montgomery's trick over its norms).  1 is the LATENCY form for the small late rounds, where a launch is
+// one wave deep anyway and eight serial outputs per thread only stretch it (with 8 a launch took 22 us whatever its size; one proof alone on the GPU: 118.6 -> 120.4
+// proofs/s, eight in flight: neutral - profiles/r04_small_round_kernels_ab.log); 2 is the evaluation side of the fused tail rounds (fri_tail.hpp).  The large rounds
+// run the THROUGHPUT form, FriFoldWgKernel below (until then: this kernel with 8).
 template <class F, int E, int ITEMS_ = 8> struct FriFoldEvalKernel {
   typedef typename F::T T;
   typedef Ext<F, E> X;
@@ -579,6 +580,175 @@ template <class F, int E, int ITEMS_ = 8> struct FriFoldEvalKernel {
       const T ni = F::mul(inv, pre[it]);             // 1 / (2 norm_it)
       inv = F::mul(inv, nrm[it]);
       if (j < total) {
+#pragma unroll
+        for (int l = 0; l < E; l++) p.dst[(size_t)l * p.dst_limb_stride + j] = F::mul(tt[it].c[l], ni);
+      }
+    }
+  }
+};
+
+// The THROUGHPUT form of the fold (launches above MS_FOLD_SMALL_MAX outputs): eight outputs per thread like FriFoldEvalKernel<F, E, 8> before it, same values, fewer
+// multiplications per output (Goldilocks: ~28 -> ~19 general-product equivalents, ~16 in the first fold):
+//  * ONE field inversion per workgroup instead of one per thread (a wave executes the 73-product chain whether one lane needs it or all): every thread leaves the
+//    product of its norms in LDS, the lanes of wave 0 combine the NW products of their column with Montgomery's trick, run one chain and unwind it, and every thread
+//    reads 1 / (2 x its product) back behind a barrier.  A thread with no output in range contributes 1; every thread reaches both barriers (cooperative style,
+//    like SuffixHornerKernel: per-thread state lives across the barriers, the emulation build runs it on fibers).
+//  * SRC_LIMBS = 1: the source codeword is a base-field one (round 0: the transform of the validity polynomial, limbs >= 1 are zero and not even loaded), so
+//    f(x) +- f(-x) are base elements and (alpha / x) d is E products instead of a tower product.
+//  * what depends on z alone (nr z1^2; BabyBear: zb, K = (u - 11) zb^2) is computed once per thread, not per output.
+//  * OCT (Goldilocks, replicated rounds with m_out >= 8): a thread's eight outputs lie m_out / 8 = D / 16 apart, so their points differ by powers of w_16, and in
+//    Goldilocks every 16th root of unity is +-2^(12 k) (2 has order 192).  x0^-1, y0 = x0^2 and u0 = alpha / x0 come from the tables once per thread; output k takes
+//    the point x = s_k x0 2^(12 k): (alpha / x) d = u0 (+-d 2^(96 - 12 k)) with the sign as a swap of f(x) and f(-x), y = y0 2^(24 k) (2^96 = -1) - shifts with the
+//    special-form reduction (GL::mul_pow2) instead of four general products.  WHICH of the eight positions i0 + q m_out / 8 has the point x0 2^(12 k), and with which
+//    sign, depends on the root of the plan: w_D^(D / 16) = 2^(12 m) for some odd m, found by the host at launch (oct_q[k], oct_neg; nothing assumes the generator).
+// Layouts: OCT as above (lanes still read and write consecutive elements); otherwise FriFoldEvalKernel's (output j0 + it x THREADS; sharded rounds, BabyBear, m_out < 8).
+template <class F, int E, int SRC_LIMBS_ = E, bool OCT_ = false> struct FriFoldWgKernel {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  typedef FriFoldEvalKernel<F, E, 1> Lat;
+  static_assert(E == 2 || E == 4, "quadratic or quartic tower");
+  static_assert(SRC_LIMBS_ == 1 || SRC_LIMBS_ == E, "base-field or full source");
+  static_assert(!OCT_ || F::ID == 0, "the octet layout needs Goldilocks' roots of unity");
+  static constexpr int THREADS = mspoly::THREADS, ITEMS = 8, NW = THREADS / 64, SRC_LIMBS = SRC_LIMBS_;
+  static constexpr bool OCT = OCT_;
+  struct Params {
+    typename Lat::Params f;
+    u32 oct_q[8];    // OCT: item k works on output i0 + oct_q[k] * m_out / 8 ...
+    u32 oct_neg;     // ... and bit k says that its d = f(x) - f(-x) enters negated
+  };
+  static MS_HD size_t lds_bytes() { return (size_t)THREADS * sizeof(T); }
+  static MS_HD size_t grid_items(const Params& p) { return OCT ? p.f.m_out / 8 : (p.f.m_out * p.f.groups + ITEMS - 1) / ITEMS; }   // threads the launch needs
+  struct ZPre { T nz; Ext<F, 2> zb, K; };   // functions of z alone
+  static MS_DEV ZPre z_pre(const X& z) {
+    ZPre zp;
+    const T nr = F::from_u64(F::NR2);
+    zp.nz = 0; zp.zb = e_zero<F, 2>(); zp.K = e_zero<F, 2>();
+    if constexpr (E == 2) zp.nz = F::mul(nr, F::mul(z.c[1], z.c[1]));
+    else { zp.zb.c[0] = z.c[2]; zp.zb.c[1] = z.c[3]; zp.K = e_mul_nr4<F>(e_mul<F>(zp.zb, zp.zb)); }
+    return zp;
+  }
+  // conjugate product C and base-field norm n of (y - z), yd = y - z0 (FriFoldEvalKernel::inv_parts with the z-only parts taken out)
+  static MS_DEV void inv_parts(const X& z, const ZPre& zp, T yd, X* C, T* n) {
+    if constexpr (E == 2) {
+      C->c[0] = yd; C->c[1] = z.c[1];
+      *n = F::sub(F::mul(yd, yd), zp.nz);
+    } else {
+      const T nr = F::from_u64(F::NR2);
+      Ext<F, 2> A;
+      A.c[0] = yd; A.c[1] = F::neg(z.c[1]);
+      const Ext<F, 2> M = e_sub<F, 2>(e_mul<F>(A, A), zp.K);
+      Ext<F, 2> Mc; Mc.c[0] = M.c[0]; Mc.c[1] = F::neg(M.c[1]);
+      *n = F::sub(F::mul(M.c[0], M.c[0]), F::mul(nr, F::mul(M.c[1], M.c[1])));
+      const Ext<F, 2> c0 = e_mul<F>(A, Mc), c1 = e_mul<F>(zp.zb, Mc);
+      C->c[0] = c0.c[0]; C->c[1] = c0.c[1]; C->c[2] = c1.c[0]; C->c[3] = c1.c[1];
+    }
+  }
+  // one output: a = f(x) at ia, b = f(-x) at ib, u = alpha / x up to the factor 2^S that d takes instead, y = x^2.  *tt = 2 (folded - c) C, *nrm = the norm
+  template <int S> static MS_DEV void item(const typename Lat::Params& p, const ZPre& zp, size_t ia, size_t ib, const X& u, T y, X* tt, T* nrm) {
+    T a[SRC_LIMBS], b[SRC_LIMBS];
+#pragma unroll
+    for (int l = 0; l < SRC_LIMBS; l++) { a[l] = p.src[(size_t)l * p.src_limb_stride + ia]; b[l] = p.src[(size_t)l * p.src_limb_stride + ib]; }
+    X num;
+    if constexpr (SRC_LIMBS == E) {
+      X s, d;
+#pragma unroll
+      for (int l = 0; l < E; l++) {
+        s.c[l] = F::add(a[l], b[l]); d.c[l] = F::sub(a[l], b[l]);
+        if constexpr (S != 0) d.c[l] = F::template mul_pow2<S>(d.c[l]);
+      }
+      num = e_sub<F, E>(e_add<F, E>(s, e_mul<F>(u, d)), p.c2);
+    } else {
+      const T s0 = F::add(a[0], b[0]);
+      T d0 = F::sub(a[0], b[0]);
+      if constexpr (S != 0) d0 = F::template mul_pow2<S>(d0);
+      num.c[0] = F::sub(F::add(s0, F::mul(u.c[0], d0)), p.c2.c[0]);
+#pragma unroll
+      for (int l = 1; l < E; l++) num.c[l] = F::sub(F::mul(u.c[l], d0), p.c2.c[l]);
+    }
+    X C;
+    inv_parts(p.z, zp, F::sub(y, p.z.c[0]), &C, nrm);
+    *tt = e_mul<F>(num, C);
+  }
+  // OCT: items K .. 7 of the thread whose first position is i0 (Q = m_out / 8); compile-time K for the shifts
+  template <int K> static MS_DEV void oct_items(const Params& pp, const ZPre& zp, bool act, size_t i0, size_t Q, const X& u0, T y0, X* tt, T* nrm, T* pre, T* prod) {
+    if constexpr (K < ITEMS) {
+      tt[K] = e_zero<F, E>(); nrm[K] = F::from_u64(1);
+      if (act) {
+        const size_t i = i0 + (size_t)pp.oct_q[K] * Q;
+        const bool ng = (pp.oct_neg >> K) & 1u;
+        T y = F::template mul_pow2<24 * (K & 3)>(y0);
+        if constexpr (K >= 4) y = F::neg(y);
+        item<(K ? 96 - 12 * K : 0)>(pp.f, zp, ng ? i + pp.f.m_out : i, ng ? i : i + pp.f.m_out, u0, y, &tt[K], &nrm[K]);
+      }
+      pre[K] = *prod;
+      *prod = F::mul(*prod, nrm[K]);
+      oct_items<K + 1>(pp, zp, act, i0, Q, u0, y0, tt, nrm, pre, prod);
+    }
+  }
+  static MS_DEV void run(const Params& pp, int bx, int, int, int tid, unsigned char* lds) {
+    const typename Lat::Params& p = pp.f;
+    const size_t total = p.m_out * p.groups, Dm = ((size_t)1 << p.log_D) - 1;
+    const ZPre zp = z_pre(p.z);
+    X tt[ITEMS]; T nrm[ITEMS], pre[ITEMS];
+    T prod = F::from_u64(1);
+    const size_t Q = p.m_out / 8;
+    size_t j0;
+    if constexpr (OCT) {
+      j0 = (size_t)bx * THREADS + tid;
+      const bool act = j0 < Q;
+      X u0 = e_zero<F, E>(); T y0 = 0;
+      if (act) {
+        const T xinv = Lat::w_tab(p, (Dm + 1 - j0) & Dm);                // table form of x0^-1 = w_D^(D - i0)
+#pragma unroll
+        for (int l = 0; l < E; l++) u0.c[l] = F::mul_tw(p.alpha.c[l], xinv);
+        y0 = F::from_tw(Lat::w_tab(p, (2 * j0) & Dm));
+      }
+      oct_items<0>(pp, zp, act, j0, Q, u0, y0, tt, nrm, pre, &prod);
+    } else {
+      j0 = (size_t)bx * ((size_t)THREADS * ITEMS) + tid;
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) {
+        const size_t j = j0 + (size_t)it * THREADS;
+        tt[it] = e_zero<F, E>(); nrm[it] = F::from_u64(1);
+        if (j < total) {
+          const size_t t = j >> p.log_m, i = j & (p.m_out - 1);
+          const size_t ia = t * 2 * p.m_out + i;
+          const size_t r = p.shard_W ? 2 * ((size_t)p.shard_k + (size_t)p.shard_W * i) + t : i;
+          const T xinv = Lat::w_tab(p, (Dm + 1 - r) & Dm);               // table form of x^-1 = w_D^(D - r)
+          X u;                                                            // alpha / x
+#pragma unroll
+          for (int l = 0; l < E; l++) u.c[l] = F::mul_tw(p.alpha.c[l], xinv);
+          item<0>(p, zp, ia, ia + p.m_out, u, F::from_tw(Lat::w_tab(p, (2 * r) & Dm)), &tt[it], &nrm[it]);
+        }
+        pre[it] = prod;                // product of the norms before this one
+        prod = F::mul(prod, nrm[it]);
+      }
+    }
+    // ---- 1 / (2 x product of this thread's norms) for every thread of the workgroup from ONE inversion per lane of wave 0
+    T* sp = reinterpret_cast<T*>(lds);
+    sp[tid] = prod;
+    msrt::wg_barrier();
+    // Wave 0 inverts for the workgroup (lane l: the products of threads l, l + 64, ...); the other waves wait at the barrier and other workgroups of the CU issue meanwhile.
+    if (tid < 64) {
+      const int ln = tid;
+      T a[NW], ap[NW];
+      T acc = F::from_u64(1);
+#pragma unroll
+      for (int w = 0; w < NW; w++) { a[w] = sp[ln + 64 * w]; ap[w] = acc; acc = w ? F::mul(acc, a[w]) : a[w]; }
+      T iv = F::mul(fold_base_inv<F>(acc), p.inv2);
+#pragma unroll
+      for (int w = NW - 1; w >= 0; w--) { sp[ln + 64 * w] = w ? F::mul(iv, ap[w]) : iv; if (w) iv = F::mul(iv, a[w]); }
+    }
+    msrt::wg_barrier();
+    T inv = sp[tid];
+#pragma unroll
+    for (int it = ITEMS - 1; it >= 0; it--) {
+      size_t j; bool in;
+      if constexpr (OCT) { in = j0 < Q; j = j0 + (size_t)pp.oct_q[it] * Q; }
+      else { j = j0 + (size_t)it * THREADS; in = j < total; }
+      const T ni = F::mul(inv, pre[it]);             // 1 / (2 norm_it)
+      inv = F::mul(inv, nrm[it]);
+      if (in) {
 #pragma unroll
         for (int l = 0; l < E; l++) p.dst[(size_t)l * p.dst_limb_stride + j] = F::mul(tt[it].c[l], ni);
       }
@@ -877,6 +1047,21 @@ template <class F, class A> struct ArithKernel {
       else if (p.op == 5) r = A::mul_x64(a);
       else if (p.op == 6) r = ArithShift<95>::template run<A>(a, (int)(p.b[i] % 96));
       else if (p.op == 7) r = A::fold_small(a, (u32)p.b[i] & 0x7FFFFFFFu);
+      else if (p.op == 8) r = GL::mul_2p24(a);
+      else if (p.op == 9) r = GL::mul_2p48(a);
+      else if (p.op == 10) r = GL::mul_2p72(a);
+      else if (p.op == 11) {   // every shift of the fold's octets: a * 2^(12 (b mod 8))
+        switch ((int)(p.b[i] & 7)) {
+          case 0: r = a; break;
+          case 1: r = GL::mul_pow2<12>(a); break;
+          case 2: r = GL::mul_pow2<24>(a); break;
+          case 3: r = GL::mul_pow2<36>(a); break;
+          case 4: r = GL::mul_pow2<48>(a); break;
+          case 5: r = GL::mul_pow2<60>(a); break;
+          case 6: r = GL::mul_pow2<72>(a); break;
+          default: r = GL::mul_pow2<84>(a); break;
+        }
+      }
     }
     p.out[i] = F::to_u64(r);
   }

@@ -261,7 +261,7 @@ int Ctx<F>::poly_read(int i, u64* out) {
 
 template <class F>
 int Ctx<F>::arith_selftest(int op, const u64* a, const u64* b, u64* out, size_t n) {
-  if (!a || !b || !out || op < 0 || op > 7 || (F::ID != 0 && op > 3)) return fail(MS_ERR_ARG, "arith_selftest: bad operation / null argument");
+  if (!a || !b || !out || op < 0 || op > 11 || (F::ID != 0 && op > 3)) return fail(MS_ERR_ARG, "arith_selftest: bad operation / null argument");
   if (!n) return MS_OK;
   if (!canonical(a, n) || (op < 6 && !canonical(b, n))) return fail(MS_ERR_ARG, "operand not canonical");
   DevBuf d;
