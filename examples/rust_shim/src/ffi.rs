@@ -24,6 +24,26 @@ pub const MS_DIGEST_BLAKE2S256: c_int = 1;
 pub const MS_DIGEST_BLAKE3: c_int = 2;
 pub const MS_DIGEST_KECCAK256: c_int = 4; // (3 is unassigned)
 pub const MS_DIGEST_SHA3_256: c_int = 5;
+pub const MS_AIR_PERIODIC: u32 = 0x8000_0000; // fac_poly = MS_AIR_PERIODIC | k names periodic column k (ms_mix_air)
+/// `ms_air` of include/ministark.h: the program of ms_mix_air.  Every pointer borrows from the caller for the duration of the call.
+#[repr(C)]
+pub struct MsAir {
+    pub ncons: u32,
+    pub term_begin: *const u32, // ncons + 1
+    pub coef: *const u64,       // nterms
+    pub fac_begin: *const u32,  // nterms + 1
+    pub fac_poly: *const u32,   // nfacs: polynomial index, or MS_AIR_PERIODIC | k
+    pub fac_row: *const u32,    // nfacs
+    pub ex_begin: *const u32,   // ncons + 1
+    pub ex_row: *const u32,     // may be null when ex_begin[ncons] == 0
+    pub nperiodic: u32,
+    pub per_begin: *const u32,  // nperiodic + 1
+    pub per_val: *const u64,
+    pub nbound: u32,
+    pub bnd_poly: *const u32,
+    pub bnd_row: *const u32,
+    pub bnd_val: *const u64,
+}
 pub type ms_exchange_fn = Option<unsafe extern "C" fn(user: *mut c_void, op: c_int, bytes: usize) -> c_int>;
 
 extern "C" {
@@ -70,6 +90,7 @@ extern "C" {
     pub fn ms_mix_cubic(ctx: *mut ms_ctx, r: u64, spec: *const c_int, s: *const u64, ncons: c_int) -> c_int;
     pub fn ms_mix_terms(ctx: *mut ms_ctx, r: u64, ncons: c_int, term_begin: *const u32, coef: *const u64, fac_begin: *const u32, fac_poly: *const u32,
                         fac_row: *const u32, nexempt: c_int) -> c_int;
+    pub fn ms_mix_air(ctx: *mut ms_ctx, r: u64, air: *const MsAir) -> c_int;
     pub fn ms_validity_len(ctx: *const ms_ctx) -> usize;
     pub fn ms_eval_ext(ctx: *mut ms_ctx, z: *const u64, q: c_int, out: *mut u64) -> c_int;
     // ---- Fri::prove stages (src/fri.rs:53-189)

@@ -182,7 +182,7 @@ int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_
 int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c */);
 /* 1.3  validity = sum_i r^i f_i (remainder of divide_by_vanishing_poly; quirk Q1).  starks.rs:108-119. */
 int ms_mix(ms_ctx* ctx, uint64_t r);
-int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms */);
+int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms / ms_mix_air */);
 /* BUILD-DEFINED, no reference counterpart (BASELINE configs[4] "degree-3 constraints"; the reference cannot express them: its validity polynomial is the
  * remainder of divide_by_vanishing_poly, starks.rs:118-119, quirk Q1).  In place of ms_mix, with the TRUE quotient:
  *   C_t(x) = P_j(w x) - P_a(x) P_b(x) P_c(x) - s_t P_d(x)         spec[t] = {j, a, b, c, d} (polynomial indices), w = the trace domain's generator
@@ -196,7 +196,7 @@ int ms_mix_cubic(ms_ctx* ctx, uint64_t r, const int* spec /* [ncons][5] */, cons
  *   C_t(x)      = sum_{m in terms(t)} coef_m * prod_{f in factors(m)} P_{poly_f}(w^{row_f} x)          (a term without factors is the constant coef_m)
  *   validity(x) = (sum_t r^t C_t(x)) * prod_{k=1..nexempt} (x - w^(N-k)) / (x^N - 1)
  * i.e. every constraint must hold on the rows 0 .. N-1-nexempt; the last `nexempt` rows are exempt for ALL constraints.  Boundary constraints and per-constraint
- * exemptions are not part of this stage.  The program is passed as CSR arrays: the terms of constraint t are term_begin[t] .. term_begin[t+1]-1, the factors of
+ * exemptions are not part of this stage (ms_mix_air below has them).  The program is passed as CSR arrays: the terms of constraint t are term_begin[t] .. term_begin[t+1]-1, the factors of
  * term m are fac_begin[m] .. fac_begin[m+1]-1 (both arrays start at 0 and do not decrease).
  * With d = the most factors of any term, VL = N * next_pow2(max(1, d - 1)) - or, when nexempt > d - 1, next_pow2 of the ceil(((d - 1) N - d + nexempt + 1) / N)
  * slots the quotient's (d - 1) N - d + nexempt + 1 coefficients then need: afterwards ms_validity_len is VL, the validity polynomial has VL coefficients (zero
@@ -215,6 +215,47 @@ int ms_mix_cubic(ms_ctx* ctx, uint64_t r, const int* spec /* [ncons][5] */, cons
 int ms_mix_terms(ms_ctx* ctx, uint64_t r, int ncons, const uint32_t* term_begin /* ncons + 1 */, const uint64_t* coef /* nterms, canonical */,
                  const uint32_t* fac_begin /* nterms + 1 */, const uint32_t* fac_poly /* nfacs: polynomial index */,
                  const uint32_t* fac_row /* nfacs: row offset, 0 <= row < N */, int nexempt /* 0..16 */);
+/* BUILD-DEFINED, no reference counterpart: ms_mix_terms completed to an AIR - an exemption set per transition constraint, periodic columns (public values that
+ * repeat with a power-of-two period: round constants, selectors) and boundary constraints.  w = the generator of the N-row trace domain, P_0 .. P_{c-1} the
+ * polynomials of the committed LDE (c = ms_polys_count at the preceding ms_lde_commit), L = blowup * N.
+ *   periodic column k   period q_k = per_begin[k+1] - per_begin[k], a power of two, 1 <= q_k <= min(N, 256), the q_k summing to at most 4096;
+ *                       K_k(x) = Q_k(x^(N/q_k)) with Q_k the polynomial of degree < q_k through Q_k((w^(N/q_k))^i) = per_val[per_begin[k] + i]: K_k(w^i) = value[i mod q_k].
+ *                       The factor (MS_AIR_PERIODIC | k, row) is K_k(w^row x); for degrees it counts like a trace column (degree <= N - 1).
+ *   transition t        C_t(x) = sum_m coef_m prod_f factor_f(x) as in ms_mix_terms; must vanish on every row outside its exemption set X_t =
+ *                       ex_row[ex_begin[t] .. ex_begin[t+1]).  Z_t(x) = prod_{rho in X_t} (x - w^rho), e_t = |X_t|, d_t = the most factors of any of its terms.
+ *   boundary b          P_{bnd_poly[b]}(w^{bnd_row[b]}) = bnd_val[b].
+ *   validity(x) = sum_t r^t C_t(x) Z_t(x) / (x^N - 1)  +  sum_b r^(ncons+b) (P_{bnd_poly[b]}(x) - bnd_val[b]) / (x - w^{bnd_row[b]})
+ * With nq = max(max_t (d_t (N - 1) + e_t - N + 1), N - 1 if nbound > 0, 1): VL = N * next_pow2(ceil(nq / N)).  Afterwards ms_validity_len is VL and ms_validity_read /
+ * ms_eval_ext / ms_fri_begin .. ms_fri_query work on the polynomial exactly as after ms_mix_terms.  A program ms_mix_terms can express (every X_t the last nexempt
+ * rows, nothing else) gives the same VL and the same outputs bit for bit (for N >= d; below that ms_mix_terms rounds VL up to d - 1 slots).
+ *   MS_ERR_STATE  called before ms_lde_commit; the LDE of the context is sharded over ranks.
+ *   MS_ERR_ARG    air or an array that is needed is null; r, a coefficient, a periodic value or a boundary value >= p; a limit named here exceeded; the malformed-CSR
+ *                 conditions of ms_mix_terms (including "no term has a factor"); a period that is no power of two or exceeds min(N, 256); a periodic index >= nperiodic;
+ *                 per_begin not starting at 0; ex_begin not starting at 0 or decreasing; an exempt row >= N or named twice in one set; more than 32 DISTINCT exemption sets; more than 16
+ *                 distinct boundary rows; a boundary polynomial >= c or row >= N.
+ *   MS_ERR_SHAPE  the LDE domain cannot decide exactness: needs max_t (d_t (N - 1) + e_t) < L, 2N - 2 < L when nbound > 0, and VL + N <= L;
+ *                 the LDE coset meets the trace domain; the divisions are not exact: a transition constraint fails on a non-exempt row or a boundary value is wrong.
+ * Everything but the last is decided before anything is launched; after any refusal the context is usable as if the call had not been made.
+ * msh_air_expected_validity (ministark_host.h) is the verifying side's evaluation of the same program.  Tests: tests/test_air_*.py. */
+#define MS_AIR_PERIODIC 0x80000000u
+typedef struct ms_air {
+  uint32_t ncons;                      /* 1..4096 transition constraints */
+  const uint32_t* term_begin;          /* ncons + 1 | exactly the CSR program of ms_mix_terms, except that  */
+  const uint64_t* coef;                /* nterms    | fac_poly[f] may be MS_AIR_PERIODIC | k (periodic      */
+  const uint32_t* fac_begin;           /* nterms+1  | column k) in place of a polynomial index              */
+  const uint32_t* fac_poly;            /* nfacs */
+  const uint32_t* fac_row;             /* nfacs, 0 <= row < N */
+  const uint32_t* ex_begin;            /* ncons + 1: constraint t is exempt on the rows ex_row[ex_begin[t] .. ex_begin[t+1]) */
+  const uint32_t* ex_row;              /* distinct within a constraint, < N, at most 16 per constraint; may be NULL when ex_begin[ncons] == 0 */
+  uint32_t nperiodic;                  /* 0..64 */
+  const uint32_t* per_begin;           /* nperiodic + 1: column k has period q_k = per_begin[k+1] - per_begin[k] */
+  const uint64_t* per_val;             /* its q_k values, canonical */
+  uint32_t nbound;                     /* 0..4096 boundary constraints */
+  const uint32_t* bnd_poly;            /* < c */
+  const uint32_t* bnd_row;             /* < N; at most 16 distinct rows over all boundary constraints */
+  const uint64_t* bnd_val;             /* canonical */
+} ms_air;
+int ms_mix_air(ms_ctx* ctx, uint64_t r, const ms_air* air);
 size_t ms_validity_len(const ms_ctx* ctx);
 /* 2.   DEEP-ALI: out[t][i] = f_i(z_t) for the c constraint polys, out[t][c] = validity(z_t);
  *      z: q*E limbs, out: q*(c+1)*E limbs.  starks.rs:124-151, field.rs:23-32. */

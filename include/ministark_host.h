@@ -85,6 +85,14 @@ int msh_hash(int digest_id, const uint8_t* data, size_t len, uint8_t out[32]);
 int msh_terms_expected_validity(int field, uint64_t r, int ncons, const uint32_t* term_begin, const uint64_t* coef, const uint32_t* fac_begin, const uint32_t* fac_poly,
                                 const uint32_t* fac_row, int nexempt, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows, const uint64_t* opened,
                                 size_t row_stride, uint32_t npolys, uint64_t* out);
+/* The verifying side of ms_mix_air (ministark.h; build-defined): the value validity(z) must have at an extension point z,
+ *   sum_t r^t C_t(z) Z_t(z) / (z^N - 1)  +  sum_b r^(ncons+b) (opened[row 0][bnd_poly[b]] - bnd_val[b]) / (z - w^bnd_row[b]),
+ * from the same ms_air program and opened values laid out as for msh_terms_expected_validity.  A periodic factor K_k(w^row z) is evaluated here and needs no
+ * opening; the boundary quotients are computed from the row-0 opening P_j(z).  Writes E limbs to out.  MS_OK; MS_ERR_ARG for a null argument, a malformed
+ * program (the conditions of ms_mix_air; a polynomial index >= npolys) or a non-canonical element; MS_ERR_OUT_OF_RANGE when the program uses a row that `rows`
+ * does not list (row 0 included when nbound > 0); MS_ERR_SHAPE when z^N = 1. */
+int msh_air_expected_validity(int field, uint64_t r, const ms_air* air, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows, const uint64_t* opened,
+                              size_t row_stride, uint32_t npolys, uint64_t* out);
 /* synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic): col_j[i+1] = col_j[i] col_{j+1}[i] col_{j+2}[i] + s_j col_{j+3}[i]; length x w row-major, w scalars */
 int msh_cubic_rows(uint64_t p, size_t length, size_t w, uint64_t seed, uint64_t* out, uint64_t* scalars);
 /* synthetic Fibonacci-AIR trace of the benchmark workload (N x 3 row-major) */

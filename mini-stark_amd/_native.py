@@ -99,6 +99,61 @@ def terms_rows(constraints):
     return sorted({int(row) for terms in constraints for _, factors in terms for _, row in factors})
 
 
+AIR_PERIODIC = 0x80000000   # MS_AIR_PERIODIC: fac_poly = AIR_PERIODIC | k names periodic column k
+
+
+class MsAir(C.Structure):
+    """ms_air (include/ministark.h)"""
+    _u32p = C.POINTER(C.c_uint32)
+    _fields_ = [("ncons", C.c_uint32), ("term_begin", _u32p), ("coef", _u64p), ("fac_begin", _u32p), ("fac_poly", _u32p), ("fac_row", _u32p),
+                ("ex_begin", _u32p), ("ex_row", _u32p), ("nperiodic", C.c_uint32), ("per_begin", _u32p), ("per_val", _u64p),
+                ("nbound", C.c_uint32), ("bnd_poly", _u32p), ("bnd_row", _u32p), ("bnd_val", _u64p)]
+
+
+AIR_ARRAYS = (("term_begin", np.uint32), ("coef", np.uint64), ("fac_begin", np.uint32), ("fac_poly", np.uint32), ("fac_row", np.uint32), ("ex_begin", np.uint32),
+              ("ex_row", np.uint32), ("per_begin", np.uint32), ("per_val", np.uint64), ("bnd_poly", np.uint32), ("bnd_row", np.uint32), ("bnd_val", np.uint64))
+
+
+def flatten_air(constraints, exempt=None, periodic=(), boundary=()):
+    """The arrays of an ms_air as a dict of contiguous numpy arrays (the names of the struct's fields, plus the counts ncons / nperiodic / nbound):
+    constraints = [[(coef, [(poly, row), ...]), ...], ...] with poly = AIR_PERIODIC | k for periodic column k; exempt = one row list per constraint (None: no
+    row is exempt); periodic = a list of value lists; boundary = [(poly, row, value), ...]."""
+    tb, cf, fb, fp, fr = flatten_terms(constraints)
+    exempt = [[] for _ in constraints] if exempt is None else [list(rows) for rows in exempt]
+    if len(exempt) != len(constraints):
+        raise ValueError("flatten_air: one exemption row list per constraint")
+    ex_begin, per_begin = [0], [0]
+    for rows in exempt:
+        ex_begin.append(ex_begin[-1] + len(rows))
+    for vals in periodic:
+        per_begin.append(per_begin[-1] + len(vals))
+    return {"ncons": len(constraints), "term_begin": tb, "coef": cf, "fac_begin": fb, "fac_poly": fp, "fac_row": fr,
+            "ex_begin": np.array(ex_begin, dtype=np.uint32), "ex_row": np.array([int(k) for rows in exempt for k in rows], dtype=np.uint32),
+            "nperiodic": len(periodic), "per_begin": np.array(per_begin, dtype=np.uint32), "per_val": np.array([int(v) for vals in periodic for v in vals], dtype=np.uint64),
+            "nbound": len(boundary), "bnd_poly": np.array([int(b[0]) for b in boundary], dtype=np.uint32), "bnd_row": np.array([int(b[1]) for b in boundary], dtype=np.uint32),
+            "bnd_val": np.array([int(b[2]) for b in boundary], dtype=np.uint64)}
+
+
+def air_struct(air):
+    """(MsAir, the arrays it points into - keep them alive while the struct is in use) from a flatten_air dict; an entry that is None becomes a NULL pointer"""
+    keep = {k: (None if air.get(k) is None else np.ascontiguousarray(air[k], dtype=t)) for k, t in AIR_ARRAYS}
+    s = MsAir()
+    s.ncons, s.nperiodic, s.nbound = int(air["ncons"]), int(air["nperiodic"]), int(air["nbound"])
+    for k, t in AIR_ARRAYS:
+        if keep[k] is not None:   # (an empty numpy array still has a valid, non-null data pointer)
+            setattr(s, k, keep[k].ctypes.data_as(_u64p if t is np.uint64 else C.POINTER(C.c_uint32)))
+    return s, keep
+
+
+def air_rows(constraints, boundary=()):
+    """The row offsets the verifying side of an AIR program needs opened, ascending: those of its factors, and row 0 when there are boundary constraints (their
+    quotients are evaluated from P_j(z))."""
+    rows = {int(row) for terms in constraints for _, factors in terms for _, row in factors}
+    if len(boundary):
+        rows.add(0)
+    return sorted(rows)
+
+
 class Context:
     """One ms_ctx: a prover session on one GPU (include/ministark.h)."""
 
@@ -292,6 +347,13 @@ class Context:
         # (an empty numpy array still has a valid, non-null data pointer)
         return self.L.ms_mix_terms(self.h, C.c_uint64(r), C.c_int(len(tb) - 1), tb.ctypes.data_as(u32p), cf.ctypes.data_as(_u64p), fb.ctypes.data_as(u32p),
                                    fp.ctypes.data_as(u32p), fr.ctypes.data_as(u32p), C.c_int(nexempt))
+
+    def mix_air(self, r, constraints, exempt=None, periodic=(), boundary=()):
+        """ms_mix_air (BUILD-DEFINED AIR composition with the true quotients; include/ministark.h): constraints as for mix_terms with AIR_PERIODIC | k naming periodic
+        column k, exempt = one row list per constraint, periodic = a list of value lists, boundary = [(poly, row, value), ...]; or a flatten_air dict as `constraints`."""
+        air = constraints if isinstance(constraints, dict) else flatten_air(constraints, exempt, periodic, boundary)
+        s, _keep = air_struct(air)
+        return self.L.ms_mix_air(self.h, C.c_uint64(r), C.byref(s))
 
     def validity_read(self):
         self.L.ms_validity_len.restype = C.c_size_t

@@ -3,7 +3,7 @@
 // instantiated - and its device code generated - in the unit that launches it, so the units also partition the device code:
 //   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / interpolate / polys_*           (transpose, narrow / widen)
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
-//   air_stages.cpp   constraint columns, LDE commit, mix, mix_cubic, mix_terms, DEEP-ALI evaluations                 (lincomb, mix, cubic, terms, eval kernels)
+//   air_stages.cpp   constraint columns, LDE commit, mix, mix_cubic, mix_terms, mix_air, DEEP-ALI evaluations        (lincomb, mix, cubic, terms, air, eval kernels)
 //   ntt_plan.cpp     NTT plans and pass dispatch, coset evaluation, ms_ntt / ms_coset_lde                           (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit                                      (SHA-256 leaf / inner kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
@@ -94,6 +94,7 @@ struct CtxBase {
   virtual int mix(u64 r) = 0;
   virtual int mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) = 0;
   virtual int mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) = 0;
+  virtual int mix_air(u64 r, const ms_air* air) = 0;
   virtual size_t validity_len_() const = 0;
   virtual int validity_read(u64* out) = 0;
   virtual int eval_ext(const u64* z, int q, u64* out) = 0;
@@ -187,7 +188,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_COUNT };
   struct ProfRec { int kid, sub; msrt::Event* a; msrt::Event* b; double bytes; bool part; };
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -406,7 +407,7 @@ template <class F> struct Ctx : CtxBase {
     if (ev_copy) msrt::event_destroy(ev_copy);
     if (copy_stream) msrt::stream_destroy(copy_stream);
     for (Round* r : rounds) { r->poly.release(); r->cw.release(); r->nodes.release(); delete r; }
-    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_deg, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &d_evdone};
+    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_deg, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &d_evdone, &d_air_inv};
     for (DevBuf* b : bufs) b->release();
     if (pinned) msrt::free_host(pinned);
     if (h_tabs) msrt::free_host(h_tabs);
@@ -472,6 +473,11 @@ template <class F> struct Ctx : CtxBase {
   int mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) override;
   // build-defined composition of any degree: constraints as sums of monomials over the polynomials, in CSR arrays (include/ministark.h; kernel: mspoly::ComposeTermsKernel)
   int mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) override;
+  // build-defined AIR composition: ms_mix_terms plus per-constraint exemption sets, periodic columns and boundary constraints (include/ministark.h; kernels:
+  // mspoly::ComposeAirKernel, mspoly::CosetInvKernel).  d_air_inv holds D[i] = 1 / (x_i - 1) over the LDE domain, built for the first program with boundary
+  // constraints and kept while (N, blowup, shift) stay what it was built for
+  DevBuf d_air_inv; bool air_inv_valid = false; size_t air_inv_N = 0, air_inv_blowup = 0; u64 air_inv_shift = 0;
+  int mix_air(u64 r, const ms_air* air) override;
   // trimmed length of a base-field coefficient vector
   int degree_launch1(const T* poly, size_t n, unsigned long long** dres_out);
   int validity_read(u64* out) override;

@@ -1024,6 +1024,115 @@ template <class F> struct ComposeTermsKernel {
   }
 };
 
+// ---------------------------------------------------------------- build-defined AIR composition (ms_mix_air)
+// ms_mix_terms plus what makes the system an AIR (include/ministark.h): an exemption set per constraint, periodic columns, boundary constraints,
+//   validity(x) = sum_t r^t C_t(x) Z_t(x) / (x^N - 1)  +  sum_b r^(ncons+b) (P_j(x) - v_b) / (x - w^rho_b),   Z_t(x) = prod_{rho in X_t} (x - w^rho)
+// on the committed LDE domain.  The program is a sequence of GROUPS, each a ComposeTerms program of its own with a multiplier per point:
+//   total_i += (sum_m c'_m prod_f factor_f(x_i)) * M_g(x_i)
+// * transition group (kind 0): the constraints that share one exemption set (r^t folded into the coefficients by the host; field addition is exact, so the
+//   grouping changes no bit).  M_g(x_i) = prod_k (x_i - root_k) * den_inv[i mod blowup], the `blowup` inverses of x^N - 1 as in ComposeTerms.
+// * boundary group (kind 1): the boundary constraints at one row rho, as the terms r^(ncons+b) w^-rho P_j and one constant term - sum r^(ncons+b) w^-rho v_b.
+//   1 / (x_i - w^rho) = w^-rho / (x_(i - rho blowup) - 1), so M_g(x_i) = D[(i + moff) mod L] with ONE table D[i] = 1 / (x_i - 1) over the domain (CosetInvKernel),
+//   read like a column at the row offset moff = ((N - rho) mod N) blowup: no inversion per point, whatever the number of boundary rows.
+// * a factor is a column of the LDE (kind 0: column src, index masked by L - 1) or a periodic column (kind 1): K_k(w^row x_i) takes only blowup q_k values
+//   over the domain, tab_k[(i + row blowup) mod (blowup q_k)], in a table the host built (src = its offset in ptab, mask = blowup q_k - 1).
+// Shape of ComposeTermsKernel: a thread owns ITEMS strided points and walks the program once for all of them; group, term and factor records are the same for every
+// lane and the loop counters uniform, so program reads are scalar loads and the branches on the kind bits uniform; stores only behind the walk.  Every index is masked
+// by a power of two minus one, so the points past L of a domain shorter than a workgroup's share stay in bounds; they are computed and dropped.  No LDS, no atomics.
+struct AirGroup { u32 nterms, nroots, kind, moff; };
+struct AirFac { u32 src, rowoff, mask, kind; };
+constexpr int AIR_MAX_EXEMPT = 16, AIR_MAX_SETS = 32, AIR_MAX_BOUNDARY_ROWS = 16, AIR_MAX_PERIODIC = 64, AIR_MAX_PERIOD = 256, AIR_MAX_PERIOD_SUM = 4096;
+template <class F> struct ComposeAirKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int ITEMS = 8;
+  struct Params { const T* lde; size_t L; u32 blowup, ngroups; const AirGroup* groups; const TermRec<F>* terms; const AirFac* facs; const T* roots /* w^rho, group by group */;
+                  const T* ptab; const T* den_inv; const T* inv /* D, L entries; unused without boundary groups */; T shift, gL, gL_step /* gL^THREADS */; T* out; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
+    const size_t i0 = (size_t)bx * (THREADS * ITEMS) + tid;
+    if (i0 >= p.L) return;
+    const size_t mask = p.L - 1;
+    const T x0 = F::mul(p.shift, f_pow<F>(p.gL, i0));
+    T total[ITEMS];
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) total[it] = 0;
+    u32 m = 0, f = 0, rk = 0;
+    for (u32 g = 0; g < p.ngroups; g++) {
+      const AirGroup gr = p.groups[g];
+      T acc[ITEMS];
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) acc[it] = 0;
+      for (u32 mg = 0; mg < gr.nterms; mg++, m++) {
+        const TermRec<F> tr = p.terms[m];
+        T v[ITEMS];
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) v[it] = tr.coef;
+        for (u32 k = 0; k < tr.nfac; k++, f++) {
+          const AirFac fc = p.facs[f];
+          const T* col = fc.kind ? p.ptab + fc.src : p.lde + (size_t)fc.src * p.L;
+          T c[ITEMS];                                   // (loaded first, multiplied behind: written as one expression the 8 loads were issued one by one, each waited for)
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) c[it] = col[(i0 + (size_t)it * THREADS + fc.rowoff) & (size_t)fc.mask];
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) v[it] = F::mul(v[it], c[it]);
+        }
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) acc[it] = F::add(acc[it], v[it]);
+      }
+      if (gr.nroots) {
+        T x[ITEMS];
+        x[0] = x0;
+#pragma unroll
+        for (int it = 1; it < ITEMS; it++) x[it] = F::mul(x[it - 1], p.gL_step);
+        for (u32 k = 0; k < gr.nroots; k++, rk++) {
+          const T root = p.roots[rk];
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) acc[it] = F::mul(acc[it], F::sub(x[it], root));
+        }
+      }
+      const T* mt = gr.kind ? p.inv : p.den_inv;
+      const size_t mm = gr.kind ? mask : (size_t)(p.blowup - 1);   // (blowup is a power of two: ms_lde_commit)
+      T mv[ITEMS];
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) mv[it] = mt[(i0 + (size_t)it * THREADS + gr.moff) & mm];
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) total[it] = F::add(total[it], F::mul(acc[it], mv[it]));
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+      const size_t i = i0 + (size_t)it * THREADS;
+      if (i < p.L) p.out[i] = total[it];
+    }
+  }
+};
+
+// D[i] = 1 / (x_i - 1) over the LDE domain x_i = shift gL^i, for the boundary groups of ComposeAirKernel: a thread owns ITEMS strided points and inverts their
+// product once (Montgomery's trick).  No x_i is 1: the stage has refused a coset that meets the trace domain, and the points past L of a short domain are
+// points of the same coset again (computed, not stored).
+template <class F> struct CosetInvKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int ITEMS = 8;
+  struct Params { size_t L; T shift, gL, gL_step /* gL^THREADS */; T* out; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
+    const size_t i0 = (size_t)bx * (THREADS * ITEMS) + tid;
+    if (i0 >= p.L) return;
+    T d[ITEMS], pre[ITEMS];
+    T x = F::mul(p.shift, f_pow<F>(p.gL, i0)), run = F::from_u64(1);
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) { d[it] = F::sub(x, F::from_u64(1)); pre[it] = run; run = F::mul(run, d[it]); x = F::mul(x, p.gL_step); }
+    T inv = fold_base_inv<F>(run);
+#pragma unroll
+    for (int it = ITEMS - 1; it >= 0; it--) {
+      const size_t i = i0 + (size_t)it * THREADS;
+      if (i < p.L) p.out[i] = F::mul(inv, pre[it]);
+      inv = F::mul(inv, d[it]);
+    }
+  }
+};
+
 // ms_arith_selftest: one operation of the NTT tiles' arithmetic class per element (A = GLM for Goldilocks: inline asm with hand-managed
 // gfx950 wait states, which only a run on the device can check; BB for BabyBear).  Ops: include/ministark.h.
 template <int S> struct ArithShift { template <class A> static MS_DEV u64 run(u64 x, int s) { return s == S ? msntt::gl_mul_pow2<S, A>(x) : ArithShift<S - 1>::template run<A>(x, s); } };

@@ -7,7 +7,7 @@ import subprocess
 
 import numpy as np
 
-from ._native import Context, MsError, flatten_terms
+from ._native import Context, MsError, air_struct, flatten_air, flatten_terms
 from .stark import FriProof, StarkProof
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,6 +75,27 @@ def terms_expected_validity(field, r, constraints, nexempt, N, z, rows, opened, 
     rc = _host().msh_terms_expected_validity(C.c_int(field), C.c_uint64(r), C.c_int(len(tb) - 1), tb.ctypes.data_as(u32p), cf.ctypes.data_as(u64p), fb.ctypes.data_as(u32p),
                                              fp.ctypes.data_as(u32p), fr.ctypes.data_as(u32p), C.c_int(nexempt), C.c_uint64(N), zz.ctypes.data_as(u64p), C.c_int(rw.size),
                                              rw.ctypes.data_as(u32p), op.ctypes.data_as(u64p), C.c_size_t(op.shape[1]), C.c_uint32(npolys), out.ctypes.data_as(u64p))
+    return rc, out
+
+
+def air_expected_validity(field, r, air, N, z, rows, opened, npolys=None):
+    """msh_air_expected_validity: the value validity(z) must have after ms_mix_air, from the opened values.  `air` = a flatten_air dict, or the tuple (constraints,
+    exempt, periodic, boundary) of Context.mix_air; `rows` the row offsets opened (air_rows: row 0 too when there are boundary constraints), `opened[k]` = the
+    ms_eval_ext output at w^rows[k] z ([c + 1][E], or [c][E] with npolys = c).  Returns (status, E limbs)."""
+    if not isinstance(air, dict):
+        air = flatten_air(*air)
+    s, _keep = air_struct(air)
+    zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1)
+    e = zz.size
+    op = np.ascontiguousarray(opened, dtype=np.uint64)
+    rw = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    op = op.reshape(max(1, rw.size), -1)
+    if npolys is None:
+        npolys = op.shape[1] // e - 1          # the last entry of an ms_eval_ext row is the validity polynomial's value
+    out = np.zeros(e, dtype=np.uint64)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    rc = _host().msh_air_expected_validity(C.c_int(field), C.c_uint64(r), C.byref(s), C.c_uint64(N), zz.ctypes.data_as(u64p), C.c_int(rw.size), rw.ctypes.data_as(u32p),
+                                           op.ctypes.data_as(u64p), C.c_size_t(op.shape[1]), C.c_uint32(npolys), out.ctypes.data_as(u64p))
     return rc, out
 
 

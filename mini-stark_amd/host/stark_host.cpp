@@ -13,6 +13,7 @@
 // Every field operation of the PROVER happens on the GPU inside libministark.so; prove() only moves challenges and
 // commitments between the transcript and the stage functions and calls nothing but ms_* symbols, which are resolved at
 // load time from the already-loaded libministark.so.  verify() is host arithmetic (csrc/field.hpp), like the reference's.
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -566,6 +567,100 @@ template <class F, int E> static int terms_expected(u64 r, int ncons, const u32*
   for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
   return MS_OK;
 }
+// The verifying side of ms_mix_air: the same program in the extension field from the opened values, the periodic columns evaluated here, the boundary quotients
+// from the row-0 opening:  sum_t r^t C_t(z) Z_t(z) / (z^N - 1)  +  sum_b r^(ncons+b) (opened[row 0][j_b] - v_b) / (z - w^rho_b)
+template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  typedef typename F::T T;
+  if (r >= F::P || !V::canon(z, E)) return MS_ERR_ARG;
+  const u32 ncons = a.ncons;
+  if (a.term_begin[0] != 0 || a.fac_begin[0] != 0 || a.ex_begin[0] != 0) return MS_ERR_ARG;
+  for (u32 t = 0; t < ncons; t++) if (a.term_begin[t + 1] < a.term_begin[t] || a.term_begin[t + 1] > 65536 || a.ex_begin[t + 1] < a.ex_begin[t] || a.ex_begin[t + 1] - a.ex_begin[t] > 16) return MS_ERR_ARG;
+  const u32 nterms = a.term_begin[ncons];
+  u32 d = 0;
+  for (u32 m = 0; m < nterms; m++) { if (a.fac_begin[m + 1] < a.fac_begin[m] || a.fac_begin[m + 1] - a.fac_begin[m] > 8 || a.coef[m] >= F::P) return MS_ERR_ARG; d = std::max(d, a.fac_begin[m + 1] - a.fac_begin[m]); }
+  if (d == 0) return MS_ERR_ARG;
+  if (a.ex_begin[ncons] && !a.ex_row) return MS_ERR_ARG;
+  int lg = 0; while (((u64)1 << lg) < N) lg++;
+  const T wN = f_root_of_unity<F>(lg), wi = f_inv<F>(wN), one = F::from_u64(1);
+  // periodic columns: Q_k by the inverse DFT of the q_k values
+  std::vector<std::vector<T>> Q(a.nperiodic);
+  if (a.nperiodic && a.per_begin[0] != 0) return MS_ERR_ARG;
+  for (u32 k = 0; k < a.nperiodic; k++) {
+    if (a.per_begin[k + 1] <= a.per_begin[k] || a.per_begin[k + 1] > 4096) return MS_ERR_ARG;
+    const u64 q = a.per_begin[k + 1] - a.per_begin[k];
+    if ((q & (q - 1)) || q > N || q > 256 || !V::canon(a.per_val + a.per_begin[k], q)) return MS_ERR_ARG;
+    const u64* val = a.per_val + a.per_begin[k];
+    const T eta_inv = f_pow<F>(wi, N / q), qinv = f_inv<F>(F::from_u64(q));
+    Q[k].resize(q);
+    T em = one;
+    for (u64 m = 0; m < q; m++) { T s = 0, e = one; for (u64 i = 0; i < q; i++) { s = F::add(s, F::mul(F::from_u64(val[i]), e)); e = F::mul(e, em); } Q[k][m] = F::mul(s, qinv); em = F::mul(em, eta_inv); }
+  }
+  { std::vector<std::vector<u32>> sets;            // the stage's limits on the exemption sets
+    for (u32 t = 0; t < ncons; t++) {
+      std::vector<u32> s(a.ex_row ? a.ex_row + a.ex_begin[t] : nullptr, a.ex_row ? a.ex_row + a.ex_begin[t + 1] : nullptr);
+      std::sort(s.begin(), s.end());
+      for (size_t k = 0; k < s.size(); k++) if ((u64)s[k] >= N || (k && s[k] == s[k - 1])) return MS_ERR_ARG;
+      if (std::find(sets.begin(), sets.end(), s) == sets.end()) { if (sets.size() == 32) return MS_ERR_ARG; sets.push_back(s); }
+    }
+    std::vector<u32> brows;
+    for (u32 b = 0; b < a.nbound; b++) {
+      if (a.bnd_poly[b] >= npolys || (u64)a.bnd_row[b] >= N || a.bnd_val[b] >= F::P) return MS_ERR_ARG;
+      if (std::find(brows.begin(), brows.end(), a.bnd_row[b]) == brows.end()) { if (brows.size() == 16) return MS_ERR_ARG; brows.push_back(a.bnd_row[b]); }
+    } }
+  const u32 nfacs = a.fac_begin[nterms];
+  for (u32 f = 0; f < nfacs; f++) {
+    const u32 fp = a.fac_poly[f];
+    if ((fp & MS_AIR_PERIODIC) ? (fp & ~MS_AIR_PERIODIC) >= a.nperiodic : fp >= npolys) return MS_ERR_ARG;
+    if ((u64)a.fac_row[f] >= N) return MS_ERR_ARG;
+  }
+  auto slot_of = [&](u32 row) { for (int k = 0; k < nrows; k++) if (rows[k] == row) return k; return -1; };
+  std::vector<int> slot(nfacs, -1);
+  for (u32 f = 0; f < nfacs; f++) {
+    if (a.fac_poly[f] & MS_AIR_PERIODIC) continue;   // (a periodic factor needs no opening)
+    slot[f] = slot_of(a.fac_row[f]);
+    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;                       // a row the program uses was not opened
+    if (!V::canon(opened + (size_t)slot[f] * row_stride + (size_t)a.fac_poly[f] * E, E)) return MS_ERR_ARG;
+  }
+  const int slot0 = a.nbound ? slot_of(0) : 0;
+  if (slot0 < 0) return MS_ERR_OUT_OF_RANGE;                           // the boundary quotients are evaluated from P_j(z)
+  for (u32 b = 0; b < a.nbound; b++) if (!V::canon(opened + (size_t)slot0 * row_stride + (size_t)a.bnd_poly[b] * E, E)) return MS_ERR_ARG;
+  const X zz = V::load(z);
+  const X den = e_sub<F, E>(e_pow<F, E>(zz, N), e_one<F, E>());
+  if (e_is_zero<F, E>(den)) return MS_ERR_SHAPE;                       // z lies in the trace domain
+  X acc = e_zero<F, E>();
+  T rp = one;
+  for (u32 t = 0; t < ncons; t++) {
+    X ct = e_zero<F, E>();
+    for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++) {
+      X v = e_from_base<F, E>(F::from_u64(a.coef[m]));
+      for (u32 f = a.fac_begin[m]; f < a.fac_begin[m + 1]; f++) {
+        if (a.fac_poly[f] & MS_AIR_PERIODIC) {                           // K_k(w^row z) = Q_k((w^row z)^(N/q))
+          const std::vector<T>& q = Q[a.fac_poly[f] & ~MS_AIR_PERIODIC];
+          const u64 step = N / q.size();
+          const X y = e_mul_base<F, E>(e_pow<F, E>(zz, step), f_pow<F>(wN, (u64)a.fac_row[f] * step % N));
+          X kv = e_zero<F, E>();
+          for (size_t i = q.size(); i-- > 0;) kv = e_add<F, E>(e_mul<F>(kv, y), e_from_base<F, E>(q[i]));
+          v = e_mul<F>(v, kv);
+        } else v = e_mul<F>(v, V::load(opened + (size_t)slot[f] * row_stride + (size_t)a.fac_poly[f] * E));
+      }
+      ct = e_add<F, E>(ct, v);
+    }
+    for (u32 k = a.ex_begin[t]; k < a.ex_begin[t + 1]; k++) ct = e_mul<F>(ct, e_sub<F, E>(zz, e_from_base<F, E>(f_pow<F>(wN, (u64)a.ex_row[k]))));
+    acc = e_add<F, E>(acc, e_mul_base<F, E>(ct, rp));
+    rp = F::mul(rp, F::from_u64(r));
+  }
+  acc = e_mul<F>(acc, e_inv<F>(den));
+  for (u32 b = 0; b < a.nbound; b++) {
+    const X num = e_sub<F, E>(V::load(opened + (size_t)slot0 * row_stride + (size_t)a.bnd_poly[b] * E), e_from_base<F, E>(F::from_u64(a.bnd_val[b])));
+    const X dn = e_sub<F, E>(zz, e_from_base<F, E>(f_pow<F>(wN, (u64)a.bnd_row[b])));   // (non-zero: z^N != 1)
+    acc = e_add<F, E>(acc, e_mul_base<F, E>(e_mul<F>(num, e_inv<F>(dn)), rp));
+    rp = F::mul(rp, F::from_u64(r));
+  }
+  for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
+  return MS_OK;
+}
 static size_t copy_out(const void* src, size_t n, void* dst, size_t cap) { if (dst && cap >= n && n) memcpy(dst, src, n); return n; }
 
 extern "C" {
@@ -750,6 +845,16 @@ int msh_terms_expected_validity(int field, u64 r, int ncons, const u32* term_beg
   try {
     if (field == MS_FIELD_GOLDILOCKS) return N > ((u64)1 << GL::TWO_ADICITY) ? MS_ERR_ARG : terms_expected<GL, 2>(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt, N, z, nrows, rows, opened, row_stride, npolys, out);
     return N > ((u64)1 << BB::TWO_ADICITY) ? MS_ERR_ARG : terms_expected<BB, 4>(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt, N, z, nrows, rows, opened, row_stride, npolys, out);
+  } catch (...) { return MS_ERR_NOMEM; }   // nothing unwinds through the C boundary
+}
+int msh_air_expected_validity(int field, u64 r, const ms_air* air, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+  if (!air || !z || !opened || !out || (nrows && !rows)) return MS_ERR_ARG;
+  const ms_air& a = *air;
+  if (!a.term_begin || !a.coef || !a.fac_begin || !a.fac_poly || !a.fac_row || !a.ex_begin || (a.nperiodic && (!a.per_begin || !a.per_val)) || (a.nbound && (!a.bnd_poly || !a.bnd_row || !a.bnd_val))) return MS_ERR_ARG;
+  if ((field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) || a.ncons < 1 || a.ncons > 4096 || a.nperiodic > 64 || a.nbound > 4096 || nrows < 0 || !N || (N & (N - 1))) return MS_ERR_ARG;
+  try {
+    if (field == MS_FIELD_GOLDILOCKS) return N > ((u64)1 << GL::TWO_ADICITY) ? MS_ERR_ARG : air_expected<GL, 2>(r, a, N, z, nrows, rows, opened, row_stride, npolys, out);
+    return N > ((u64)1 << BB::TWO_ADICITY) ? MS_ERR_ARG : air_expected<BB, 4>(r, a, N, z, nrows, rows, opened, row_stride, npolys, out);
   } catch (...) { return MS_ERR_NOMEM; }   // nothing unwinds through the C boundary
 }
 // synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic; BASELINE configs[4]): row 0 and the w scalars from SplitMix64(seed), then
