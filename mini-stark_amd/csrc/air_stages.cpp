@@ -1,5 +1,5 @@
-// air_stages.cpp — constraint columns by linear provenance, coset LDE + commitment (starks.rs:80-95), constraint mixing (starks.rs:108-119; build-defined
-// ms_mix_cubic, ms_mix_terms and ms_mix_air), DEEP-ALI evaluations (starks.rs:124-151).
+// air_stages.cpp — constraint columns by linear provenance, coset LDE + commitment (starks.rs:80-95), constraint mixing (starks.rs:108-119; build-defined ms_mix_cubic,
+// ms_mix_terms and ms_mix_air: one host pipeline - gate, table, upload, compose launch, finish_mix - and a compose kernel each), DEEP-ALI evaluations (starks.rs:124-151).
 #include "ctx.hpp"
 
 #include <algorithm>
@@ -220,99 +220,131 @@ int Ctx<F>::mix(u64 r) {
   return MS_OK;
 }
 
+// ------------------------------------------------------------------ the build-defined mix stages: one pipeline
+// ms_mix_cubic, ms_mix_terms and ms_mix_air (include/ministark.h) give the true quotient of a composition by x^N - 1.  Each stage is
+//   mix_gate -> its own checks -> coset_vanishing_inv -> its host table -> upload_mix_table -> its ONE compose launch into d_cubic -> finish_mix
+// and differs from the others in the checks, the table and the kernel only.  Everything that can be refused is refused before the first launch, except the
+// exactness of the division, which only the interpolant shows; nothing of the session changes before that result (but see the store guard in finish_mix).
 template <class F>
-int Ctx<F>::mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) {
-  if (!have_lde) return fail(MS_ERR_STATE, "mix_cubic before lde_commit");
-  if (lde_ts.sharded) return fail(MS_ERR_STATE, "mix_cubic: the LDE of a sharded proof is distributed over the ranks");
-  if (!spec || !sc || ncons < 1 || ncons > 4096 || r >= F::P) return fail(MS_ERR_ARG, "mix_cubic arguments");
-  if (blowup < 4) return fail(MS_ERR_SHAPE, "mix_cubic needs blowup >= 4 (the quotient has 2N coefficients, the composition 3N)");
-  const size_t c = lde_c;
-  for (int t = 0; t < ncons; t++) { for (int u = 0; u < 5; u++) if (spec[5 * t + u] < 0 || (size_t)spec[5 * t + u] >= c) return fail(MS_ERR_ARG, "mix_cubic: polynomial index out of range"); if (sc[t] >= F::P) return fail(MS_ERR_ARG, "mix_cubic: scalar not canonical"); }
+int Ctx<F>::mix_gate(const char* who, u64 r) {
+  if (!have_lde) return fail(MS_ERR_STATE, std::string(who) + " before lde_commit");
+  if (lde_ts.sharded) return fail(MS_ERR_STATE, std::string(who) + ": the LDE of a sharded proof is distributed over the ranks");
+  if (r >= F::P) return fail(MS_ERR_ARG, std::string(who) + " arguments");
+  return 0;
+}
+
+template <class F>
+int Ctx<F>::coset_vanishing_inv(const char* who, std::vector<T>& dinv) {
+  const T one = F::from_u64(1), shN = f_pow<F>(F::from_u64(lde_shift), (u64)N), zeta = f_pow<F>(f_root_of_unity<F>(ctz64(L)), (u64)N);
+  dinv.resize(blowup);
+  T z = one;
+  for (size_t k = 0; k < blowup; k++, z = F::mul(z, zeta)) {
+    const T den = F::sub(F::mul(shN, z), one);
+    if (den == 0) return fail(MS_ERR_SHAPE, std::string(who) + ": the LDE coset meets the trace domain (shift^N is a blowup-th root of unity)");
+    dinv[k] = f_inv<F>(den);
+  }
+  return 0;
+}
+
+template <class F>
+int Ctx<F>::check_term_program(const char* who, u32 ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, u32* deg_per_constraint, u32* d) {
+  auto bad = [&](const char* what) { return fail(MS_ERR_ARG, std::string(who) + what); };
+  if (term_begin[0] != 0) return bad(": term_begin[0] must be 0");
+  for (u32 t = 0; t < ncons; t++) if (term_begin[t + 1] < term_begin[t] || term_begin[t + 1] > 65536) return bad(": term_begin not monotone, or more than 65536 terms");
+  if (fac_begin[0] != 0) return bad(": fac_begin[0] must be 0");
+  *d = 0;
+  for (u32 t = 0; t < ncons; t++)
+    for (u32 m = term_begin[t]; m < term_begin[t + 1]; m++) {
+      if (fac_begin[m + 1] < fac_begin[m]) return bad(": fac_begin not monotone");
+      const u32 nf = fac_begin[m + 1] - fac_begin[m];
+      if (nf > (u32)mspoly::TERMS_MAX_FACTORS) return bad(": a term with more than 8 factors");
+      if (coef[m] >= F::P) return bad(": coefficient not canonical");
+      if (deg_per_constraint && nf > deg_per_constraint[t]) deg_per_constraint[t] = nf;
+      if (nf > *d) *d = nf;
+    }
+  if (*d == 0) return bad(": no term has a factor (d = 0)");
+  return 0;
+}
+
+template <class F>
+int Ctx<F>::upload_mix_table(const char* who, const u8* tab, size_t bytes) {
   if (lde_cols_virtual) { RQ(lincomb_linear_columns(d_lde.as<T>(), lde_col_stride, lde_col_len)); lde_cols_virtual = false; }
-  typedef mspoly::CubicSpec<F> CS;
-  typedef mspoly::CubicComposeKernel<F> CK_;
-  const int logL = ctz64(L), logN = ctz64(N);
-  const T gL = f_root_of_unity<F>(logL), wN = f_root_of_unity<F>(logN), sh = F::from_u64(lde_shift);
-  // x^N - 1 on the coset: shift^N * zeta^(i mod blowup) - 1, zeta = g_L^N
-  const T shN = f_pow<F>(sh, (u64)N), zeta = f_pow<F>(gL, (u64)N);
-  std::vector<T> dinv(blowup);
-  { T z = F::from_u64(1);
-    for (size_t k = 0; k < blowup; k++) { const T den = F::sub(F::mul(shN, z), F::from_u64(1)); if (den == 0) return fail(MS_ERR_SHAPE, "mix_cubic: the LDE coset meets the trace domain (shift^N is a blowup-th root of unity)"); dinv[k] = f_inv<F>(den); z = F::mul(z, zeta); } }
-  std::vector<CS> hs(ncons);
-  { T rp = F::from_u64(1);
-    for (int t = 0; t < ncons; t++) { hs[t].j = (u32)spec[5 * t]; hs[t].a = (u32)spec[5 * t + 1]; hs[t].b = (u32)spec[5 * t + 2]; hs[t].c = (u32)spec[5 * t + 3]; hs[t].d = (u32)spec[5 * t + 4]; hs[t].s = F::from_u64(sc[t]); hs[t].rpow = rp; rp = F::mul(rp, F::from_u64(r)); } }
-  const size_t tab_bytes = hs.size() * sizeof(CS) + dinv.size() * sizeof(T);
-  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(tab_bytes + 64)) return fail(MS_ERR_NOMEM, "mix_cubic buffers");
+  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(bytes + 64)) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
   u8* ht;
-  RQ(tabs_host(tab_bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
-  memcpy(ht, hs.data(), hs.size() * sizeof(CS));
-  memcpy(ht + hs.size() * sizeof(CS), dinv.data(), dinv.size() * sizeof(T));
-  CK(msrt::h2d(d_tabs.p, ht, tab_bytes, stream));
-  typename CK_::Params cp;
-  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.ncons = (u32)ncons; cp.spec = d_tabs.as<CS>();
-  cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + hs.size() * sizeof(CS));
-  cp.shift = sh; cp.gL = gL; cp.gL_step = f_pow<F>(gL, (u64)CK_::THREADS); cp.w_last = f_pow<F>(wN, (u64)(N - 1)); cp.out = d_cubic.as<T>();
-  CK(run<CK_>(K_MIX, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
-  // evaluations on shift * <g_L>  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k
-  T* coef = d_cubic.as<T>() + L;
-  RQ(ntt_run(logL, true, d_cubic.as<T>(), L, L, coef, L, 1));
-  RQ(ensure_polys(npolys + 2));
-  // exactness: nothing above 2N coefficients (the reference's `assert_eq!(rest, zero)` of starks.rs:119, for the true quotient)
+  RQ(tabs_host(bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
+  memcpy(ht, tab, bytes);
+  CK(msrt::h2d(d_tabs.p, ht, bytes, stream));
+  return 0;
+}
+
+// evaluations on shift * <g_L> (d_cubic)  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k.  The size-L interpolant I of the pointwise quotient satisfies
+// I (x^N - 1) = numerator on L points: with both sides of degree < L (the stages' SHAPE conditions), "I has at most VL coefficients" is "the division is exact" - the
+// reference's `assert_eq!(rest, zero)` of starks.rs:119, for the true quotient.  The stage's one stream synchronisation is here, for that answer.
+template <class F>
+int Ctx<F>::finish_mix(const char* refusal, size_t VL) {
+  T* cf = d_cubic.as<T>() + L;
+  RQ(ntt_run(ctz64(L), true, d_cubic.as<T>(), L, L, cf, L, 1));
+  if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
+  RQ(ensure_polys(npolys + VL / N));
   unsigned long long* dres;
-  RQ(degree_launch1(coef, L, &dres));
+  RQ(degree_launch1(cf, L, &dres));
   CK(msrt::d2h(pinned, dres, 8, stream));
   CK(msrt::sync(stream));
-  if (*reinterpret_cast<unsigned long long*>(pinned) > 2 * N) return fail(MS_ERR_SHAPE, "mix_cubic: the constraints do not vanish on the trace domain (the quotient by x^N - 1 is not a polynomial of 2N coefficients)");
-  validity_ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned)); validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
-  const T shi = f_inv<F>(sh);
-  RQ(scale_pow(coef, 0, d_polys.as<T>() + (size_t)npolys * N, 0, 2 * N, shi, 1));
-  have_validity = true; validity_len = 2 * N; nrounds_done = 0;
+  const size_t ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
+  if (ncoef > VL) return fail(MS_ERR_SHAPE, refusal);
+  RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, f_inv<F>(F::from_u64(lde_shift)), 1));
+  validity_ncoef = ncoef; validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
+  have_validity = true; validity_len = VL; nrounds_done = 0;
   return MS_OK;
 }
 
-// Build-defined composition of any degree (include/ministark.h): the constraints as sums of monomials over the polynomials, factors at row offsets, with the true
-// quotient by x^N - 1.  Same sequence as mix_cubic with 2N replaced by VL = N * next_pow2(slots), slots = max(1, d - 1) (one more when nexempt > d - 1), d = the most factors of any term.  Everything that can be
-// refused is refused before the first launch, except the exactness of the division, which only the interpolant shows; nothing of the session changes before that.
+// Degree-3 composition, C_t = P_j(w x) - P_a P_b P_c - s P_d with the last row exempt: a quotient of 2N coefficients (the composition has 3N)
+template <class F>
+int Ctx<F>::mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) {
+  RQ(mix_gate("mix_cubic", r));
+  if (!spec || !sc || ncons < 1 || ncons > 4096) return fail(MS_ERR_ARG, "mix_cubic arguments");
+  if (blowup < 4) return fail(MS_ERR_SHAPE, "mix_cubic needs blowup >= 4 (the quotient has 2N coefficients, the composition 3N)");
+  for (int t = 0; t < ncons; t++) { for (int u = 0; u < 5; u++) if (spec[5 * t + u] < 0 || (size_t)spec[5 * t + u] >= lde_c) return fail(MS_ERR_ARG, "mix_cubic: polynomial index out of range"); if (sc[t] >= F::P) return fail(MS_ERR_ARG, "mix_cubic: scalar not canonical"); }
+  typedef mspoly::CubicSpec<F> CS; typedef mspoly::CubicComposeKernel<F> CK_;
+  std::vector<T> dinv;
+  RQ(coset_vanishing_inv("mix_cubic", dinv));
+  // the device table: [constraints | den_inv], r^t beside constraint t
+  const size_t off_d = (size_t)ncons * sizeof(CS), tab_bytes = off_d + dinv.size() * sizeof(T);
+  std::vector<u8> tab(tab_bytes, 0);
+  { CS* hs = reinterpret_cast<CS*>(tab.data());
+    T rp = F::from_u64(1);
+    for (int t = 0; t < ncons; t++) { hs[t].j = (u32)spec[5 * t]; hs[t].a = (u32)spec[5 * t + 1]; hs[t].b = (u32)spec[5 * t + 2]; hs[t].c = (u32)spec[5 * t + 3]; hs[t].d = (u32)spec[5 * t + 4]; hs[t].s = F::from_u64(sc[t]); hs[t].rpow = rp; rp = F::mul(rp, F::from_u64(r)); }
+    memcpy(tab.data() + off_d, dinv.data(), dinv.size() * sizeof(T)); }
+  RQ(upload_mix_table("mix_cubic", tab.data(), tab_bytes));
+  const T gL = f_root_of_unity<F>(ctz64(L)), wN = f_root_of_unity<F>(ctz64(N));
+  typename CK_::Params cp;
+  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.ncons = (u32)ncons; cp.spec = d_tabs.as<CS>();
+  cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_d);
+  cp.shift = F::from_u64(lde_shift); cp.gL = gL; cp.gL_step = f_pow<F>(gL, (u64)CK_::THREADS); cp.w_last = f_pow<F>(wN, (u64)(N - 1)); cp.out = d_cubic.as<T>();
+  CK(run<CK_>(K_MIX, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
+  return finish_mix("mix_cubic: the constraints do not vanish on the trace domain (the quotient by x^N - 1 is not a polynomial of 2N coefficients)", 2 * N);
+}
+
+// Composition of any degree: the constraints as sums of monomials over the polynomials, factors at row offsets, the last nexempt rows exempt.
+// VL = N * next_pow2(slots), slots = max(1, d - 1) (one more when nexempt > d - 1), d = the most factors of any term.
 template <class F>
 int Ctx<F>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) {
-  if (!have_lde) return fail(MS_ERR_STATE, "mix_terms before lde_commit");
-  if (lde_ts.sharded) return fail(MS_ERR_STATE, "mix_terms: the LDE of a sharded proof is distributed over the ranks");
+  RQ(mix_gate("mix_terms", r));
   if (!term_begin || !coef || !fac_begin || !fac_poly || !fac_row) return fail(MS_ERR_ARG, "mix_terms: null array");
-  if (ncons < 1 || ncons > 4096 || r >= F::P || nexempt < 0 || nexempt > mspoly::TERMS_MAX_EXEMPT) return fail(MS_ERR_ARG, "mix_terms arguments");
-  if (term_begin[0] != 0) return fail(MS_ERR_ARG, "mix_terms: term_begin[0] must be 0");
-  for (int t = 0; t < ncons; t++) if (term_begin[t + 1] < term_begin[t] || term_begin[t + 1] > 65536) return fail(MS_ERR_ARG, "mix_terms: term_begin not monotone, or more than 65536 terms");
-  const u32 nterms = term_begin[ncons];
-  if (fac_begin[0] != 0) return fail(MS_ERR_ARG, "mix_terms: fac_begin[0] must be 0");
-  u32 d = 0;
-  for (u32 m = 0; m < nterms; m++) {
-    if (fac_begin[m + 1] < fac_begin[m]) return fail(MS_ERR_ARG, "mix_terms: fac_begin not monotone");
-    const u32 nf = fac_begin[m + 1] - fac_begin[m];
-    if (nf > (u32)mspoly::TERMS_MAX_FACTORS) return fail(MS_ERR_ARG, "mix_terms: a term with more than 8 factors");
-    if (coef[m] >= F::P) return fail(MS_ERR_ARG, "mix_terms: coefficient not canonical");
-    if (nf > d) d = nf;
-  }
-  if (d == 0) return fail(MS_ERR_ARG, "mix_terms: no term has a factor (d = 0)");
-  const u32 nfacs = fac_begin[nterms];
-  const size_t c = lde_c;
-  for (u32 f = 0; f < nfacs; f++) if ((size_t)fac_poly[f] >= c || (size_t)fac_row[f] >= N) return fail(MS_ERR_ARG, "mix_terms: polynomial index or row offset out of range");
+  if (ncons < 1 || ncons > 4096 || nexempt < 0 || nexempt > mspoly::TERMS_MAX_EXEMPT) return fail(MS_ERR_ARG, "mix_terms arguments");
+  u32 d;
+  RQ(check_term_program("mix_terms", (u32)ncons, term_begin, coef, fac_begin, nullptr, &d));
+  const u32 nterms = term_begin[ncons], nfacs = fac_begin[nterms];
+  for (u32 f = 0; f < nfacs; f++) if ((size_t)fac_poly[f] >= lde_c || (size_t)fac_row[f] >= N) return fail(MS_ERR_ARG, "mix_terms: polynomial index or row offset out of range");
   // the quotient has at most (d - 1) N - d + nexempt + 1 coefficients: d - 1 slots of N, one more when nexempt > d - 1
   const size_t need = (size_t)(d - 1) * N + (size_t)nexempt + 1 - d, need_slots = (need + N - 1) / N;
   size_t slots = d > 1 ? d - 1 : 1; if (need_slots > slots) slots = need_slots;
   size_t vmul = 1; while (vmul < slots) vmul <<= 1;
   const size_t VL = N * vmul;
-  // the size-L interpolant I of the pointwise quotient satisfies I (x^N - 1) = numerator on L points: with both sides of degree < L, "I has at most VL coefficients"
-  // is "the division is exact"
   if (!((size_t)d * (N - 1) + (size_t)nexempt < L) || VL + N > L) return fail(MS_ERR_SHAPE, "mix_terms: the LDE domain is too small to decide exactness (need d (N - 1) + nexempt < L and VL + N <= L)");
-  typedef mspoly::TermRec<F> TR;
-  typedef mspoly::TermFac TF;
-  typedef mspoly::ComposeTermsKernel<F> CK_;
-  const int logL = ctz64(L), logN = ctz64(N);
-  const T gL = f_root_of_unity<F>(logL), wN = f_root_of_unity<F>(logN), sh = F::from_u64(lde_shift);
-  // x^N - 1 on the coset: shift^N * zeta^(i mod blowup) - 1, zeta = g_L^N
-  const T shN = f_pow<F>(sh, (u64)N), zeta = f_pow<F>(gL, (u64)N);
-  std::vector<T> dinv(blowup);
-  { T z = F::from_u64(1);
-    for (size_t k = 0; k < blowup; k++) { const T den = F::sub(F::mul(shN, z), F::from_u64(1)); if (den == 0) return fail(MS_ERR_SHAPE, "mix_terms: the LDE coset meets the trace domain (shift^N is a blowup-th root of unity)"); dinv[k] = f_inv<F>(den); z = F::mul(z, zeta); } }
+  typedef mspoly::TermRec<F> TR; typedef mspoly::TermFac TF; typedef mspoly::ComposeTermsKernel<F> CK_;
+  std::vector<T> dinv;
+  RQ(coset_vanishing_inv("mix_terms", dinv));
   // the device table: [terms | factors | exemption roots | den_inv], r^t folded into the coefficients of constraint t's terms
   const size_t off_f = ((size_t)nterms * sizeof(TR) + 15) & ~(size_t)15, off_x = (off_f + (size_t)nfacs * sizeof(TF) + 15) & ~(size_t)15;
   const size_t off_d = off_x + mspoly::TERMS_MAX_EXEMPT * sizeof(T), tab_bytes = off_d + dinv.size() * sizeof(T);
@@ -324,86 +356,48 @@ int Ctx<F>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, 
       rp = F::mul(rp, F::from_u64(r));
     }
     for (u32 f = 0; f < nfacs; f++) { hf[f].poly = fac_poly[f]; hf[f].rowoff = (u32)((size_t)fac_row[f] * blowup); }
-    T wk = f_inv<F>(wN), wi = wk;                                // w^(N-k) = w^-k
+    T wi = f_inv<F>(f_root_of_unity<F>(ctz64(N))), wk = wi;      // w^(N-k) = w^-k
     for (int k = 0; k < nexempt; k++) { hx[k] = wk; wk = F::mul(wk, wi); }
     memcpy(tab.data() + off_d, dinv.data(), dinv.size() * sizeof(T)); }
-  if (lde_cols_virtual) { RQ(lincomb_linear_columns(d_lde.as<T>(), lde_col_stride, lde_col_len)); lde_cols_virtual = false; }
-  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(tab_bytes + 64)) return fail(MS_ERR_NOMEM, "mix_terms buffers");
-  u8* ht;
-  RQ(tabs_host(tab_bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
-  memcpy(ht, tab.data(), tab_bytes);
-  CK(msrt::h2d(d_tabs.p, ht, tab_bytes, stream));
+  RQ(upload_mix_table("mix_terms", tab.data(), tab_bytes));
+  const T gL = f_root_of_unity<F>(ctz64(L));
   typename CK_::Params cp;
   cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.nterms = nterms; cp.nexempt = (u32)nexempt;
   cp.terms = d_tabs.as<TR>(); cp.facs = reinterpret_cast<const TF*>(d_tabs.as<u8>() + off_f);
   cp.ex_roots = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_x); cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_d);
-  cp.shift = sh; cp.gL = gL; cp.gL_step = f_pow<F>(gL, (u64)CK_::THREADS); cp.out = d_cubic.as<T>();
+  cp.shift = F::from_u64(lde_shift); cp.gL = gL; cp.gL_step = f_pow<F>(gL, (u64)CK_::THREADS); cp.out = d_cubic.as<T>();
   next_bytes = (double)(nfacs + 1) * L * sizeof(T);
   CK(run<CK_>(K_MIX_TERMS, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
-  // evaluations on shift * <g_L>  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k
-  T* cf = d_cubic.as<T>() + L;
-  RQ(ntt_run(logL, true, d_cubic.as<T>(), L, L, cf, L, 1));
-  if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
-  RQ(ensure_polys(npolys + VL / N));
-  unsigned long long* dres;
-  RQ(degree_launch1(cf, L, &dres));
-  CK(msrt::d2h(pinned, dres, 8, stream));
-  CK(msrt::sync(stream));
-  if (*reinterpret_cast<unsigned long long*>(pinned) > VL) return fail(MS_ERR_SHAPE, "mix_terms: the constraints do not vanish on the non-exempt rows (the quotient by x^N - 1 is not a polynomial of VL coefficients)");
-  const size_t ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
-  const T shi = f_inv<F>(sh);
-  RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, shi, 1));
-  validity_ncoef = ncoef; validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
-  have_validity = true; validity_len = VL; nrounds_done = 0;
-  return MS_OK;
+  return finish_mix("mix_terms: the constraints do not vanish on the non-exempt rows (the quotient by x^N - 1 is not a polynomial of VL coefficients)", VL);
 }
 
-// Build-defined AIR composition (include/ministark.h): ms_mix_terms with an exemption set per constraint, periodic columns and boundary constraints.  Same sequence as
-// mix_terms - validate, materialise virtual columns, one device table [groups | terms | factors | exemption roots | periodic tables | den_inv], compose launch, size-L
-// INTT, degree check against VL, un-shift - with the program regrouped for mspoly::ComposeAirKernel: the constraints that share an exemption set form one group, the
-// boundary constraints at one row another.  Everything that can be refused is refused before the first launch, except the exactness of the divisions.
+// ---- ms_mix_air: ms_mix_terms with an exemption set per constraint, periodic columns and boundary constraints, the program regrouped for mspoly::ComposeAirKernel -
+// the constraints that share an exemption set form one group, the boundary constraints at one row another.
+// Every MS_ERR_ARG refusal of the stage; fills pg
 template <class F>
-int Ctx<F>::mix_air(u64 r, const ms_air* air) {
-  if (!have_lde) return fail(MS_ERR_STATE, "mix_air before lde_commit");
-  if (lde_ts.sharded) return fail(MS_ERR_STATE, "mix_air: the LDE of a sharded proof is distributed over the ranks");
-  if (!air) return fail(MS_ERR_ARG, "mix_air: null program");
-  const ms_air& a = *air;
+int Ctx<F>::air_validate(const ms_air& a, AirProgram& pg) {
   if (!a.term_begin || !a.coef || !a.fac_begin || !a.fac_poly || !a.fac_row || !a.ex_begin) return fail(MS_ERR_ARG, "mix_air: null array");
-  if (a.ncons < 1 || a.ncons > 4096 || r >= F::P || a.nperiodic > (u32)mspoly::AIR_MAX_PERIODIC || a.nbound > 4096) return fail(MS_ERR_ARG, "mix_air arguments");
+  if (a.ncons < 1 || a.ncons > 4096 || a.nperiodic > (u32)mspoly::AIR_MAX_PERIODIC || a.nbound > 4096) return fail(MS_ERR_ARG, "mix_air arguments");
   if ((a.nperiodic && (!a.per_begin || !a.per_val)) || (a.nbound && (!a.bnd_poly || !a.bnd_row || !a.bnd_val))) return fail(MS_ERR_ARG, "mix_air: null array");
   const u32 ncons = a.ncons;
   const size_t c = lde_c;
-  // ---- the term program: the conditions of mix_terms, the degree per constraint
-  if (a.term_begin[0] != 0) return fail(MS_ERR_ARG, "mix_air: term_begin[0] must be 0");
-  for (u32 t = 0; t < ncons; t++) if (a.term_begin[t + 1] < a.term_begin[t] || a.term_begin[t + 1] > 65536) return fail(MS_ERR_ARG, "mix_air: term_begin not monotone, or more than 65536 terms");
-  const u32 nterms = a.term_begin[ncons];
-  if (a.fac_begin[0] != 0) return fail(MS_ERR_ARG, "mix_air: fac_begin[0] must be 0");
-  std::vector<u32> deg(ncons, 0);
-  u32 d = 0;
-  for (u32 t = 0; t < ncons; t++)
-    for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++) {
-      if (a.fac_begin[m + 1] < a.fac_begin[m]) return fail(MS_ERR_ARG, "mix_air: fac_begin not monotone");
-      const u32 nf = a.fac_begin[m + 1] - a.fac_begin[m];
-      if (nf > (u32)mspoly::TERMS_MAX_FACTORS) return fail(MS_ERR_ARG, "mix_air: a term with more than 8 factors");
-      if (a.coef[m] >= F::P) return fail(MS_ERR_ARG, "mix_air: coefficient not canonical");
-      if (nf > deg[t]) deg[t] = nf;
-      if (nf > d) d = nf;
-    }
-  if (d == 0) return fail(MS_ERR_ARG, "mix_air: no term has a factor (d = 0)");
-  const u32 nfacs = a.fac_begin[nterms];
+  u32 d;                                     // ---- the term program: the conditions of mix_terms, the degree per constraint
+  pg.deg.assign(ncons, 0);
+  RQ(check_term_program("mix_air", ncons, a.term_begin, a.coef, a.fac_begin, pg.deg.data(), &d));
+  pg.nterms = a.term_begin[ncons]; pg.nfacs = a.fac_begin[pg.nterms];
   // ---- periodic columns
-  std::vector<u32> per_off(a.nperiodic + 1, 0);   // offsets of the columns' tables in the device table, in elements: column k has blowup * q_k entries
+  pg.per_off.assign(a.nperiodic + 1, 0);
   if (a.nperiodic) {
     if (a.per_begin[0] != 0) return fail(MS_ERR_ARG, "mix_air: per_begin[0] must be 0");
     for (u32 k = 0; k < a.nperiodic; k++) {
       if (a.per_begin[k + 1] <= a.per_begin[k] || a.per_begin[k + 1] > (u32)mspoly::AIR_MAX_PERIOD_SUM) return fail(MS_ERR_ARG, "mix_air: per_begin not increasing, or the periods sum to more than 4096");
       const size_t q = a.per_begin[k + 1] - a.per_begin[k];
       if (!is_pow2(q) || q > N || q > (size_t)mspoly::AIR_MAX_PERIOD) return fail(MS_ERR_ARG, "mix_air: a period that is no power of two or exceeds min(N, 256)");
-      per_off[k + 1] = per_off[k] + (u32)(q * blowup);
+      pg.per_off[k + 1] = pg.per_off[k] + (u32)(q * blowup);
     }
     if (!canonical(a.per_val, a.per_begin[a.nperiodic])) return fail(MS_ERR_ARG, "mix_air: periodic value not canonical");
   }
-  for (u32 f = 0; f < nfacs; f++) {
+  for (u32 f = 0; f < pg.nfacs; f++) {
     const u32 fp = a.fac_poly[f];
     if ((fp & MS_AIR_PERIODIC) ? (fp & ~MS_AIR_PERIODIC) >= a.nperiodic : (size_t)fp >= c) return fail(MS_ERR_ARG, "mix_air: polynomial or periodic column index out of range");
     if ((size_t)a.fac_row[f] >= N) return fail(MS_ERR_ARG, "mix_air: row offset out of range");
@@ -412,150 +406,149 @@ int Ctx<F>::mix_air(u64 r, const ms_air* air) {
   if (a.ex_begin[0] != 0) return fail(MS_ERR_ARG, "mix_air: ex_begin[0] must be 0");
   for (u32 t = 0; t < ncons; t++) if (a.ex_begin[t + 1] < a.ex_begin[t] || a.ex_begin[t + 1] - a.ex_begin[t] > (u32)mspoly::AIR_MAX_EXEMPT) return fail(MS_ERR_ARG, "mix_air: ex_begin not monotone, or more than 16 exempt rows for a constraint");
   if (a.ex_begin[ncons] && !a.ex_row) return fail(MS_ERR_ARG, "mix_air: null array");
-  std::vector<std::vector<u32>> sets;
-  std::vector<u32> set_of(ncons);
-  { std::map<std::vector<u32>, u32> seen;
-    for (u32 t = 0; t < ncons; t++) {
-      std::vector<u32> s(a.ex_row ? a.ex_row + a.ex_begin[t] : nullptr, a.ex_row ? a.ex_row + a.ex_begin[t + 1] : nullptr);
-      std::sort(s.begin(), s.end());
-      for (size_t k = 0; k < s.size(); k++) if ((size_t)s[k] >= N || (k && s[k] == s[k - 1])) return fail(MS_ERR_ARG, "mix_air: exempt row out of range, or named twice in one set");
-      auto it = seen.find(s);
-      if (it == seen.end()) {
-        if (sets.size() == (size_t)mspoly::AIR_MAX_SETS) return fail(MS_ERR_ARG, "mix_air: more than 32 distinct exemption sets");
-        it = seen.emplace(s, (u32)sets.size()).first; sets.push_back(s);
-      }
-      set_of[t] = it->second;
-    } }
+  pg.set_of.assign(ncons, 0);
+  std::map<std::vector<u32>, u32> seen;
+  for (u32 t = 0; t < ncons; t++) {
+    std::vector<u32> s(a.ex_row ? a.ex_row + a.ex_begin[t] : nullptr, a.ex_row ? a.ex_row + a.ex_begin[t + 1] : nullptr);
+    std::sort(s.begin(), s.end());
+    for (size_t k = 0; k < s.size(); k++) if ((size_t)s[k] >= N || (k && s[k] == s[k - 1])) return fail(MS_ERR_ARG, "mix_air: exempt row out of range, or named twice in one set");
+    auto it = seen.find(s);
+    if (it == seen.end()) {
+      if (pg.sets.size() == (size_t)mspoly::AIR_MAX_SETS) return fail(MS_ERR_ARG, "mix_air: more than 32 distinct exemption sets");
+      it = seen.emplace(s, (u32)pg.sets.size()).first; pg.sets.push_back(s);
+    }
+    pg.set_of[t] = it->second;
+  }
   // ---- boundary constraints: one group per distinct row
-  std::vector<u32> brows;
-  std::vector<u32> brow_of(a.nbound);
+  pg.brow_of.assign(a.nbound, 0);
   for (u32 b = 0; b < a.nbound; b++) {
     if ((size_t)a.bnd_poly[b] >= c || (size_t)a.bnd_row[b] >= N || a.bnd_val[b] >= F::P) return fail(MS_ERR_ARG, "mix_air: boundary polynomial or row out of range, or value not canonical");
-    size_t k = 0; while (k < brows.size() && brows[k] != a.bnd_row[b]) k++;
-    if (k == brows.size()) { if (k == (size_t)mspoly::AIR_MAX_BOUNDARY_ROWS) return fail(MS_ERR_ARG, "mix_air: more than 16 distinct boundary rows"); brows.push_back(a.bnd_row[b]); }
-    brow_of[b] = (u32)k;
+    size_t k = 0; while (k < pg.brows.size() && pg.brows[k] != a.bnd_row[b]) k++;
+    if (k == pg.brows.size()) { if (k == (size_t)mspoly::AIR_MAX_BOUNDARY_ROWS) return fail(MS_ERR_ARG, "mix_air: more than 16 distinct boundary rows"); pg.brows.push_back(a.bnd_row[b]); }
+    pg.brow_of[b] = (u32)k;
   }
-  // ---- sizes.  Constraint t's quotient has d_t (N - 1) + e_t - N + 1 coefficients, a boundary quotient N - 1
+  return 0;
+}
+
+// Sizes, and the stage's MS_ERR_SHAPE refusal.  Constraint t's quotient has d_t (N - 1) + e_t - N + 1 coefficients, a boundary quotient N - 1
+template <class F>
+int Ctx<F>::air_layout(const ms_air& a, const AirProgram& pg, AirLayout& lay) {
   size_t top = 0;                                      // max_t (d_t (N - 1) + e_t): >= N - 1, some d_t is at least 1
-  for (u32 t = 0; t < ncons; t++) { const size_t v = (size_t)deg[t] * (N - 1) + (a.ex_begin[t + 1] - a.ex_begin[t]); if (v > top) top = v; }
+  for (u32 t = 0; t < a.ncons; t++) { const size_t v = (size_t)pg.deg[t] * (N - 1) + (a.ex_begin[t + 1] - a.ex_begin[t]); if (v > top) top = v; }
   size_t nq = top + 1 - N;
   if (a.nbound && N - 1 > nq) nq = N - 1;
   if (nq < 1) nq = 1;
   size_t vmul = 1; while (vmul < (nq + N - 1) / N) vmul <<= 1;
-  const size_t VL = N * vmul;
+  lay.VL = N * vmul;
   // multiplied by x^N - 1 the pointwise sum is a polynomial of degree < L under exactly these conditions: then "the size-L interpolant has at most VL coefficients"
   // is "every division is exact" (for the random combination)
-  if (!(top < L) || (a.nbound && !(2 * N - 2 < L)) || VL + N > L)
+  if (!(top < L) || (a.nbound && !(2 * N - 2 < L)) || lay.VL + N > L)
     return fail(MS_ERR_SHAPE, "mix_air: the LDE domain is too small to decide exactness (need max_t (d_t (N - 1) + e_t) < L, 2N - 2 < L with boundary constraints, VL + N <= L)");
-  typedef mspoly::TermRec<F> TR;
-  typedef mspoly::AirFac AF;
-  typedef mspoly::AirGroup AG;
-  typedef mspoly::ComposeAirKernel<F> CK_;
-  const int logL = ctz64(L), logN = ctz64(N);
-  const T gL = f_root_of_unity<F>(logL), wN = f_root_of_unity<F>(logN), sh = F::from_u64(lde_shift), one = F::from_u64(1);
-  // x^N - 1 on the coset: shift^N * zeta^(i mod blowup) - 1, zeta = g_L^N
-  const T shN = f_pow<F>(sh, (u64)N), zeta = f_pow<F>(gL, (u64)N);
-  std::vector<T> dinv(blowup);
-  { T z = one;
-    for (size_t k = 0; k < blowup; k++) { const T den = F::sub(F::mul(shN, z), one); if (den == 0) return fail(MS_ERR_SHAPE, "mix_air: the LDE coset meets the trace domain (shift^N is a blowup-th root of unity)"); dinv[k] = f_inv<F>(den); z = F::mul(z, zeta); } }
-  // ---- the device table
-  const size_t ngroups = sets.size() + brows.size(), tterms = (size_t)nterms + a.nbound + brows.size(), tfacs = (size_t)nfacs + a.nbound;
-  size_t nroots = 0; for (auto& s : sets) nroots += s.size();
-  const size_t off_t = ((size_t)ngroups * sizeof(AG) + 15) & ~(size_t)15, off_f = (off_t + tterms * sizeof(TR) + 15) & ~(size_t)15, off_x = (off_f + tfacs * sizeof(AF) + 15) & ~(size_t)15;
-  const size_t off_p = (off_x + nroots * sizeof(T) + 15) & ~(size_t)15, off_d = (off_p + (size_t)per_off[a.nperiodic] * sizeof(T) + 15) & ~(size_t)15, tab_bytes = off_d + dinv.size() * sizeof(T);
-  std::vector<u8> tab(tab_bytes, 0);
-  { AG* hg = reinterpret_cast<AG*>(tab.data()); TR* ht = reinterpret_cast<TR*>(tab.data() + off_t); AF* hf = reinterpret_cast<AF*>(tab.data() + off_f);
-    T* hx = reinterpret_cast<T*>(tab.data() + off_x); T* hp = reinterpret_cast<T*>(tab.data() + off_p);
-    std::vector<T> rpow((size_t)ncons + a.nbound);
-    { T rp = one; for (auto& v : rpow) { v = rp; rp = F::mul(rp, F::from_u64(r)); } }
-    size_t m_out = 0, f_out = 0, x_out = 0;
-    for (size_t g = 0; g < sets.size(); g++) {      // transition groups: the terms of the group's constraints in the caller's order, r^t folded into the coefficients
-      const size_t m_first = m_out;
-      for (u32 t = 0; t < ncons; t++) {
-        if (set_of[t] != g) continue;
-        for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++, m_out++) {
-          ht[m_out].coef = F::mul(rpow[t], F::from_u64(a.coef[m])); ht[m_out].nfac = a.fac_begin[m + 1] - a.fac_begin[m];
-          for (u32 f = a.fac_begin[m]; f < a.fac_begin[m + 1]; f++, f_out++) {
-            const u32 fp = a.fac_poly[f];
-            hf[f_out].rowoff = (u32)((size_t)a.fac_row[f] * blowup);
-            if (fp & MS_AIR_PERIODIC) { const u32 k = fp & ~MS_AIR_PERIODIC; hf[f_out].src = per_off[k]; hf[f_out].mask = per_off[k + 1] - per_off[k] - 1; hf[f_out].kind = 1; }
-            else { hf[f_out].src = fp; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; }
-          }
+  lay.ngroups = pg.sets.size() + pg.brows.size(); lay.tterms = (size_t)pg.nterms + a.nbound + pg.brows.size(); lay.tfacs = (size_t)pg.nfacs + a.nbound;
+  size_t nroots = 0; for (auto& s : pg.sets) nroots += s.size();
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  lay.off_t = up16(lay.ngroups * sizeof(mspoly::AirGroup)); lay.off_f = up16(lay.off_t + lay.tterms * sizeof(mspoly::TermRec<F>)); lay.off_x = up16(lay.off_f + lay.tfacs * sizeof(mspoly::AirFac));
+  lay.off_p = up16(lay.off_x + nroots * sizeof(T)); lay.off_d = up16(lay.off_p + (size_t)pg.per_off[a.nperiodic] * sizeof(T)); lay.bytes = lay.off_d + blowup * sizeof(T);
+  return 0;
+}
+
+// The device table (lay.bytes zeroed bytes at tab), r^t folded into the coefficients of constraint t's terms, r^(ncons+b) into boundary constraint b's
+template <class F>
+void Ctx<F>::air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLayout& lay, const std::vector<T>& dinv, u8* tab) {
+  typedef mspoly::AirFac AF; typedef mspoly::AirGroup AG;
+  AG* hg = reinterpret_cast<AG*>(tab); mspoly::TermRec<F>* ht = reinterpret_cast<mspoly::TermRec<F>*>(tab + lay.off_t); AF* hf = reinterpret_cast<AF*>(tab + lay.off_f);
+  T* hx = reinterpret_cast<T*>(tab + lay.off_x); T* hp = reinterpret_cast<T*>(tab + lay.off_p);
+  const u32 ncons = a.ncons;
+  const T gL = f_root_of_unity<F>(ctz64(L)), wN = f_root_of_unity<F>(ctz64(N)), wi = f_inv<F>(wN), sh = F::from_u64(lde_shift), one = F::from_u64(1);
+  std::vector<T> rpow((size_t)ncons + a.nbound);
+  { T rp = one; for (auto& v : rpow) { v = rp; rp = F::mul(rp, F::from_u64(r)); } }
+  size_t m_out = 0, f_out = 0, x_out = 0;
+  for (size_t g = 0; g < pg.sets.size(); g++) {      // transition groups: the terms of the group's constraints in the caller's order
+    const size_t m_first = m_out;
+    for (u32 t = 0; t < ncons; t++) {
+      if (pg.set_of[t] != g) continue;
+      for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++, m_out++) {
+        ht[m_out].coef = F::mul(rpow[t], F::from_u64(a.coef[m])); ht[m_out].nfac = a.fac_begin[m + 1] - a.fac_begin[m];
+        for (u32 f = a.fac_begin[m]; f < a.fac_begin[m + 1]; f++, f_out++) {
+          const u32 fp = a.fac_poly[f];
+          hf[f_out].rowoff = (u32)((size_t)a.fac_row[f] * blowup);
+          if (fp & MS_AIR_PERIODIC) { const u32 k = fp & ~MS_AIR_PERIODIC; hf[f_out].src = pg.per_off[k]; hf[f_out].mask = pg.per_off[k + 1] - pg.per_off[k] - 1; hf[f_out].kind = 1; }
+          else { hf[f_out].src = fp; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; }
         }
       }
-      for (u32 rho : sets[g]) hx[x_out++] = f_pow<F>(wN, (u64)rho);
-      hg[g].nterms = (u32)(m_out - m_first); hg[g].nroots = (u32)sets[g].size(); hg[g].kind = 0; hg[g].moff = 0;
     }
-    const T wi = f_inv<F>(wN);
-    for (size_t k = 0; k < brows.size(); k++) {     // boundary groups: (sum_b r^(ncons+b) w^-rho (P_j - v_b)) * D[i - rho blowup]
-      const size_t m_first = m_out;
-      const T wr = f_pow<F>(wi, (u64)brows[k]);
-      T cst = 0;
-      for (u32 b = 0; b < a.nbound; b++) {
-        if (brow_of[b] != k) continue;
-        const T cf = F::mul(rpow[(size_t)ncons + b], wr);
-        ht[m_out].coef = cf; ht[m_out].nfac = 1; m_out++;
-        hf[f_out].src = a.bnd_poly[b]; hf[f_out].rowoff = 0; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; f_out++;
-        cst = F::add(cst, F::mul(cf, F::from_u64(a.bnd_val[b])));
-      }
-      ht[m_out].coef = F::neg(cst); ht[m_out].nfac = 0; m_out++;
-      AG& gr = hg[sets.size() + k];
-      gr.nterms = (u32)(m_out - m_first); gr.nroots = 0; gr.kind = 1; gr.moff = (u32)(((N - brows[k]) % N) * blowup);
-    }
-    // periodic column k on the domain: K_k(x_i) = Q_k(x_i^(N/q)) takes blowup * q values, tab[u] = Q_k(shift^(N/q) g_L^(u N/q))
-    for (u32 k = 0; k < a.nperiodic; k++) {
-      const size_t q = a.per_begin[k + 1] - a.per_begin[k], step = N / q;
-      const u64* val = a.per_val + a.per_begin[k];
-      const T eta_inv = f_pow<F>(wi, (u64)step), qinv = f_inv<F>(F::from_u64((u64)q));
-      std::vector<T> Q(q);
-      { T em = one;                                  // eta^-m
-        for (size_t m = 0; m < q; m++) { T s = 0, e = one; for (size_t i = 0; i < q; i++) { s = F::add(s, F::mul(F::from_u64(val[i]), e)); e = F::mul(e, em); } Q[m] = F::mul(s, qinv); em = F::mul(em, eta_inv); } }
-      const T zq = f_pow<F>(gL, (u64)step);
-      T x = f_pow<F>(sh, (u64)step);
-      for (size_t u = 0; u < q * blowup; u++) { T v = 0; for (size_t m = q; m-- > 0;) v = F::add(F::mul(v, x), Q[m]); hp[per_off[k] + u] = v; x = F::mul(x, zq); }
-    }
-    memcpy(tab.data() + off_d, dinv.data(), dinv.size() * sizeof(T)); }
-  if (lde_cols_virtual) { RQ(lincomb_linear_columns(d_lde.as<T>(), lde_col_stride, lde_col_len)); lde_cols_virtual = false; }
-  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(tab_bytes + 64)) return fail(MS_ERR_NOMEM, "mix_air buffers");
-  const T gstep = f_pow<F>(gL, (u64)CK_::THREADS);
-  if (a.nbound && !(air_inv_valid && air_inv_N == N && air_inv_blowup == blowup && air_inv_shift == lde_shift)) {   // D[i] = 1 / (x_i - 1): one table for every boundary row
-    typedef mspoly::CosetInvKernel<F> IK;
-    static_assert(IK::THREADS == CK_::THREADS, "gL_step is shared");
-    air_inv_valid = false;
-    if (d_air_inv.ensure(L * sizeof(T))) return fail(MS_ERR_NOMEM, "mix_air: boundary inverse table");
-    typename IK::Params ip{L, sh, gL, gstep, d_air_inv.as<T>()};
-    next_bytes = (double)L * sizeof(T);
-    CK(run<IK>(K_AIR_INV, grid1(L, IK::THREADS * IK::ITEMS), 1, IK::THREADS, 0, ip));
-    air_inv_valid = true; air_inv_N = N; air_inv_blowup = blowup; air_inv_shift = lde_shift;
+    for (u32 rho : pg.sets[g]) hx[x_out++] = f_pow<F>(wN, (u64)rho);
+    hg[g].nterms = (u32)(m_out - m_first); hg[g].nroots = (u32)pg.sets[g].size(); hg[g].kind = 0; hg[g].moff = 0;
   }
-  u8* ht;
-  RQ(tabs_host(tab_bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
-  memcpy(ht, tab.data(), tab_bytes);
-  CK(msrt::h2d(d_tabs.p, ht, tab_bytes, stream));
+  for (size_t k = 0; k < pg.brows.size(); k++) {     // boundary groups: (sum_b r^(ncons+b) w^-rho (P_j - v_b)) * D[i - rho blowup]
+    const size_t m_first = m_out;
+    const T wr = f_pow<F>(wi, (u64)pg.brows[k]);
+    T cst = 0;
+    for (u32 b = 0; b < a.nbound; b++) {
+      if (pg.brow_of[b] != k) continue;
+      const T cf = F::mul(rpow[(size_t)ncons + b], wr);
+      ht[m_out].coef = cf; ht[m_out].nfac = 1; m_out++;
+      hf[f_out].src = a.bnd_poly[b]; hf[f_out].rowoff = 0; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; f_out++;
+      cst = F::add(cst, F::mul(cf, F::from_u64(a.bnd_val[b])));
+    }
+    ht[m_out].coef = F::neg(cst); ht[m_out].nfac = 0; m_out++;
+    AG& gr = hg[pg.sets.size() + k];
+    gr.nterms = (u32)(m_out - m_first); gr.nroots = 0; gr.kind = 1; gr.moff = (u32)(((N - pg.brows[k]) % N) * blowup);
+  }
+  // periodic column k on the domain: K_k(x_i) = Q_k(x_i^(N/q)) takes blowup * q values, tab[u] = Q_k(shift^(N/q) g_L^(u N/q))
+  for (u32 k = 0; k < a.nperiodic; k++) {
+    const size_t q = a.per_begin[k + 1] - a.per_begin[k], step = N / q;
+    const u64* val = a.per_val + a.per_begin[k];
+    const T eta_inv = f_pow<F>(wi, (u64)step), qinv = f_inv<F>(F::from_u64((u64)q));
+    std::vector<T> Q(q);
+    { T em = one;                                  // eta^-m
+      for (size_t m = 0; m < q; m++) { T s = 0, e = one; for (size_t i = 0; i < q; i++) { s = F::add(s, F::mul(F::from_u64(val[i]), e)); e = F::mul(e, em); } Q[m] = F::mul(s, qinv); em = F::mul(em, eta_inv); } }
+    const T zq = f_pow<F>(gL, (u64)step);
+    T x = f_pow<F>(sh, (u64)step);
+    for (size_t u = 0; u < q * blowup; u++) { T v = 0; for (size_t m = q; m-- > 0;) v = F::add(F::mul(v, x), Q[m]); hp[pg.per_off[k] + u] = v; x = F::mul(x, zq); }
+  }
+  memcpy(tab + lay.off_d, dinv.data(), dinv.size() * sizeof(T));
+}
+
+// D[i] = 1 / (x_i - 1) over the LDE domain: one table for every boundary row, kept while (N, blowup, shift) stay what it was built for
+template <class F>
+int Ctx<F>::air_inv_table(T gL_step) {
+  if (air_inv_valid && air_inv_N == N && air_inv_blowup == blowup && air_inv_shift == lde_shift) return 0;
+  typedef mspoly::CosetInvKernel<F> IK;
+  static_assert(IK::THREADS == mspoly::ComposeAirKernel<F>::THREADS, "gL_step is shared");
+  air_inv_valid = false;
+  if (d_air_inv.ensure(L * sizeof(T))) return fail(MS_ERR_NOMEM, "mix_air: boundary inverse table");
+  typename IK::Params ip{L, F::from_u64(lde_shift), f_root_of_unity<F>(ctz64(L)), gL_step, d_air_inv.as<T>()};
+  next_bytes = (double)L * sizeof(T);
+  CK(run<IK>(K_AIR_INV, grid1(L, IK::THREADS * IK::ITEMS), 1, IK::THREADS, 0, ip));
+  air_inv_valid = true; air_inv_N = N; air_inv_blowup = blowup; air_inv_shift = lde_shift;
+  return 0;
+}
+
+template <class F>
+int Ctx<F>::mix_air(u64 r, const ms_air* air) {
+  RQ(mix_gate("mix_air", r));
+  if (!air) return fail(MS_ERR_ARG, "mix_air: null program");
+  const ms_air& a = *air;
+  AirProgram pg; AirLayout lay; std::vector<T> dinv;
+  RQ(air_validate(a, pg));
+  RQ(air_layout(a, pg, lay));
+  RQ(coset_vanishing_inv("mix_air", dinv));
+  std::vector<u8> tab(lay.bytes, 0);
+  air_table(r, a, pg, lay, dinv, tab.data());
+  typedef mspoly::ComposeAirKernel<F> CK_;
+  const T gL = f_root_of_unity<F>(ctz64(L)), gstep = f_pow<F>(gL, (u64)CK_::THREADS);
+  RQ(upload_mix_table("mix_air", tab.data(), lay.bytes));
+  if (a.nbound) RQ(air_inv_table(gstep));   // (behind the buffers' sizing, as every refusal for want of memory but its own)
   typename CK_::Params cp;
-  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.ngroups = (u32)ngroups;
-  cp.groups = d_tabs.as<AG>(); cp.terms = reinterpret_cast<const TR*>(d_tabs.as<u8>() + off_t); cp.facs = reinterpret_cast<const AF*>(d_tabs.as<u8>() + off_f);
-  cp.roots = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_x); cp.ptab = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_p);
-  cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + off_d); cp.inv = a.nbound ? d_air_inv.as<T>() : nullptr;
-  cp.shift = sh; cp.gL = gL; cp.gL_step = gstep; cp.out = d_cubic.as<T>();
-  next_bytes = (double)(tfacs + ngroups + 1) * L * sizeof(T);
+  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.ngroups = (u32)lay.ngroups;
+  cp.groups = d_tabs.as<mspoly::AirGroup>(); cp.terms = reinterpret_cast<const mspoly::TermRec<F>*>(d_tabs.as<u8>() + lay.off_t); cp.facs = reinterpret_cast<const mspoly::AirFac*>(d_tabs.as<u8>() + lay.off_f);
+  cp.roots = reinterpret_cast<const T*>(d_tabs.as<u8>() + lay.off_x); cp.ptab = reinterpret_cast<const T*>(d_tabs.as<u8>() + lay.off_p);
+  cp.den_inv = reinterpret_cast<const T*>(d_tabs.as<u8>() + lay.off_d); cp.inv = a.nbound ? d_air_inv.as<T>() : nullptr;
+  cp.shift = F::from_u64(lde_shift); cp.gL = gL; cp.gL_step = gstep; cp.out = d_cubic.as<T>();
+  next_bytes = (double)(lay.tfacs + lay.ngroups + 1) * L * sizeof(T);
   CK(run<CK_>(K_MIX_AIR, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
-  // evaluations on shift * <g_L>  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k
-  T* cf = d_cubic.as<T>() + L;
-  RQ(ntt_run(logL, true, d_cubic.as<T>(), L, L, cf, L, 1));
-  if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
-  RQ(ensure_polys(npolys + VL / N));
-  unsigned long long* dres;
-  RQ(degree_launch1(cf, L, &dres));
-  CK(msrt::d2h(pinned, dres, 8, stream));
-  CK(msrt::sync(stream));
-  if (*reinterpret_cast<unsigned long long*>(pinned) > VL) return fail(MS_ERR_SHAPE, "mix_air: a transition constraint fails on a non-exempt row or a boundary value is wrong (the pointwise quotients do not interpolate to a polynomial of VL coefficients)");
-  const size_t ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
-  const T shi = f_inv<F>(sh);
-  RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, shi, 1));
-  validity_ncoef = ncoef; validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
-  have_validity = true; validity_len = VL; nrounds_done = 0;
-  return MS_OK;
+  return finish_mix("mix_air: a transition constraint fails on a non-exempt row or a boundary value is wrong (the pointwise quotients do not interpolate to a polynomial of VL coefficients)", lay.VL);
 }
 
 // trimmed length of a base-field coefficient vector
@@ -711,7 +704,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   return MS_OK;
 }
 
-// the members this unit defines, for both fields (the other units see declarations only)
+// the members this unit defines, for both fields (the other units see declarations only; the mix stages' shared steps are called from here alone and come with them)
 #define MS_INSTANTIATE(FF) \
   template int Ctx<FF>::lincomb_into(const Ctx<FF>::T* base, size_t stride, size_t n, const u64* sc, const int* idx, int k, int self_index, Ctx<FF>::T* dst); \
   template int Ctx<FF>::lincomb_linear_columns(Ctx<FF>::T* base, size_t stride, size_t n); \

@@ -3,7 +3,8 @@
 // instantiated - and its device code generated - in the unit that launches it, so the units also partition the device code:
 //   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / interpolate / polys_*           (transpose, narrow / widen)
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
-//   air_stages.cpp   constraint columns, LDE commit, mix, mix_cubic, mix_terms, mix_air, DEEP-ALI evaluations        (lincomb, mix, cubic, terms, air, eval kernels)
+//   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels)
+//                    one host pipeline, a compose kernel each), DEEP-ALI evaluations
 //   ntt_plan.cpp     NTT plans and pass dispatch, coset evaluation, ms_ntt / ms_coset_lde                           (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit                                      (SHA-256 leaf / inner kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
@@ -185,6 +186,7 @@ template <class F> struct Ctx : CtxBase {
 
   int fail_rt(int e, const char* what) { err = std::string("runtime error ") + std::to_string(e) + " in " + what + ": " + msrt::last_error_string(); return MS_ERR_HIP; }
   int fail(int code, const char* msg) { err = msg; return code; }
+  int fail(int code, const std::string& msg) { err = msg; return code; }   // (a shared step's message, prefixed with the entry point that ran it)
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
@@ -478,6 +480,31 @@ template <class F> struct Ctx : CtxBase {
   // constraints and kept while (N, blowup, shift) stay what it was built for
   DevBuf d_air_inv; bool air_inv_valid = false; size_t air_inv_N = 0, air_inv_blowup = 0; u64 air_inv_shift = 0;
   int mix_air(u64 r, const ms_air* air) override;
+  // ms_mix_air's program regrouped for ComposeAirKernel: filled by air_validate, read by air_layout and air_table
+  struct AirProgram {
+    u32 nterms = 0, nfacs = 0;
+    std::vector<u32> deg;                    // per constraint: the most factors of any of its terms
+    std::vector<u32> per_off;                // offsets of the periodic columns' tables in the device table, in elements: column k has blowup * q_k entries
+    std::vector<std::vector<u32>> sets;      // the distinct exemption sets, sorted: one transition group each
+    std::vector<u32> set_of;                 // per constraint: its set
+    std::vector<u32> brows, brow_of;         // the distinct boundary rows (one boundary group each); per boundary constraint: its row's index
+  };
+  struct AirLayout { size_t VL, ngroups, tterms, tfacs, off_t, off_f, off_x, off_p, off_d, bytes; };   // [groups | terms | factors | exemption roots | periodic tables | den_inv]
+  int air_validate(const ms_air& a, AirProgram& pg);
+  int air_layout(const ms_air& a, const AirProgram& pg, AirLayout& lay);
+  void air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLayout& lay, const std::vector<T>& dinv, u8* tab);
+  int air_inv_table(T gL_step);
+  // ---- the pipeline the three build-defined mix stages share (air_stages.cpp): gate, [the stage's own checks and host table], upload, [its compose launch], finish.
+  // `who` is the entry point, for the messages
+  int mix_gate(const char* who, u64 r);
+  // 1 / (x^N - 1) on the LDE coset, blowup values: x^N - 1 is shift^N * zeta^(i mod blowup) - 1 there, zeta = g_L^N.  Refuses a coset that meets the trace domain
+  int coset_vanishing_inv(const char* who, std::vector<T>& dinv);
+  // what ms_mix_terms and ms_mix_air ask of the CSR term arrays; *d = the most factors of any term (deg_per_constraint, when given and zeroed: the same per constraint)
+  int check_term_program(const char* who, u32 ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, u32* deg_per_constraint, u32* d);
+  // virtual LDE columns written out, d_cubic / d_tabs sized, the host table staged and copied to d_tabs
+  int upload_mix_table(const char* who, const u8* tab, size_t bytes);
+  // d_cubic's evaluations -> the validity polynomial of VL coefficients behind the constraint polynomials, or MS_ERR_SHAPE with `refusal` when the division was not exact
+  int finish_mix(const char* refusal, size_t VL);
   // trimmed length of a base-field coefficient vector
   int degree_launch1(const T* poly, size_t n, unsigned long long** dres_out);
   int validity_read(u64* out) override;

@@ -525,22 +525,29 @@ template <class F, int E> struct Verifier {
 // ---- C entry points for the Python test / bench harness ---------------------------------------
 using namespace ministark;
 struct msh_stark { Stark s; };
+// What ms_mix_terms and ms_mix_air ask of the CSR term arrays (the stages' own limits): the most factors of any term, or -1 for a program they refuse
+template <class F> static int term_program_degree(u32 ncons, const u32* tb, const u64* coef, const u32* fb) {
+  if (tb[0] != 0 || fb[0] != 0) return -1;
+  for (u32 t = 0; t < ncons; t++) if (tb[t + 1] < tb[t] || tb[t + 1] > 65536) return -1;
+  u32 d = 0;
+  for (u32 m = 0; m < tb[ncons]; m++) { if (fb[m + 1] < fb[m] || fb[m + 1] - fb[m] > 8 || coef[m] >= F::P) return -1; d = std::max(d, fb[m + 1] - fb[m]); }
+  return (int)d;
+}
+static int slot_of(const u32* rows, int nrows, u32 row) { for (int k = 0; k < nrows; k++) if (rows[k] == row) return k; return -1; }   // the opening at w^row z; -1: not opened
+template <class F> static typename F::T trace_root(u64 N) { int lg = 0; while (((u64)1 << lg) < N) lg++; return f_root_of_unity<F>(lg); }
 // The verifying side of ms_mix_terms: the value validity(z) must have, from the opened values opened[k][j] = P_j(w^rows[k] z) - the same program in the extension field,
 //   (sum_t r^t C_t(z)) prod_{k=1..nexempt} (z - w^(N-k)) / (z^N - 1),   C_t(z) = sum_m coef_m prod_f opened[row_f][poly_f]
 template <class F, int E> static int terms_expected(u64 r, int ncons, const u32* tb, const u64* coef, const u32* fb, const u32* fp, const u32* fr, int nexempt, u64 N,
                                                     const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
   typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
-  if (r >= F::P || !V::canon(z, E)) return MS_ERR_ARG;
-  if (tb[0] != 0 || fb[0] != 0) return MS_ERR_ARG;
-  for (int t = 0; t < ncons; t++) if (tb[t + 1] < tb[t] || tb[t + 1] > 65536) return MS_ERR_ARG;
+  if (r >= F::P || !V::canon(z, E) || term_program_degree<F>((u32)ncons, tb, coef, fb) < 0) return MS_ERR_ARG;   // (d = 0, which the stage refuses, evaluates here)
   const u32 nterms = tb[ncons];
-  for (u32 m = 0; m < nterms; m++) if (fb[m + 1] < fb[m] || fb[m + 1] - fb[m] > 8 || coef[m] >= F::P) return MS_ERR_ARG;
   std::vector<int> slot(fb[nterms], -1);
   for (u32 f = 0; f < fb[nterms]; f++) {
     if (fp[f] >= npolys || (u64)fr[f] >= N) return MS_ERR_ARG;
-    for (int k = 0; k < nrows; k++) if (rows[k] == fr[f]) { slot[f] = k; break; }
-    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;                       // a row the program uses was not opened
+    slot[f] = slot_of(rows, nrows, fr[f]);
+    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;
     if (!V::canon(opened + (size_t)slot[f] * row_stride + (size_t)fp[f] * E, E)) return MS_ERR_ARG;
   }
   const X zz = V::load(z);
@@ -556,13 +563,11 @@ template <class F, int E> static int terms_expected(u64 r, int ncons, const u32*
     acc = e_add<F, E>(acc, e_mul_base<F, E>(ct, rp));
     rp = F::mul(rp, F::from_u64(r));
   }
-  int lg = 0; while (((u64)1 << lg) < N) lg++;
-  const typename F::T wi = f_inv<F>(f_root_of_unity<F>(lg));
+  const typename F::T wi = f_inv<F>(trace_root<F>(N));
   typename F::T wk = wi;                                                // w^(N-k) = w^-k
   for (int k = 0; k < nexempt; k++) { acc = e_mul<F>(acc, e_sub<F, E>(zz, e_from_base<F, E>(wk))); wk = F::mul(wk, wi); }
   const X den = e_sub<F, E>(e_pow<F, E>(zz, N), e_one<F, E>());
-  bool zero = true; for (int l = 0; l < E; l++) zero = zero && den.c[l] == 0;
-  if (zero) return MS_ERR_SHAPE;                                        // z lies in the trace domain
+  if (e_is_zero<F, E>(den)) return MS_ERR_SHAPE;                       // z lies in the trace domain
   acc = e_mul<F>(acc, e_inv<F>(den));
   for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
   return MS_OK;
@@ -573,17 +578,12 @@ template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N,
   typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
   typedef typename F::T T;
-  if (r >= F::P || !V::canon(z, E)) return MS_ERR_ARG;
   const u32 ncons = a.ncons;
-  if (a.term_begin[0] != 0 || a.fac_begin[0] != 0 || a.ex_begin[0] != 0) return MS_ERR_ARG;
-  for (u32 t = 0; t < ncons; t++) if (a.term_begin[t + 1] < a.term_begin[t] || a.term_begin[t + 1] > 65536 || a.ex_begin[t + 1] < a.ex_begin[t] || a.ex_begin[t + 1] - a.ex_begin[t] > 16) return MS_ERR_ARG;
+  if (r >= F::P || !V::canon(z, E) || term_program_degree<F>(ncons, a.term_begin, a.coef, a.fac_begin) <= 0 || a.ex_begin[0] != 0) return MS_ERR_ARG;   // (d = 0 too)
+  for (u32 t = 0; t < ncons; t++) if (a.ex_begin[t + 1] < a.ex_begin[t] || a.ex_begin[t + 1] - a.ex_begin[t] > 16) return MS_ERR_ARG;
   const u32 nterms = a.term_begin[ncons];
-  u32 d = 0;
-  for (u32 m = 0; m < nterms; m++) { if (a.fac_begin[m + 1] < a.fac_begin[m] || a.fac_begin[m + 1] - a.fac_begin[m] > 8 || a.coef[m] >= F::P) return MS_ERR_ARG; d = std::max(d, a.fac_begin[m + 1] - a.fac_begin[m]); }
-  if (d == 0) return MS_ERR_ARG;
   if (a.ex_begin[ncons] && !a.ex_row) return MS_ERR_ARG;
-  int lg = 0; while (((u64)1 << lg) < N) lg++;
-  const T wN = f_root_of_unity<F>(lg), wi = f_inv<F>(wN), one = F::from_u64(1);
+  const T wN = trace_root<F>(N), wi = f_inv<F>(wN), one = F::from_u64(1);
   // periodic columns: Q_k by the inverse DFT of the q_k values
   std::vector<std::vector<T>> Q(a.nperiodic);
   if (a.nperiodic && a.per_begin[0] != 0) return MS_ERR_ARG;
@@ -615,15 +615,14 @@ template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N,
     if ((fp & MS_AIR_PERIODIC) ? (fp & ~MS_AIR_PERIODIC) >= a.nperiodic : fp >= npolys) return MS_ERR_ARG;
     if ((u64)a.fac_row[f] >= N) return MS_ERR_ARG;
   }
-  auto slot_of = [&](u32 row) { for (int k = 0; k < nrows; k++) if (rows[k] == row) return k; return -1; };
   std::vector<int> slot(nfacs, -1);
   for (u32 f = 0; f < nfacs; f++) {
     if (a.fac_poly[f] & MS_AIR_PERIODIC) continue;   // (a periodic factor needs no opening)
-    slot[f] = slot_of(a.fac_row[f]);
-    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;                       // a row the program uses was not opened
+    slot[f] = slot_of(rows, nrows, a.fac_row[f]);
+    if (slot[f] < 0) return MS_ERR_OUT_OF_RANGE;
     if (!V::canon(opened + (size_t)slot[f] * row_stride + (size_t)a.fac_poly[f] * E, E)) return MS_ERR_ARG;
   }
-  const int slot0 = a.nbound ? slot_of(0) : 0;
+  const int slot0 = a.nbound ? slot_of(rows, nrows, 0) : 0;
   if (slot0 < 0) return MS_ERR_OUT_OF_RANGE;                           // the boundary quotients are evaluated from P_j(z)
   for (u32 b = 0; b < a.nbound; b++) if (!V::canon(opened + (size_t)slot0 * row_stride + (size_t)a.bnd_poly[b] * E, E)) return MS_ERR_ARG;
   const X zz = V::load(z);

@@ -529,6 +529,14 @@ def test_mix_cubic_true_quotient(mk, field, log_n, w):
     pc.case_mix_cubic(lambda f, fresh=False: mk(f, fresh=True), field, log_n=log_n, w=w)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("field", [0, 1])
+def test_mix_cubic_failing_across_a_store_growth(mk, field):
+    """A refused ms_mix_cubic that grew the polynomial store leaves no validity polynomial behind (ms_fri_begin refuses as before any mix stage); one that did not
+    grow it leaves the earlier one in place."""
+    pc.case_mix_cubic_store_growth(lambda f, fresh=False: mk(f, fresh=True), field)
+
+
 def test_config4_degree3_constraints_full_width_self_verifies(mk):
     """BASELINE configs[4] as written - 64 trace columns, degree-3 constraints - at 2^18 rows (2^22 in bench.py's `extra.wide_air_cubic_2p22`): the build-defined
     composition has no reference to compare with, so it verifies itself: ms_mix_cubic accepts (exact division: nothing above 2N coefficients), and the DEEP-ALI

@@ -8,18 +8,21 @@ The times are the per-kernel times of ms_profile_begin / ms_profile_end (HIP eve
 builds the boundary inverse table on C's first leg.  Writes one JSON line to profiles/mix_air_vs_terms.json and prints it.
 On a shared GPU box run it under a time limit of its own, chained behind whatever precedes it:
   timeout -k 10 600 python3 tools/air_bench.py [--passes 8] [--log-rows 18] [--width 64] [--blowup 8] [--out profiles/mix_air_vs_terms.json]"""
-import argparse, ctypes as C, json, os, statistics, sys
+import argparse, ctypes as C, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
 def profile(ctx, stage):
-    """runs `stage` with every launch bracketed by events; (status, the profile)"""
+    """runs `stage` with every launch bracketed by events; (status, the profile, host milliseconds of the whole call: the stage ends behind its one stream
+    synchronisation, so this is what a caller waits)"""
     buf = C.create_string_buffer(1 << 15)
     ctx.check(ctx.L.ms_profile_begin(ctx.h))
+    t0 = time.perf_counter()
     rc = stage()
+    call_ms = (time.perf_counter() - t0) * 1e3
     ctx.check(ctx.L.ms_profile_end(ctx.h, buf, C.c_size_t(len(buf))))
-    return rc, json.loads(buf.value.decode())
+    return rc, json.loads(buf.value.decode()), call_ms
 
 
 def main():
@@ -53,7 +56,7 @@ def main():
     # the untimed first legs (code objects, the interpolation's NTT plan, the inverse table), and B's outputs against A's
     outs, inv_ms = {}, None
     for k, (stage, key) in legs.items():
-        rc, prof = profile(ctx, stage)
+        rc, prof, _ = profile(ctx, stage)
         ctx.check(rc)
         assert prof[key]["launches"] == 1 and prof["air_inv"]["launches"] == (1 if k == "C" else 0), (k, prof[key], prof["air_inv"])
         if k == "C":
@@ -62,13 +65,14 @@ def main():
     assert outs["A"].size == 2 * N
     assert (outs["A"] == outs["B"]).all() and outs["A"].any(), "ms_mix_air and ms_mix_terms disagree"
     assert (outs["C"] != outs["A"]).any()
-    times = {k: [] for k in legs}
+    times, calls = {k: [] for k in legs}, {k: [] for k in legs}
     for _ in range(args.passes):
         for k, (stage, key) in legs.items():
-            rc, prof = profile(ctx, stage)
+            rc, prof, call_ms = profile(ctx, stage)
             ctx.check(rc)
             assert prof["air_inv"]["launches"] == 0
             times[k].append(prof[key]["ms"])
+            calls[k].append(call_ms)
     med = {k: statistics.median(v) for k, v in times.items()}
     spread = {k: (max(v) - min(v)) / med[k] for k, v in times.items()}
     try:
@@ -80,7 +84,8 @@ def main():
            f"{args.passes} legs per stage, alternated; C = B + {len(boundary)} boundary constraints (every column at rows 0 and N - 1)", "unit": "ms per compose kernel (HIP events)",
            "terms_compose_ms": med["A"], "air_compose_ms": med["B"], "air_boundary_compose_ms": med["C"], "ratio_air_over_terms": med["B"] / med["A"],
            "ratio_air_boundary_over_terms": med["C"] / med["A"], "terms_spread": spread["A"], "air_spread": spread["B"], "air_boundary_spread": spread["C"],
-           "b_within_a_spread_plus_0_05": med["B"] / med["A"] <= 1.0 + spread["A"] + 0.05, "air_inv_build_ms": inv_ms, "legs_ms": times, "outputs_identical": True, "device": device}
+           "b_within_a_spread_plus_0_05": med["B"] / med["A"] <= 1.0 + spread["A"] + 0.05, "air_inv_build_ms": inv_ms, "legs_ms": times, "call_ms_mean": {k: statistics.mean(v) for k, v in calls.items()},
+           "legs_call_ms": calls, "outputs_identical": True, "device": device}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -6,19 +6,22 @@ ms_profile_begin / ms_profile_end (HIP events around every launch): class "mix" 
 same validity polynomial, which is checked before anything is timed.  Writes one JSON line to profiles/mix_terms_vs_cubic.json and prints it.
 On a shared GPU box run it under a time limit of its own, chained behind whatever precedes it:
   timeout -k 10 600 python3 tools/compose_bench.py [--passes 8] [--log-rows 18] [--width 64] [--blowup 8] [--out profiles/mix_terms_vs_cubic.json]"""
-import argparse, ctypes as C, json, os, statistics, sys
+import argparse, ctypes as C, json, os, statistics, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
 def kernel_ms(ctx, stage, key):
-    """runs `stage` with every launch bracketed by events; (status, milliseconds of kernel class `key`, launches of it)"""
+    """runs `stage` with every launch bracketed by events; (status, milliseconds of kernel class `key`, launches of it, host milliseconds of the whole call:
+    the stage ends behind its one stream synchronisation, so this is what a caller waits)"""
     buf = C.create_string_buffer(1 << 15)
     ctx.check(ctx.L.ms_profile_begin(ctx.h))
+    t0 = time.perf_counter()
     rc = stage()
+    call_ms = (time.perf_counter() - t0) * 1e3
     ctx.check(ctx.L.ms_profile_end(ctx.h, buf, C.c_size_t(len(buf))))
     prof = json.loads(buf.value.decode())
-    return rc, prof[key]["ms"], prof[key]["launches"]
+    return rc, prof[key]["ms"], prof[key]["launches"], call_ms
 
 
 def main():
@@ -48,17 +51,18 @@ def main():
     # same polynomial from both, and the untimed first legs (code objects, the interpolation's NTT plan)
     outs = {}
     for k, (stage, key) in legs.items():
-        rc, _, n = kernel_ms(ctx, stage, key)
+        rc, _, n, _ = kernel_ms(ctx, stage, key)
         ctx.check(rc)
         assert n == 1, (k, n)
         outs[k] = ctx.validity_read()
     assert (outs["cubic"] == outs["terms"]).all() and outs["cubic"].any(), "ms_mix_terms and ms_mix_cubic disagree"
-    times = {k: [] for k in legs}
+    times, calls = {k: [] for k in legs}, {k: [] for k in legs}
     for _ in range(args.passes):
         for k, (stage, key) in legs.items():
-            rc, t, _ = kernel_ms(ctx, stage, key)
+            rc, t, _, call_ms = kernel_ms(ctx, stage, key)
             ctx.check(rc)
             times[k].append(t)
+            calls[k].append(call_ms)
     med = {k: statistics.median(v) for k, v in times.items()}
     try:
         import torch
@@ -68,7 +72,8 @@ def main():
     res = {"metric": "mix_terms_vs_cubic", "workload": f"{w}-column cubic spec, Goldilocks, 2^{args.log_rows} rows, blowup {args.blowup}: one compose launch over the 2^{args.log_rows + args.blowup.bit_length() - 1}-point LDE domain, "
            f"{args.passes} legs per stage, alternated", "unit": "ms per compose kernel (HIP events)", "cubic_compose_ms": med["cubic"], "terms_compose_ms": med["terms"],
            "ratio_terms_over_cubic": med["terms"] / med["cubic"], "cubic_spread": (max(times["cubic"]) - min(times["cubic"])) / med["cubic"],
-           "terms_spread": (max(times["terms"]) - min(times["terms"])) / med["terms"], "legs_ms": times, "outputs_identical": True, "device": device}
+           "terms_spread": (max(times["terms"]) - min(times["terms"])) / med["terms"], "legs_ms": times, "call_ms_mean": {k: statistics.mean(v) for k, v in calls.items()}, "legs_call_ms": calls,
+           "outputs_identical": True, "device": device}
     line = json.dumps(res)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
