@@ -44,6 +44,19 @@ pub struct MsAir {
     pub bnd_row: *const u32,
     pub bnd_val: *const u64,
 }
+pub const MS_AUX_SUM: u32 = 0; // z_{i+1} = z_i + s_i, z_0 = 0 (LogUp)
+pub const MS_AUX_PRODUCT: u32 = 1; // z_{i+1} = z_i * s_i, z_0 = 1 (grand product)
+/// `ms_aux` of include/ministark.h: the program of ms_aux_running.  Every pointer borrows from the caller for the duration of the call.
+#[repr(C)]
+pub struct MsAux {
+    pub op: u32,
+    pub ext: u32,                // 1, or ms_ext_degree
+    pub nfrac: u32,              // 1..4
+    pub form_begin: *const u32,  // 2 * nfrac + 1
+    pub term_col: *const u32,    // nterms: a trace column
+    pub term_coef: *const u64,   // nterms * ext limbs
+    pub form_const: *const u64,  // 2 * nfrac * ext limbs
+}
 pub type ms_exchange_fn = Option<unsafe extern "C" fn(user: *mut c_void, op: c_int, bytes: usize) -> c_int>;
 
 extern "C" {
@@ -78,6 +91,8 @@ extern "C" {
     pub fn ms_trace_commit(ctx: *mut ms_ctx, trace_rowmajor: *const u64, n: usize, w: usize, lpn: usize, root: *mut u8 /* [32] */) -> c_int;
     pub fn ms_trace_commit_device(ctx: *mut ms_ctx, d_trace_rowmajor: *const c_void, n: usize, w: usize, lpn: usize, root: *mut u8) -> c_int;
     pub fn ms_trace_upload_async(ctx: *mut ms_ctx, trace_rowmajor: *const u64, n: usize, w: usize) -> c_int;
+    pub fn ms_aux_running(ctx: *mut ms_ctx, aux: *const MsAux, final_out: *mut u64, column_out: *mut u64) -> c_int;
+    pub fn ms_aux_count(ctx: *const ms_ctx) -> c_int;
     pub fn ms_interpolate(ctx: *mut ms_ctx) -> c_int;
     pub fn ms_polys_lincomb(ctx: *mut ms_ctx, scalars: *const u64, idx: *const c_int, k: c_int) -> c_int;
     pub fn ms_polys_append(ctx: *mut ms_ctx, coeffs: *const u64, n: usize) -> c_int;

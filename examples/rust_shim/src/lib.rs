@@ -51,6 +51,22 @@ impl Gpu {
         self.check(unsafe { ms_trace_upload_async(self.ctx, trace.as_ptr(), n, w) })
     }
     /// air.rs:147-160: TraceTable::get_trace_polys (per-column INTT)
+    /// build-defined (no reference counterpart): the running product / running sum column of a permutation or lookup argument, from the committed trace and
+    /// challenges drawn after its root; between trace_commit and interpolate.  Returns `final` (ext limbs); Err(Shape) when a denominator vanished on some row.
+    /// form 2k / 2k+1 = numerator / denominator of fraction k: form_begin has 2 * nfrac + 1 entries, term_coef and form_const hold ext limbs per element.
+    pub fn aux_running(&mut self, op: u32, ext: u32, form_begin: &[u32], term_col: &[u32], term_coef: &[u64], form_const: &[u64]) -> Result<Vec<u64>, GpuError> {
+        assert!(form_begin.len() >= 3 && form_begin.len() % 2 == 1);
+        let nforms = form_begin.len() - 1;
+        assert_eq!(term_col.len(), form_begin[nforms] as usize);
+        assert_eq!(term_coef.len(), term_col.len() * ext as usize);
+        assert_eq!(form_const.len(), nforms * ext as usize);
+        let aux = MsAux { op, ext, nfrac: (nforms / 2) as u32, form_begin: form_begin.as_ptr(), term_col: term_col.as_ptr(), term_coef: term_coef.as_ptr(), form_const: form_const.as_ptr() };
+        let mut fin = vec![0u64; ext as usize];
+        self.check(unsafe { ms_aux_running(self.ctx, &aux, fin.as_mut_ptr(), std::ptr::null_mut()) })?;
+        Ok(fin)
+    }
+    /// limb columns ms_aux_running has appended since the last trace_commit
+    pub fn aux_count(&self) -> i32 { unsafe { ms_aux_count(self.ctx) } }
     pub fn interpolate(&mut self) -> Result<(), GpuError> { self.check(unsafe { ms_interpolate(self.ctx) }) }
     /// air.rs:127-144: a transition closure that is a linear combination of earlier polynomials (tests/e2e_goldilocks.rs:48-59)
     pub fn polys_lincomb(&mut self, scalars: &[u64], idx: &[i32]) -> Result<(), GpuError> {

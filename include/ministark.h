@@ -167,6 +167,44 @@ int ms_trace_commit_device(ms_ctx* ctx, const void* d_trace_rowmajor, size_t N, 
  * the current proof computes.  A hint: pageable memory, MS_UPLOAD=hip or a busy engine queue nothing (MS_OK all the same) and ms_trace_commit uploads as before.
  * `trace` must stay valid and unchanged until that ms_trace_commit returns; one prefetch in flight per context (a second one waits for the first). */
 int ms_trace_upload_async(ms_ctx* ctx, const uint64_t* trace_rowmajor, size_t N, size_t w);
+/* BUILD-DEFINED, no reference counterpart: a column that depends on a verifier challenge - the running product of a permutation argument or the running sum of a
+ * LogUp lookup - computed on the GPU from the committed trace.  Between ms_trace_commit[_device] (the trace root is in the caller's transcript, so the challenges
+ * in the coefficients may depend on it; the column values are still in HBM) and ms_interpolate (which transforms them in place).
+ *   K = Fp for ext = 1, otherwise the context's extension (ext = ms_ext_degree).  T_j[i] = row i of committed trace column j, canonical (MS_FLAG_TRACE_MONT64 has
+ *   been undone by the transpose).  N rows, w columns.
+ *   form f at row i     a_f(i) = form_const[f] + sum_{m in form_begin[f] .. form_begin[f+1]-1} term_coef[m] * T_{term_col[m]}[i]                    (in K)
+ *   s_i                 sum_{k < nfrac} a_{2k}(i) / a_{2k+1}(i)  for MS_AUX_SUM,  the product of the same fractions for MS_AUX_PRODUCT
+ *   the column          z_0 = the identity (0 for SUM, 1 for PRODUCT),  z_{i+1} = z_i o s_i for 0 <= i < N-1   (o: + for SUM, * for PRODUCT)
+ *   final_out           z_{N-1} o s_{N-1}.  If it equals the identity the recurrence also holds from row N-1 back to row 0, and the caller's transition
+ *                       constraint needs no exemption.
+ * Limb l of the column becomes column w + ms_aux_count_before + l of the context and ms_aux_count grows by ext.  ms_interpolate then transforms w + ms_aux_count
+ * columns and ms_polys_count is that number afterwards; ms_polys_lincomb, ms_lde_commit, ms_mix_*, ms_eval_ext and ms_poly_read treat the new columns like any
+ * other (they are materialised columns, never lazy ones).  ms_trace_commit resets the count.  Several calls per proof are allowed, up to 16 limb columns in all.
+ * With ms_aux_count == 0 nothing that existed before this stage changes by a bit.  column_out, when not NULL, receives the column row-major (N * ext limbs).
+ * The recurrence and z_0 are ordinary constraints of ms_mix_air (mini_stark_amd.aux_constraints writes them out); msh_air_expected_validity checks them on the
+ * verifying side.
+ * SOUNDNESS.  ext = 1 puts the challenges in Fp: the argument is then only |Fp|-sound - what the base-field `r` of the mix stages gives today - which for BabyBear
+ * is 31 bits: use ext = 4 there.  Binding the trace columns of the LDE tree to the trace root stays the caller's linking step, as before.
+ *   MS_ERR_STATE  no committed trace; ms_interpolate already called for this trace; a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1).
+ *   MS_ERR_ARG    a null argument (column_out may be null, final_out may not); op > 1; ext not in {1, ms_ext_degree}; nfrac outside 1..4; form_begin not starting at 0 or
+ *                 decreasing; more than 16 terms in a form; a column >= w; a non-canonical limb; more than 16 limb columns in all.
+ *   MS_ERR_SHAPE  a denominator is zero on some row: the caller draws another challenge.  Decided on the device; the flag word rides back with final_out.
+ *   MS_ERR_NOMEM / MS_ERR_HIP as everywhere.
+ * After any refusal or failure the context is as if the call had not been made: the count is unchanged, a following valid call gives what a fresh context gives, and
+ * proving without aux columns gives the usual proof.  Everything except the zero denominator is decided before anything is launched.  Tests: tests/test_aux_*.py. */
+#define MS_AUX_SUM 0u      /* z_{i+1} = z_i + s_i, z_0 = 0  (LogUp)            */
+#define MS_AUX_PRODUCT 1u  /* z_{i+1} = z_i * s_i, z_0 = 1  (grand product)    */
+typedef struct ms_aux {
+  uint32_t op;                 /* MS_AUX_SUM / MS_AUX_PRODUCT */
+  uint32_t ext;                /* 1: column and coefficients in the base field; ms_ext_degree(ctx): in the extension (ext limbs per element, limb order as everywhere in this header) */
+  uint32_t nfrac;              /* 1..4 fractions per row */
+  const uint32_t* form_begin;  /* 2*nfrac + 1, starts at 0, does not decrease: form 2k is the numerator of fraction k, form 2k+1 its denominator; at most 16 terms per form */
+  const uint32_t* term_col;    /* nterms: a TRACE column, < w */
+  const uint64_t* term_coef;   /* nterms * ext limbs, canonical */
+  const uint64_t* form_const;  /* 2*nfrac * ext limbs, canonical */
+} ms_aux;
+int ms_aux_running(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out /* ext limbs */, uint64_t* column_out /* NULL, or N*ext limbs, row-major */);
+int ms_aux_count(const ms_ctx* ctx);   /* limb columns appended since the last ms_trace_commit */
 /* 1.2a TraceTable::get_trace_polys: per-column INTT.  air.rs:147-160. */
 int ms_interpolate(ms_ctx* ctx);
 /* 1.2b constraint polynomial appended as sum_t scalars[t] * poly[idx[t]] (the

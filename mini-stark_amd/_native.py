@@ -154,6 +154,155 @@ def air_rows(constraints, boundary=()):
     return sorted(rows)
 
 
+AUX_SUM, AUX_PRODUCT = 0, 1   # MS_AUX_SUM / MS_AUX_PRODUCT
+
+
+class MsAux(C.Structure):
+    """ms_aux (include/ministark.h)"""
+    _u32p = C.POINTER(C.c_uint32)
+    _fields_ = [("op", C.c_uint32), ("ext", C.c_uint32), ("nfrac", C.c_uint32), ("form_begin", _u32p), ("term_col", _u32p), ("term_coef", _u64p), ("form_const", _u64p)]
+
+
+def _limbs(v, ext):
+    """an element of K as `ext` ints: an int for ext = 1, an ext-tuple otherwise"""
+    if ext == 1 and not isinstance(v, (tuple, list)):
+        return [int(v)]
+    v = [int(x) for x in v]
+    if len(v) != ext:
+        raise ValueError(f"an element of {ext} limbs expected")
+    return v
+
+
+def flatten_aux(op, fractions, ext=1):
+    """The arrays of an ms_aux as a dict (the names of the struct's fields) from fractions = [((const, [(col, coef), ...]), (const, [(col, coef), ...])), ...]: numerator
+    and denominator of every fraction as affine forms over the trace columns; const / coef are ints for ext = 1 and ext-tuples otherwise."""
+    form_begin, term_col, term_coef, form_const = [0], [], [], []
+    for frac in fractions:
+        if len(frac) != 2:
+            raise ValueError("flatten_aux: a fraction is a (numerator, denominator) pair of forms")
+        for const, terms in frac:
+            form_const += _limbs(const, ext)
+            for col, coef in terms:
+                term_col.append(int(col))
+                term_coef += _limbs(coef, ext)
+            form_begin.append(len(term_col))
+    return {"op": int(op), "ext": int(ext), "nfrac": len(fractions), "form_begin": np.array(form_begin, dtype=np.uint32), "term_col": np.array(term_col, dtype=np.uint32),
+            "term_coef": np.array(term_coef, dtype=np.uint64), "form_const": np.array(form_const, dtype=np.uint64)}
+
+
+AUX_ARRAYS = (("form_begin", np.uint32), ("term_col", np.uint32), ("term_coef", np.uint64), ("form_const", np.uint64))
+
+
+def aux_struct(aux):
+    """(MsAux, the arrays it points into) from a flatten_aux dict; an entry that is None becomes a NULL pointer"""
+    keep = {k: (None if aux.get(k) is None else np.ascontiguousarray(aux[k], dtype=t)) for k, t in AUX_ARRAYS}
+    s = MsAux()
+    s.op, s.ext, s.nfrac = int(aux["op"]), int(aux["ext"]), int(aux["nfrac"])
+    for k, t in AUX_ARRAYS:
+        if keep[k] is not None:
+            setattr(s, k, keep[k].ctypes.data_as(_u64p if t is np.uint64 else C.POINTER(C.c_uint32)))
+    return s, keep
+
+
+_MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
+_EXT = {GOLDILOCKS: 2, BABYBEAR: 4}
+_NR2 = {GOLDILOCKS: 7, BABYBEAR: 11}       # Fp2 = Fp[u] / (u^2 - NR2)
+_NR4 = (2013265910, 1)                     # Fp4 = Fp2[v] / (v^2 - (2013265910 + u))  (BabyBear)
+
+
+def _tower_mul(field, ext, a, b):
+    """a * b in K (tuples of `ext` limbs; the towers of csrc/field.hpp)"""
+    p = _MODULUS[field]
+    if ext == 1:
+        return (a[0] * b[0] % p,)
+    nr = _NR2[field]
+
+    def m2(x, y):
+        return ((x[0] * y[0] + nr * x[1] * y[1]) % p, (x[0] * y[1] + x[1] * y[0]) % p)
+    if ext == 2:
+        return m2(a, b)
+    a0, a1, b0, b1 = a[:2], a[2:], b[:2], b[2:]
+    lo, t = m2(a0, b0), m2(_NR4, m2(a1, b1))
+    x, y = m2(a0, b1), m2(a1, b0)
+    return ((lo[0] + t[0]) % p, (lo[1] + t[1]) % p, (x[0] + y[0]) % p, (x[1] + y[1]) % p)
+
+
+def aux_constraints(field, op, fractions, ext, first_poly, exempt_last=False, N=None):
+    """The constraints a column of Context.aux_running satisfies, as (constraints, exempt, boundary) in the formats Context.mix_air takes.  The column's limbs are the
+    polynomials first_poly .. first_poly + ext - 1; the forms of `fractions` (as for aux_running) are over the trace columns, whose polynomials keep their indices.
+    Transition, cleared of denominators, with z' = z(w x):
+        AUX_PRODUCT   z' * prod_k den_k - z * prod_k num_k
+        AUX_SUM       (z' - z) * prod_k den_k - sum_k num_k * prod_{j != k} den_j
+    For ext > 1 this identity in K is expanded into one base-field constraint per limb over the limb columns, by a symbolic product (monomial -> coefficient in K).
+    Boundary: z(w^0) = the identity, limb by limb.  exempt_last: the transition constraints are exempt on row N - 1 (needed when `final` is not the identity; pass N).
+    ValueError when the expansion exceeds ms_mix_air's limits (8 factors per term, 65536 terms)."""
+    p = _MODULUS[field]
+    if ext not in (1, _EXT[field]):
+        raise ValueError("aux_constraints: ext must be 1 or the field's extension degree")
+    if exempt_last and N is None:
+        raise ValueError("aux_constraints: exempt_last needs the number of rows N")
+    unit = lambda l: tuple(1 if i == l else 0 for i in range(ext))   # noqa: E731
+
+    def padd(a, b, sign=1):
+        out = dict(a)
+        for mono, c in b.items():
+            out[mono] = tuple((x + sign * y) % p for x, y in zip(out.get(mono, (0,) * ext), c))
+        return out
+
+    def pmul(a, b):
+        out = {}
+        for ma, ca in a.items():
+            for mb, cb in b.items():
+                mono = tuple(sorted(ma + mb))
+                if len(mono) > 8:
+                    raise ValueError("aux_constraints: a term with more than 8 factors (ms_mix_air's limit)")
+                c = _tower_mul(field, ext, ca, cb)
+                out[mono] = tuple((x + y) % p for x, y in zip(out.get(mono, (0,) * ext), c))
+            if len(out) * ext > 65536:
+                raise ValueError("aux_constraints: more than 65536 terms (ms_mix_air's limit)")
+        return out
+
+    def form(f):
+        const, terms = f
+        out = {(): tuple(v % p for v in _limbs(const, ext))}
+        for col, coef in terms:
+            out = padd(out, {((int(col), 0),): tuple(v % p for v in _limbs(coef, ext))})
+        return out
+    z = {((first_poly + l, 0),): unit(l) for l in range(ext)}
+    zn = {((first_poly + l, 1),): unit(l) for l in range(ext)}
+    one = {(): unit(0)}
+    nums, dens = [form(fr[0]) for fr in fractions], [form(fr[1]) for fr in fractions]
+    den_all = one
+    for d in dens:
+        den_all = pmul(den_all, d)
+    if op == AUX_PRODUCT:
+        num_all = one
+        for n_ in nums:
+            num_all = pmul(num_all, n_)
+        expr = padd(pmul(zn, den_all), pmul(z, num_all), -1)
+    elif op == AUX_SUM:
+        expr = pmul(padd(zn, z, -1), den_all)
+        for k, n_ in enumerate(nums):
+            t = n_
+            for j, d in enumerate(dens):
+                if j != k:
+                    t = pmul(t, d)
+            expr = padd(expr, t, -1)
+    else:
+        raise ValueError("aux_constraints: op must be AUX_SUM or AUX_PRODUCT")
+    constraints = []
+    for l in range(ext):
+        terms = [(c[l], list(mono)) for mono, c in sorted(expr.items()) if c[l]]
+        if not any(factors for _, factors in terms):
+            raise ValueError("aux_constraints: a limb's constraint has no term with a factor")
+        constraints.append(terms)
+    if sum(len(t) for t in constraints) > 65536:
+        raise ValueError("aux_constraints: more than 65536 terms (ms_mix_air's limit)")
+    exempt = [[N - 1] if exempt_last else [] for _ in range(ext)]
+    boundary = [(first_poly + l, 0, 1 if (op == AUX_PRODUCT and l == 0) else 0) for l in range(ext)]
+    return constraints, exempt, boundary
+
+
 class Context:
     """One ms_ctx: a prover session on one GPU (include/ministark.h)."""
 
@@ -293,6 +442,23 @@ class Context:
         if rc == 0:
             self.N, self.w = N, w
         return rc, bytes(root)
+
+    def aux_running(self, op, fractions, ext=1, read=False):
+        """ms_aux_running (BUILD-DEFINED running product / running sum of fractions of affine forms over the committed trace; include/ministark.h), between trace_commit
+        and interpolate: fractions as for flatten_aux, or a flatten_aux dict.  Returns (rc, final, column or None): final an int for ext = 1 and an ext-tuple otherwise,
+        column (read=True) an (N, ext) array."""
+        aux = fractions if isinstance(fractions, dict) else flatten_aux(op, fractions, ext)
+        s, _keep = aux_struct(aux)
+        e = int(aux["ext"])
+        fin = np.zeros(max(1, e), dtype=np.uint64)
+        col = np.zeros((self.N, e), dtype=np.uint64) if read else None
+        rc = self.L.ms_aux_running(self.h, C.byref(s), fin.ctypes.data_as(_u64p), col.ctypes.data_as(_u64p) if read else None)
+        if rc != 0:
+            return rc, None, None
+        return 0, (int(fin[0]) if e == 1 else tuple(int(v) for v in fin)), col
+
+    def aux_count(self):
+        return self.L.ms_aux_count(self.h)
 
     def interpolate(self):
         return self.L.ms_interpolate(self.h)

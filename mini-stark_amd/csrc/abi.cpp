@@ -119,6 +119,8 @@ uint64_t ms_root_of_unity(ms_field f, uint64_t n) {
 int ms_trace_commit(ms_ctx* ctx, const uint64_t* t, size_t N, size_t w, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->trace_commit(t, false, N, w, lpn, root)); }
 int ms_trace_commit_device(ms_ctx* ctx, const void* t, size_t N, size_t w, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->trace_commit(reinterpret_cast<const u64*>(t), true, N, w, lpn, root)); }
 int ms_trace_upload_async(ms_ctx* ctx, const uint64_t* t, size_t N, size_t w) { MS_ENTRY(ctx, B(ctx)->trace_upload_async(t, N, w)); }
+int ms_aux_running(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out, uint64_t* column_out) { MS_ENTRY(ctx, B(ctx)->aux_running(aux, final_out, column_out)); }
+int ms_aux_count(const ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->aux_count()); }
 int ms_interpolate(ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->interpolate()); }
 int ms_polys_lincomb(ms_ctx* ctx, const uint64_t* s, const int* idx, int k) { MS_ENTRY(ctx, B(ctx)->polys_lincomb(s, idx, k)); }
 int ms_polys_append(ms_ctx* ctx, const uint64_t* c, size_t n) { MS_ENTRY(ctx, B(ctx)->polys_append(c, n)); }

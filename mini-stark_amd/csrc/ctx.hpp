@@ -1,7 +1,7 @@
 // ctx.hpp — the prover session behind the C ABI (include/ministark.h): one class template per field, Ctx<F>, declared here and DEFINED in
 // the translation units below (r05: one 2547-line unit until then; every kernel experiment paid its 2.5-minute rebuild).  A kernel template is
 // instantiated - and its device code generated - in the unit that launches it, so the units also partition the device code:
-//   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / interpolate / polys_*           (transpose, narrow / widen)
+//   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / aux_running / interpolate / polys_*  (transpose, narrow / widen, running-column kernels)
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
 //   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels)
 //                    one host pipeline, a compose kernel each), DEEP-ALI evaluations
@@ -85,6 +85,8 @@ struct CtxBase {
   virtual int rccl_selftest() = 0;
   virtual int trace_commit(const u64* trace, bool on_device, size_t N, size_t w, size_t lpn, u8* root) = 0;
   virtual int trace_upload_async(const u64* trace, size_t N, size_t w) = 0;
+  virtual int aux_running(const ms_aux* aux, u64* final_out, u64* column_out) = 0;
+  virtual int aux_count() const = 0;
   virtual int interpolate() = 0;
   virtual int polys_lincomb(const u64* s, const int* idx, int k) = 0;
   virtual int polys_append(const u64* coeffs, size_t n) = 0;
@@ -190,7 +192,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_COUNT };
   struct ProfRec { int kid, sub; msrt::Event* a; msrt::Event* b; double bytes; bool part; };
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -409,7 +411,7 @@ template <class F> struct Ctx : CtxBase {
     if (ev_copy) msrt::event_destroy(ev_copy);
     if (copy_stream) msrt::stream_destroy(copy_stream);
     for (Round* r : rounds) { r->poly.release(); r->cw.release(); r->nodes.release(); delete r; }
-    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_deg, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &d_evdone, &d_air_inv};
+    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_deg, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &d_evdone, &d_air_inv, &d_aux};
     for (DevBuf* b : bufs) b->release();
     if (pinned) msrt::free_host(pinned);
     if (h_tabs) msrt::free_host(h_tabs);
@@ -430,6 +432,17 @@ template <class F> struct Ctx : CtxBase {
 
   // ------------------------------------------------------------------ starks.rs:68-73
   int trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_, size_t lpn, u8* root) override;
+  // ------------------------------------------------------------------ build-defined: running columns of permutation / lookup arguments (include/ministark.h; kernels: running.hpp)
+  // naux limb columns sit behind the w trace columns of d_polys until ms_interpolate transforms them with the trace.  d_aux: [flag word | final, E u64 | tile
+  // aggregates | carries]; the flag is a word of its own (not the zero pool, which may be wiped between the launch that sets it and the copy that reads it)
+  int naux = 0;
+  static constexpr int AUX_TILE_DEFAULT = 2048;
+  int aux_tile = AUX_TILE_DEFAULT;   // MS_AUX_TILE: rows per workgroup of the tile launch, a power of two from 256 up to the default (each value its own kernel instance)
+  DevBuf d_aux;
+  int aux_running(const ms_aux* aux, u64* final_out, u64* column_out) override;
+  int aux_count() const override { return naux; }
+  template <int EA> int aux_running_t(const ms_aux& a, u64* final_out, u64* column_out);
+  template <int EA, int SEG> int aux_tile_launch(const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag);
   // ------------------------------------------------------------------ air.rs:147-160
   int interpolate() override;
   int polys_lincomb(const u64* s, const int* idx, int k) override;

@@ -1,13 +1,14 @@
 // session.cpp — context life cycle, device pools, I/O staging, per-kernel profile, and the first stages of Stark::prove: trace commitment (starks.rs:68-73),
 // interpolation (air.rs:147-160), constraint polynomials (air.rs:127-144).
 #include "ctx.hpp"
+#include "running.hpp"
 
 namespace msctx {
 
 template <class F>
 int Ctx<F>::profile_end(char* out, size_t cap) {
   static const char* names[K_COUNT] = {"ntt_pass", "scale_pow", "leaf_hash", "inner_hash", "transpose_in", "io_copy", "lincomb", "mix", "eval", "eval_reduce",
-                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv"};
+                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv", "aux_running"};
   msrt::sync(stream);
   double ms[K_COUNT] = {0}, by[K_COUNT] = {0}, ms_part = 0, ms_repl = 0, repl_by[K_COUNT] = {0}; unsigned long long cnt[K_COUNT] = {0};
   std::map<int, double> sub_ms, sub_by; std::map<int, unsigned long long> sub_cnt;
@@ -84,7 +85,9 @@ int Ctx<F>::ensure_polys(size_t count) {
   while (ncap < count) ncap *= 2;
   DevBuf nb;
   if (nb.ensure(ncap * N * sizeof(T))) return fail(MS_ERR_NOMEM, "polys");
-  if (d_polys.p && npolys > 0) { CK(msrt::d2d(nb.p, d_polys.p, (size_t)npolys * N * sizeof(T), stream)); CK(msrt::sync(stream)); }
+  // what is live moves along: the polynomials, or - between ms_trace_commit and ms_interpolate - the trace columns and the running columns behind them
+  const size_t live = have_polys ? (size_t)npolys : (have_trace ? w + (size_t)naux : 0);
+  if (d_polys.p && live > 0) { CK(msrt::d2d(nb.p, d_polys.p, live * N * sizeof(T), stream)); CK(msrt::sync(stream)); }
   d_polys.release();
   d_polys = nb; polys_cap = ncap;
   return 0;
@@ -114,6 +117,7 @@ int Ctx<F>::init(int dev, u32 flags) {
   if (const char* e = getenv("MS_SYNC_POLL")) poll_sync = atoi(e);
   if (const char* e = getenv("MS_EVAL_SMALL_MAX")) eval_small_max = (size_t)atol(e);
   if (const char* e = getenv("MS_TREE_SUBTREE_PARENTS")) subtree_parents = (size_t)atol(e);
+  if (const char* e = getenv("MS_AUX_TILE")) { const int v = atoi(e); if (v >= msrun::THREADS && v <= AUX_TILE_DEFAULT && !(v & (v - 1))) aux_tile = v; }
   // the boundary's bulk copies (r04): page-locked trace in / FRI proof out on SDMA engines through the HSA runtime by default (measured with 8 provers in flight,
   // tools/io_probe3.py: resident 251 proofs/s; upload by hipMemcpyAsync 238, by SDMA 251; read-back by hipMemcpyAsync 217-223, by SDMA 242-248; both by SDMA 245.5 = 0.978)
   if (const char* e = getenv("MS_UPLOAD")) upload_sdma = !strcmp(e, "hip") ? 0 : 1;
@@ -183,7 +187,7 @@ int Ctx<F>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_,
   RQ(tree_shape(N_ * w_, lpn, 2, &ts));
   // (the canonical range of the trace is checked by the transposing kernel for host and device input alike: a host-side scan of the N x w matrix
   //  cost ~3 ms of the proving thread per 2^20-row proof, with its stream idle - r04, I/O leg)
-  have_trace = have_polys = have_lde = have_validity = false; npolys = 0; nrounds_done = 0; have_deep = false; blob_size = 0;
+  have_trace = have_polys = have_lde = have_validity = false; npolys = 0; naux = 0; nrounds_done = 0; have_deep = false; blob_size = 0;
   if (N_ != N) { polys_cap = 0; d_polys.release(); }
   N = N_; w = w_;
   const u64* dsrc;
@@ -213,14 +217,104 @@ int Ctx<F>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_,
   return MS_OK;
 }
 
+// ------------------------------------------------------------------ build-defined: ms_aux_running (include/ministark.h; kernels: running.hpp)
+template <class F>
+template <int EA, int SEG>
+int Ctx<F>::aux_tile_launch(const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag) {
+  typedef msrun::AuxTileKernel<F, EA, SEG> TK;
+  typename TK::Params tp{d_polys.as<T>(), N, N, reinterpret_cast<const typename TK::Program*>(prog), out, N, agg, ntiles, ntiles == 1 ? fin : nullptr, flag};
+  CK(run_coop<TK>(K_AUX, (unsigned)ntiles, TK::THREADS, TK::lds_bytes(), tp));
+  return 0;
+}
+
+template <class F>
+template <int EA>
+int Ctx<F>::aux_running_t(const ms_aux& a, u64* final_out, u64* column_out) {
+  typedef msrun::AuxProgram<F, EA> Program;
+  const u32 nforms = 2 * a.nfrac, nterms = a.form_begin[nforms];
+  const size_t tile = N < (size_t)aux_tile ? (N < (size_t)msrun::THREADS ? (size_t)msrun::THREADS : N) : (size_t)aux_tile;   // (a trace shorter than the tile: the smallest instance that holds it)
+  const size_t ntiles = (N + tile - 1) / tile;
+  // d_aux: [0, 8) the zero-denominator flag | [64, 64 + 8 EA) final as u64 limbs | [256, ..) the tile aggregates [EA][ntiles] | the carries [EA][ntiles]
+  const size_t off_fin = 64, off_agg = 256, agg_bytes = ((size_t)EA * ntiles * sizeof(T) + 255) & ~(size_t)255;
+  if (d_aux.ensure(off_agg + 2 * agg_bytes) || d_tabs.ensure(sizeof(Program) + 64)) return fail(MS_ERR_NOMEM, "aux_running buffers");
+  RQ(ensure_polys(w + (size_t)naux + EA + 1));
+  // the program, staged in page-locked memory (tabs_host synchronises the stream first: nothing of an earlier stage still reads the area)
+  u8* ht;
+  RQ(tabs_host(sizeof(Program) + 64, &ht));
+  Program* pg = reinterpret_cast<Program*>(ht);
+  memset(pg, 0, sizeof(Program));
+  pg->op = a.op; pg->nfrac = a.nfrac;
+  for (u32 f = 0; f <= nforms; f++) pg->form_begin[f] = a.form_begin[f];
+  for (u32 m = 0; m < nterms; m++) { pg->term_col[m] = a.term_col[m]; for (int l = 0; l < EA; l++) pg->term_coef[m].c[l] = F::from_u64(a.term_coef[(size_t)m * EA + l]); }
+  for (u32 f = 0; f < nforms; f++) for (int l = 0; l < EA; l++) pg->form_const[f].c[l] = F::from_u64(a.form_const[(size_t)f * EA + l]);
+  CK(msrt::h2d(d_tabs.p, ht, sizeof(Program), stream));
+  u32* flag = d_aux.as<u32>();
+  u64* fin = reinterpret_cast<u64*>(d_aux.as<u8>() + off_fin);
+  T* agg = reinterpret_cast<T*>(d_aux.as<u8>() + off_agg);
+  T* carry = reinterpret_cast<T*>(d_aux.as<u8>() + off_agg + agg_bytes);
+  T* out = d_polys.as<T>() + (w + (size_t)naux) * N;
+  CK(msrt::memset_dev(flag, 0, 8, stream));
+  const double row_bytes = (double)N * sizeof(T);
+  next_bytes = row_bytes * (double)(w + EA);      // (at most: the columns the forms name, and the column out)
+  switch (tile / msrun::THREADS) {
+    case 1: RQ((aux_tile_launch<EA, 1>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    case 2: RQ((aux_tile_launch<EA, 2>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    case 4: RQ((aux_tile_launch<EA, 4>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    default: RQ((aux_tile_launch<EA, 8>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
+  }
+  if (ntiles > 1) {
+    typedef msrun::AuxCarryKernel<F, EA> CKn;
+    typename CKn::Params cp{agg, carry, ntiles, a.op, fin};
+    CK(run_coop<CKn>(K_AUX, 1, CKn::THREADS, CKn::lds_bytes(), cp));
+    typedef msrun::AuxApplyKernel<F, EA> AK;
+    typename AK::Params ap{out, N, N, carry, ntiles, (u32)ctz64(tile), a.op};
+    next_bytes = 2 * row_bytes * EA;
+    CK(run<AK>(K_AUX, grid1(N, AK::THREADS), 1, AK::THREADS, 0, ap));
+  }
+  u64 res[8 + 4];   // [flag | 7 words of padding | final]
+  CK(msrt::d2h(res, d_aux.p, off_fin + (size_t)EA * 8, stream));
+  CK(msrt::sync(stream));
+  if (res[0] & 0xFFFFFFFFu) return fail(MS_ERR_SHAPE, "aux_running: a denominator is zero on some row (draw another challenge)");
+  if (column_out) RQ(download_widen(out, N, N, (u32)EA, column_out));
+  for (int l = 0; l < EA; l++) final_out[l] = res[off_fin / 8 + l];
+  naux += EA;
+  return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::aux_running(const ms_aux* aux, u64* final_out, u64* column_out) {
+  if (!aux || !final_out) return fail(MS_ERR_ARG, "aux_running: null argument");
+  if (!have_trace) return fail(MS_ERR_STATE, "aux_running before trace_commit");
+  if (have_polys) return fail(MS_ERR_STATE, "aux_running after interpolate: the trace columns have been transformed");
+  if (sh_on) return fail(MS_ERR_STATE, "aux_running: not available on a context with sharding on");
+  const ms_aux& a = *aux;
+  if (a.op > 1) return fail(MS_ERR_ARG, "aux_running: op must be MS_AUX_SUM or MS_AUX_PRODUCT");
+  if (a.ext != 1 && a.ext != (u32)E) return fail(MS_ERR_ARG, "aux_running: ext must be 1 or the extension degree");
+  if (a.nfrac < 1 || a.nfrac > (u32)msrun::MAX_FRAC) return fail(MS_ERR_ARG, "aux_running: nfrac outside 1..4");
+  if (!a.form_begin || !a.form_const) return fail(MS_ERR_ARG, "aux_running: null array");
+  const u32 nforms = 2 * a.nfrac;
+  if (a.form_begin[0] != 0) return fail(MS_ERR_ARG, "aux_running: form_begin[0] must be 0");
+  for (u32 f = 0; f < nforms; f++) {
+    if (a.form_begin[f + 1] < a.form_begin[f]) return fail(MS_ERR_ARG, "aux_running: form_begin decreases");
+    if (a.form_begin[f + 1] - a.form_begin[f] > (u32)msrun::MAX_FORM_TERMS) return fail(MS_ERR_ARG, "aux_running: more than 16 terms in a form");
+  }
+  const u32 nterms = a.form_begin[nforms];
+  if (nterms && (!a.term_col || !a.term_coef)) return fail(MS_ERR_ARG, "aux_running: null array");
+  for (u32 m = 0; m < nterms; m++) if (a.term_col[m] >= w) return fail(MS_ERR_ARG, "aux_running: a term names a column >= w");
+  if (!canonical(a.term_coef, (size_t)nterms * a.ext) || !canonical(a.form_const, (size_t)nforms * a.ext)) return fail(MS_ERR_ARG, "aux_running: limb not canonical");
+  if ((size_t)naux + a.ext > (size_t)msrun::MAX_COLUMNS) return fail(MS_ERR_ARG, "aux_running: more than 16 limb columns in all");
+  return a.ext == 1 ? aux_running_t<1>(a, final_out, column_out) : aux_running_t<E>(a, final_out, column_out);
+}
+
 // ------------------------------------------------------------------ air.rs:147-160
 template <class F>
 int Ctx<F>::interpolate() {
   if (!have_trace) return fail(MS_ERR_STATE, "interpolate before trace_commit");
-  RQ(ntt_run(ctz64(N), true, d_polys.as<T>(), N, N, d_polys.as<T>(), N, w));
-  poly_lin.assign(w, Lin());   // (first: if this allocation fails the session keeps no half-set state)
-  poly_mat.assign(w, 1);
-  npolys = (int)w; have_polys = true; have_lde = have_validity = false;
+  const size_t cols = w + (size_t)naux;   // the trace columns and the running columns of ms_aux_running behind them
+  RQ(ntt_run(ctz64(N), true, d_polys.as<T>(), N, N, d_polys.as<T>(), N, cols));
+  poly_lin.assign(cols, Lin());   // (first: if this allocation fails the session keeps no half-set state)
+  poly_mat.assign(cols, 1);
+  npolys = (int)cols; have_polys = true; have_lde = have_validity = false;
   return MS_OK;
 }
 
@@ -291,6 +385,7 @@ int Ctx<F>::arith_selftest(int op, const u64* a, const u64* b, u64* out, size_t 
   template int Ctx<FF>::download_widen(const Ctx<FF>::T* src, size_t n, size_t limb_stride, u32 e, u64* host); \
   template int Ctx<FF>::transpose_in(const u64* src, Ctx<FF>::T* dst, size_t rows, size_t cols, Ctx<FF>::T rinv, int mont, u32* bad); \
   template int Ctx<FF>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_, size_t lpn, u8* root); \
+  template int Ctx<FF>::aux_running(const ms_aux* aux, u64* final_out, u64* column_out); \
   template int Ctx<FF>::interpolate(); \
   template int Ctx<FF>::polys_lincomb(const u64* s, const int* idx, int k); \
   template int Ctx<FF>::polys_append(const u64* coeffs, size_t n); \
