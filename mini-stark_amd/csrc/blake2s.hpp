@@ -13,6 +13,8 @@
 //   * Instructions by the measured issue rates (profiles/r04_valu_issue_rate.txt): a + b + m is one v_add3_u32, every rotate one v_alignbit_b32 (a v_perm_b32
 //     for 16 and 8 issues no faster), the closing h ^= v[i] ^ v[i + 8] one v_bitop3_b32.
 //   * One node per lane on every level: the pair-of-lanes node of the SHA-256 subtree kernel (Sha256Pair) has no counterpart here (open latency item).
+//     The inner kernels are therefore the shared pair of merkle.hpp, LaneInnerHashKernelT<IC, ND> and LaneSubtreeKernel<ND>, with ND = Blake2sNode below: this file
+//     holds the compression, the stream, the node policy and the family.
 #pragma once
 #include "merkle.hpp"
 
@@ -70,19 +72,6 @@ struct Blake2s {
   }
 };
 
-// 64 bytes (two digests) at src as the 16 message words of a block
-MS_HD void b2_load_block(const u32* src, u32 (&w)[16]) {
-  const uint4_t* c4 = reinterpret_cast<const uint4_t*>(src);
-#pragma unroll
-  for (int q = 0; q < 4; q++) { const uint4_t v = c4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-}
-// the thread that produced the root hands it (and the optional aux word) to page-locked host memory, as InnerHashKernelT does
-MS_DEV void b2_forward_root(const InnerHashParams& p, const Blake2s& h) {
-  h.store(p.host_root);
-  if (p.aux_src) { *p.aux_dst = *p.aux_src; *p.aux_src = 0; }
-  msrt::raise_host_flag(p.flag);
-}
-
 // byte stream -> BLAKE2s-256 over the buffer of PackStream.  `drain` holds the ONE compression site of the kernel, for inner and final blocks alike (t and the final
 // flag are run-time values).  Before the final drain a block is compressed once MORE than 64 bytes are pending (LAZY: and some lane of the wave is out of room), so
 // at most 64 bytes are pending behind a non-LAZY drain - which is why the buffer is one word longer than ShaStream's (EXTRA_WORDS): an append may start at word 16.
@@ -125,64 +114,17 @@ template <int NWORDS, int NT, int MAXW, bool LAZY> struct B2Stream : PackStream<
   }
 };
 
-// Inner levels, as InnerHashKernelT: ic * 32 bytes = ic / 2 blocks, the last one final.  IC > 0: inner_children fixed at compile time; IC = 0: from Params.
-template <int IC> struct B2InnerHashKernelT {
-  static constexpr int THREADS = msmerkle::THREADS;
-  typedef InnerHashParams Params;
-  static MS_HD int nphases(const Params& p) { return (int)p.nlevels; }
-  static MS_DEV void phase(int ph, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
-    const u32 ic = IC ? (u32)IC : p.ic;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    for (int l = 0; l < ph; l++) { child_off += nchildren; nchildren /= ic; }
-    const size_t nparents = nchildren / ic;
-    const size_t stride = (p.nlevels > 1) ? (size_t)nthreads : 0;
-    for (size_t g = (size_t)bx * nthreads + tid; g < nparents; g += stride) {
-      const u32* ch = p.nodes + (child_off + g * ic) * 8;
-      Blake2s h; h.init();
-      for (u32 b = 0; b < ic / 2; b++) {
-        u32 w[16];
-        b2_load_block(ch + b * 16, w);
-        h.compress(w, 64u * (b + 1), b + 1 == ic / 2);
-      }
-      h.store(p.nodes + (child_off + nchildren + g) * 8);
-      if (p.host_root && nparents == 1) b2_forward_root(p, h);
-      if (stride == 0) break;
-    }
-  }
-};
-typedef B2InnerHashKernelT<0> B2InnerHashKernel;
-typedef B2InnerHashKernelT<2> B2InnerHashKernel2;
-
-// InnerSubtreeKernel's scheme (workgroup b hashes the nlevels levels above its 2^nlevels children, a level's parents read their children from LDS) with one
-// parent per lane on every level.  A digest in LDS is the same 8 words as in global memory.
-struct B2InnerSubtreeKernel {
-  static constexpr int THREADS = msmerkle::THREADS;
-  static constexpr int MAX_LEVELS = InnerSubtreeKernel::MAX_LEVELS;
-  typedef InnerHashParams Params;
-  static MS_HD size_t lds_bytes() { return InnerSubtreeKernel::lds_bytes(); }
-  static MS_DEV void run(const Params& p, int bx, int, int, int tid, unsigned char* lds) {
-    u32* const buf0 = reinterpret_cast<u32*>(lds);          // levels 0, 2, 4, ...: <= THREADS digests
-    u32* const buf1 = buf0 + (size_t)THREADS * 8;           // levels 1, 3, ...: <= THREADS / 2 digests
-    const u32 nl = p.nlevels;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    u32 pp = 1u << nl;
-    for (u32 l = 0; l < nl; l++) {
-      pp >>= 1;   // parents of this workgroup at this level
-      const size_t nparents = nchildren >> 1;
-      if ((u32)tid < pp) {
-        const size_t g = (size_t)bx * pp + (u32)tid;
-        u32 w[16];
-        if (l == 0) b2_load_block(p.nodes + (child_off + 2 * g) * 8, w);
-        else b2_load_block(((l & 1) ? buf0 : buf1) + (size_t)tid * 16, w);
-        Blake2s h; h.init();
-        h.compress(w, 64u, true);
-        if (l + 1 < nl) h.store(((l & 1) ? buf1 : buf0) + (size_t)tid * 8);
-        h.store(p.nodes + (child_off + nchildren + g) * 8);
-        if (p.host_root && nparents == 1) b2_forward_root(p, h);
-      }
-      if (l + 1 < nl) msrt::wg_barrier();
-      child_off += nchildren; nchildren = nparents;
-    }
+// The node policy of the shared one-node-per-lane kernels (merkle.hpp: LaneInnerHashKernelT, LaneSubtreeKernel): ic * 32 bytes = ic / 2 blocks, the last one final.
+struct Blake2sNode {
+  typedef Blake2s State;
+  static MS_HD Blake2s node(const u32 (&w)[16]) { Blake2s h; h.init(); h.compress(w, 64u, true); return h; }
+  template <int IC> static MS_HD u32 nblocks(u32 ic) { return ic / 2; }
+  template <int IC> static MS_HD void block(Blake2s& st, const u32* ch, u32 b, u32 ic) {
+    Blake2s h = st;   // (a local copy: compressing through the reference swaps the operands of some of G's xors)
+    u32 w[16];
+    load_node64(ch + b * 16, w);
+    h.compress(w, 64u * (b + 1), b + 1 == ic / 2);
+    st = h;
   }
 };
 
@@ -192,7 +134,9 @@ struct Blake2sKernels {
   static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
   static constexpr int EXTRA_WORDS = 1;
   static constexpr bool DEFERS = false;
-  typedef B2InnerSubtreeKernel Subtree;
+  typedef LaneInnerHashKernelT<0, Blake2sNode> Inner;
+  typedef LaneInnerHashKernelT<2, Blake2sNode> Inner2;
+  typedef LaneSubtreeKernel<Blake2sNode> Subtree;
 };
 
 }  // namespace msmerkle

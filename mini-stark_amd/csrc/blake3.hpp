@@ -16,7 +16,9 @@
 //     B3InnerHashMultiKernel), picked by the host from an upper bound of the message length, so that the single-chunk kernels pay nothing and carry no stack.
 //     LIMIT: B3_MAX_BYTES = 16 KiB per message = 16 chunks = a stack of B3_STACK = 4 chaining values, which lives in LDS (word-interleaved like the message
 //     buffer), never in scratch.  Above the limit the host returns MS_ERR_ARG (merkle_tree.cpp); no kernel is launched.
-//   * One node per lane on every level: no pair-of-lanes variant, as for BLAKE2s.
+//   * One node per lane on every level: no pair-of-lanes variant, as for BLAKE2s.  The single-chunk inner kernels are the shared pair of merkle.hpp,
+//     LaneInnerHashKernelT<IC, ND> and LaneSubtreeKernel<ND>, with ND = Blake3Node below; B3InnerHashMultiKernel (LDS for its stack) is a kernel of its own.  The
+//     family Blake3Kernels names the bounds and the multi-chunk instances the host chooses by.
 #pragma once
 #include "merkle.hpp"
 
@@ -81,19 +83,6 @@ struct Blake3 {
     out[0] = o0; out[1] = o1;
   }
 };
-
-// 64 bytes (two digests) at src as the 16 message words of a block
-MS_HD void b3_load_block(const u32* src, u32 (&w)[16]) {
-  const uint4_t* c4 = reinterpret_cast<const uint4_t*>(src);
-#pragma unroll
-  for (int q = 0; q < 4; q++) { const uint4_t v = c4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-}
-// the thread that produced the root hands it (and the optional aux word) to page-locked host memory, as InnerHashKernelT does
-MS_DEV void b3_forward_root(const InnerHashParams& p, const Blake3& h) {
-  h.store(p.host_root);
-  if (p.aux_src) { *p.aux_dst = *p.aux_src; *p.aux_src = 0; }
-  msrt::raise_host_flag(p.flag);
-}
 
 // The chaining values of the finished chunks of ONE message that wait for their right siblings: B3_STACK entries of 8 words in LDS, word-interleaved over the NT
 // threads of the workgroup (word i of entry s at base[(8 * s + i) * NT]: conflict free, and no dynamically indexed registers).  `merge` holds the one PARENT
@@ -189,39 +178,25 @@ template <int NWORDS, int NT, int MAXW, bool LAZY, bool MULTI> struct B3StreamT 
   }
 };
 
-// Inner levels, as InnerHashKernelT: ic * 32 bytes = ic / 2 blocks of ONE chunk (ic <= 32; more children: B3InnerHashMultiKernel).  IC > 0: inner_children fixed at
-// compile time (IC = 2: one compression with flags 11); IC = 0: from Params.
-template <int IC> struct B3InnerHashKernelT {
-  static constexpr int THREADS = msmerkle::THREADS;
+// The node policy of the shared one-node-per-lane kernels (merkle.hpp: LaneInnerHashKernelT, LaneSubtreeKernel): ic * 32 bytes = ic / 2 blocks of ONE chunk
+// (ic <= MAX_IC = 32; more children: B3InnerHashMultiKernel).  A node of the binary tree is one compression with flags START | END | ROOT = 11.
+struct Blake3Node {
+  typedef Blake3 State;
   static constexpr u32 MAX_IC = B3_CHUNK_BYTES / 32;
-  static_assert(IC <= (int)MAX_IC, "one chunk");
-  typedef InnerHashParams Params;
-  static MS_HD int nphases(const Params& p) { return (int)p.nlevels; }
-  static MS_DEV void phase(int ph, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
-    const u32 ic = IC ? (u32)IC : p.ic;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    for (int l = 0; l < ph; l++) { child_off += nchildren; nchildren /= ic; }
-    const size_t nparents = nchildren / ic;
-    const size_t stride = (p.nlevels > 1) ? (size_t)nthreads : 0;
-    for (size_t g = (size_t)bx * nthreads + tid; g < nparents; g += stride) {
-      const u32* ch = p.nodes + (child_off + g * ic) * 8;
-      Blake3 h; h.init();
-      for (u32 b = 0; b < ic / 2; b++) {
-        u32 w[16];
-        b3_load_block(ch + b * 16, w);
-        h.compress(w, 0u, 64u, (b == 0 ? B3_CHUNK_START : 0u) | (b + 1 == ic / 2 ? (B3_CHUNK_END | B3_ROOT) : 0u));
-      }
-      h.store(p.nodes + (child_off + nchildren + g) * 8);
-      if (p.host_root && nparents == 1) b3_forward_root(p, h);
-      if (stride == 0) break;
-    }
+  static MS_HD Blake3 node(const u32 (&w)[16]) { Blake3 h; h.init(); h.compress(w, 0u, 64u, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT); return h; }
+  template <int IC> static MS_HD u32 nblocks(u32 ic) { static_assert(IC <= (int)MAX_IC, "one chunk"); return ic / 2; }
+  template <int IC> static MS_HD void block(Blake3& st, const u32* ch, u32 b, u32 ic) {
+    Blake3 h = st;   // (a local copy, as Blake2sNode's)
+    u32 w[16];
+    load_node64(ch + b * 16, w);
+    h.compress(w, 0u, 64u, (b == 0 ? B3_CHUNK_START : 0u) | (b + 1 == ic / 2 ? (B3_CHUNK_END | B3_ROOT) : 0u));
+    st = h;
   }
 };
-typedef B3InnerHashKernelT<0> B3InnerHashKernel;
-typedef B3InnerHashKernelT<2> B3InnerHashKernel2;
 
 // Inner levels whose nodes have more than 32 children (ic * 32 bytes > one chunk), up to B3_MAX_BYTES / 32 = 512: ic / 32 whole chunks (ic is a power of two) and
-// the parents above them, the waiting chaining values in LDS.  Launched with lds_bytes() of dynamic LDS.
+// the parents above them, the waiting chaining values in LDS.  Launched with lds_bytes() of dynamic LDS.  (The stack needs the workgroup's LDS and the thread's
+// index, which a node policy does not see: a kernel of its own, on the shared loader and root forwarder.)
 struct B3InnerHashMultiKernel {
   static constexpr int THREADS = msmerkle::THREADS;
   static constexpr u32 MAX_IC = B3_MAX_BYTES / 32;
@@ -241,7 +216,7 @@ struct B3InnerHashMultiKernel {
       B3CvStack<THREADS> stack; stack.init(reinterpret_cast<u32*>(lds) + tid);
       for (u32 b = 0; b < nblocks; b++) {
         u32 w[16];
-        b3_load_block(ch + b * 16, w);
+        load_node64(ch + b * 16, w);
         const u32 bic = b & 15u, chunk = b >> 4;
         const bool last = b + 1 == nblocks, chunk_end = last || bic == 15u;
         h.compress(w, chunk, 64u, (bic == 0 ? B3_CHUNK_START : 0u) | (chunk_end ? B3_CHUNK_END : 0u) | ((last && nchunks == 1) ? B3_ROOT : 0u));
@@ -251,59 +226,35 @@ struct B3InnerHashMultiKernel {
         }
       }
       h.store(p.nodes + (child_off + nchildren + g) * 8);
-      if (p.host_root && nparents == 1) b3_forward_root(p, h);
+      if (p.host_root && nparents == 1) forward_root(p, h);
       if (stride == 0) break;
     }
   }
 };
 
-// InnerSubtreeKernel's scheme (workgroup b hashes the nlevels levels above its 2^nlevels children, a level's parents read their children from LDS) with one
-// parent per lane on every level.  A digest in LDS is the same 8 words as in global memory.
-struct B3InnerSubtreeKernel {
-  static constexpr int THREADS = msmerkle::THREADS;
-  static constexpr int MAX_LEVELS = InnerSubtreeKernel::MAX_LEVELS;
-  typedef InnerHashParams Params;
-  static MS_HD size_t lds_bytes() { return InnerSubtreeKernel::lds_bytes(); }
-  static MS_DEV void run(const Params& p, int bx, int, int, int tid, unsigned char* lds) {
-    u32* const buf0 = reinterpret_cast<u32*>(lds);          // levels 0, 2, 4, ...: <= THREADS digests
-    u32* const buf1 = buf0 + (size_t)THREADS * 8;           // levels 1, 3, ...: <= THREADS / 2 digests
-    const u32 nl = p.nlevels;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    u32 pp = 1u << nl;
-    for (u32 l = 0; l < nl; l++) {
-      pp >>= 1;   // parents of this workgroup at this level
-      const size_t nparents = nchildren >> 1;
-      if ((u32)tid < pp) {
-        const size_t g = (size_t)bx * pp + (u32)tid;
-        u32 w[16];
-        if (l == 0) b3_load_block(p.nodes + (child_off + 2 * g) * 8, w);
-        else b3_load_block(((l & 1) ? buf0 : buf1) + (size_t)tid * 16, w);
-        Blake3 h; h.init();
-        h.compress(w, 0u, 64u, B3_CHUNK_START | B3_CHUNK_END | B3_ROOT);
-        if (l + 1 < nl) h.store(((l & 1) ? buf1 : buf0) + (size_t)tid * 8);
-        h.store(p.nodes + (child_off + nchildren + g) * 8);
-        if (p.host_root && nparents == 1) b3_forward_root(p, h);
-      }
-      if (l + 1 < nl) msrt::wg_barrier();
-      child_off += nchildren; nchildren = nparents;
-    }
-  }
-};
-
 // The BLAKE3 kernel families (DG of LeafHashKernel and msfri::FriTailKernel): messages of at most one chunk, and (leaf hashing only) of up to B3_MAX_BYTES.
-struct Blake3Kernels {
-  template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B3StreamT<NWORDS, NT, MAXW, LAZY, false>;
-  static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
-  static constexpr int EXTRA_WORDS = 1;
-  static constexpr bool DEFERS = false;
-  typedef B3InnerSubtreeKernel Subtree;
-};
 struct Blake3MultiKernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B3StreamT<NWORDS, NT, MAXW, LAZY, true>;
   static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
   static constexpr int EXTRA_WORDS = 1 + B3CvStack<THREADS>::WORDS;
   static constexpr bool DEFERS = false;
-  typedef B3InnerSubtreeKernel Subtree;
+  typedef LaneInnerHashKernelT<0, Blake3Node> Inner;
+  typedef LaneInnerHashKernelT<2, Blake3Node> Inner2;
+  typedef LaneSubtreeKernel<Blake3Node> Subtree;
+};
+struct Blake3Kernels {
+  template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = B3StreamT<NWORDS, NT, MAXW, LAZY, false>;
+  static constexpr int BLOCK_WORDS = 16, LAZY_BLOCKS = 2;
+  static constexpr int EXTRA_WORDS = 1;
+  static constexpr bool DEFERS = false;
+  typedef LaneInnerHashKernelT<0, Blake3Node> Inner;
+  typedef LaneInnerHashKernelT<2, Blake3Node> Inner2;
+  typedef LaneSubtreeKernel<Blake3Node> Subtree;
+  // what the host picks an instance by: a message (a leaf group's upper bound, an inner node's ic * 32 bytes) of up to CHUNK_BYTES takes the kernels above,
+  // up to MAX_BYTES the multi-chunk ones, a longer one is refused
+  static constexpr u32 CHUNK_BYTES = B3_CHUNK_BYTES, MAX_BYTES = B3_MAX_BYTES;
+  typedef Blake3MultiKernels Multi;            // DG of the multi-chunk leaf kernels
+  typedef B3InnerHashMultiKernel InnerMulti;   // launched with its lds_bytes()
 };
 
 }  // namespace msmerkle

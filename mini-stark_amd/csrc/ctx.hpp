@@ -315,7 +315,7 @@ template <class F> struct Ctx : CtxBase {
   struct TreeShape { size_t leaf_num = 0, lpn = 0, ic = 0, levels = 0, nodes = 0, local_nodes = 0, Mloc = 0; bool sharded = false; };
   // src/merkle.rs:89-118 (shape checks and node count)
   int tree_shape(size_t leaf_num, size_t lpn, size_t ic, TreeShape* ts);
-  // leaf-group digests of `ngroups` groups into `out`: LeafHashKernel + (SHA-256) the compacted pad-only blocks it deferred; by the context's digest
+  // leaf-group digests of `ngroups` groups into `out`: LeafHashKernel + (a family that defers them: SHA-256) the compacted pad-only blocks; the family by the context's digest (msmerkle::with_digest)
   template <int EL>
   int leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
                 size_t g_first = 0, u32 run_len = 0, u32 run_stride = 0, const msmerkle::LinColSpec* lin = nullptr, size_t out_g0 = 0);
@@ -607,7 +607,7 @@ template <class F> struct Ctx : CtxBase {
   struct StreamScope { Ctx* c; msrt::Stream* keep; StreamScope(Ctx* c_, msrt::Stream* s) : c(c_), keep(c_->stream) { c->stream = s; } ~StreamScope() { c->stream = keep; } };
   int join_side() { if (side_pending) { side_pending = false; CK(msrt::stream_wait_event(stream, ev_side)); } return 0; }   // the context's stream goes on only behind the side stream's work
   int fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done);
-  template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: msmerkle::Sha256Kernels / Blake2sKernels / Blake3Kernels / KeccakKernels<SUFFIX>, by `digest`
+  template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: the kernel family of `digest` (msmerkle::with_digest, digest.hpp)
   int fri_round_info(int r, u64* ncoef, u64* D) override;
   int fri_round_poly_read(int r, u64* out) override;
   int fri_round_codeword_read(int r, u64* out) override;

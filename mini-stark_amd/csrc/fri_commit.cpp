@@ -1,6 +1,7 @@
 // fri_commit.cpp — the FRI commit phase (fri.rs:64-113, 301-377): round commitments, even(z) / odd(z), fold + DEEP quotient (replicated and by coefficient range),
 // and the suffix-Horner job planning the query phase shares.
 #include "ctx.hpp"
+#include "digest.hpp"
 #include "fri_tail.hpp"
 
 namespace msctx {
@@ -346,10 +347,8 @@ int Ctx<F>::fold_dist(Round* pr, Round* nr, const XE& a, size_t* nq_coef_out) {
 // level, root and length word into page-locked memory.  *done = false: the round does not qualify (the caller takes the launch-per-step path).
 template <class F>
 int Ctx<F>::fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done) {
-  if (digest == MS_DIGEST_KECCAK256) return fri_tail_round_t<msmerkle::Keccak256Kernels>(pr, nr, a, done);
-  if (digest == MS_DIGEST_SHA3_256) return fri_tail_round_t<msmerkle::Sha3_256Kernels>(pr, nr, a, done);
-  if (digest == MS_DIGEST_BLAKE3) return fri_tail_round_t<msmerkle::Blake3Kernels>(pr, nr, a, done);   // (a round's leaf group is 2 extension elements: far below one chunk)
-  return digest == MS_DIGEST_BLAKE2S256 ? fri_tail_round_t<msmerkle::Blake2sKernels>(pr, nr, a, done) : fri_tail_round_t<msmerkle::Sha256Kernels>(pr, nr, a, done);
+  // (BLAKE3: a round's leaf group is 2 extension elements, far below one chunk)
+  return msmerkle::with_digest(digest, [&](auto family) { return fri_tail_round_t<decltype(family)>(pr, nr, a, done); });
 }
 template <class F> template <class DG>
 int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {

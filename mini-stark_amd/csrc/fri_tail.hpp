@@ -17,9 +17,7 @@
 // stand-alone kernel (mspoly::FoldKernel, SuffixHornerKernel, DegreeKernel, FriFoldEvalKernel, msmerkle::LeafHashKernel, InnerSubtreeKernel): same
 // arithmetic, same bytes - the parity suite runs with the fused round forced on and off (MS_FRI_TAIL_MAX).
 #pragma once
-#include "blake2s.hpp"
-#include "blake3.hpp"
-#include "keccak.hpp"
+#include "digest.hpp"
 #include "poly.hpp"
 
 namespace msfri {

@@ -16,7 +16,8 @@
 //     there is no hold-back rule as for the BLAKE families: a block is absorbed whenever 136 bytes are pending, and the final drain absorbs what is left - 0
 //     to 135 bytes - with the padding written by position.  A message whose length is a multiple of 136 (the empty message included) ends in a block of
 //     padding only, absorbed right there: no deferred blocks, no lists, one launch per commitment.  No message-length limit.
-//   * One node per lane on every level, as for the BLAKE families.
+//   * One node per lane on every level, as for the BLAKE families: the inner kernels are the shared pair of merkle.hpp, LaneInnerHashKernelT<IC, ND>
+//     and LaneSubtreeKernel<ND>, with ND = KeccakNode<SUFFIX> below.
 #pragma once
 #include "merkle.hpp"
 
@@ -121,19 +122,6 @@ struct Keccak1600 {
   }
 };
 
-// 64 bytes (two digests) at src as 16 words
-MS_HD void keccak_load_node(const u32* src, u32 (&w)[16]) {
-  const uint4_t* c4 = reinterpret_cast<const uint4_t*>(src);
-#pragma unroll
-  for (int q = 0; q < 4; q++) { const uint4_t v = c4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
-}
-// the thread that produced the root hands it (and the optional aux word) to page-locked host memory, as InnerHashKernelT does
-MS_DEV void keccak_forward_root(const InnerHashParams& p, const Keccak1600& h) {
-  h.store(p.host_root);
-  if (p.aux_src) { *p.aux_dst = *p.aux_src; *p.aux_src = 0; }
-  msrt::raise_host_flag(p.flag);
-}
-
 // byte stream -> Keccak over the buffer of PackStream.  `drain` holds the ONE permutation site of the kernel.  Before the final drain a block is absorbed once 34
 // full words are pending (LAZY: and some lane of the wave is out of room), so fewer than 136 bytes are pending behind a non-LAZY drain and its final drain is
 // one block.  The buffer is one rate block + room for one element for both forms (LeafHashKernel::NWORDS with LAZY_BLOCKS = 1): two rate blocks per thread
@@ -186,74 +174,29 @@ template <int NWORDS, int NT, int MAXW, bool LAZY, u32 SUFFIX> struct KeccakStre
   }
 };
 
-// Inner levels, as InnerHashKernelT.  IC = 2: one permutation over the 64 bytes, the padding constant.  IC = 0 (inner_children from Params): the ic * 32 bytes of
-// the contiguous children absorbed 136 at a time, ic * 32 / 136 + 1 blocks - when 136 divides the length the last one holds the padding only.
-template <int IC, u32 SUFFIX> struct KeccakInnerHashKernelT {
-  static_assert(IC == 0 || IC == 2, "the binary tree's instance, or the general one");
-  static constexpr int THREADS = msmerkle::THREADS;
-  typedef InnerHashParams Params;
-  static MS_HD int nphases(const Params& p) { return (int)p.nlevels; }
-  static MS_DEV void phase(int ph, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
-    const u32 ic = IC ? (u32)IC : p.ic;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    for (int l = 0; l < ph; l++) { child_off += nchildren; nchildren /= ic; }
-    const size_t nparents = nchildren / ic;
-    const size_t stride = (p.nlevels > 1) ? (size_t)nthreads : 0;
-    for (size_t g = (size_t)bx * nthreads + tid; g < nparents; g += stride) {
-      const u32* ch = p.nodes + (child_off + g * ic) * 8;
-      Keccak1600 h;
-      if constexpr (IC == 2) {
-        u32 w[16];
-        keccak_load_node(ch, w);
-        h.template node64<SUFFIX>(w);
-      } else {
-        h.init();
-        const u32 nw = ic * 8u, nblocks = nw / KECCAK_RATE_WORDS + 1u;   // message words (digests are whole words: the suffix byte starts a word)
-        for (u32 b = 0; b < nblocks; b++) {
-          const u32 w0 = b * KECCAK_RATE_WORDS;
-          u32 w[34];
-#pragma unroll
-          for (int i = 0; i < 34; i++) w[i] = (w0 + i < nw) ? ch[w0 + i] : ((w0 + i == nw) ? SUFFIX : 0u);
-          if (b + 1 == nblocks) w[33] ^= 0x80000000u;
-          h.absorb(w);
-        }
-      }
-      h.store(p.nodes + (child_off + nchildren + g) * 8);
-      if (p.host_root && nparents == 1) keccak_forward_root(p, h);
-      if (stride == 0) break;
-    }
+// The node policy of the shared one-node-per-lane kernels (merkle.hpp: LaneInnerHashKernelT, LaneSubtreeKernel).  IC = 2: one permutation over the 64 bytes, the
+// padding constant.  IC = 0 (inner_children from Params): the ic * 32 bytes of the contiguous children absorbed 136 at a time, ic * 32 / 136 + 1 blocks - when 136
+// divides the length the last one holds the padding only.
+template <u32 SUFFIX> struct KeccakNode {
+  typedef Keccak1600 State;
+  static MS_HD Keccak1600 node(const u32 (&w)[16]) { Keccak1600 h; h.template node64<SUFFIX>(w); return h; }
+  // message words ic * 8 (digests are whole words: the suffix byte starts a word)
+  template <int IC> static MS_HD u32 nblocks(u32 ic) {
+    static_assert(IC == 0 || IC == 2, "the binary tree's instance, or the general one");
+    return IC == 2 ? 1u : ic * 8u / KECCAK_RATE_WORDS + 1u;
   }
-};
-
-// InnerSubtreeKernel's scheme (workgroup b hashes the nlevels levels above its 2^nlevels children, a level's parents read their children from LDS) with one
-// parent per lane on every level.  A digest in LDS is the same 8 words as in global memory.
-template <u32 SUFFIX> struct KeccakInnerSubtreeKernel {
-  static constexpr int THREADS = msmerkle::THREADS;
-  static constexpr int MAX_LEVELS = InnerSubtreeKernel::MAX_LEVELS;
-  typedef InnerHashParams Params;
-  static MS_HD size_t lds_bytes() { return InnerSubtreeKernel::lds_bytes(); }
-  static MS_DEV void run(const Params& p, int bx, int, int, int tid, unsigned char* lds) {
-    u32* const buf0 = reinterpret_cast<u32*>(lds);          // levels 0, 2, 4, ...: <= THREADS digests
-    u32* const buf1 = buf0 + (size_t)THREADS * 8;           // levels 1, 3, ...: <= THREADS / 2 digests
-    const u32 nl = p.nlevels;
-    size_t child_off = p.child_off, nchildren = p.nchildren;
-    u32 pp = 1u << nl;
-    for (u32 l = 0; l < nl; l++) {
-      pp >>= 1;   // parents of this workgroup at this level
-      const size_t nparents = nchildren >> 1;
-      if ((u32)tid < pp) {
-        const size_t g = (size_t)bx * pp + (u32)tid;
-        u32 w[16];
-        if (l == 0) keccak_load_node(p.nodes + (child_off + 2 * g) * 8, w);
-        else keccak_load_node(((l & 1) ? buf0 : buf1) + (size_t)tid * 16, w);
-        Keccak1600 h;
-        h.template node64<SUFFIX>(w);
-        if (l + 1 < nl) h.store(((l & 1) ? buf1 : buf0) + (size_t)tid * 8);
-        h.store(p.nodes + (child_off + nchildren + g) * 8);
-        if (p.host_root && nparents == 1) keccak_forward_root(p, h);
-      }
-      if (l + 1 < nl) msrt::wg_barrier();
-      child_off += nchildren; nchildren = nparents;
+  template <int IC> static MS_HD void block(Keccak1600& h, const u32* ch, u32 b, u32 ic) {
+    if constexpr (IC == 2) {
+      u32 w[16];
+      load_node64(ch, w);
+      h.template node64<SUFFIX>(w);
+    } else {
+      const u32 nw = ic * 8u, w0 = b * KECCAK_RATE_WORDS;
+      u32 w[34];
+#pragma unroll
+      for (int i = 0; i < 34; i++) w[i] = (w0 + i < nw) ? ch[w0 + i] : ((w0 + i == nw) ? SUFFIX : 0u);
+      if (b + 1 == nblocks<IC>(ic)) w[33] ^= 0x80000000u;
+      h.absorb(w);
     }
   }
 };
@@ -265,9 +208,9 @@ template <u32 SUFFIX> struct KeccakKernels {
   static constexpr int LAZY_BLOCKS = 1;
   static constexpr int EXTRA_WORDS = 0;
   static constexpr bool DEFERS = false;
-  typedef KeccakInnerSubtreeKernel<SUFFIX> Subtree;
-  typedef KeccakInnerHashKernelT<0, SUFFIX> Inner;
-  typedef KeccakInnerHashKernelT<2, SUFFIX> Inner2;
+  typedef LaneInnerHashKernelT<0, KeccakNode<SUFFIX>> Inner;
+  typedef LaneInnerHashKernelT<2, KeccakNode<SUFFIX>> Inner2;
+  typedef LaneSubtreeKernel<KeccakNode<SUFFIX>> Subtree;
 };
 typedef KeccakKernels<KECCAK_SUFFIX_KECCAK256> Keccak256Kernels;
 typedef KeccakKernels<KECCAK_SUFFIX_SHA3_256> Sha3_256Kernels;

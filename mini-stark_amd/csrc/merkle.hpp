@@ -723,13 +723,91 @@ struct InnerSubtreeKernel {
   }
 };
 
-// The SHA-256 kernel family (the default DG of LeafHashKernel and of msfri::FriTailKernel).
+// The inner kernels of the digests whose words are little-endian = memory order and whose nodes are hashed one per lane on every level (BLAKE2s-256, BLAKE3,
+// Keccak-256 / SHA3-256): the level walk and the subtree scheme once, the hash through a node policy ND of the digest's header (Blake2sNode, Blake3Node,
+// KeccakNode<SUFFIX>):
+//   ND::State                   the hash state: `init()`, and `store(u32*)` writes its digest
+//   ND::node(w)                 the state behind the 64-byte message w (two children): the subtree kernel's node
+//   ND::nblocks<IC>(ic)         the compressions / permutations that hash ic contiguous children (IC > 0: ic = IC at compile time; the policy asserts the IC it supports)
+//   ND::block<IC>(h, ch, b, ic) the b-th of them, on the children at ch
+// (The loop over the blocks stands in the level kernel, not behind one call of the policy: a loop inlined from a callee ends up with its exit block behind its body,
+// which flips branch conditions in the general-ic kernels - same instructions, another sequence than the per-digest kernels these replace.)
+// 64 bytes (two digests) at src as 16 words, no byte swap
+MS_HD void load_node64(const u32* src, u32 (&w)[16]) {
+  const uint4_t* c4 = reinterpret_cast<const uint4_t*>(src);
+#pragma unroll
+  for (int q = 0; q < 4; q++) { const uint4_t v = c4[q]; w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w; }
+}
+// the thread that produced the root hands it (and the optional aux word) to page-locked host memory, as InnerHashKernelT does
+template <class H> MS_DEV void forward_root(const InnerHashParams& p, const H& h) {
+  h.store(p.host_root);
+  if (p.aux_src) { *p.aux_dst = *p.aux_src; *p.aux_src = 0; }
+  msrt::raise_host_flag(p.flag);
+}
+// Inner levels, as InnerHashKernelT.  IC > 0: inner_children fixed at compile time; IC = 0: from Params.
+template <int IC, class ND> struct LaneInnerHashKernelT {
+  static constexpr int THREADS = msmerkle::THREADS;
+  typedef InnerHashParams Params;
+  static MS_HD int nphases(const Params& p) { return (int)p.nlevels; }
+  static MS_DEV void phase(int ph, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
+    const u32 ic = IC ? (u32)IC : p.ic;
+    size_t child_off = p.child_off, nchildren = p.nchildren;
+    for (int l = 0; l < ph; l++) { child_off += nchildren; nchildren /= ic; }
+    const size_t nparents = nchildren / ic;
+    const size_t stride = (p.nlevels > 1) ? (size_t)nthreads : 0;
+    for (size_t g = (size_t)bx * nthreads + tid; g < nparents; g += stride) {
+      const u32* ch = p.nodes + (child_off + g * ic) * 8;
+      typename ND::State h; h.init();
+      const u32 nblocks = ND::template nblocks<IC>(ic);
+      for (u32 b = 0; b < nblocks; b++) ND::template block<IC>(h, ch, b, ic);
+      h.store(p.nodes + (child_off + nchildren + g) * 8);
+      if (p.host_root && nparents == 1) forward_root(p, h);
+      if (stride == 0) break;
+    }
+  }
+};
+// InnerSubtreeKernel's scheme (workgroup b hashes the nlevels levels above its 2^nlevels children, a level's parents read their children from LDS) with one
+// parent per lane on every level.  A digest in LDS is the same 8 words as in global memory.
+template <class ND> struct LaneSubtreeKernel {
+  static constexpr int THREADS = msmerkle::THREADS;
+  static constexpr int MAX_LEVELS = InnerSubtreeKernel::MAX_LEVELS;
+  typedef InnerHashParams Params;
+  static MS_HD size_t lds_bytes() { return InnerSubtreeKernel::lds_bytes(); }
+  static MS_DEV void run(const Params& p, int bx, int, int, int tid, unsigned char* lds) {
+    u32* const buf0 = reinterpret_cast<u32*>(lds);          // levels 0, 2, 4, ...: <= THREADS digests
+    u32* const buf1 = buf0 + (size_t)THREADS * 8;           // levels 1, 3, ...: <= THREADS / 2 digests
+    const u32 nl = p.nlevels;
+    size_t child_off = p.child_off, nchildren = p.nchildren;
+    u32 pp = 1u << nl;
+    for (u32 l = 0; l < nl; l++) {
+      pp >>= 1;   // parents of this workgroup at this level
+      const size_t nparents = nchildren >> 1;
+      if ((u32)tid < pp) {
+        const size_t g = (size_t)bx * pp + (u32)tid;
+        u32 w[16];
+        if (l == 0) load_node64(p.nodes + (child_off + 2 * g) * 8, w);
+        else load_node64(((l & 1) ? buf0 : buf1) + (size_t)tid * 16, w);
+        const typename ND::State h = ND::node(w);
+        if (l + 1 < nl) h.store(((l & 1) ? buf1 : buf0) + (size_t)tid * 8);
+        h.store(p.nodes + (child_off + nchildren + g) * 8);
+        if (p.host_root && nparents == 1) forward_root(p, h);
+      }
+      if (l + 1 < nl) msrt::wg_barrier();
+      child_off += nchildren; nchildren = nparents;
+    }
+  }
+};
+
+// The SHA-256 kernel family (the default DG of LeafHashKernel and of msfri::FriTailKernel).  Every family names its stream, the stream's block size, whether final
+// blocks without message bytes exist, and its inner kernels: Inner (inner_children from Params), Inner2 (the binary tree's instance), Subtree.
 struct Sha256Kernels {
   template <int NWORDS, int NT, int MAXW, bool LAZY> using Stream = ShaStream<NWORDS, NT, MAXW, LAZY>;
   static constexpr int BLOCK_WORDS = 16;   // words the stream compresses at a time
   static constexpr int LAZY_BLOCKS = 2;    // blocks a LAZY buffer holds
   static constexpr int EXTRA_WORDS = 0;
   static constexpr bool DEFERS = true;   // a final block may hold no message bytes: PadOnlyBlockKernel (or, without lists, in place)
+  typedef InnerHashKernel Inner;
+  typedef InnerHashKernel2 Inner2;
   typedef InnerSubtreeKernel Subtree;
 };
 

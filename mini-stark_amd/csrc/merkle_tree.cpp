@@ -1,9 +1,7 @@
-// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the SHA-256 kernels of merkle.hpp or, by the context's digest, the BLAKE2s-256 kernels of blake2s.hpp
-// or the BLAKE3 kernels of blake3.hpp or the Keccak-256 / SHA3-256 kernels of keccak.hpp: replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
+// merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the kernel family of the context's digest (msmerkle::with_digest, digest.hpp: SHA-256, BLAKE2s-256, BLAKE3,
+// Keccak-256 / SHA3-256): replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
 #include "ctx.hpp"
-#include "blake2s.hpp"
-#include "blake3.hpp"
-#include "keccak.hpp"
+#include "digest.hpp"
 
 namespace msctx {
 
@@ -28,68 +26,52 @@ template <class F> template <int EL>
 int Ctx<F>::leaf_hash(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, size_t lpn, size_t ngroups, u32* out,
               size_t g_first, u32 run_len, u32 run_stride, const msmerkle::LinColSpec* lin, size_t out_g0) {
   if (ngroups >> 32) return fail(MS_ERR_SHAPE, "more than 2^32 leaf groups");
-  if (digest != MS_DIGEST_SHA256) {   // BLAKE2s-256 / BLAKE3: one launch - no block without message bytes, so no lists, no zeroed counters, no follow-up kernel.  Keccak-256 / SHA3-256: one launch - a block of padding only is absorbed in place
-    auto launch = [&](auto kernel) -> int {
-      typedef decltype(kernel) LK;
-      typename LK::Params lp;
-      lp.base = base; lp.col_stride = col_stride; lp.row_stride = row_stride; lp.limb_stride = limb_stride;
-      lp.width = width; lp.lpn = (u32)lpn; lp.zero_as_empty = zae; lp.ngroups = ngroups; lp.nodes = out;
-      lp.ovf_count = nullptr; lp.ovf = nullptr; lp.ovf_cap = 0;
-      lp.g_first = g_first; lp.run_len = run_len; lp.run_stride = run_stride; lp.lin = lin; lp.out_g0 = out_g0;
-      next_bytes = (double)ngroups * (lpn * EL * sizeof(T) + 32);
-      CK(run<LK>(K_LEAF_HASH, grid1(ngroups, msmerkle::THREADS), 1, msmerkle::THREADS, LK::lds_bytes(), lp));
-      return 0;
-    };
-    const bool lazy = lpn * EL >= (size_t)leaf_lazy_min;
-    if (digest == MS_DIGEST_BLAKE3) {
+  const size_t nwg = grid1(ngroups, msmerkle::THREADS);
+  // one launch of the leaf kernel LK; counters / cap: the deferred-block lists of a family that has them, or null / 0
+  auto launch = [&](auto kernel, u32* counters, size_t cap) -> int {
+    typedef decltype(kernel) LK;
+    typename LK::Params lp;
+    lp.base = base; lp.col_stride = col_stride; lp.row_stride = row_stride; lp.limb_stride = limb_stride;
+    lp.width = width; lp.lpn = (u32)lpn; lp.zero_as_empty = zae; lp.ngroups = ngroups; lp.nodes = out;
+    lp.ovf_count = counters; lp.ovf = counters ? d_ovf.as<u32>() : nullptr; lp.ovf_cap = (u32)cap;
+    lp.g_first = g_first; lp.run_len = run_len; lp.run_stride = run_stride; lp.lin = lin; lp.out_g0 = out_g0;
+    next_bytes = (double)ngroups * (lpn * EL * sizeof(T) + 32);
+    CK(run<LK>(K_LEAF_HASH, (unsigned)nwg, 1, msmerkle::THREADS, LK::lds_bytes(), lp));
+    return 0;
+  };
+  // the launches of the family DG.  SHA-256 (DG::DEFERS): final blocks without message bytes go to lists and a compacted follow-up kernel.  BLAKE2s-256 / BLAKE3:
+  // no such block exists; Keccak-256 / SHA3-256: a block of padding only is absorbed in place - one launch, no lists, no zeroed counters
+  auto hash = [&](auto family) -> int {
+    typedef decltype(family) DG;
+    // deferred pad-only blocks: OVF_LISTS lists, list l fed by the workgroups bx = l (mod OVF_LISTS); capacity = all their threads
+    const size_t lists = msmerkle::OVF_LISTS, cap = DG::DEFERS ? ((nwg + lists - 1) / lists) * msmerkle::THREADS : 0;
+    void* counters = nullptr;
+    if constexpr (DG::DEFERS) {
+      if (d_ovf.ensure(lists * cap * msmerkle::OVF_WORDS * 4)) return fail(MS_ERR_NOMEM, "deferred-block lists");
+      RQ(zero_alloc(lists * 4, &counters));
+    }
+    // long messages (wide rows): the buffer of LAZY_BLOCKS blocks that compresses wave-synchronously
+    if (lpn * EL >= (size_t)leaf_lazy_min) RQ(launch(msmerkle::LeafHashKernel<F, EL, true, DG>(), reinterpret_cast<u32*>(counters), cap));
+    else RQ(launch(msmerkle::LeafHashKernel<F, EL, false, DG>(), reinterpret_cast<u32*>(counters), cap));
+    if constexpr (DG::DEFERS) {
+      msmerkle::PadOnlyBlockKernel::Params pp{reinterpret_cast<u32*>(counters), d_ovf.as<u32>(), (u32)cap, out};
+      const size_t used = nwg < lists ? nwg : lists, per_list = grid1(cap, msmerkle::THREADS);
+      CK(run<msmerkle::PadOnlyBlockKernel>(K_LEAF_HASH, (unsigned)used, (unsigned)(per_list < (size_t)msmerkle::PAD_GRID_Y ? per_list : (size_t)msmerkle::PAD_GRID_Y), msmerkle::THREADS, 0, pp));
+    }
+    return 0;
+  };
+  return msmerkle::with_digest(digest, [&](auto family) -> int {
+    typedef decltype(family) DG;
+    if constexpr (std::is_same<DG, msmerkle::Blake3Kernels>::value) {
       // an upper bound of a leaf group's message: every limb at its longest, with its share of the extension's affixes.  Up to one chunk: the kernels without
-      // a chunk tree; up to B3_MAX_BYTES: the multi-chunk instances; beyond: refused (never a wrong digest)
-      const size_t bound = lpn * EL * (size_t)msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3Kernels>::MAX_BYTES;
-      if (lpn > msmerkle::B3_MAX_BYTES || bound > msmerkle::B3_MAX_BYTES)
+      // a chunk tree; up to MAX_BYTES: the multi-chunk instances; beyond: refused (never a wrong digest)
+      const size_t bound = lpn * EL * (size_t)msmerkle::LeafHashKernel<F, EL, false, DG>::MAX_BYTES;
+      if (lpn > DG::MAX_BYTES || bound > DG::MAX_BYTES)
         return fail(MS_ERR_ARG, "BLAKE3: a leaf group's message may exceed 16384 bytes (leafs_per_node x limbs x longest decimal): not supported by the BLAKE3 kernels");
-      if (bound > msmerkle::B3_CHUNK_BYTES) {
-        if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake3MultiKernels>());
-        return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3MultiKernels>());
-      }
-      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake3Kernels>());
-      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake3Kernels>());
+      if (bound > DG::CHUNK_BYTES) return hash(typename DG::Multi());
     }
-    if (digest == MS_DIGEST_KECCAK256) {   // a sponge: any length
-      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Keccak256Kernels>());
-      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Keccak256Kernels>());
-    }
-    if (digest == MS_DIGEST_SHA3_256) {
-      if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Sha3_256Kernels>());
-      return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Sha3_256Kernels>());
-    }
-    if (lazy) return launch(msmerkle::LeafHashKernel<F, EL, true, msmerkle::Blake2sKernels>());
-    return launch(msmerkle::LeafHashKernel<F, EL, false, msmerkle::Blake2sKernels>());
-  }
-  // deferred pad-only blocks: OVF_LISTS lists, list l fed by the workgroups bx = l (mod OVF_LISTS); capacity = all their threads
-  const size_t nwg = grid1(ngroups, msmerkle::THREADS), lists = msmerkle::OVF_LISTS;
-  const size_t cap = ((nwg + lists - 1) / lists) * msmerkle::THREADS;
-  if (d_ovf.ensure(lists * cap * msmerkle::OVF_WORDS * 4)) return fail(MS_ERR_NOMEM, "deferred-block lists");
-  void* counters;
-  RQ(zero_alloc(lists * 4, &counters));
-  typename msmerkle::LeafHashKernel<F, EL>::Params lp;
-  lp.base = base; lp.col_stride = col_stride; lp.row_stride = row_stride; lp.limb_stride = limb_stride;
-  lp.width = width; lp.lpn = (u32)lpn; lp.zero_as_empty = zae; lp.ngroups = ngroups; lp.nodes = out;
-  lp.ovf_count = reinterpret_cast<u32*>(counters); lp.ovf = d_ovf.as<u32>(); lp.ovf_cap = (u32)cap;
-  lp.g_first = g_first; lp.run_len = run_len; lp.run_stride = run_stride; lp.lin = lin; lp.out_g0 = out_g0;
-  next_bytes = (double)ngroups * (lpn * EL * sizeof(T) + 32);
-  if (lpn * EL >= (size_t)leaf_lazy_min) {  // long messages (wide rows): the two-block buffer that compresses wave-synchronously
-    typedef msmerkle::LeafHashKernel<F, EL, true> LK;
-    typename LK::Params ll;
-    ll.base = lp.base; ll.col_stride = lp.col_stride; ll.row_stride = lp.row_stride; ll.limb_stride = lp.limb_stride; ll.width = lp.width; ll.lpn = lp.lpn;
-    ll.zero_as_empty = lp.zero_as_empty; ll.ngroups = lp.ngroups; ll.nodes = lp.nodes; ll.ovf_count = lp.ovf_count; ll.ovf = lp.ovf; ll.ovf_cap = lp.ovf_cap;
-    ll.g_first = g_first; ll.run_len = run_len; ll.run_stride = run_stride; ll.lin = lin; ll.out_g0 = out_g0;
-    CK(run<LK>(K_LEAF_HASH, grid1(ngroups, msmerkle::THREADS), 1, msmerkle::THREADS, LK::lds_bytes(), ll));
-  } else
-  CK(run<msmerkle::LeafHashKernel<F, EL>>(K_LEAF_HASH, grid1(ngroups, msmerkle::THREADS), 1, msmerkle::THREADS, msmerkle::LeafHashKernel<F, EL>::lds_bytes(), lp));
-  msmerkle::PadOnlyBlockKernel::Params pp{lp.ovf_count, lp.ovf, (u32)cap, out};
-  const size_t used = nwg < lists ? nwg : lists, per_list = grid1(cap, msmerkle::THREADS);
-  CK(run<msmerkle::PadOnlyBlockKernel>(K_LEAF_HASH, (unsigned)used, (unsigned)(per_list < (size_t)msmerkle::PAD_GRID_Y ? per_list : (size_t)msmerkle::PAD_GRID_Y), msmerkle::THREADS, 0, pp));
-  return 0;
+    return hash(family);
+  });
 }
 
 template <class F> template <int EL>
@@ -104,27 +86,19 @@ int Ctx<F>::tree_build(const T* base, size_t col_stride, size_t row_stride, size
 // `grid` workgroups of the level kernel of the context's digest (ic == 2: the binary tree's instance)
 template <class F>
 int Ctx<F>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip) {
-  if (digest == MS_DIGEST_KECCAK256 || digest == MS_DIGEST_SHA3_256) {
-    auto launch = [&](auto family) -> int {
-      typedef decltype(family) DG;
-      if (ip.ic == 2) CK(run<typename DG::Inner2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-      else CK(run<typename DG::Inner>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-      return 0;
-    };
-    return digest == MS_DIGEST_KECCAK256 ? launch(msmerkle::Keccak256Kernels()) : launch(msmerkle::Sha3_256Kernels());
-  } else if (digest == MS_DIGEST_BLAKE3) {
-    if (ip.ic > msmerkle::B3InnerHashMultiKernel::MAX_IC) return fail(MS_ERR_ARG, "BLAKE3: inner nodes of more than 512 children (16384 bytes) are not supported by the BLAKE3 kernels");
-    if (ip.ic == 2) CK(run<msmerkle::B3InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-    else if (ip.ic <= msmerkle::B3InnerHashKernel::MAX_IC) CK(run<msmerkle::B3InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-    else CK(run<msmerkle::B3InnerHashMultiKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, msmerkle::B3InnerHashMultiKernel::lds_bytes(), ip));   // more than one chunk: the chunk tree, chaining values in LDS
-  } else if (digest == MS_DIGEST_BLAKE2S256) {
-    if (ip.ic == 2) CK(run<msmerkle::B2InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-    else CK(run<msmerkle::B2InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-  } else {
-    if (ip.ic == 2) CK(run<msmerkle::InnerHashKernel2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-    else CK(run<msmerkle::InnerHashKernel>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
-  }
-  return 0;
+  return msmerkle::with_digest(digest, [&](auto family) -> int {
+    typedef decltype(family) DG;
+    if constexpr (std::is_same<DG, msmerkle::Blake3Kernels>::value) {
+      if (ip.ic > DG::MAX_BYTES / 32) return fail(MS_ERR_ARG, "BLAKE3: inner nodes of more than 512 children (16384 bytes) are not supported by the BLAKE3 kernels");
+      if (ip.ic > DG::CHUNK_BYTES / 32) {   // more than one chunk: the chunk tree, chaining values in LDS
+        CK(run<typename DG::InnerMulti>(K_INNER_HASH, grid, 1, msmerkle::THREADS, DG::InnerMulti::lds_bytes(), ip));
+        return 0;
+      }
+    }
+    if (ip.ic == 2) CK(run<typename DG::Inner2>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    else CK(run<typename DG::Inner>(K_INNER_HASH, grid, 1, msmerkle::THREADS, 0, ip));
+    return 0;
+  });
 }
 
 template <class F>
@@ -155,11 +129,7 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       } else if (rec_out && left == 1) to_rec(ip);
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
-      if (digest == MS_DIGEST_KECCAK256) CK(run_coop<msmerkle::Keccak256Kernels::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
-      else if (digest == MS_DIGEST_SHA3_256) CK(run_coop<msmerkle::Sha3_256Kernels::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
-      else if (digest == MS_DIGEST_BLAKE3) CK(run_coop<msmerkle::B3InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
-      else if (digest == MS_DIGEST_BLAKE2S256) CK(run_coop<msmerkle::B2InnerSubtreeKernel>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
-      else CK(run_coop<SK>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip));
+      CK(msmerkle::with_digest(digest, [&](auto family) { return run_coop<typename decltype(family)::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip); }));
       for (u32 l = 0; l < nl; l++) { child_off += nchildren; nchildren >>= 1; }
       continue;
     }
