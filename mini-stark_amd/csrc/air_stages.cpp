@@ -149,6 +149,7 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
   TreeShape ts;
   RQ(tree_shape(L_ * c, lpn, 2, &ts));
   L = L_; blowup = blowup_; lde_c = c; lde_shift = shift;
+  auto stage = res.expect();
   if (lpn == c && shardable(L_)) {  // one LDE row per leaf group: rank k evaluates and hashes the rows k (mod world)
     RQ(lde_compute_sharded(blowup_, shift));
     RQ((tree_build_sharded<1>(d_lde.as<T>(), L / (size_t)sh_world, 1, 0, (u32)c, ts, d_lde_nodes, lde_lin())));
@@ -208,13 +209,13 @@ int Ctx<F>::mix(u64 r) {
   }
   // the trimmed length ms_fri_begin needs (fri.rs:74), found HERE: the word travels to the host on DEEP-ALI's last evaluation launch (ms_eval_ext), which the caller
   // waits for anyway - ms_fri_begin then starts its transform without a launch, a copy and a host round trip of its own (r05)
-  validity_len_host = false; validity_len_dev = nullptr;
+  validity_len_at = VLEN_RESCAN;
   if (!dist_eval()) {   // (a sharded proof's DEEP-ALI ends in a collective, not in an evaluation launch: ms_fri_begin keeps its own scan there)
-  RQ(ensure_evdone());
-  validity_len_dev = reinterpret_cast<unsigned long long*>(d_evdone.as<u8>() + 128);   // (a word of its own, not the zero pool: the pool may be wiped before ms_eval_ext comes)
-  CK(msrt::memset_dev(validity_len_dev, 0, 8, stream));
-  { typename mspoly::DegreeKernel<F, 1>::Params dp{d_polys.as<T>() + (size_t)npolys * N, 0, N, validity_len_dev, 0};
-    CK(run<mspoly::DegreeKernel<F, 1>>(K_DEGREE, grid1(N, mspoly::THREADS), 1, mspoly::THREADS, 0, dp)); }
+    unsigned long long* vlen = res.word(Results::VALIDITY_LEN);   // (a word of its own, not the zero pool: the pool may be wiped before ms_eval_ext comes)
+    CK(msrt::memset_dev(vlen, 0, 8, stream));
+    typename mspoly::DegreeKernel<F, 1>::Params dp{d_polys.as<T>() + (size_t)npolys * N, 0, N, vlen, 0};
+    CK(run<mspoly::DegreeKernel<F, 1>>(K_DEGREE, grid1(N, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
+    validity_len_at = VLEN_DEVICE;
   }
   have_validity = true; validity_len = N; nrounds_done = 0;
   return MS_OK;
@@ -286,14 +287,12 @@ int Ctx<F>::finish_mix(const char* refusal, size_t VL) {
   RQ(ntt_run(ctz64(L), true, d_cubic.as<T>(), L, L, cf, L, 1));
   if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
   RQ(ensure_polys(npolys + VL / N));
-  unsigned long long* dres;
+  unsigned long long* dres, ncoef = 0;
   RQ(degree_launch1(cf, L, &dres));
-  CK(msrt::d2h(pinned, dres, 8, stream));
-  CK(msrt::sync(stream));
-  const size_t ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
+  { auto scan = res.expect(dres, false, false); RQ(res.collect(nullptr, nullptr, &ncoef)); }
   if (ncoef > VL) return fail(MS_ERR_SHAPE, refusal);
   RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, f_inv<F>(F::from_u64(lde_shift)), 1));
-  validity_ncoef = ncoef; validity_len_host = true; validity_len_dev = nullptr;   // (scaling by shift^-k keeps the trimmed length)
+  validity_ncoef = (size_t)ncoef; validity_len_at = VLEN_HOST;   // (scaling by shift^-k keeps the trimmed length)
   have_validity = true; validity_len = VL; nrounds_done = 0;
   return MS_OK;
 }
@@ -570,18 +569,16 @@ int Ctx<F>::validity_read(u64* out) {
 
 // evaluate `npoly` polynomials (views) at ext point z into dst as [npoly][E] T
 template <class F> template <int EC>
-int Ctx<F>::eval_views(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst) {
+int Ctx<F>::eval_views(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, bool stage_end) {
   size_t maxc = 0;
   for (int i = 0; i < npoly; i++) if (count[i] > maxc) maxc = count[i];
-  return maxc <= eval_small_max ? eval_views_i<EC, 4>(base, poly_stride, limb_stride, kstride, off, count, npoly, z, dst, maxc)
-                                : eval_views_i<EC, 16>(base, poly_stride, limb_stride, kstride, off, count, npoly, z, dst, maxc);
+  return maxc <= eval_small_max ? eval_views_i<EC, 4>(base, poly_stride, limb_stride, kstride, off, count, npoly, z, dst, maxc, stage_end)
+                                : eval_views_i<EC, 16>(base, poly_stride, limb_stride, kstride, off, count, npoly, z, dst, maxc, stage_end);
 }
 
 template <class F> template <int EC, int ITEMS>
-int Ctx<F>::eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, size_t maxc) {
+int Ctx<F>::eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, size_t maxc, bool stage_end) {
   typedef mspoly::EvalKernel<F, EC, E, ITEMS> EK;
-  const bool arm = arm_next_eval; arm_next_eval = false;   // the caller's LAST evaluation: its results end the stage (sync_results).  (Taken first: no exit below leaves it set)
-  const unsigned long long* fwd = fwd_next_eval; fwd_next_eval = nullptr;   // ... and a device word it takes along to host_aux2()
   const size_t chunk = (size_t)EK::THREADS * EK::ITEMS;
   const size_t nblocks = maxc ? (maxc + chunk - 1) / chunk : 1;
   if (nblocks > 1 && d_partials.ensure(nblocks * npoly * E * sizeof(T))) return fail(MS_ERR_NOMEM, "partials");
@@ -592,10 +589,7 @@ int Ctx<F>::eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, 
   for (int i = 0; i < 9; i++) { p.zpow2[i] = sq; sq = e_mul<F>(sq, sq); }
   p.partials = nblocks > 1 ? d_partials.as<T>() : dst;  // single block: P_0 is the value
   p.flag = msrt::HostFlag{nullptr, 0}; p.aux_src = nullptr; p.aux_dst = nullptr; p.single = nblocks == 1;
-  if (nblocks == 1) {
-    if (fwd) { p.aux_src = fwd; p.aux_dst = host_aux2(); }
-    if (arm) p.flag = arm_flag();
-  }
+  if (stage_end && nblocks == 1) RQ(res.attach(p));   // the caller's LAST evaluation: its results end the stage
   CK(run_coop<EK>(K_EVAL, (unsigned)nblocks, EK::THREADS, EK::lds_bytes(), p));
   if (nblocks > 1) {
     typedef mspoly::ReducePartialsKernel<F, E> RK;
@@ -608,8 +602,7 @@ int Ctx<F>::eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, 
     for (int i = 0; i < 8; i++) { rp.zs2[i] = zs; zs = e_mul<F>(zs, zs); }   // zc^(2^i)
     rp.zc_step = zs;                                                          // zc^256 = zc^THREADS
     static_assert(RK::THREADS == 256, "zc_step = zc^THREADS");
-    if (fwd) { rp.aux_src = fwd; rp.aux_dst = host_aux2(); }
-    if (arm) rp.flag = arm_flag();
+    if (stage_end) RQ(res.attach(rp));
     CK(run_coop<RK>(K_EVAL_REDUCE, 1, RK::THREADS, RK::lds_bytes(), rp));
   }
   return 0;
@@ -684,6 +677,12 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   const size_t tot = (size_t)q * nev * E;
   if (d_small.ensure(tot * sizeof(T) + 4096)) return fail(MS_ERR_NOMEM, "small");
   if (tot * sizeof(T) > pinned_cap) return fail(MS_ERR_ARG, "too many evaluation points");
+  if (!tot) return MS_OK;
+  // the validity polynomial's trimmed length (ms_mix's scan) comes along on the last evaluation launch; until it has arrived, ms_fri_begin would scan for itself
+  const bool fwd = validity_len_at == VLEN_DEVICE;
+  unsigned long long vlen = 0;
+  auto stage = res.expect(fwd ? res.word(Results::VALIDITY_LEN) : nullptr);
+  if (fwd) validity_len_at = VLEN_RESCAN;
   for (int t = 0; t < q; t++) {
     XE zz;
     if (!load_ext(z + (size_t)t * E, &zz)) return fail(MS_ERR_ARG, "query point not canonical");
@@ -691,17 +690,12 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
       const int nb = (nev - i0 < mspoly::MAX_POLYS) ? nev - i0 : mspoly::MAX_POLYS;
       size_t off[mspoly::MAX_POLYS], cnt[mspoly::MAX_POLYS];
       for (int i = 0; i < nb; i++) { const int pi = ev[i0 + i]; off[i] = (size_t)pi * N; cnt[i] = (pi == npolys) ? validity_len : N; }   // the validity polynomial has 2N coefficients after ms_mix_cubic
-      arm_next_eval = t == q - 1 && i0 + mspoly::MAX_POLYS >= nev;
-      if (arm_next_eval && validity_len_dev && !validity_len_host) fwd_next_eval = validity_len_dev;
-      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, reinterpret_cast<T*>(pinned) + ((size_t)t * nev + i0) * E)));   // results land in page-locked host memory
+      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, reinterpret_cast<T*>(pinned) + ((size_t)t * nev + i0) * E, t == q - 1 && i0 + mspoly::MAX_POLYS >= nev)));   // results land in page-locked host memory
     }
   }
-  if (tot) {
-    CK(sync_results());
-    if (validity_len_dev && !validity_len_host) { validity_ncoef = (size_t)*host_aux2(); validity_len_host = true; }
-    RQ(eval_finish(q, ev, out));
-  }
-  return MS_OK;
+  RQ(res.collect(nullptr, nullptr, &vlen));
+  if (fwd) { validity_ncoef = (size_t)vlen; validity_len_at = VLEN_HOST; }
+  return eval_finish(q, ev, out);
 }
 
 // the members this unit defines, for both fields (the other units see declarations only; the mix stages' shared steps are called from here alone and come with them)
@@ -730,7 +724,7 @@ MS_INSTANTIATE(BB)
 
 // eval_views<EC>: base-field coefficients (DEEP-ALI, EC = 1) here, extension coefficients (a FRI round's even(z) / odd(z)) from fri_commit.cpp
 #define MS_INSTANTIATE_EC(FF, EC) \
-  template int Ctx<FF>::eval_views<EC>(const Ctx<FF>::T*, size_t, size_t, size_t, const size_t*, const size_t*, int, const Ctx<FF>::XE&, Ctx<FF>::T*);
+  template int Ctx<FF>::eval_views<EC>(const Ctx<FF>::T*, size_t, size_t, size_t, const size_t*, const size_t*, int, const Ctx<FF>::XE&, Ctx<FF>::T*, bool);
 MS_INSTANTIATE_EC(GL, 1)
 MS_INSTANTIATE_EC(GL, 2)
 MS_INSTANTIATE_EC(BB, 1)

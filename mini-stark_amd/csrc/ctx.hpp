@@ -212,46 +212,95 @@ template <class F> struct Ctx : CtxBase {
   }
   static const char* fname() { return F::ID == 0 ? "GL" : "BB"; }
   template <class A> static const char* aname() { return std::is_same<A, GLM>::value ? "GLM" : (std::is_same<A, GLT>::value ? "GLT" : (std::is_same<A, GL>::value ? "GL" : "BB")); }
-  // MS_FLAG_LATENCY: the launch that ends a stage raises a sequence number in page-locked memory behind its results (msrt::HostFlag, rt.hpp) and the host polls that
-  // word instead of synchronising with the stream (sync_results): 4-5 us less per host round trip, 44 of them per proof.  arm_flag() is for the Params of the NEXT
-  // launch only: run / run_coop move the number from "pending" to "armed" and every other launch disarms, so a stale number never stands for work enqueued behind it;
-  // stages that enqueue copies behind their last launch keep the stream synchronisation.
+  // ------------------------------------------------------------------ stage results: ONE owner of what a stage brings home
+  // Every stage that ends in a host round trip brings home a Merkle root, one 8-byte device word, or just the news that it is done.  The stage's LAST launch stores
+  // them in page-locked memory (the host_root / aux_src -> aux_dst / flag fields of its Params) and, under MS_FLAG_LATENCY, raises a sequence number behind them
+  // (msrt::HostFlag, rt.hpp) that the host polls instead of synchronising with the stream: 4-5 us less per round trip, 44 of them per proof.
+  //   expect   the stage says what it wants; the guard it gets back abandons on every exit that is not a clean collect
+  //   attach   called with the Params of the launch that is the stage's last: joins the side stream, fills root slot, word and flag
+  //   collect  copies what no launch carried, waits (the polled flag if one is armed and nothing was enqueued behind it, the stream otherwise), hands back root and word
+  //   abandon  nothing pending, flag disarmed, the context's stream behind the side stream, the owned word zero
+  // The device words that must outlive a zero_alloc piece live here too: one 128-byte line each, zeroed once at ms_create; whoever forwards or copies one leaves it zero.
   int poll_sync = 0;   // MS_FLAG_LATENCY at ms_create (MS_SYNC_POLL=0/1 overrides: A/B)
-  unsigned long long seq_no = 0, seq_pending = 0, seq_armed = 0;
-  unsigned long long* host_seq() const { return reinterpret_cast<unsigned long long*>(reinterpret_cast<u8*>(pinned) + pinned_cap); }   // (64 bytes behind the staging area)
-  msrt::HostFlag arm_flag() { if (!poll_sync || prof_on) return msrt::HostFlag{nullptr, 0}; seq_pending = ++seq_no; return msrt::HostFlag{host_seq(), seq_pending}; }
-  void launched() { seq_armed = seq_pending; seq_pending = 0; }
-  bool arm_next_eval = false;   // eval_views: the next evaluation is its caller's last (its launch carries the flag)
-  const unsigned long long* fwd_next_eval = nullptr;   // ... and takes this device word along to host_aux2()
-  unsigned long long* host_aux2() const { return host_seq() + 1; }
-  // trimmed length of the validity polynomial: a device word since ms_mix (validity_len_dev), on the host once ms_eval_ext has brought it along (validity_len_host)
-  unsigned long long* validity_len_dev = nullptr; bool validity_len_host = false; size_t validity_ncoef = 0;
-  DevBuf d_evdone;              // + 128: the validity polynomial's length word (ms_mix)
-  int ensure_evdone() { if (!d_evdone.p) { if (d_evdone.ensure(256)) return fail(MS_ERR_NOMEM, "length word"); CK(msrt::memset_dev(d_evdone.p, 0, 256, stream)); } return 0; }
-  int sync_results() { const unsigned long long a = seq_armed; seq_armed = 0; return a ? msrt::sync_flag(stream, host_seq(), a) : msrt::sync(stream); }
-  template <class K> int run_coop(int kid, unsigned gx, int threads, size_t lds, const typename K::Params& p, unsigned gy = 1) {
-    launched();
-    if (gx == 0 || gy == 0) return 0;
-    if (!prof_on) return msrt::launch_coop<K>(stream, gx, gy, threads, lds, p);
-    ProfRec r; r.kid = kid; r.sub = next_sub; r.bytes = next_bytes; r.part = part_depth > 0; next_bytes = 0; next_sub = 0;
-    if (msrt::event_create(&r.a) || msrt::event_create(&r.b)) return 1;
-    msrt::event_record(r.a, stream);
-    int e = msrt::launch_coop<K>(stream, gx, gy, threads, lds, p);
-    msrt::event_record(r.b, stream);
-    prof_recs.push_back(r);
+  struct Results {
+    Ctx& c;
+    enum Word { FRI_LEN = 0, TAIL_DONE = 128, VALIDITY_LEN = 256, TRACE_BAD = 384, WORD_BYTES = 512 };   // round polynomial's length (+ the fused tail's completion counter: ms_fri_begin re-zeroes both lines) | validity polynomial's length | trace range-check flag
+    DevBuf words;
+    unsigned long long* word(Word w) const { return reinterpret_cast<unsigned long long*>(words.as<u8>() + w); }
+    bool owns(const void* p) const { return p >= words.p && p < words.as<u8>() + WORD_BYTES; }
+    // page-locked slots behind the staging area, a 64-byte line each (the host spins on the first: the results land on lines of their own): sequence number | word | root
+    static constexpr size_t SLOT_BYTES = 192;
+    unsigned long long* seq_slot() const { return reinterpret_cast<unsigned long long*>(reinterpret_cast<u8*>(c.pinned) + c.pinned_cap); }
+    unsigned long long* word_slot() const { return seq_slot() + 8; }
+    u32* root_slot() const { return reinterpret_cast<u32*>(seq_slot() + 16); }
+    bool open = false, may_poll = false, attached = false, root_sent = false, word_sent = false;
+    enum { SIDE_NONE, SIDE_FORKED, SIDE_DONE } side = SIDE_NONE;   // FORKED: launches on the side stream, its event not yet recorded
+    unsigned long long* want = nullptr; bool over_ranks = false;
+    unsigned long long seq_no = 0, seq_pending = 0, seq_armed = 0;
+    int fail_rt(int e, const char* what) { return c.fail_rt(e, what); }
+    struct Guard { Results& r; ~Guard() { if (r.open) r.abandon(); } };
+    // w: a device word to bring home (over_ranks_: it also rides on a sharded tree's root all-gather and comes back as the maximum over the ranks); poll: the stage's end may be polled
+    Guard expect(unsigned long long* w = nullptr, bool over_ranks_ = false, bool poll = true) {
+      open = true; want = w; over_ranks = over_ranks_; may_poll = poll; attached = root_sent = word_sent = false; return Guard{*this};
+    }
+    unsigned long long* shard_word() const { return open && over_ranks ? want : nullptr; }
+    // the coefficient side of a FRI round goes to the side stream: call BEHIND expect (the guard then orders the context's stream behind it on every exit)
+    // side_done (behind the side stream's last launch) records the event early: it is long up when the join, in front of the stage's last launch, waits for it
+    int fork_side() { if (!c.side_stream) CK(msrt::stream_create(&c.side_stream)); if (!c.ev_side) CK(msrt::event_create(&c.ev_side)); side = SIDE_FORKED; return 0; }
+    int side_done() { if (side == SIDE_FORKED) { CK(msrt::event_record(c.ev_side, c.side_stream)); side = SIDE_DONE; } return 0; }
+    int join_side() { if (side == SIDE_NONE) return 0; RQ(side_done()); side = SIDE_NONE; CK(msrt::stream_wait_event(c.stream, c.ev_side)); return 0; }
+    template <class P> int attach(P& p) {   // (outside a stage nobody reads the slots: nothing is attached)
+      if (!open) return 0;
+      RQ(join_side());
+      if constexpr (std::is_same<P, msmerkle::InnerHashParams>::value) { p.host_root = root_slot(); root_sent = true; }
+      if (want && !word_sent) { p.aux_src = want; p.aux_dst = word_slot(); word_sent = true; }
+      if (may_poll && c.poll_sync && !c.prof_on) { seq_pending = ++seq_no; p.flag = msrt::HostFlag{seq_slot(), seq_pending}; }
+      attached = true;
+      return 0;
+    }
+    // every launch of the context reports here: the attached one arms the flag, any other (work enqueued behind the results) and a launch that never ran disarm it
+    void launched(bool ran) { seq_armed = ran ? seq_pending : 0; seq_pending = 0; if (attached && !ran) root_sent = word_sent = false; attached = false; }
+    int collect(const void* dev_root = nullptr, u8* root = nullptr, unsigned long long* word_out = nullptr) {
+      if (!open) return c.fail(MS_ERR_STATE, "stage results collected outside a stage");
+      bool behind = side != SIDE_NONE;   // something is enqueued behind the flagged launch: the stream synchronisation it is
+      RQ(join_side());
+      if (want && !word_sent) { CK(msrt::d2h(word_slot(), want, 8, c.stream)); if (owns(want)) CK(msrt::memset_dev(want, 0, 8, c.stream)); behind = true; }   // (a tree of one leaf group, a scan outside a tree)
+      if (dev_root && !root_sent) { CK(msrt::d2h(root_slot(), dev_root, 32, c.stream)); behind = true; }
+      const unsigned long long a = behind ? 0 : seq_armed; seq_armed = 0;
+      CK(a ? msrt::sync_flag(c.stream, seq_slot(), a) : msrt::sync(c.stream));
+      if (root) memcpy(root, root_slot(), 32);
+      if (word_out) *word_out = *word_slot();
+      open = false; want = nullptr;
+      return 0;
+    }
+    void abandon() {   // (the stage is leaving with an error of its own, or never asked: failures of the calls below are not reported)
+      if (side == SIDE_FORKED) msrt::event_record(c.ev_side, c.side_stream);
+      if (side != SIDE_NONE) msrt::stream_wait_event(c.stream, c.ev_side);
+      side = SIDE_NONE;
+      if (want && owns(want)) msrt::memset_dev(want, 0, 8, c.stream);
+      open = attached = false; want = nullptr; seq_pending = seq_armed = 0;
+    }
+  } res{*this};
+  // trimmed length of the validity polynomial: unknown (ms_fri_begin scans), in its device word since ms_mix, on the host once ms_eval_ext has brought it along
+  enum { VLEN_RESCAN, VLEN_DEVICE, VLEN_HOST } validity_len_at = VLEN_RESCAN; size_t validity_ncoef = 0;
+  // one launch: `go` enqueues it; an empty grid and a failed launch count as never run
+  template <class Go> int run_as(int kid, unsigned gx, unsigned gy, const Go& go) {
+    int e = 0; bool ran = false;
+    if (gx == 0 || gy == 0) ;
+    else if (!prof_on) { e = go(); ran = !e; }
+    else {
+      ProfRec r; r.kid = kid; r.sub = next_sub; r.bytes = next_bytes; r.part = part_depth > 0; next_bytes = 0; next_sub = 0;
+      if (msrt::event_create(&r.a) || msrt::event_create(&r.b)) e = 1;
+      else { msrt::event_record(r.a, stream); e = go(); msrt::event_record(r.b, stream); prof_recs.push_back(r); ran = !e; }
+    }
+    res.launched(ran);
     return e;
   }
+  template <class K> int run_coop(int kid, unsigned gx, int threads, size_t lds, const typename K::Params& p, unsigned gy = 1) {
+    return run_as(kid, gx, gy, [&] { return msrt::launch_coop<K>(stream, gx, gy, threads, lds, p); });
+  }
   template <class K> int run(int kid, unsigned gx, unsigned gy, int threads, size_t lds, const typename K::Params& p) {
-    launched();
-    if (gx == 0 || gy == 0) return 0;
-    if (!prof_on) return msrt::launch<K>(stream, gx, gy, threads, lds, p);
-    ProfRec r; r.kid = kid; r.sub = next_sub; r.bytes = next_bytes; r.part = part_depth > 0; next_bytes = 0; next_sub = 0;
-    if (msrt::event_create(&r.a) || msrt::event_create(&r.b)) return 1;
-    msrt::event_record(r.a, stream);
-    int e = msrt::launch<K>(stream, gx, gy, threads, lds, p);
-    msrt::event_record(r.b, stream);
-    prof_recs.push_back(r);
-    return e;
+    return run_as(kid, gx, gy, [&] { return msrt::launch<K>(stream, gx, gy, threads, lds, p); });
   }
   int profile_begin() override { prof_on = true; return 0; }
   int profile_end(char* out, size_t cap) override;
@@ -301,6 +350,8 @@ template <class F> struct Ctx : CtxBase {
   // Counters that kernels bump (deferred-block lists, the degree result) must start at zero.  One memset clears a 256 KiB
   // pool; zero_alloc hands out fresh pieces of it and clears it again only when it runs out (stream order keeps earlier
   // users ahead of the clear) — a proof needs ~50 such counters, i.e. one memset instead of ~50 four-microsecond fills.
+  // CONTRACT: a piece is valid only until the next zero_alloc call on the context (that call may wipe the whole pool): its last reader must be enqueued before
+  // then.  A word that has to live longer is one of res.word()'s.
   // page-locked staging for the per-proof job tables (r03): uploads out of it are plain DMA, not the runtime's pageable-memory path (which pins or stages the
   // caller's pages on the fly), and need no synchronisation of their own - the area is rewritten by the NEXT proof's same stage, behind that stage's final
   // stream synchronisation
@@ -322,11 +373,7 @@ template <class F> struct Ctx : CtxBase {
   template <int EL>
   int tree_build(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, const TreeShape& ts, DevBuf& nodes, const msmerkle::LinColSpec* lin = nullptr);
   // inner levels above `nchildren` digests at nodes[0..): level-major, root last (merkle.rs:131-140)
-  // `final_levels`: these levels end in the tree's root, which the last launch also stores to the page-locked slot host_root()
-  // (root_on_host: read_root / read_degree_and_root then need no copy launch, only the stream synchronisation they do anyway)
-  u32* host_root() const { return reinterpret_cast<u32*>(reinterpret_cast<u8*>(pinned) + 256); }
-  bool root_on_host = false;
-  unsigned long long* pending_aux = nullptr; bool aux_on_host = false;   // a device word the tree's final launch forwards to pinned[0] (the degree result)
+  // `final_levels`: these levels end in the tree's root: their last launch is the stage's last (res.attach)
   int inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels = true, u8* rec_out = nullptr);
   int inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip);
   // Sharded MerkleTree::new over a binary tree of M = leaf_num/lpn leaf groups, of which this rank hashes the groups
@@ -334,15 +381,14 @@ template <class F> struct Ctx : CtxBase {
   template <int EL>
   int tree_build_sharded(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, TreeShape& ts, DevBuf& nodes, const msmerkle::LinColSpec* lin = nullptr);
   // the subtree over this rank's Mloc contiguous leaf digests (at nodes[0..)), the all-gather of the W subtree roots, the replicated top.
-  // shard_aux (a device word, optional): rides on the root all-gather; every rank gets the maximum over the ranks back in the same word.
-  unsigned long long* shard_aux = nullptr;
+  // res.shard_word() (a device word, optional): rides on the root all-gather; every rank gets the maximum over the ranks back in the same word.
   int finish_sharded_tree(TreeShape& ts, DevBuf& nodes, size_t Mloc);
   // MerkleTree::new over data EVERY rank holds (the raw trace): rank k hashes the contiguous leaf groups [k*M/W, (k+1)*M/W) - no digest exchange at all -
   // builds that subtree, and the ranks all-gather the W subtree roots
   template <int EL>
   int tree_build_sharded_contiguous(const T* base, size_t col_stride, size_t row_stride, size_t limb_stride, u32 width, TreeShape& ts, DevBuf& nodes);
-  // root of the tree built LAST on this context (every caller reads it right behind the build)
-  int read_root(const DevBuf& nodes, const TreeShape& ts, u8* root);
+  // root of the tree built LAST on this context (every caller reads it right behind the build): the stage's collect
+  int read_root(const DevBuf& nodes, const TreeShape& ts, u8* root, unsigned long long* word_out = nullptr) { return res.collect(nodes.as<u8>() + (ts.local_nodes - 1) * 32, root, word_out); }
 
   // ------------------------------------------------------------------ session state
   size_t N = 0, w = 0, L = 0, blowup = 0;
@@ -388,7 +434,7 @@ template <class F> struct Ctx : CtxBase {
   DevBuf d_carry, d_lq, d_pack, d_fullpoly;
   std::vector<Round*> rounds; size_t nrounds_done = 0, fri_rounds = 0, fri_blowup = 0;
   bool have_deep = false; XE cur_z; XE cur_B[2];
-  DevBuf d_folded, d_sh, d_blob, d_tabs, d_targets, d_idx, d_deg, d_ovf;
+  DevBuf d_folded, d_sh, d_blob, d_tabs, d_targets, d_idx, d_ovf;
   size_t blob_size = 0;
 
   int ensure_polys(size_t count);
@@ -411,7 +457,7 @@ template <class F> struct Ctx : CtxBase {
     if (ev_copy) msrt::event_destroy(ev_copy);
     if (copy_stream) msrt::stream_destroy(copy_stream);
     for (Round* r : rounds) { r->poly.release(); r->cw.release(); r->nodes.release(); delete r; }
-    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_deg, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &d_evdone, &d_air_inv, &d_aux};
+    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &res.words, &d_air_inv, &d_aux};
     for (DevBuf* b : bufs) b->release();
     if (pinned) msrt::free_host(pinned);
     if (h_tabs) msrt::free_host(h_tabs);
@@ -522,11 +568,11 @@ template <class F> struct Ctx : CtxBase {
   int degree_launch1(const T* poly, size_t n, unsigned long long** dres_out);
   int validity_read(u64* out) override;
 
-  // evaluate `npoly` polynomials (views) at ext point z into dst as [npoly][E] T
+  // evaluate `npoly` polynomials (views) at ext point z into dst as [npoly][E] T.  stage_end: the caller's LAST evaluation - its final launch is the stage's (res.attach)
   template <int EC>
-  int eval_views(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst);
+  int eval_views(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, bool stage_end = false);
   template <int EC, int ITEMS>
-  int eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, size_t maxc);
+  int eval_views_i(const T* base, size_t poly_stride, size_t limb_stride, size_t kstride, const size_t* off, const size_t* count, int npoly, const XE& z, T* dst, size_t maxc, bool stage_end);
   static bool load_ext(const u64* v, XE* out) { for (int l = 0; l < E; l++) { if (v[l] >= F::P) return false; out->c[l] = F::from_u64(v[l]); } return true; }
 
   // sharded proof: out[i] = sum_r part_r[i] * zstep^r for n extension elements of the all-gathered partials (rank r's payload rank_stride limbs apart, the elements from `off` on)
@@ -554,7 +600,6 @@ template <class F> struct Ctx : CtxBase {
   int round_commit(Round* r, size_t ncoef_in, int nonzero_limbs = E, const Round* prev = nullptr, const XE* alpha = nullptr);
   // trimmed length of a round polynomial (DegreeKernel) into a zeroed device word
   int degree_launch(const T* poly, size_t limb_stride, size_t n, unsigned long long** dres_out);
-  int read_degree_and_root(const T* poly, size_t limb_stride, size_t n, Round* r, size_t* ncoef, u8* root);
   // fri.rs:73-82
   int fri_begin(size_t blowup_, size_t nrounds, u8* root0) override;
   // fri.rs:89-94
@@ -603,9 +648,8 @@ template <class F> struct Ctx : CtxBase {
   // while the evaluation side (pointwise codeword, leaf hashing, tree) runs on the context's stream - the two are independent (the codeword never reads the
   // quotient); the launch that forwards root and length word to the host waits for the side stream's event.  The fused tail rounds do the same inside one kernel.
   int fri_overlap = 0;   // MS_FLAG_LATENCY at ms_create (MS_FRI_OVERLAP=0/1 overrides: A/B)
-  msrt::Stream* side_stream = nullptr; msrt::Event* ev_side = nullptr; bool side_pending = false;
+  msrt::Stream* side_stream = nullptr; msrt::Event* ev_side = nullptr;   // (forked and joined by `res`)
   struct StreamScope { Ctx* c; msrt::Stream* keep; StreamScope(Ctx* c_, msrt::Stream* s) : c(c_), keep(c_->stream) { c->stream = s; } ~StreamScope() { c->stream = keep; } };
-  int join_side() { if (side_pending) { side_pending = false; CK(msrt::stream_wait_event(stream, ev_side)); } return 0; }   // the context's stream goes on only behind the side stream's work
   int fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done);
   template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: the kernel family of `digest` (msmerkle::with_digest, digest.hpp)
   int fri_round_info(int r, u64* ncoef, u64* D) override;

@@ -85,7 +85,7 @@ int Ctx<F>::round_commit(Round* r, size_t ncoef_in, int nonzero_limbs, const Rou
       return 0;
     }
   }
-  RQ(join_side());   // from here on the round polynomial itself is transformed: the side stream's quotient must be complete
+  RQ(res.join_side());   // from here on the round polynomial itself is transformed: the side stream's quotient must be complete
   if (shardable(r->D / 2)) {  // leaf group j = codeword elements 2j, 2j+1: rank k owns the groups k (mod world) = two cosets of size m
     const size_t m = r->D / (2 * (size_t)sh_world);
     r->m = m;
@@ -125,19 +125,6 @@ int Ctx<F>::degree_launch(const T* poly, size_t limb_stride, size_t n, unsigned 
   return 0;
 }
 
-template <class F>
-int Ctx<F>::read_degree_and_root(const T* poly, size_t limb_stride, size_t n, Round* r, size_t* ncoef, u8* root) {
-  unsigned long long* dres = nullptr;
-  RQ(degree_launch(poly, limb_stride, n, &dres));
-  const bool on_host = r && root_on_host;   // r's tree is the one built last (round_commit just before)
-  CK(msrt::d2h(pinned, dres, 8, stream));
-  if (r && !on_host) CK(msrt::d2h(reinterpret_cast<u8*>(pinned) + 64, r->nodes.template as<u8>() + (r->ts.local_nodes - 1) * 32, 32, stream));
-  CK(msrt::sync(stream));
-  *ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
-  if (r && root) memcpy(root, on_host ? reinterpret_cast<const u8*>(host_root()) : reinterpret_cast<const u8*>(pinned) + 64, 32);
-  return 0;
-}
-
 // fri.rs:73-82
 template <class F>
 int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
@@ -145,11 +132,11 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   if (!root0 || nrounds < 1 || !blowup_) return fail(MS_ERR_ARG, "fri_begin");
   nrounds_done = 0; have_deep = false; blob_size = 0;
   fri_rounds = nrounds; fri_blowup = blowup_;
-  // the self-clearing length word (and completion counter) of ms_fri_fold_commit: allocated and zeroed HERE, behind this stage's stream synchronisation - zeroing it
+  // the self-clearing length word (and completion counter) of ms_fri_fold_commit: zeroed HERE, behind this stage's stream synchronisation - zeroing it
   // lazily in the first ms_fri_fold_commit raced with the side stream's length scan (r05: first proof of a context, eight lanes in flight) - and zero again even if
   // an earlier proof was abandoned mid-round
-  if (!d_deg.p && d_deg.ensure(256)) return fail(MS_ERR_NOMEM, "degree word");
-  CK(msrt::memset_dev(d_deg.p, 0, 256, stream));
+  static_assert(Results::TAIL_DONE == Results::FRI_LEN + 128, "one fill clears both lines");
+  CK(msrt::memset_dev(res.word(Results::FRI_LEN), 0, 256, stream));
   Round* r = round_slot(0);
   const size_t VL = validity_len;   // N (ms_mix) or 2N (ms_mix_cubic)
   r->cap = VL;
@@ -157,16 +144,21 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   // field.rs:23-32 extend_poly: limb 0 = validity, higher limbs zero
   CK(msrt::memset_dev(r->poly.p, 0, VL * E * sizeof(T), stream));
   CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * sizeof(T), stream));
-  size_t nc;
-  if (validity_len_host) nc = validity_ncoef;   // (came to the host with DEEP-ALI's values: ms_mix scans, ms_eval_ext forwards)
-  else RQ(read_degree_and_root(r->poly.template as<T>(), r->cap, VL, nullptr, &nc, nullptr));
-  r->ncoef = nc;
+  unsigned long long nc = validity_ncoef;   // (came to the host with DEEP-ALI's values: ms_mix scans, ms_eval_ext forwards)
+  if (validity_len_at != VLEN_HOST) {   // a scan of its own and a copy behind it
+    unsigned long long* dres;
+    RQ(degree_launch(r->poly.template as<T>(), r->cap, VL, &dres));
+    auto scan = res.expect(dres, false, false);
+    RQ(res.collect(nullptr, nullptr, &nc));
+  }
+  r->ncoef = (size_t)nc;
   const size_t deg = nc ? nc - 1 : 0;
   size_t dsize = (deg + 1) * blowup_;  // fri.rs:74 (quirk Q11)
   size_t D = 1; while (D < dsize) D <<= 1;
   r->D = D;
   r->S = dist_chunk(D); r->dist = r->S != 0; r->local_store = false;   // the validity polynomial is replicated: a distributed round 0 means every rank WORKS on its range of it
-  RQ(round_commit(r, nc, 1));
+  auto stage = res.expect();
+  RQ(round_commit(r, (size_t)nc, 1));
   RQ(read_root(r->nodes, r->ts, root0));
   nrounds_done = 1;
   return MS_OK;
@@ -179,6 +171,7 @@ int Ctx<F>::fri_deep(const u64* z, u64* B) {
   if (!z || !B) return fail(MS_ERR_ARG, "fri_deep");
   if (!load_ext(z, &cur_z)) return fail(MS_ERR_ARG, "z not canonical");
   Round* r = rounds[nrounds_done - 1];
+  auto stage = res.expect();
   size_t off[2] = {0, 1}, cnt[2] = {(r->ncoef + 1) / 2, r->ncoef / 2};
   T* dst = reinterpret_cast<T*>(pinned);   // the last kernel of the evaluation stores its 2 E words straight into page-locked host memory
   if (r->dist) {   // even(z), odd(z) by coefficient range: partial sums over this rank's coefficients, one all-gather, combination with z^(S/2)
@@ -188,8 +181,8 @@ int Ctx<F>::fri_deep(const u64* z, u64* B) {
     RQ(exchange(MS_XCHG_ALL_GATHER, 2 * E * sizeof(T)));
     RQ(shard_combine_launch(0, 2 * E, 2, e_pow<F, E>(cur_z, (u64)(r->S / 2)), dst));
   } else
-  { arm_next_eval = true; RQ((eval_views<E>(r->poly.template as<T>(), 0, r->cap, 2, off, cnt, 2, cur_z, dst))); }  // fri.rs:354-359
-  CK(sync_results());
+  RQ((eval_views<E>(r->poly.template as<T>(), 0, r->cap, 2, off, cnt, 2, cur_z, dst, true)));  // fri.rs:354-359
+  RQ(res.collect());
   const T* h = reinterpret_cast<const T*>(pinned);
   for (int s = 0; s < 2; s++) for (int l = 0; l < E; l++) { cur_B[s].c[l] = h[s * E + l]; B[s * E + l] = F::to_u64(h[s * E + l]); }
   have_deep = true;
@@ -378,8 +371,7 @@ int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {
     if (sp.nl != 1) return fail(MS_ERR_STATE, "fused FRI round: scan of more than one block");
     tp.scan.jobs = nullptr; tp.scan.inline_job = sp.fin[0]; tp.scan.final_mode = 1;
   }
-  unsigned long long* dres = d_deg.as<unsigned long long>();       // the length word: zero between rounds (the forwarding thread clears it)
-  tp.deg = typename TK::DegK::Params{nr->poly.template as<T>(), nr->cap, m >= 2 ? m - 1 : 0, dres, 0};
+  tp.deg = typename TK::DegK::Params{nr->poly.template as<T>(), nr->cap, m >= 2 ? m - 1 : 0, res.word(Results::FRI_LEN), 0};   // the length word: zero between rounds (the forwarding thread clears it)
   // ---- evaluation side
   const size_t per = M < (size_t)TK::WG_GROUPS ? M : (size_t)TK::WG_GROUPS, G = M / per;
   tp.G = (u32)G;
@@ -394,12 +386,11 @@ int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {
   tp.sub.nodes = nr->nodes.template as<u32>(); tp.sub.child_off = 0; tp.sub.nchildren = M; tp.sub.ic = 2; tp.sub.nlevels = nl;
   u32 tl = 0; while (((size_t)1 << tl) < G) tl++;
   tp.top.nodes = nr->nodes.template as<u32>(); tp.top.child_off = 2 * M - 2 * G; tp.top.nchildren = G; tp.top.ic = 2; tp.top.nlevels = tl;
-  tp.top.host_root = host_root(); tp.top.aux_src = dres; tp.top.aux_dst = reinterpret_cast<unsigned long long*>(pinned); tp.top.flag = arm_flag();
+  RQ(res.attach(tp.top));
   tp.root_index = nr->ts.nodes - 1;
-  tp.done = reinterpret_cast<u32*>(d_deg.as<u8>() + 128);            // (same zeroed line as the length word; the last workgroup leaves it zero)
+  tp.done = reinterpret_cast<u32*>(res.word(Results::TAIL_DONE));    // (zeroed with the length word; the last workgroup leaves it zero)
   next_bytes = (double)Dn * E * sizeof(T) * 3 + (double)M * 96;
   CK(run_coop<TK>(K_FRI_TAIL, (unsigned)(G + 1), TK::THREADS, TK::lds_bytes(), tp));
-  root_on_host = true; aux_on_host = true;
   *done = true;
   return 0;
 }
@@ -419,21 +410,20 @@ int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
   nr->dist = false; nr->local_store = false; nr->S = 0;
   size_t nq_coef = 0;
   bool fused = false, side = false;
-  RQ(fri_tail_round(pr, nr, a, &fused));
-  if (fused) {   // one launch did the whole round; the length word and the root are in page-locked memory behind the stream synchronisation (or the polled flag)
-    CK(sync_results());
-    nr->ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
-    memcpy(root, reinterpret_cast<const u8*>(host_root()), 32);
-    nrounds_done++; have_deep = false;
-    return MS_OK;
-  }
+  // the round brings home its root and the next round polynomial's trimmed length; that word is scanned BEFORE the commitment, whose last launch forwards it with the
+  // root: no copy launch in front of the round's one host round trip (r03; the trace showed a 4 us copyBuffer kernel + its launch gap per round).  A distributed
+  // next round: this rank's part reports the GLOBAL length and the maximum over the ranks comes back with the subtree roots (finish_sharded_tree)
+  unsigned long long* dres = res.word(Results::FRI_LEN), ncoef = 0;   // (zeroed by ms_fri_begin, left zero by whoever forwards it)
+  auto stage = res.expect(dres, pr->dist && dist_chunk(nr->D) == pr->S / 2);
+  RQ(fri_tail_round(pr, nr, a, &fused));   // one launch does the whole round, if it qualifies
+  if (!fused) {
   if (pr->dist) RQ(fold_dist(pr, nr, a, &nq_coef));
   else {
   if (nr->poly.ensure(nr->cap * E * sizeof(T)) || d_folded.ensure((m + 1) * E * sizeof(T))) return fail(MS_ERR_NOMEM, "fold");
   if (m >= 2) {
     // the coefficient side on the side stream (every stage ends with a synchronisation of the context's stream behind a join: the side stream starts on finished data)
     side = fri_overlap && !prof_on;   // (the per-kernel profile times launches one behind the other on ONE stream)
-    if (side && !side_stream) { CK(msrt::stream_create(&side_stream)); CK(msrt::event_create(&ev_side)); }
+    if (side) RQ(res.fork_side());
     StreamScope on_side(this, side ? side_stream : stream);
     typename mspoly::FoldKernel<F, E>::Params fp{pr->poly.template as<T>(), pr->cap, n, d_folded.as<T>(), m, a, nullptr};  // fri.rs:361-372
     CK(run<mspoly::FoldKernel<F, E>>(K_FOLD, grid1(m, mspoly::THREADS), 1, mspoly::THREADS, 0, fp));
@@ -442,33 +432,23 @@ int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
     nq_coef = m - 1;
   }
   }
-  // the degree scan runs BEFORE the commitment and the tree's final launch forwards its 8-byte result, with the root, into page-locked host memory:
-  // no copy launch in front of the round's one stream synchronisation (r03; the trace showed a 4 us copyBuffer kernel + its launch gap per round)
-  // (the word lives in d_deg, zeroed once: the forwarding thread clears it again - the pool of zero_alloc may be wiped while the tree is being built)
-  unsigned long long* dres = d_deg.as<unsigned long long>();   // (zeroed by ms_fri_begin)
-  if (nr->dist) {   // this rank's part reports the GLOBAL trimmed length; the maximum over the ranks comes back with the subtree roots (finish_sharded_tree)
+  if (nr->dist) {
     const size_t lc = lcount(nr, nq_coef);
     if (lc) {
       typename mspoly::DegreeKernel<F, E>::Params dp{lpoly(nr), lstride(nr), lc, dres, (size_t)sh_rank * nr->S};
       PartScope part(this);
       CK(run<mspoly::DegreeKernel<F, E>>(K_DEGREE, grid1(lc, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
     }
-    shard_aux = dres;
   } else if (nq_coef) {
     StreamScope on_side(this, side ? side_stream : stream);
     typename mspoly::DegreeKernel<F, E>::Params dp{nr->poly.template as<T>(), nr->cap, nq_coef, dres, 0};
     CK(run<mspoly::DegreeKernel<F, E>>(K_DEGREE, grid1(nq_coef, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
   }
-  if (side) { CK(msrt::event_record(ev_side, side_stream)); side_pending = true; }
-  pending_aux = dres; aux_on_host = false;
-  { auto clear = scope_exit([this] { pending_aux = nullptr; shard_aux = nullptr; });   // (also on an error exit: neither word may ride on the NEXT commitment's launches - ADVICE r4)
-    auto join = scope_exit([this] { if (side_pending) { side_pending = false; seq_armed = 0; msrt::stream_wait_event(stream, ev_side); } });   // whatever path the commitment took (or left on): the context's stream ends behind the side stream
-    RQ(round_commit(nr, nq_coef, E, pr, &a)); }
-  if (!aux_on_host) { seq_armed = 0; CK(msrt::d2h(pinned, dres, 8, stream)); CK(msrt::memset_dev(dres, 0, 8, stream)); }
-  if (!root_on_host) { seq_armed = 0; CK(msrt::d2h(reinterpret_cast<u8*>(pinned) + 64, nr->nodes.template as<u8>() + (nr->ts.local_nodes - 1) * 32, 32, stream)); }
-  CK(sync_results());   // (polls the flag of the tree's last launch if nothing was enqueued behind it)
-  nr->ncoef = (size_t)(*reinterpret_cast<unsigned long long*>(pinned));
-  memcpy(root, root_on_host ? reinterpret_cast<const u8*>(host_root()) : reinterpret_cast<const u8*>(pinned) + 64, 32);
+  RQ(res.side_done());
+  RQ(round_commit(nr, nq_coef, E, pr, &a));
+  }
+  RQ(read_root(nr->nodes, nr->ts, root, &ncoef));   // (whatever path the commitment took, the context's stream ends behind the side stream; the flag of the last launch is polled if nothing was enqueued behind it)
+  nr->ncoef = (size_t)ncoef;
   nrounds_done++; have_deep = false;
   return MS_OK;
 }
@@ -499,7 +479,6 @@ int Ctx<F>::fri_round_codeword_read(int r, u64* out) {
 #define MS_INSTANTIATE(FF) \
   template int Ctx<FF>::round_commit(Ctx<FF>::Round* r, size_t ncoef_in, int nonzero_limbs, const Ctx<FF>::Round* prev, const Ctx<FF>::XE* alpha); \
   template int Ctx<FF>::degree_launch(const Ctx<FF>::T* poly, size_t limb_stride, size_t n, unsigned long long** dres_out); \
-  template int Ctx<FF>::read_degree_and_root(const Ctx<FF>::T* poly, size_t limb_stride, size_t n, Ctx<FF>::Round* r, size_t* ncoef, u8* root); \
   template int Ctx<FF>::fri_begin(size_t blowup_, size_t nrounds, u8* root0); \
   template int Ctx<FF>::fri_deep(const u64* z, u64* B); \
   template Ctx<FF>::SHPlan Ctx<FF>::sh_plan(const Ctx<FF>::T* in, size_t in_limb_stride, size_t in_off, size_t in_stride, size_t m, const Ctx<FF>::XE& z, void* out, bool out_u64, size_t out_limb_stride, size_t out_off, size_t out_stride, Ctx<FF>::T* h0, Ctx<FF>::T* scratch, const Ctx<FF>::T* ext_carry, Ctx<FF>::T* top_agg, bool out_h0); \

@@ -104,9 +104,9 @@ int Ctx<F>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip) {
 template <class F>
 int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels, u8* rec_out) {
   size_t child_off = 0;
-  if (final_levels) root_on_host = false;
   // rec_out (a subtree of a sharded tree, final_levels false): the launch that produces the subtree's root also stores the rank's record of the root all-gather -
-  // root at rec_out, the aux word (shard_aux, if any) 32 bytes behind it - instead of a fill and two copy launches behind the subtree (r05)
+  // root at rec_out, the aux word (res.shard_word(), if any) 32 bytes behind it - instead of a fill and two copy launches behind the subtree (r05)
+  unsigned long long* const shard_aux = res.shard_word();
   bool rec_done = false;
   auto to_rec = [&](msmerkle::InnerHashKernel::Params& ip) {
     ip.host_root = reinterpret_cast<u32*>(rec_out);
@@ -121,24 +121,16 @@ int Ctx<F>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_lev
       typedef msmerkle::InnerSubtreeKernel SK;
       u32 nl = 0; for (size_t m = nchildren; m > 1 && nl < (u32)SK::MAX_LEVELS; m >>= 1) nl++;
       const size_t left = nchildren >> nl;
-      if (final_levels && left == 1) {
-        RQ(join_side());   // this launch forwards the length word the side stream's scan produces
-        ip.host_root = host_root(); root_on_host = true;
-        if (pending_aux) { ip.aux_src = pending_aux; ip.aux_dst = reinterpret_cast<unsigned long long*>(pinned); pending_aux = nullptr; aux_on_host = true; }
-        ip.flag = arm_flag();
-      } else if (rec_out && left == 1) to_rec(ip);
+      if (final_levels && left == 1) RQ(res.attach(ip));   // (joins the side stream: this launch forwards the length word its scan produces)
+      else if (rec_out && left == 1) to_rec(ip);
       ip.nlevels = nl;
       next_bytes = (double)nchildren * 32 * 2;
       CK(msmerkle::with_digest(digest, [&](auto family) { return run_coop<typename decltype(family)::Subtree>(K_INNER_HASH, (unsigned)left, SK::THREADS, SK::lds_bytes(), ip); }));
       for (u32 l = 0; l < nl; l++) { child_off += nchildren; nchildren >>= 1; }
       continue;
     }
-    if (final_levels && (nparents == 1 || nparents <= (size_t)tree_top_parents)) {
-      RQ(join_side());
-      ip.host_root = host_root(); root_on_host = true;
-      if (pending_aux) { ip.aux_src = pending_aux; ip.aux_dst = reinterpret_cast<unsigned long long*>(pinned); pending_aux = nullptr; aux_on_host = true; }
-      ip.flag = arm_flag();   // (the launch below is the tree's last either way: the fused top, or the level whose one parent is the root)
-    } else if (rec_out && (nparents == 1 || nparents <= (size_t)tree_top_parents)) to_rec(ip);
+    if (final_levels && (nparents == 1 || nparents <= (size_t)tree_top_parents)) RQ(res.attach(ip));   // (the launch below is the tree's last either way: the fused top, or the level whose one parent is the root)
+    else if (rec_out && (nparents == 1 || nparents <= (size_t)tree_top_parents)) to_rec(ip);
     if (nparents <= (size_t)tree_top_parents) {  // fused tree top: one workgroup walks the remaining levels
       u32 nl = 0; for (size_t m = nchildren; m > 1; m /= ic) nl++;
       ip.nlevels = nl;
@@ -202,15 +194,11 @@ int Ctx<F>::finish_sharded_tree(TreeShape& ts, DevBuf& nodes, size_t Mloc) {
   if (W > ((size_t)1 << msmerkle::InnerSubtreeKernel::MAX_LEVELS)) return fail(MS_ERR_STATE, "sharded tree: more ranks than the top kernel's levels");
   typename TT::Params tk;
   memset(&tk, 0, sizeof tk);
-  tk.recs = xr; tk.W = (u32)W; tk.aux_max = shard_aux;
+  tk.recs = xr; tk.W = (u32)W; tk.aux_max = res.shard_word();
   tk.tree.nodes = reinterpret_cast<u32*>(top); tk.tree.child_off = 0; tk.tree.nchildren = W; tk.tree.ic = 2;
   u32 tl = 0; while (((size_t)1 << tl) < W) tl++;
   tk.tree.nlevels = tl;
-  RQ(join_side());
-  tk.tree.host_root = host_root(); root_on_host = true;
-  if (pending_aux) { tk.tree.aux_src = pending_aux; tk.tree.aux_dst = reinterpret_cast<unsigned long long*>(pinned); pending_aux = nullptr; aux_on_host = true; }
-  tk.tree.flag = arm_flag();
-  shard_aux = nullptr;
+  RQ(res.attach(tk.tree));
   CK(run_coop<TT>(K_INNER_HASH, 1, TT::THREADS, TT::lds_bytes(), tk));
   ts.sharded = true; ts.Mloc = Mloc; ts.local_nodes = sub_nodes + top_nodes;
   return 0;
@@ -229,16 +217,6 @@ int Ctx<F>::tree_build_sharded_contiguous(const T* base, size_t col_stride, size
   return finish_sharded_tree(ts, nodes, Mloc);
 }
 
-// root of the tree built LAST on this context (every caller reads it right behind the build)
-template <class F>
-int Ctx<F>::read_root(const DevBuf& nodes, const TreeShape& ts, u8* root) {
-  const bool on_host = root_on_host;
-  if (!on_host) { CK(msrt::d2h(pinned, nodes.as<u8>() + (ts.local_nodes - 1) * 32, 32, stream)); CK(msrt::sync(stream)); }
-  else CK(sync_results());   // (polls the flag the tree's last launch raises, if it carried one)
-  memcpy(root, on_host ? reinterpret_cast<const void*>(host_root()) : pinned, 32);
-  return 0;
-}
-
 // ------------------------------------------------------------------ standalone entry points
 template <class F>
 int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root) {
@@ -249,6 +227,7 @@ int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn
   if (!canonical(leafs, leaf_num * ext)) return fail(MS_ERR_ARG, "leaf not canonical");
   DevBuf dl, dn;
   if (dl.ensure(leaf_num * ext * sizeof(T))) return fail(MS_ERR_NOMEM, "leafs");
+  auto stage = res.expect();
   int rc = upload_narrow(leafs, leaf_num * ext, dl.as<T>());
   // AoS view: element f limb k at base + f*ext + k
   if (!rc) rc = (ext == 1) ? tree_build<1>(dl.as<T>(), 0, 1, 0, 1, ts, dn) : tree_build<E>(dl.as<T>(), 0, (size_t)ext, 1, 1, ts, dn);
@@ -269,7 +248,6 @@ int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn
   template int Ctx<FF>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip); \
   template int Ctx<FF>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels, u8* rec_out); \
   template int Ctx<FF>::finish_sharded_tree(Ctx<FF>::TreeShape& ts, DevBuf& nodes, size_t Mloc); \
-  template int Ctx<FF>::read_root(const DevBuf& nodes, const Ctx<FF>::TreeShape& ts, u8* root); \
   template int Ctx<FF>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)

@@ -137,9 +137,11 @@ int Ctx<F>::init(int dev, u32 flags) {
   CK(msrt::stream_create(&own_stream));
   stream = own_stream;
   pinned_cap = 1 << 16;
-  CK(msrt::malloc_host_coherent(&pinned, pinned_cap + 64));   // (+ the polled sequence word, host_seq())
-  *host_seq() = 0;
-  if (d_small.ensure(4096)) return fail(MS_ERR_NOMEM, "small");
+  CK(msrt::malloc_host_coherent(&pinned, pinned_cap + Results::SLOT_BYTES));   // (+ the slots of the stage results: polled sequence number, word, root)
+  *res.seq_slot() = 0;
+  if (d_small.ensure(4096) || res.words.ensure(Results::WORD_BYTES)) return fail(MS_ERR_NOMEM, "small");
+  CK(msrt::memset_dev(res.words.p, 0, Results::WORD_BYTES, stream));
+  CK(msrt::sync(stream));   // (the caller may move the context to a stream of its own)
   return 0;
 }
 
@@ -198,21 +200,19 @@ int Ctx<F>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_,
   RQ(ensure_polys(w + 1));
   // 2^-64 mod p: arkworks stores Montgomery representatives (R = 2^64 for the one-limb Fp of both fields)
   const T rinv = f_inv<F>(F::from_u64((u64)(((unsigned __int128)1 << 64) % F::P)));
-  void* badw;
-  RQ(zero_alloc(8, &badw));  // device input cannot be range-checked on the host: the kernel flags elements >= p
+  // device input cannot be range-checked on the host: the kernel flags elements >= p.  The flag word rides to the host on the tree's last launch, like a round's
+  // length word (r05: the 4-byte copy behind the tree cost ~30 us of launch latency per proof); whoever takes it along leaves it zero for the next trace
+  unsigned long long* badw = res.word(Results::TRACE_BAD), bad = 0;
+  auto stage = res.expect(badw);
   RQ(transpose_in(dsrc, d_polys.as<T>(), N, w, rinv, trace_mont, reinterpret_cast<u32*>(badw)));
-  // the flag word rides to the host on the tree's last launch, like a round's length word (r05: the 4-byte copy behind the tree cost ~30 us of launch latency per proof)
-  pending_aux = reinterpret_cast<unsigned long long*>(badw); aux_on_host = false;
-  auto clear = scope_exit([this] { pending_aux = nullptr; });
   // element f of trace.get_data() = column f % w, row f / w of the column-major copy
   // one proof over several ranks: every rank holds the whole trace, so rank k hashes the contiguous leaf groups [k*M/W, (k+1)*M/W) and only the W subtree roots travel (r04)
   if (sh_on && shard_dist && shardable(ts.leaf_num / ts.lpn)) RQ((tree_build_sharded_contiguous<1>(d_polys.as<T>(), N, 1, 0, (u32)w, ts, d_trace_nodes)));
   else
   RQ((tree_build<1>(d_polys.as<T>(), N, 1, 0, (u32)w, ts, d_trace_nodes)));
   trace_ts = ts;
-  if (!aux_on_host) { pending_aux = nullptr; seq_armed = 0; CK(msrt::d2h(pinned, badw, 8, stream)); if (root_on_host) CK(msrt::sync(stream)); }   // (a tree of one leaf group: no launch took it along)
-  RQ(read_root(d_trace_nodes, ts, root));
-  if (*reinterpret_cast<const unsigned long long*>(pinned)) return fail(MS_ERR_ARG, "trace element not canonical (>= p)");
+  RQ(read_root(d_trace_nodes, ts, root, &bad));
+  if (bad) return fail(MS_ERR_ARG, "trace element not canonical (>= p)");
   have_trace = true;
   return MS_OK;
 }

@@ -163,6 +163,11 @@ def test_device_trace_range_check(mk, field):
     pc.case_device_trace_range_check(mk, field, lambda a: (a.ctypes.data, a))   # emulation: "device" memory is host memory
 
 
+@pytest.mark.parametrize("field", [0, 1])
+def test_device_trace_range_check_across_pool_wraps(mk, field):
+    pc.case_device_trace_range_check_across_pool_wraps(mk, field)
+
+
 @pytest.mark.parametrize("v2", ["1", "0"])
 def test_babybear_on_the_round2_tiles(mk, monkeypatch, v2):
     """BabyBear runs the cooperative round-2 tiles by default since r03; MS_NTT_V2=0 keeps the round-1 tiles, which stay in the
@@ -307,8 +312,9 @@ def test_prove_several_padding_rows(mk, field, log_n, steps):
     pc.case_prove(mk, field, log_n, 8, read_big=False, steps=steps)
 
 
-@pytest.mark.parametrize("field", [0, 1])
-def test_c_abi_never_unwinds(field):
+@pytest.mark.parametrize("field,flags", [pytest.param(0, 1, id="0"), pytest.param(1, 1, id="1"),
+                                         pytest.param(0, 1 | ms.FLAG_LATENCY, id="0-latency"), pytest.param(1, 1 | ms.FLAG_LATENCY, id="1-latency")])
+def test_c_abi_never_unwinds(field, flags):
     """SURVEY 8(b) "never unwind" (VERDICT r3 #5): every entry point of libministark runs inside a guard that turns std::bad_alloc into MS_ERR_NOMEM (anything else
     into MS_ERR_HIP).  The emulation build's operator new (hidden: this library's allocations only) can be armed to fail on its N-th call: a whole proof is driven
     with the failure placed at EVERY allocation it makes, one after the other - the stage that hits it must return a negative code (never abort the process, never
@@ -370,7 +376,7 @@ def test_c_abi_never_unwinds(field):
     for k in range(6):
         L.ms_emu_fail_alloc_after(k)
         h = C.c_void_p()
-        rc = L.ms_create(C.byref(h), 0, field, 1)
+        rc = L.ms_create(C.byref(h), 0, field, flags)
         L.ms_emu_fail_alloc_after(-1)
         assert rc in (0, ms.ERR_NOMEM)
         if rc == 0:
@@ -378,7 +384,7 @@ def test_c_abi_never_unwinds(field):
         else:
             assert not h.value
     h = C.c_void_p()
-    assert L.ms_create(C.byref(h), 0, field, 1) == 0
+    assert L.ms_create(C.byref(h), 0, field, flags) == 0
     want = []
     assert all(rc == 0 for _, rc in stages(h, want))   # (the first proof also builds the NTT plans, which later proofs reuse)
     n0 = L.ms_emu_alloc_count()
@@ -593,7 +599,7 @@ def test_fri_tail_rounds_fused_and_launch_per_step(monkeypatch, field, log_n, bl
 @pytest.mark.parametrize("log_n,blowup", [(4, 8), (9, 8), (12, 4)])
 def test_latency_flag_polled_results(field, log_n, blowup):
     """r05: MS_FLAG_LATENCY - the launch that ends a stage raises a sequence number behind its results and the host polls it instead of synchronising (ctx.hpp
-    arm_flag / sync_results; emulated launches are synchronous, so this covers the bookkeeping: every polled stage carried a flag, no stale number is ever waited for),
+    Results::attach / collect; emulated launches are synchronous, so this covers the bookkeeping: every polled stage carried a flag, no stale number is ever waited for),
     evaluation launches that sum their own partials, the trace's range flag riding on the tree's last launch.  The oracle's proof, twice on one context."""
     subprocess.check_call(["make", "-C", os.path.join(HERE, "emu")], stdout=subprocess.DEVNULL)
     ctx = ms.Context(field, lib_path=EMU, flags=ms.FLAG_ZERO_DISPLAY_EMPTY | ms.FLAG_LATENCY)

@@ -293,6 +293,11 @@ def test_device_trace_range_check(mk, field):
     pc.case_device_trace_range_check(mk, field, to_device)
 
 
+@pytest.mark.parametrize("field", [0, 1])
+def test_device_trace_range_check_across_pool_wraps(mk, field):
+    pc.case_device_trace_range_check_across_pool_wraps(mk, field)
+
+
 @pytest.mark.parametrize("field,log_n", [(0, 10), (1, 10), (0, 16)])
 def test_mont64_trace_input_on_gpu(mk, field, log_n):
     """MS_FLAG_TRACE_MONT64 on the HIP build (the flag INTEGRATION.md tells the Rust shim to use: arkworks keeps Fp as x * 2^64 mod p):
@@ -738,7 +743,7 @@ def test_fri_tail_rounds_fused_and_launch_per_step(monkeypatch, field, log_n, bl
 def test_latency_flag_side_stream_same_proof(field, log_n):
     """r05: MS_FLAG_LATENCY - a FRI round's coefficient side (fold, DEEP-quotient scan, trimmed length) on a side stream beside its evaluation side, joined by an event in
     front of the launch that forwards root and length word: the oracle's proof, twice on the same context (the second proof reuses streams, events and the length word).
-    The flag also makes the host POLL a sequence number the stage's last kernel stores behind its results instead of synchronising with the stream (ctx.hpp sync_results);
+    The flag also makes the host POLL a sequence number the stage's last kernel stores behind its results instead of synchronising with the stream (ctx.hpp Results::collect);
     2^21 rows: stages longer than the 2 ms the host spins for, which fall back to the blocking wait."""
     if log_n >= 16:
         orc.set_threads(8)
