@@ -86,6 +86,7 @@ extern "C" {
     pub fn ms_logarithm_of_two_k(n: u64, base: u64) -> c_long;
     pub fn ms_ceil_log2_k(n: u64, base: u64) -> u64;
     pub fn ms_num_queries(f: ms_field, security_bits: u64, blowup: u64, steps: u64, linking_queries: *mut u64, fri_queries_per_round: *mut u64) -> c_int;
+    pub fn ms_num_queries_grind(f: ms_field, security_bits: u64, grinding_bits: u64, blowup: u64, steps: u64, constrain_queries: *mut u64, fri_queries: *mut u64) -> c_int;
     pub fn ms_root_of_unity(f: ms_field, n: u64) -> u64;
     // ---- Stark::prove stages (src/starks.rs:59-169)
     pub fn ms_trace_commit(ctx: *mut ms_ctx, trace_rowmajor: *const u64, n: usize, w: usize, lpn: usize, root: *mut u8 /* [32] */) -> c_int;
@@ -123,6 +124,8 @@ extern "C" {
     pub fn ms_fri_proof_wait(ctx: *mut ms_ctx) -> c_int;
     pub fn ms_io_engine(ctx: *const ms_ctx) -> c_int;
     pub fn ms_io_runtime_path() -> *const c_char;
+    // ---- proof-of-work grinding (build-defined): the smallest nonce of [start, start + limit) whose digest D(seed || nonce LE) starts with `bits` zero bits
+    pub fn ms_grind(ctx: *mut ms_ctx, seed: *const u8 /* [32] */, bits: u32, start: u64, limit: u64, nonce: *mut u64) -> c_int;
     // ---- Tree trait (src/merkle.rs:8-30) on its own
     pub fn ms_merkle_commit(ctx: *mut ms_ctx, leafs: *const u64, leaf_num: usize, ext: c_int, lpn: usize, ic: usize,
                             nodes_out: *mut u8, nodes_cap: usize, nnodes: *mut usize, root: *mut u8) -> c_int;

@@ -142,6 +142,20 @@ impl Gpu {
         self.check(unsafe { ms_fri_proof_read(self.ctx, blob.as_mut_ptr()) })?;
         Ok(blob)
     }
+    /// Build-defined proof of work between `Fri::commit_phase` and `Fri::query_phase`: the smallest nonce in `[start, start + limit)` whose digest
+    /// `D(seed || nonce.to_le_bytes())` starts with `bits` zero bits (`pow_ok` of include/ministark.h; D = the context's digest).  `Err(OutOfRange)` when the
+    /// range holds none.  The caller draws `seed` from its transcript and absorbs the nonce's 8 bytes before it draws the query positions.
+    pub fn grind(&mut self, seed: &[u8; 32], bits: u32, start: u64, limit: u64) -> Result<u64, GpuError> {
+        let mut nonce = 0u64;
+        self.check(unsafe { ms_grind(self.ctx, seed.as_ptr(), bits, start, limit, &mut nonce) })?;
+        Ok(nonce)
+    }
+    /// `StarkConfig::num_queries` (starks.rs:312-332) with `grinding_bits` of the security taken by the proof of work: (constrain_queries, fri_queries)
+    pub fn num_queries_grind(&self, field: ms_field, security_bits: u64, grinding_bits: u64, blowup: u64, steps: u64) -> Result<(u64, u64), GpuError> {
+        let (mut cq, mut fq) = (0u64, 0u64);
+        self.check(unsafe { ms_num_queries_grind(field, security_bits, grinding_bits, blowup, steps, &mut cq, &mut fq) })?;
+        Ok((cq, fq))
+    }
     /// merkle.rs:81-148 on its own (the `impl Tree` of INTEGRATION.md §5 calls this): all nodes, level-major, root last
     pub fn merkle_commit(&mut self, leaf_limbs: &[u64], leaf_num: usize, ext: i32, lpn: usize, ic: usize) -> Result<(Vec<u8>, Digest), GpuError> {
         let mut nn = 0usize;

@@ -345,6 +345,27 @@ int ms_fri_query_into(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, 
  * MerklePath = u64 leaf_index | lpn*E u64 leaf_neighbours | u64 nlevels | nlevels*ic*32 bytes
  *              (merkle.rs:272-298; leaf located BY VALUE, first match, quirk Q7). */
 
+/* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
+ * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI
+ * queries (ms_num_queries_grind).  The transcript stays with the caller: the library is given a seed and returns the nonce.
+ *   pow_ok(D, seed, nonce, bits):
+ *     d    = D(seed[0..32] || nonce as 8 little-endian bytes)            a message of 40 bytes; D the context's digest (ms_digest: 0, 1, 2, 4 or 5)
+ *     head = d[0..8] read as a big-endian integer
+ *     true iff head < 2^(64 - bits): the digest starts with at least `bits` zero bits in byte order, most significant bit first.  bits = 0 always holds.
+ * ms_grind writes the SMALLEST n in [start, start + limit) with pow_ok(D, seed, n, bits) to *nonce and returns MS_OK - the same n whatever the grid, the split into
+ * launches or the scheduling - or returns MS_ERR_OUT_OF_RANGE when there is none and leaves *nonce untouched.  MS_ERR_ARG: a null pointer, bits >
+ * MS_GRIND_MAX_BITS, limit == 0, start + limit > 2^64 - 1.  Valid in any state of the context: it needs no proof and changes none (a proof that grinds between
+ * its last ms_fri_fold_commit and ms_fri_query comes out as it would without the call).  It runs on the context's stream.  A sharded context grinds like any other:
+ * every rank computes the same nonce, nothing is exchanged.  No launch covers more than MS_GRIND_LAUNCH_MAX nonces (env, read at ms_create; default 2^30); env
+ * MS_GRIND_GRID sets the workgroups of a launch (default: by the device's compute units). */
+#define MS_GRIND_MAX_BITS 40u
+int ms_grind(ms_ctx* ctx, const uint8_t seed[32], uint32_t bits, uint64_t start, uint64_t limit, uint64_t* nonce);
+/* ms_num_queries with `grinding_bits` of the security taken by the proof of work: constrain_queries as ms_num_queries' linking_queries, fri_queries =
+ * max(1, ceil(((security_bits - grinding_bits) / log2(2 / (1 + rho))) / rounds)).  MS_ERR_SHAPE for security_bits < 20 (as ms_num_queries), MS_ERR_ARG for
+ * grinding_bits > min(security_bits, MS_GRIND_MAX_BITS).  grinding_bits = 0: ms_num_queries, value for value. */
+int ms_num_queries_grind(ms_field f, uint64_t security_bits, uint64_t grinding_bits, uint64_t blowup, uint64_t steps,
+                         uint64_t* constrain_queries, uint64_t* fri_queries);
+
 /* ---- Tree trait (src/merkle.rs:8-30) on its own -------------------------- */
 /* MerkleTree::new over `leaf_num` elements of `ext` limbs each; writes all nodes
  * (level-major, root last) if nodes_out != NULL.  ext in {1, E}. */

@@ -9,7 +9,9 @@
  *   trace_commit[32] | constrain_trace_commit[32]
  *   constrain_queries q*c*E u64 | validity_queries q*E u64                     (StarkProof.constrain_queries / validity_query)
  *   fri_roots rounds*32   (round 0 first; not in the reference's StarkProof: round 0's root never reaches its transcript)
- *   arthur bytes          (the prover's transcript, StarkProof.arthur; build-defined hash chain over the context's digest, NOT nimue's bytes)
+ *   arthur bytes          (the prover's transcript, StarkProof.arthur; build-defined hash chain over the context's digest, NOT nimue's bytes.  With grinding
+ *                          bits configured - msh_stark_set_grinding - arthur also carries the proof of work's nonce, 8 little-endian bytes behind the last
+ *                          round's root: the layout and the version stay what they are, arthur is 8 bytes longer)
  *   FriProof in the MSFP layout of ministark.h
  * The Python mirror writes the same bytes (mini_stark_amd.stark.StarkProof.to_bytes). */
 #ifndef MINISTARK_HOST_H
@@ -35,6 +37,16 @@ typedef struct { const uint64_t* points; /* 6*E: x1 y1 x2 y2 x3 y3 */ uint64_t q
 msh_stark* msh_stark_new(ms_ctx* ctx, int field, uint64_t security_bits, uint64_t blowup, uint64_t steps, uint64_t trace_columns, int* err);
 void msh_stark_free(msh_stark* h);
 int msh_stark_config(const msh_stark* h, uint64_t* rounds, uint64_t* constrain_queries, uint64_t* fri_queries);
+/* Build-defined proof of work (ministark.h: pow_ok, ms_grind): `bits` of the security bits come from a nonce ground between the FRI commit phase and the query
+ * phase; fri_queries is recomputed with ms_num_queries_grind.  Call before msh_stark_prove / msh_stark_verify*; prover and verifier must agree on `bits`.  Prover:
+ * seed = 32 challenge bytes behind the last round's root, the nonce's 8 little-endian bytes are absorbed (they travel in arthur), then the query positions are drawn.
+ * Verifier: the same steps; a nonce that fails pow_ok rejects with a `why` naming the proof of work.  0 bits (the default): nothing is drawn or absorbed.
+ * Returns what ms_num_queries_grind returns. */
+int msh_stark_set_grinding(msh_stark* h, uint32_t bits);
+/* the nonce of the last proof: MS_OK, MS_ERR_STATE when that proof was made without grinding */
+int msh_proof_pow_nonce(const msh_stark* h, uint64_t* nonce);
+/* pow_ok(D, seed, nonce, bits) of ministark.h with the hasher behind msh_hash: 1, 0, or -1 for an unknown digest id or bits > 64 */
+int msh_pow_check(int digest_id, const uint8_t seed[32], uint64_t nonce, uint32_t bits);
 /* Stark::prove (starks.rs:59-169): trace from host memory or already in HBM; transitions as lincombs of trace polynomials */
 int msh_stark_prove(msh_stark* h, const uint64_t* trace_host, const void* trace_dev, size_t N, size_t w, int ntrans, const int* tr_k,
                     const uint64_t* tr_scalars, const int* tr_idx, int read_fri_proof);

@@ -359,6 +359,23 @@ class Context:
         rc = self.L.ms_num_queries(C.c_int(self.field), C.c_uint64(security_bits), C.c_uint64(blowup), C.c_uint64(steps), C.byref(a), C.byref(b))
         return rc, a.value, b.value
 
+    def num_queries_grind(self, security_bits, grinding_bits, blowup, steps):
+        """ms_num_queries_grind: (rc, constrain_queries, fri_queries) with `grinding_bits` of the security taken by the proof of work (0: num_queries)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        rc = self.L.ms_num_queries_grind(C.c_int(self.field), C.c_uint64(security_bits), C.c_uint64(grinding_bits), C.c_uint64(blowup), C.c_uint64(steps),
+                                         C.byref(a), C.byref(b))
+        return rc, a.value, b.value
+
+    def grind(self, seed, bits, start=0, limit=2**64 - 1):
+        """ms_grind (BUILD-DEFINED proof of work; include/ministark.h): (rc, nonce) with nonce the smallest n in [start, start + limit) whose digest
+        D(seed || n as 8 little-endian bytes) starts with `bits` zero bits, D the context's digest; (ERR_OUT_OF_RANGE, None) when the range holds none."""
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("grind: a seed of 32 bytes expected")
+        out = C.c_uint64(0)
+        rc = self.L.ms_grind(self.h, (C.c_uint8 * 32).from_buffer_copy(seed), C.c_uint32(bits), C.c_uint64(start), C.c_uint64(limit), C.byref(out))
+        return (rc, None) if rc != 0 else (0, int(out.value))
+
     def arith_selftest(self, op, a, b):
         """ms_arith_selftest: a (op) b element-wise ON THE DEVICE with the arithmetic class of the NTT tiles (ops: include/ministark.h)."""
         a, pa = _u64(a)

@@ -109,6 +109,21 @@ int ms_num_queries(ms_field f, uint64_t security_bits, uint64_t blowup, uint64_t
   *fri = (u64)__builtin_ceil(total / (double)rounds);
   return MS_OK;
 }
+int ms_num_queries_grind(ms_field f, uint64_t security_bits, uint64_t grinding_bits, uint64_t blowup, uint64_t steps, uint64_t* constrain, uint64_t* fri) {
+  if (!constrain || !fri) return MS_ERR_ARG;
+  u64 linking = 0, q = 0;
+  const int rc = ms_num_queries(f, security_bits, blowup, steps, &linking, &q);
+  if (rc) return rc;
+  if (grinding_bits > security_bits || grinding_bits > MS_GRIND_MAX_BITS) return MS_ERR_ARG;
+  if (grinding_bits) {   // the same expression with the grinding bits taken off (0 bits: ms_num_queries' own value)
+    const u64 rounds = ceil_log2_k(steps * blowup, 2);
+    const double denominator = __builtin_log2(2.0 / (1.0 + 1.0 / (double)blowup));
+    q = (u64)__builtin_ceil(((double)(security_bits - grinding_bits) / denominator) / (double)rounds);
+    if (q < 1) q = 1;
+  }
+  *constrain = linking; *fri = q;
+  return MS_OK;
+}
 uint64_t ms_root_of_unity(ms_field f, uint64_t n) {
   if (!n || !is_pow2(n)) return 0;
   const int lg = ctz64(n);
@@ -160,6 +175,7 @@ int ms_merkle_commit(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ex
 int ms_merkle_prove(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext, size_t lpn, const uint64_t* leaf, uint8_t* out, size_t cap, size_t* len) {
   MS_ENTRY(ctx, B(ctx)->merkle_prove(leafs, leaf_num, ext, lpn, leaf, out, cap, len));
 }
+int ms_grind(ms_ctx* ctx, const uint8_t seed[32], uint32_t bits, uint64_t start, uint64_t limit, uint64_t* nonce) { MS_ENTRY(ctx, B(ctx)->grind(seed, bits, start, limit, nonce)); }
 int ms_ntt(ms_ctx* ctx, uint64_t* data, size_t n, size_t batch, int inverse) { MS_ENTRY(ctx, B(ctx)->ntt(data, n, batch, inverse)); }
 int ms_coset_lde(ms_ctx* ctx, const uint64_t* c, size_t ncoef, size_t batch, uint64_t shift, uint64_t* out, size_t L) { MS_ENTRY(ctx, B(ctx)->coset_lde(c, ncoef, batch, shift, out, L)); }
 int ms_bench_lde(ms_ctx* ctx, size_t blowup, uint64_t shift) { MS_ENTRY(ctx, B(ctx)->bench_lde(blowup, shift)); }

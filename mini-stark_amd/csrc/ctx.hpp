@@ -6,7 +6,7 @@
 //   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels)
 //                    one host pipeline, a compose kernel each), DEEP-ALI evaluations
 //   ntt_plan.cpp     NTT plans and pass dispatch, coset evaluation, ms_ntt / ms_coset_lde                           (every NTT pass instance)
-//   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit                                      (SHA-256 leaf / inner kernels)
+//   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
 //   fri_query.cpp    FRI query phase, proof read-back, ms_merkle_prove                                              (find-first, path, copy kernels)
 //   shard.cpp        one proof over several ranks: exchange (RCCL or callback), ms_set_shard*
@@ -115,6 +115,7 @@ struct CtxBase {
   virtual int io_engine() const = 0;
   virtual int merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root) = 0;
   virtual int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) = 0;
+  virtual int grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce) = 0;
   virtual int ntt(u64* data, size_t n, size_t batch, int inverse) = 0;
   virtual int coset_lde(const u64* coeffs, size_t ncoef, size_t batch, u64 shift, u64* out, size_t L) = 0;
   virtual int bench_lde(size_t blowup, u64 shift) = 0;
@@ -192,7 +193,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_COUNT };
   struct ProfRec { int kid, sub; msrt::Event* a; msrt::Event* b; double bytes; bool part; };
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -224,7 +225,7 @@ template <class F> struct Ctx : CtxBase {
   int poll_sync = 0;   // MS_FLAG_LATENCY at ms_create (MS_SYNC_POLL=0/1 overrides: A/B)
   struct Results {
     Ctx& c;
-    enum Word { FRI_LEN = 0, TAIL_DONE = 128, VALIDITY_LEN = 256, TRACE_BAD = 384, WORD_BYTES = 512 };   // round polynomial's length (+ the fused tail's completion counter: ms_fri_begin re-zeroes both lines) | validity polynomial's length | trace range-check flag
+    enum Word { FRI_LEN = 0, TAIL_DONE = 128, VALIDITY_LEN = 256, TRACE_BAD = 384, GRIND = 512, WORD_BYTES = 640 };   // round polynomial's length (+ the fused tail's completion counter: ms_fri_begin re-zeroes both lines) | validity polynomial's length | trace range-check flag | ms_grind's found word
     DevBuf words;
     unsigned long long* word(Word w) const { return reinterpret_cast<unsigned long long*>(words.as<u8>() + w); }
     bool owns(const void* p) const { return p >= words.p && p < words.as<u8>() + WORD_BYTES; }
@@ -713,6 +714,10 @@ template <class F> struct Ctx : CtxBase {
   template <int EL>
   int merkle_prove_t(const u64* leafs, size_t leaf_num, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len);
   int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) override;
+  // ------------------------------------------------------------------ build-defined: proof-of-work grinding (include/ministark.h; kernel: grind.hpp, host side: merkle_tree.cpp)
+  u64 grind_launch_max = (u64)1 << 30;   // MS_GRIND_LAUNCH_MAX: most nonces of one launch
+  unsigned grind_grid = 0;               // MS_GRIND_GRID: workgroups of a launch (0: by the device's compute units at the kernel's occupancy)
+  int grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce) override;
   int ntt(u64* data, size_t n, size_t batch, int inverse) override;
   int coset_lde(const u64* coeffs, size_t ncoef, size_t batch, u64 shift, u64* out, size_t L_) override;
 };

@@ -1,7 +1,9 @@
 // merkle_tree.cpp — MerkleTree::new (merkle.rs:81-177) on the kernel family of the context's digest (msmerkle::with_digest, digest.hpp: SHA-256, BLAKE2s-256, BLAKE3,
-// Keccak-256 / SHA3-256): replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.
+// Keccak-256 / SHA3-256): replicated, sharded by leaf-group residue (digest all-to-all) and sharded by contiguous range; ms_merkle_commit.  Also the host side of
+// ms_grind (grind.hpp): the other pure-hashing stage that picks its kernel by the context's digest.
 #include "ctx.hpp"
 #include "digest.hpp"
+#include "grind.hpp"
 
 namespace msctx {
 
@@ -242,13 +244,57 @@ int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn
   return rc;
 }
 
+// ------------------------------------------------------------------ build-defined: proof-of-work grinding (include/ministark.h; kernel: grind.hpp)
+// Launches of at most grind_launch_max nonces in ascending order on the context's stream; the found word (res.word(GRIND): 0, or ~ the smallest hit) comes home
+// through the stage results.  The first look follows the first launch (short: sized by `bits`; the usual grind ends there); after that GRIND_AHEAD launches are enqueued per look - a launch
+// behind a hit finds the word set at its first read and returns at once.  Field-independent: a sharded context runs it like any other, every rank for itself.
+template <class F>
+int Ctx<F>::grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce) {
+  if (!seed || !nonce) return fail(MS_ERR_ARG, "grind: null argument");
+  if (bits > MS_GRIND_MAX_BITS) return fail(MS_ERR_ARG, "grind: more than MS_GRIND_MAX_BITS bits");
+  if (limit == 0 || limit > ~(u64)0 - start) return fail(MS_ERR_ARG, "grind: limit must be positive and start + limit at most 2^64 - 1");
+  constexpr int GRIND_AHEAD = 4;
+  msmerkle::GrindParams gp;
+  memcpy(gp.seed, seed, 32);
+  gp.mask = bits ? ~(u64)0 << (64 - bits) : 0;
+  gp.found = res.word(Results::GRIND);
+  int cus = 0;
+  if (!grind_grid) CK(msrt::cu_count(device, &cus));
+  const u64 end = start + limit;
+  u64 at = start;
+  for (int ahead = 1; at < end; ahead = GRIND_AHEAD) {
+    auto stage = res.expect(gp.found);
+    for (int k = 0; k < ahead && at < end; k++) {
+      gp.start = at; gp.n = end - at < grind_launch_max ? end - at : grind_launch_max;
+      // the first launch covers 64 times the expected distance to a hit (it fails with probability e^-64) and no more: at few bits a whole grid's worth of
+      // threads each find a hit of their own in the first sweep (measured at 4 bits: 0.17 ms of kernel time for a search that needs 16 hashes, 0.01 ms this way;
+      // DESIGN 3.2)
+      if (at == start && bits + 6 < 64 && gp.n > ((u64)1 << (bits + 6))) gp.n = (u64)1 << (bits + 6);
+      RQ(msmerkle::with_digest(digest, [&](auto family) -> int {
+        typedef msmerkle::GrindPolicy<decltype(family)> GD;
+        typedef msmerkle::GrindKernel<decltype(family)> GK;
+        const u64 cap = grind_grid ? grind_grid : (u64)cus * GD::WGS_PER_CU, want = (gp.n + GK::THREADS - 1) / GK::THREADS;
+        next_bytes = 0;
+        CK(run_coop<GK>(K_GRIND, (unsigned)(want < cap ? want : cap), GK::THREADS, 0, gp));
+        return 0;
+      }));
+      at += gp.n;
+    }
+    unsigned long long word = 0;
+    RQ(res.collect(nullptr, nullptr, &word));
+    if (word) { *nonce = ~word; return MS_OK; }
+  }
+  return fail(MS_ERR_OUT_OF_RANGE, "grind: no nonce of the range satisfies the proof of work");
+}
+
 // the members this unit defines, for both fields (the other units see declarations only)
 #define MS_INSTANTIATE(FF) \
   template int Ctx<FF>::tree_shape(size_t leaf_num, size_t lpn, size_t ic, Ctx<FF>::TreeShape* ts); \
   template int Ctx<FF>::inner_launch(unsigned grid, const msmerkle::InnerHashParams& ip); \
   template int Ctx<FF>::inner_levels(u32* nodes, size_t nchildren, size_t ic, bool final_levels, u8* rec_out); \
   template int Ctx<FF>::finish_sharded_tree(Ctx<FF>::TreeShape& ts, DevBuf& nodes, size_t Mloc); \
-  template int Ctx<FF>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root);
+  template int Ctx<FF>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root); \
+  template int Ctx<FF>::grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -40,6 +40,7 @@ inline int sync_flag(Stream*, const unsigned long long* f, unsigned long long v)
 inline int stream_create(Stream** s) { *s = new Stream(); return 0; }
 inline int stream_destroy(Stream* s) { delete s; return 0; }
 inline int set_device(int) { return 0; }
+inline int cu_count(int, int* n) { *n = 4; return 0; }   // (a persistent grid sized by it stays small: every emulated thread is a fiber)
 inline const char* last_error_string() { return "emu"; }
 struct Event { int dummy; };
 inline int event_create(Event** e) { *e = new Event(); return 0; }
@@ -290,6 +291,7 @@ inline int sync_flag(Stream* s, const unsigned long long* f, unsigned long long 
 inline int stream_create(Stream** s) { return (int)hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
 inline int stream_destroy(Stream* s) { return (int)hipStreamDestroy(s); }
 inline int set_device(int d) { return (int)hipSetDevice(d); }
+inline int cu_count(int d, int* n) { return (int)hipDeviceGetAttribute(n, hipDeviceAttributeMultiprocessorCount, d); }   // compute units of device d
 inline const char* last_error_string() { return hipGetErrorString(hipGetLastError()); }
 typedef ihipEvent_t Event;
 inline int event_create(Event** e) { return (int)hipEventCreate(e); }

@@ -8,7 +8,7 @@ namespace msctx {
 template <class F>
 int Ctx<F>::profile_end(char* out, size_t cap) {
   static const char* names[K_COUNT] = {"ntt_pass", "scale_pow", "leaf_hash", "inner_hash", "transpose_in", "io_copy", "lincomb", "mix", "eval", "eval_reduce",
-                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv", "aux_running"};
+                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv", "aux_running", "grind"};
   msrt::sync(stream);
   double ms[K_COUNT] = {0}, by[K_COUNT] = {0}, ms_part = 0, ms_repl = 0, repl_by[K_COUNT] = {0}; unsigned long long cnt[K_COUNT] = {0};
   std::map<int, double> sub_ms, sub_by; std::map<int, unsigned long long> sub_cnt;
@@ -117,6 +117,8 @@ int Ctx<F>::init(int dev, u32 flags) {
   if (const char* e = getenv("MS_SYNC_POLL")) poll_sync = atoi(e);
   if (const char* e = getenv("MS_EVAL_SMALL_MAX")) eval_small_max = (size_t)atol(e);
   if (const char* e = getenv("MS_TREE_SUBTREE_PARENTS")) subtree_parents = (size_t)atol(e);
+  if (const char* e = getenv("MS_GRIND_LAUNCH_MAX")) { const long long v = atoll(e); if (v >= 1 && v <= ((long long)1 << 40)) grind_launch_max = (u64)v; }
+  if (const char* e = getenv("MS_GRIND_GRID")) { const long v = atol(e); if (v >= 1 && v <= 65536) grind_grid = (unsigned)v; }
   if (const char* e = getenv("MS_AUX_TILE")) { const int v = atoi(e); if (v >= msrun::THREADS && v <= AUX_TILE_DEFAULT && !(v & (v - 1))) aux_tile = v; }
   // the boundary's bulk copies (r04): page-locked trace in / FRI proof out on SDMA engines through the HSA runtime by default (measured with 8 provers in flight,
   // tools/io_probe3.py: resident 251 proofs/s; upload by hipMemcpyAsync 238, by SDMA 251; read-back by hipMemcpyAsync 217-223, by SDMA 242-248; both by SDMA 245.5 = 0.978)

@@ -58,6 +58,16 @@ def hash_bytes(digest_id: int, data: bytes) -> bytes:
     return out.raw
 
 
+def pow_check(digest_id: int, seed: bytes, nonce: int, bits: int) -> bool:
+    """msh_pow_check: pow_ok(D, seed, nonce, bits) of include/ministark.h - D(seed || nonce as 8 little-endian bytes) starts with `bits` zero bits."""
+    H = _host()
+    H.msh_pow_check.argtypes = [C.c_int, C.c_char_p, C.c_uint64, C.c_uint32]
+    rc = H.msh_pow_check(int(digest_id), bytes(seed), int(nonce), int(bits))
+    if rc < 0 or len(seed) != 32:
+        raise MsError(-5, f"msh_pow_check: unknown digest id {digest_id}, a seed that is not 32 bytes, or more than 64 bits")
+    return rc == 1
+
+
 def terms_expected_validity(field, r, constraints, nexempt, N, z, rows, opened, npolys=None):
     """msh_terms_expected_validity: the value validity(z) must have after ms_mix_terms, from the opened values.  `constraints` as for Context.mix_terms (or the CSR
     5-tuple); `rows` the row offsets opened, `opened[k]` = the ms_eval_ext output at w^rows[k] z ([c + 1][E], or [c][E] with npolys = c).  Returns (status, E limbs)."""
@@ -102,13 +112,18 @@ def air_expected_validity(field, r, air, N, z, rows, opened, npolys=None):
 class HostStark:
     """StarkConfig::new + Stark::new + Stark::prove + Stark::verify (src/starks.rs:268-310, 40-57, 59-169, 171-235) in C++."""
 
-    def __init__(self, ctx: Context, security_bits: int, blowup_factor: int, steps: int, trace_columns: int):
+    def __init__(self, ctx: Context, security_bits: int, blowup_factor: int, steps: int, trace_columns: int, grinding_bits: int = 0):
         self.H, self.ctx = _host(), ctx
         err = C.c_int(0)
         self.h = C.c_void_p(self.H.msh_stark_new(ctx.h, C.c_int(ctx.field), C.c_uint64(security_bits), C.c_uint64(blowup_factor), C.c_uint64(steps),
                                                  C.c_uint64(trace_columns), C.byref(err)))
         if not self.h.value:
             raise MsError(err.value, "STARK Config: security bits has to be at least 20")
+        self.grinding_bits = grinding_bits
+        if grinding_bits:   # (0: msh_stark_set_grinding is not called at all - the handle is what it always was)
+            rc = self.H.msh_stark_set_grinding(self.h, C.c_uint32(grinding_bits))
+            if rc != 0:
+                raise MsError(rc, "STARK Config: grinding bits exceed the security bits or MS_GRIND_MAX_BITS")
         a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self.H.msh_stark_config(self.h, C.byref(a), C.byref(b), C.byref(c))
         self.rounds, self.constrain_queries, self.fri_queries = a.value, b.value, c.value
@@ -135,6 +150,11 @@ class HostStark:
         return self.H.msh_stark_prove(self.h, host_ptr, C.c_void_p(trace_device_ptr), C.c_size_t(trace.length), C.c_size_t(trace.width), C.c_int(len(k)),
                                       k.ctypes.data_as(C.POINTER(C.c_int)), sc.ctypes.data_as(C.POINTER(C.c_uint64)), ix.ctypes.data_as(C.POINTER(C.c_int)),
                                       C.c_int({"async": 2, "into": 3}.get(read_fri_proof, 1 if read_fri_proof else 0)))
+
+    def pow_nonce(self):
+        """msh_proof_pow_nonce: the proof-of-work nonce of the last proof (grinding_bits > 0), None for a proof made without grinding."""
+        n = C.c_uint64(0)
+        return int(n.value) if self.H.msh_proof_pow_nonce(self.h, C.byref(n)) == 0 else None
 
     def next_trace(self, host_ptr, N, w):
         """msh_stark_next_trace: the page-locked trace of the proof after the next prove_raw - that call prefetches it (ms_trace_upload_async)."""

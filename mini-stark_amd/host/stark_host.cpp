@@ -27,6 +27,10 @@
 
 // (weak: a libministark build from before the symbol existed - MS_LIB_PATH naming an older library in an A/B run - commits with SHA-256 only)
 extern "C" int ms_digest(const ms_ctx* ctx) __attribute__((weak));
+// (weak for the same reason: such a library has no grinding; msh_stark_set_grinding then refuses any bits but 0)
+extern "C" int ms_grind(ms_ctx* ctx, const uint8_t seed[32], uint32_t bits, uint64_t start, uint64_t limit, uint64_t* nonce) __attribute__((weak));
+extern "C" int ms_num_queries_grind(ms_field f, uint64_t security_bits, uint64_t grinding_bits, uint64_t blowup, uint64_t steps, uint64_t* constrain_queries,
+                                    uint64_t* fri_queries) __attribute__((weak));
 
 namespace ministark {
 
@@ -201,6 +205,16 @@ struct Hasher {
   void finish(u8 out[32]) { if (keccak()) k.finish(out); else if (id == MS_DIGEST_BLAKE3) b3.finish(out); else if (id == MS_DIGEST_BLAKE2S256) b.finish(out); else s.finish(out); }
 };
 
+// pow_ok of include/ministark.h: D(seed || nonce as 8 little-endian bytes) starts with `bits` zero bits (most significant bit of byte 0 first)
+static bool pow_ok(int digest, const u8 seed[32], u64 nonce, u32 bits) {
+  u8 d[32], le[8];
+  for (int k = 0; k < 8; k++) le[k] = (u8)(nonce >> (8 * k));
+  Hasher h(digest); h.update(seed, 32); h.update(le, 8); h.finish(d);
+  u64 head = 0;
+  for (int k = 0; k < 8; k++) head = (head << 8) | d[k];
+  return bits == 0 || (head >> (64 - bits)) == 0;
+}
+
 // Build-defined Fiat–Shamir hash chain (byte-identical to mini-stark_amd/stark.py::Transcript): the stand-in for `DigestBridge<D>`, over the context's digest.
 struct Transcript {
   u8 state[32]; std::vector<u8> prover_bytes; int digest;
@@ -267,11 +281,13 @@ struct StarkProof {  // src/starks.rs:21-28 (+ the per-round roots and drawn cha
   PinnedBuf fri_blob;            // FriProof, MSFP layout (empty if left resident in HBM); page-locked: read back by DMA
   std::vector<u64> challenges;   // shift, r, z[q*E], then per round z[E], alpha[E], finally betas
   size_t c = 0;
+  u64 pow_nonce = 0; bool has_pow = false;   // the proof of work's nonce (grinding_bits > 0: its 8 bytes are the last of arthur)
 };
 
 struct StarkConfig {  // src/starks.rs:238-333
   ms_ctx* ctx; ms_field field; u64 p; int e; int digest;   // digest: ms_digest(ctx), the D of commitments, transcript and check_proof
   u64 security_bits, blowup_factor, steps, rounds, constrain_queries, fri_queries, degree, trace_columns;
+  u32 grinding_bits = 0;   // build-defined (msh_stark_set_grinding): bits of the security that a proof of work in front of the query phase gives
   std::string domsep;
   static int create(ms_ctx* ctx, ms_field field, u64 security_bits, u64 blowup, u64 steps, u64 trace_columns, StarkConfig* out) {
     u64 cq, fq;
@@ -302,7 +318,7 @@ struct Stark {
     const StarkConfig& c = cfg; ms_ctx* ctx = c.ctx; const int e = c.e; const u64 p = c.p;
     std::swap(proof, prev);   // (PinnedBuf moves by pointer swap below: the buffers stay where the device writes them)
     StarkProof& pr = proof;
-    pr.arthur.clear(); pr.evals.clear(); pr.fri_roots.clear(); pr.challenges.clear(); pr.c = 0; pr.fri_blob.n = 0;   // the page-locked proof buffers are kept across proofs
+    pr.arthur.clear(); pr.evals.clear(); pr.fri_roots.clear(); pr.challenges.clear(); pr.c = 0; pr.fri_blob.n = 0; pr.pow_nonce = 0; pr.has_pow = false;   // the page-locked proof buffers are kept across proofs
     Transcript t(c.domsep, c.digest);
     int rc;
     // 1.1 commit to the raw trace (starks.rs:68-73)
@@ -342,6 +358,15 @@ struct Stark {
       t.add_bytes(pr.fri_roots.data() + i * 32, 32);                            // fri.rs:108
       pr.challenges.insert(pr.challenges.end(), zq.begin(), zq.end());
       pr.challenges.insert(pr.challenges.end(), alpha.begin(), alpha.end());
+    }
+    // build-defined: the proof of work, behind the last commitment and in front of the query positions; the nonce travels in arthur
+    if (c.grinding_bits) {
+      u8 seed[32]; t.challenge_bytes(seed, 32);
+      if (!ms_grind) return MS_ERR_ARG;
+      if ((rc = ms_grind(ctx, seed, c.grinding_bits, 0, ~(u64)0, &pr.pow_nonce))) return rc;
+      u8 le[8]; for (int k = 0; k < 8; k++) le[k] = (u8)(pr.pow_nonce >> (8 * k));
+      t.add_bytes(le, 8);
+      pr.has_pow = true;
     }
     // FRI query phase (fri.rs:115-189)
     std::vector<u8> raw(8 * c.fri_queries); t.challenge_bytes(raw.data(), raw.size());        // fri.rs:121-122
@@ -468,6 +493,12 @@ template <class F, int E> struct Verifier {
       // round i's commitment is in the transcript; round 0's never is (fri.rs:73-82: as in the reference) and is taken from the proof
       if (memcmp(d, pr.fri_roots.data() + i * 32, 32)) { *why = "FRI round root does not match the transcript"; return 0; }
       zs.push_back(load(v.data())); alphas.push_back(load(a.data())); B0.push_back(load(b.data())); B1.push_back(load(b.data() + e));
+    }
+    if (c.grinding_bits) {   // the prover's step at the same place: seed drawn, nonce read (and absorbed), predicate checked
+      u8 seed[32], le[8]; ar.t.challenge_bytes(seed, 32);
+      if (!ar.next_bytes(le, 8)) { *why = "transcript too short: no proof of work nonce"; return 0; }
+      u64 nonce = 0; for (int k = 0; k < 8; k++) nonce |= (u64)le[k] << (8 * k);
+      if (!pow_ok(c.digest, seed, nonce, c.grinding_bits)) { *why = "proof of work: the nonce's digest has fewer leading zero bits than the configured grinding bits"; return 0; }
     }
     if (ar.pos != ar.len) { *why = "trailing bytes in the transcript"; return 0; }
     std::vector<u8> raw(8 * nq); ar.t.challenge_bytes(raw.data(), raw.size());
@@ -696,6 +727,25 @@ int msh_proof_wait(const msh_stark* h) { return h->s.wait_proof(); }
 size_t msh_proof_fri_blob(const msh_stark* h, u8* out, size_t cap) { h->s.wait_proof(); return copy_out(h->s.proof.fri_blob.data(), h->s.proof.fri_blob.size(), out, cap); }
 size_t msh_proof_challenges(const msh_stark* h, u64* out, size_t cap_elems) { return copy_out(h->s.proof.challenges.data(), h->s.proof.challenges.size() * 8, out, cap_elems * 8) / 8; }
 size_t msh_proof_num_polys(const msh_stark* h) { return h->s.proof.c; }
+// build-defined proof of work (ministark.h: pow_ok).  set_grinding: before msh_stark_prove / msh_stark_verify*; fri_queries follows ms_num_queries_grind
+int msh_stark_set_grinding(msh_stark* h, uint32_t bits) {
+  if (!h) return MS_ERR_ARG;
+  StarkConfig& c = h->s.cfg;
+  u64 cq = 0, fq = 0;
+  int rc;
+  if (bits == 0) rc = ms_num_queries(c.field, c.security_bits, c.blowup_factor, c.steps, &cq, &fq);
+  else if (!ms_num_queries_grind || !ms_grind) return MS_ERR_ARG;
+  else rc = ms_num_queries_grind(c.field, c.security_bits, bits, c.blowup_factor, c.steps, &cq, &fq);
+  if (rc) return rc;
+  c.grinding_bits = bits; c.constrain_queries = cq; c.fri_queries = fq;
+  return MS_OK;
+}
+int msh_proof_pow_nonce(const msh_stark* h, uint64_t* nonce) {
+  if (!h || !nonce) return MS_ERR_ARG;
+  if (!h->s.proof.has_pow) return MS_ERR_STATE;
+  *nonce = h->s.proof.pow_nonce;
+  return MS_OK;
+}
 // the proof BEFORE the last one (the other slot): still whole while / after the next msh_stark_prove runs.  msh_prev_proof_fri_blob waits for an
 // asynchronous read-back in flight on the context (mode 2: at most the copy of the last proof, issued after this one's had finished).
 size_t msh_prev_proof_arthur(const msh_stark* h, u8* out, size_t cap) { return copy_out(h->s.prev.arthur.data(), h->s.prev.arthur.size(), out, cap); }
@@ -877,6 +927,11 @@ int msh_hash(int digest_id, const u8* data, size_t len, u8 out[32]) {
   if (!known || !out || (!data && len)) return -1;
   ministark::Hasher h(digest_id); if (len) h.update(data, len); h.finish(out);
   return 0;
+}
+int msh_pow_check(int digest_id, const u8 seed[32], u64 nonce, uint32_t bits) {
+  const bool known = (digest_id >= MS_DIGEST_SHA256 && digest_id <= MS_DIGEST_BLAKE3) || digest_id == MS_DIGEST_KECCAK256 || digest_id == MS_DIGEST_SHA3_256;
+  if (!known || !seed || bits > 64) return -1;
+  return ministark::pow_ok(digest_id, seed, nonce, bits) ? 1 : 0;
 }
 // the synthetic Fibonacci-AIR trace of the benchmark workload (tests/e2e_goldilocks.rs:20-63 rows + SplitMix64 padding; = mini_stark_amd.synthetic.fibonacci_rows)
 int msh_fibonacci_rows(u64 p, size_t length, size_t steps, u64 secret_b, u64 pad_seed, u64* out) {

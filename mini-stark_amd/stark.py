@@ -22,7 +22,7 @@ from typing import List
 
 import numpy as np
 
-from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
+from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, ERR_ARG, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
 
@@ -174,11 +174,19 @@ class StarkProof:  # src/starks.rs:21-28
 class StarkConfig:
     """src/starks.rs:238-333."""
 
-    def __init__(self, ctx: Context, security_bits: int, blowup_factor: int, steps: int, trace_columns: int):
-        rc, cq, fq = ctx.num_queries(security_bits, blowup_factor, steps)  # starks.rs:274-275, 312-332
+    def __init__(self, ctx: Context, security_bits: int, blowup_factor: int, steps: int, trace_columns: int, grinding_bits: int = 0):
+        """grinding_bits (build-defined, default 0: the reference's proof byte for byte): that many of the security bits come from a proof of work between the
+        FRI commit phase and the query phase (Context.grind) instead of from FRI queries; its nonce travels in `arthur`."""
+        if grinding_bits:
+            rc, cq, fq = ctx.num_queries_grind(security_bits, grinding_bits, blowup_factor, steps)
+        else:
+            rc, cq, fq = ctx.num_queries(security_bits, blowup_factor, steps)  # starks.rs:274-275, 312-332
+        if rc == ERR_ARG:
+            raise MsError(rc, "STARK Config: grinding bits exceed the security bits or MS_GRIND_MAX_BITS")
         if rc != 0:
             raise MsError(rc, "STARK Config: security bits has to be at least 20")  # starks.rs:317-320
         self.ctx = ctx
+        self.grinding_bits = grinding_bits
         self.security_bits, self.blowup_factor, self.steps = security_bits, blowup_factor, steps
         self.constrain_queries, self.fri_queries = cq, fq
         self.degree = steps - 1                                        # starks.rs:276
@@ -235,6 +243,13 @@ class Stark:
             ctx.check(rc)
             t.add_bytes(root)
             roots.append(root)
+        self.last_pow = None
+        if cfg.grinding_bits:                                     # build-defined: the proof of work, behind the last commitment and in front of the query positions
+            seed = t.challenge_bytes(32)
+            rc, nonce = ctx.grind(seed, cfg.grinding_bits)
+            ctx.check(rc)
+            t.add_bytes(struct.pack("<Q", nonce))
+            self.last_pow = (seed, nonce)
         raw = t.challenge_bytes(8 * cfg.fri_queries)              # fri.rs:121-126
         betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(cfg.fri_queries)]
         rc, blob = ctx.fri_query(betas, read=read_fri_proof)
