@@ -395,7 +395,21 @@ int ms_bench_lde(ms_ctx* ctx, size_t blowup, uint64_t shift);
  * test can compare every operation with big-integer arithmetic on directed edge values.  a, b canonical.  op: 0 add, 1 sub, 2 mul,
  * 3 mul by the table form of b (mul_tw(a, to_tw(b))), 4 a * 2^32, 5 a * 2^64, 6 a * 2^(b mod 96) through the compile-time shift
  * chains of the butterflies (Goldilocks only), 7 fold: a + (b mod 2^31) * 2^64 mod p (Goldilocks only), 8 / 9 / 10 a * 2^24 / 2^48 / 2^72 and
- * 11 a * 2^(12 (b mod 8)): the multiplier-free products by 8th and 16th roots of unity of the FRI fold (GL::mul_pow2; Goldilocks only).  No reference counterpart. */
+ * 11 a * 2^(12 (b mod 8)): the multiplier-free products by 8th and 16th roots of unity of the FRI fold (GL::mul_pow2; Goldilocks only).  No reference counterpart.
+ *
+ * `op` = operation | class << 8.  Class 0 is as above (GLM / BB).  Goldilocks also takes class 1 = GL (compare + select: every kernel outside the NTT),
+ * 2 = GLT (sign bits through v_bitop3_b32: the two-sub-round tiles), 3 = GLM; BabyBear takes class 0 only.  Operations 0-7 run under every Goldilocks class
+ * that has them: GL has no mul_x32 / mul_x64 / fold_small, so class 1 refuses 4, 5 and 7, and its operation 6 is GL::mul_pow2<b mod 96>, every shift of it.
+ * Further operations:
+ *   12  reduce128(lo = a, hi = b) on RAW 64-bit words (no canonical check; any 128-bit value), Goldilocks classes 1 and 2 only
+ *   13  a * 2^(b mod 96) through the round-1 shift form (msntt::gl_mul_pow2_v1), Goldilocks
+ *   14  1 / a (Goldilocks: the addition chain gl_inv_chain; BabyBear: f_inv); 0 -> 0
+ *   15  BabyBear: the table form of a RUN-TIME value, out = mul_tw(a, tw_of(b)) | from_tw(tw_of(a)) << 32  (= a b | a << 32)
+ * and on extension elements (E = ms_ext_degree consecutive limbs per element, n counts limbs and is a multiple of E, a and b canonical):
+ *   32  e_mul   33  e_mul_tw(a, e_to_tw(b))   34  e_add   35  e_sub   36  e_mul_base(a, b.c[0])
+ *   37  BabyBear: e_mul on Fp2, every Fp4 operand read as two Fp2 values   38  BabyBear: e_mul_nr4(a) on the same pairs (b unused)
+ * Operations 8-11, 13, 14 and 32-36 are GL's own code: Goldilocks class 0 or 1.  Every other combination of field, class and operation, and an n that
+ * is no multiple of E for an operation >= 32, returns MS_ERR_ARG before anything is launched. */
 int ms_arith_selftest(ms_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 int ms_profile_begin(ms_ctx* ctx);
 int ms_profile_end(ms_ctx* ctx, char* json_out, size_t cap);

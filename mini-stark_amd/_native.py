@@ -376,8 +376,10 @@ class Context:
         rc = self.L.ms_grind(self.h, (C.c_uint8 * 32).from_buffer_copy(seed), C.c_uint32(bits), C.c_uint64(start), C.c_uint64(limit), C.byref(out))
         return (rc, None) if rc != 0 else (0, int(out.value))
 
-    def arith_selftest(self, op, a, b):
-        """ms_arith_selftest: a (op) b element-wise ON THE DEVICE with the arithmetic class of the NTT tiles (ops: include/ministark.h)."""
+    def arith_selftest(self, op, a, b, cls=0):
+        """ms_arith_selftest: a (op) b element-wise ON THE DEVICE with arithmetic class `cls` (0: the class of the NTT tiles; Goldilocks 1 GL, 2 GLT, 3 GLM);
+        operations >= 32 take extension elements as consecutive limbs (ops and classes: include/ministark.h).  Raises MsError on a refusal."""
+        op = int(op) | int(cls) << 8
         a, pa = _u64(a)
         b, pb = _u64(b)
         out = np.zeros(len(a), dtype=np.uint64)

@@ -526,6 +526,7 @@ template <class F> struct Ctx : CtxBase {
   int lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) override;
   int bench_lde(size_t blowup_, u64 shift) override;
   int arith_selftest(int op, const u64* a, const u64* b, u64* out, size_t n) override;
+  template <class A> int arith_launch(int op, u64* buf, size_t n);   // one operation of class A on buf = a | b | out, n words each
   int lde_read(u64* out) override;
   // ------------------------------------------------------------------ starks.rs:108-119
   int mix(u64 r) override;

@@ -13,6 +13,7 @@
 // All are streaming kernels over SoA limb arrays: HBM-bound, algorithmic bytes
 // = elements read + written once.
 #pragma once
+#include <type_traits>
 #include "field.hpp"
 #include "ntt.hpp"
 
@@ -1133,30 +1134,87 @@ template <class F> struct CosetInvKernel {
   }
 };
 
-// ms_arith_selftest: one operation of the NTT tiles' arithmetic class per element (A = GLM for Goldilocks: inline asm with hand-managed
-// gfx950 wait states, which only a run on the device can check; BB for BabyBear).  Ops: include/ministark.h.
-template <int S> struct ArithShift { template <class A> static MS_DEV u64 run(u64 x, int s) { return s == S ? msntt::gl_mul_pow2<S, A>(x) : ArithShift<S - 1>::template run<A>(x, s); } };
-template <> struct ArithShift<0> { template <class A> static MS_DEV u64 run(u64 x, int) { return x; } };
+// a * 2^s for a run-time s < 96 through one of the compile-time shift forms: FORM 0 the chain of class A's fold_small / mul_x32 / mul_x64 (msntt::gl_mul_pow2<S, A>,
+// the butterflies of the round-2 tiles), FORM 1 the round-1 form (msntt::gl_mul_pow2_v1), FORM 2 GL::mul_pow2 (one reduction whatever S: the FRI fold's octets)
+template <int S, int FORM, class A> struct ArithShift {
+  static MS_DEV u64 one(u64 x) {
+    if constexpr (FORM == 0) return msntt::gl_mul_pow2<S, A>(x);
+    else if constexpr (FORM == 1) return msntt::gl_mul_pow2_v1<S>(x);
+    else return GL::mul_pow2<S>(x);
+  }
+  static MS_DEV u64 run(u64 x, int s) { return s == S ? one(x) : ArithShift<S - 1, FORM, A>::run(x, s); }
+};
+template <int FORM, class A> struct ArithShift<0, FORM, A> { static MS_DEV u64 run(u64 x, int) { return x; } };
+// ms_arith_selftest: one operation of one arithmetic class per element.  A is the class of operations 0-7 and 12: GL (compare + select), GLT (sign bits through
+// v_bitop3_b32) or GLM (inline asm with hand-managed gfx950 wait states, which only a run on the device can check) for Goldilocks, BB for BabyBear.  The operations
+// that belong to no class (the round-1 shift form, the inversion chain, the table form of a run-time value, the extension arithmetic - all of it F's own) are
+// compiled into the instance A = F only.  `op` is the operation without the class bits; the host (session.cpp) has refused what an instance does not hold.
+// Ops: include/ministark.h.
 template <class F, class A> struct ArithKernel {
   typedef typename F::T T;
   static constexpr int THREADS = 256;
+  static constexpr int OP_EXT = 32;   // first extension operation: operands are elements of several consecutive limbs
   struct Params { const u64* a; const u64* b; u64* out; size_t n; int op; };
   static MS_HD int nphases(const Params&) { return 1; }
+  template <int E> static MS_DEV Ext<F, E> load(const u64* v) { Ext<F, E> r; for (int k = 0; k < E; k++) r.c[k] = F::from_u64(v[k]); return r; }
+  template <int E> static MS_DEV void store(u64* v, const Ext<F, E>& x) { for (int k = 0; k < E; k++) v[k] = F::to_u64(x.c[k]); }
+  // operations 32-36 on elements of E limbs at limb offset o (o + E <= n: the host has refused an n that is no multiple of E)
+  template <int E> static MS_DEV void ext_op(const Params& p, size_t o) {
+    const Ext<F, E> a = load<E>(p.a + o), b = load<E>(p.b + o);
+    Ext<F, E> r = a;
+    if (p.op == 32) r = e_mul<F>(a, b);
+    else if (p.op == 33) r = e_mul_tw<F>(a, e_to_tw<F, E>(b));
+    else if (p.op == 34) r = e_add<F, E>(a, b);
+    else if (p.op == 35) r = e_sub<F, E>(a, b);
+    else if (p.op == 36) r = e_mul_base<F, E>(a, b.c[0]);
+    store<E>(p.out + o, r);
+  }
   static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
     const size_t i = (size_t)bx * THREADS + tid;
+    if constexpr (std::is_same<A, F>::value) {
+      if (p.op >= OP_EXT) {
+        if constexpr (F::ID == 1) {
+          if (p.op >= 37) {   // an Fp4 operand read as two Fp2 values: thread i owns limbs 2 i, 2 i + 1
+            if (2 * i + 2 > p.n) return;
+            const Ext<F, 2> a = load<2>(p.a + 2 * i), b = load<2>(p.b + 2 * i);
+            store<2>(p.out + 2 * i, p.op == 37 ? e_mul<F>(a, b) : e_mul_nr4<F>(a));
+            return;
+          }
+        }
+        if ((i + 1) * F::EXT > p.n) return;
+        ext_op<F::EXT>(p, i * F::EXT);
+        return;
+      }
+    }
     if (i >= p.n) return;
+    if constexpr (F::ID == 0 && !std::is_same<A, GLM>::value) {
+      if (p.op == 12) { p.out[i] = A::reduce128(p.a[i], p.b[i]); return; }   // raw words: lo = a, hi = b
+    }
     const T a = F::from_u64(p.a[i]), b = F::from_u64(p.b[i]);
     T r = 0;
+    if constexpr (std::is_same<A, F>::value) {
+      if constexpr (F::ID == 0) {
+        if (p.op == 13) r = ArithShift<95, 1, GL>::run(a, (int)(p.b[i] % 96));
+        else if (p.op == 14) r = gl_inv_chain(a);
+      } else {
+        if (p.op == 14) r = f_inv<F>(a);
+        else if (p.op == 15) { p.out[i] = (u64)F::mul_tw(a, F::tw_of(b)) | ((u64)F::from_tw(F::tw_of(a)) << 32); return; }
+      }
+    }
     if (p.op == 0) r = A::add(a, b);
     else if (p.op == 1) r = A::sub(a, b);
     else if (p.op == 2) r = A::mul(a, b);
     else if (p.op == 3) r = A::mul_tw(a, F::to_tw(b));
     if constexpr (F::ID == 0) {
-      if (p.op == 4) r = A::mul_x32(a);
-      else if (p.op == 5) r = A::mul_x64(a);
-      else if (p.op == 6) r = ArithShift<95>::template run<A>(a, (int)(p.b[i] % 96));
-      else if (p.op == 7) r = A::fold_small(a, (u32)p.b[i] & 0x7FFFFFFFu);
-      else if (p.op == 8) r = GL::mul_2p24(a);
+      if constexpr (std::is_same<A, GL>::value) {   // compare + select has no fold_small / mul_x32 / mul_x64: its shift is GL::mul_pow2
+        if (p.op == 6) r = ArithShift<95, 2, GL>::run(a, (int)(p.b[i] % 96));
+      } else {
+        if (p.op == 4) r = A::mul_x32(a);
+        else if (p.op == 5) r = A::mul_x64(a);
+        else if (p.op == 6) r = ArithShift<95, 0, A>::run(a, (int)(p.b[i] % 96));
+        else if (p.op == 7) r = A::fold_small(a, (u32)p.b[i] & 0x7FFFFFFFu);
+      }
+      if (p.op == 8) r = GL::mul_2p24(a);
       else if (p.op == 9) r = GL::mul_2p48(a);
       else if (p.op == 10) r = GL::mul_2p72(a);
       else if (p.op == 11) {   // every shift of the fold's octets: a * 2^(12 (b mod 8))

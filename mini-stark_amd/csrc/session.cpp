@@ -356,23 +356,47 @@ int Ctx<F>::poly_read(int i, u64* out) {
 }
 
 template <class F>
-int Ctx<F>::arith_selftest(int op, const u64* a, const u64* b, u64* out, size_t n) {
-  if (!a || !b || !out || op < 0 || op > 11 || (F::ID != 0 && op > 3)) return fail(MS_ERR_ARG, "arith_selftest: bad operation / null argument");
+int Ctx<F>::arith_selftest(int op_word, const u64* a, const u64* b, u64* out, size_t n) {
+  // op_word = operation | class << 8.  Which class holds which operation (include/ministark.h); cls becomes the instance that runs it: 1 GL, 2 GLT, 3 GLM, 0 BB
+  const int op = op_word & 0xFF;
+  int cls = op_word >> 8;
+  bool ok = a && b && out && op_word >= 0;
+  if (F::ID == 0) {
+    const bool own = (op >= 8 && op <= 11) || op == 13 || op == 14 || (op >= 32 && op <= 36);   // GL's own code, whatever the class of the tiles: class 0 or 1
+    if (op <= 7) ok = ok && cls <= 3 && !(cls == 1 && (op == 4 || op == 5 || op == 7));   // (compare + select has no mul_x32 / mul_x64 / fold_small; its shift, op 6, is GL::mul_pow2)
+    else if (op == 12) ok = ok && (cls == 1 || cls == 2);
+    else ok = ok && own && cls <= 1;
+    if (cls == 0) cls = (own && op > 11) ? 1 : 3;    // (operations 8-11 of class 0 stay in the instance they have always run in)
+  } else {
+    ok = ok && cls == 0 && (op <= 3 || op == 14 || op == 15 || (op >= 32 && op <= 38));
+  }
+  if (!ok) return fail(MS_ERR_ARG, "arith_selftest: bad operation / class / null argument");
+  if (op >= 32 && n % F::EXT) return fail(MS_ERR_ARG, "arith_selftest: an extension operation takes whole elements");
   if (!n) return MS_OK;
-  if (!canonical(a, n) || (op < 6 && !canonical(b, n))) return fail(MS_ERR_ARG, "operand not canonical");
+  if (op != 12 && (!canonical(a, n) || ((op < 6 || op == 15 || op >= 32) && !canonical(b, n)))) return fail(MS_ERR_ARG, "operand not canonical");
   DevBuf d;
   if (d.ensure(3 * n * 8)) return fail(MS_ERR_NOMEM, "arith_selftest");
-  typedef typename std::conditional<F::ID == 0, GLM, F>::type A;
-  typedef mspoly::ArithKernel<F, A> AK;
   int e = msrt::h2d(d.p, a, n * 8, stream);
   if (!e) e = msrt::h2d(d.as<u64>() + n, b, n * 8, stream);
   if (!e) e = msrt::sync(stream);
-  typename AK::Params ap{d.as<u64>(), d.as<u64>() + n, d.as<u64>() + 2 * n, n, op};
-  if (!e) e = run<AK>(K_IO, grid1(n, AK::THREADS), 1, AK::THREADS, 0, ap);
+  if (!e) {
+    if constexpr (F::ID == 0) {
+      if (cls == 1) e = arith_launch<GL>(op, d.as<u64>(), n);
+      else if (cls == 2) e = arith_launch<GLT>(op, d.as<u64>(), n);
+      else e = arith_launch<GLM>(op, d.as<u64>(), n);
+    } else e = arith_launch<F>(op, d.as<u64>(), n);
+  }
   if (!e) e = msrt::d2h(out, d.as<u64>() + 2 * n, n * 8, stream);
   if (!e) e = msrt::sync(stream);
   d.release();
   return e ? fail_rt(e, "arith_selftest") : MS_OK;
+}
+
+template <class F> template <class A>
+int Ctx<F>::arith_launch(int op, u64* buf, size_t n) {
+  typedef mspoly::ArithKernel<F, A> AK;
+  typename AK::Params ap{buf, buf + n, buf + 2 * n, n, op};
+  return run<AK>(K_IO, grid1(n, AK::THREADS), 1, AK::THREADS, 0, ap);
 }
 
 // the members this unit defines, for both fields (the other units see declarations only)
