@@ -38,6 +38,15 @@ MS_HIDDEN void operator delete(void* p, size_t) noexcept { std::free(p); }
 MS_HIDDEN void operator delete[](void* p, size_t) noexcept { std::free(p); }
 extern "C" void ms_emu_fail_alloc_after(long n) { g_emu_fail_at = n < 0 ? -1 : g_emu_alloc_count + n; }
 extern "C" long ms_emu_alloc_count() { return g_emu_alloc_count; }
+// ---- what the emulated runtime has handed out (rt.hpp, msrt::EmuLive).  out: live device buffers, page-locked buffers, streams, events, copy-engine signals, then
+// the device / page-locked allocations and the handle creations made so far.  The two hooks fail the n-th such call from now (n < 0: disarmed), as the one above
+extern "C" void ms_emu_live(long out[7]) {
+  const msrt::EmuLive& l = msrt::EmuLive::get();
+  for (int k = 0; k < msrt::EmuLive::KINDS; k++) out[k] = l.live[k];
+  out[5] = l.allocs; out[6] = l.handles;
+}
+extern "C" void ms_emu_fail_device_alloc_after(long n) { msrt::EmuLive& l = msrt::EmuLive::get(); l.fail_alloc_at = n < 0 ? -1 : l.allocs + n; }
+extern "C" void ms_emu_fail_handle_after(long n) { msrt::EmuLive& l = msrt::EmuLive::get(); l.fail_handle_at = n < 0 ? -1 : l.handles + n; }
 #endif
 
 extern "C" {

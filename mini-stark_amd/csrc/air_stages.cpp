@@ -115,8 +115,8 @@ int Ctx<F>::finish_linear_columns(size_t stride, size_t n) {
   if (d_lin.ensure(c * sizeof(msmerkle::LinColSpec))) return fail(MS_ERR_NOMEM, "virtual column table");
   if (c * sizeof(msmerkle::LinColSpec) > pinned_cap - 8192) return lincomb_linear_columns(d_lde.as<T>(), stride, n);
   // staged through page-locked memory behind the small results: the previous proof's copy out of it completed before that proof's lde_commit returned
-  memcpy(reinterpret_cast<u8*>(pinned) + 8192, spec.data(), c * sizeof(msmerkle::LinColSpec));
-  CK(msrt::h2d(d_lin.p, reinterpret_cast<u8*>(pinned) + 8192, c * sizeof(msmerkle::LinColSpec), stream));
+  memcpy(pinned.as<u8>() + 8192, spec.data(), c * sizeof(msmerkle::LinColSpec));
+  CK(msrt::h2d(d_lin.p, pinned.as<u8>() + 8192, c * sizeof(msmerkle::LinColSpec), stream));
   lde_cols_virtual = true;
   return 0;
 }
@@ -621,7 +621,7 @@ int Ctx<F>::shard_combine_launch(size_t off, size_t rank_stride, u32 n, const XE
 template <class F>
 int Ctx<F>::eval_finish(int q, const std::vector<int>& ev, u64* out) {
   const size_t nev = ev.size(), np = (size_t)npolys + 1;
-  const T* h = reinterpret_cast<const T*>(pinned);
+  const T* h = pinned.as<const T>();
   std::vector<int> slot(np, -1);
   for (size_t k = 0; k < nev; k++) slot[ev[k]] = (int)k;
   std::vector<std::map<int, T>> exp_(np);
@@ -659,7 +659,7 @@ int Ctx<F>::eval_ext_sharded(const u64* z, int q, u64* out) {
   }
   if (tot) {
     RQ(exchange(MS_XCHG_ALL_GATHER, tot * sizeof(T)));
-    for (int t = 0; t < q; t++) RQ(shard_combine_launch((size_t)t * nev * E, tot, (u32)nev, e_pow<F, E>(zs[t], (u64)Sx), reinterpret_cast<T*>(pinned) + (size_t)t * nev * E));
+    for (int t = 0; t < q; t++) RQ(shard_combine_launch((size_t)t * nev * E, tot, (u32)nev, e_pow<F, E>(zs[t], (u64)Sx), pinned.as<T>() + (size_t)t * nev * E));
     CK(msrt::sync(stream));
     RQ(eval_finish(q, ev, out));
   }
@@ -690,7 +690,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
       const int nb = (nev - i0 < mspoly::MAX_POLYS) ? nev - i0 : mspoly::MAX_POLYS;
       size_t off[mspoly::MAX_POLYS], cnt[mspoly::MAX_POLYS];
       for (int i = 0; i < nb; i++) { const int pi = ev[i0 + i]; off[i] = (size_t)pi * N; cnt[i] = (pi == npolys) ? validity_len : N; }   // the validity polynomial has 2N coefficients after ms_mix_cubic
-      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, reinterpret_cast<T*>(pinned) + ((size_t)t * nev + i0) * E, t == q - 1 && i0 + mspoly::MAX_POLYS >= nev)));   // results land in page-locked host memory
+      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, pinned.as<T>() + ((size_t)t * nev + i0) * E, t == q - 1 && i0 + mspoly::MAX_POLYS >= nev)));   // results land in page-locked host memory
     }
   }
   RQ(res.collect(nullptr, nullptr, &vlen));

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -31,19 +32,51 @@
 
 namespace msctx {
 
-struct DevBuf {
+// ---- owners.  Whatever the runtime hands out is held by exactly one of these and goes back when its owner dies: they move, they do not copy.
+// Memory: a pointer and its capacity, freed by Free.  release() is the deliberate early free.
+template <int (*Free)(void*)> struct Owned {
   void* p = nullptr; size_t cap = 0;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Owned& operator=(Owned&& o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
+  ~Owned() { release(); }
+  void release() { if (p) Free(p); p = nullptr; cap = 0; }
+  template <class U> U* as() const { return reinterpret_cast<U*>(p); }
+};
+struct DevBuf : Owned<msrt::free_dev> {
   int ensure(size_t bytes) {
     if (bytes <= cap) return 0;
-    if (p) msrt::free_dev(p);
-    p = nullptr; cap = 0;
+    release();
     size_t want = bytes + bytes / 8 + 256;
     if (msrt::malloc_dev(&p, want)) { p = nullptr; return 1; }
     cap = want;
     return 0;
   }
-  void release() { if (p) msrt::free_dev(p); p = nullptr; cap = 0; }
-  template <class U> U* as() const { return reinterpret_cast<U*>(p); }
+};
+// page-locked host memory, exactly `bytes` of it (coherent: msrt::malloc_host_coherent); what it held is freed first
+struct HostBuf : Owned<msrt::free_host> {
+  int alloc(size_t bytes, bool coherent = false) {
+    release();
+    if (coherent ? msrt::malloc_host_coherent(&p, bytes) : msrt::malloc_host(&p, bytes)) { p = nullptr; return 1; }
+    cap = bytes;
+    return 0;
+  }
+};
+// Handles: a unique_ptr whose deleter is the runtime's destroy call.  make() creates into an EMPTY owner.  Handles that only work together (a stream and its
+// events, the two signals of a context) are made into locals and moved into the context when the last one exists: a failure half-way leaves nothing behind
+template <class H, int (*Destroy)(H*)> struct Destroyer { void operator()(H* h) const { Destroy(h); } };
+typedef std::unique_ptr<msrt::Stream, Destroyer<msrt::Stream, msrt::stream_destroy>> StreamOwner;
+typedef std::unique_ptr<msrt::Event, Destroyer<msrt::Event, msrt::event_destroy>> EventOwner;
+inline int make(StreamOwner& o) { msrt::Stream* s = nullptr; const int e = msrt::stream_create(&s); if (!e) o.reset(s); return e; }
+inline int make(EventOwner& o) { msrt::Event* v = nullptr; const int e = msrt::event_create(&v); if (!e) o.reset(v); return e; }
+struct SdmaSignal {
+  msrt::Sdma::Signal s{0};
+  SdmaSignal() = default;
+  SdmaSignal(SdmaSignal&& o) noexcept : s(o.s) { o.s.handle = 0; }
+  SdmaSignal& operator=(SdmaSignal&& o) noexcept { if (this != &o) { reset(); s = o.s; o.s.handle = 0; } return *this; }
+  ~SdmaSignal() { reset(); }
+  void reset() { if (s.handle) msrt::Sdma::get().signal_destroy(s); s.handle = 0; }
+  int create() { msrt::Sdma::Signal n{0}; if (msrt::Sdma::get().signal_create(&n)) return 1; reset(); s = n; return 0; }
 };
 
 // ---- src/util.rs:4-44 ------------------------------------------------------
@@ -150,9 +183,16 @@ template <class F> struct Ctx : CtxBase {
   // flight 127.0 / 129.6 / 130.3; against 0 (one launch per level): 4096 -> +0.8 % in flight, +1.2 % alone
   size_t subtree_parents = 16384;
   int fri_pointwise = 1;  // MS_FRI_POINTWISE=0: codewords of FRI rounds >= 1 by NTT of the round polynomial instead of the evaluation-domain fold
-  msrt::Stream* own_stream = nullptr;
-  msrt::Stream* stream = nullptr;
-  void* pinned = nullptr; size_t pinned_cap = 0;
+  // MEMBER ORDER, the one rule: the context's own stream and its page-locked memory stand in front of every device buffer, so they are destroyed behind them.
+  // Freeing device memory waits for the device; until then a launch may still store to the result slots in `pinned` and a copy may still read `h_tabs`.
+  StreamOwner own_stream;
+  msrt::Stream* stream = nullptr;   // own_stream, or the caller's (ms_set_stream)
+  HostBuf pinned; size_t pinned_cap = 0;   // pinned_cap: the staging area; the slots of the stage results lie behind it
+  // page-locked staging for the per-proof job tables (r03): uploads out of it are plain DMA, not the runtime's pageable-memory path (which pins or stages the
+  // caller's pages on the fly), and need no synchronisation of their own - the area is rewritten by the NEXT proof's same stage, behind that stage's final
+  // stream synchronisation
+  HostBuf h_tabs;
+  int tabs_host(size_t bytes, u8** out);
 
   // ---- one proof sharded over `sh_world` ranks (ms_set_shard; include/ministark.h)
   int sh_rank = 0, sh_world = 1;
@@ -170,7 +210,7 @@ template <class F> struct Ctx : CtxBase {
   // one slice of a sliced digest all-to-all: peer r's piece at offset `off + r * stride`, `bytes` long, in both exchange buffers
   int shard_slices = 4; bool shard_slices_set = false; size_t shard_slice_min = 1024;   // (RCCL path: 1 unless MS_SHARD_SLICES is set - ADVICE r3: the two-stream overlap has never run on more than one GPU)
   size_t xl_off = 0, xl_stride = 0;
-  msrt::Stream* comm_stream = nullptr; std::vector<msrt::Event*> ev_hash, ev_xchg;
+  StreamOwner comm_stream; struct SliceEvents { EventOwner hashed, exchanged; }; std::vector<SliceEvents> ev_slice;   // (a slice's two events are made, and kept, together)
   int shard_slice_layout(size_t* off, size_t* stride) override { if (!off || !stride) return fail(MS_ERR_ARG, "shard_slice_layout"); *off = xl_off; *stride = xl_stride; return MS_OK; }
   int exchange_slice(size_t off, size_t stride, size_t bytes, int sl, int S);
   void drop_rccl();
@@ -194,7 +234,7 @@ template <class F> struct Ctx : CtxBase {
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
          K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_COUNT };
-  struct ProfRec { int kid, sub; msrt::Event* a; msrt::Event* b; double bytes; bool part; };
+  struct ProfRec { int kid, sub; EventOwner a, b; double bytes; bool part; };   // (the records of a profile never ended go with the context)
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
   int part_depth = 0;
@@ -231,7 +271,7 @@ template <class F> struct Ctx : CtxBase {
     bool owns(const void* p) const { return p >= words.p && p < words.as<u8>() + WORD_BYTES; }
     // page-locked slots behind the staging area, a 64-byte line each (the host spins on the first: the results land on lines of their own): sequence number | word | root
     static constexpr size_t SLOT_BYTES = 192;
-    unsigned long long* seq_slot() const { return reinterpret_cast<unsigned long long*>(reinterpret_cast<u8*>(c.pinned) + c.pinned_cap); }
+    unsigned long long* seq_slot() const { return reinterpret_cast<unsigned long long*>(c.pinned.template as<u8>() + c.pinned_cap); }
     unsigned long long* word_slot() const { return seq_slot() + 8; }
     u32* root_slot() const { return reinterpret_cast<u32*>(seq_slot() + 16); }
     bool open = false, may_poll = false, attached = false, root_sent = false, word_sent = false;
@@ -247,9 +287,12 @@ template <class F> struct Ctx : CtxBase {
     unsigned long long* shard_word() const { return open && over_ranks ? want : nullptr; }
     // the coefficient side of a FRI round goes to the side stream: call BEHIND expect (the guard then orders the context's stream behind it on every exit)
     // side_done (behind the side stream's last launch) records the event early: it is long up when the join, in front of the stage's last launch, waits for it
-    int fork_side() { if (!c.side_stream) CK(msrt::stream_create(&c.side_stream)); if (!c.ev_side) CK(msrt::event_create(&c.ev_side)); side = SIDE_FORKED; return 0; }
-    int side_done() { if (side == SIDE_FORKED) { CK(msrt::event_record(c.ev_side, c.side_stream)); side = SIDE_DONE; } return 0; }
-    int join_side() { if (side == SIDE_NONE) return 0; RQ(side_done()); side = SIDE_NONE; CK(msrt::stream_wait_event(c.stream, c.ev_side)); return 0; }
+    int fork_side() {
+      if (!c.side_stream) { StreamOwner s; EventOwner e; CK(make(s)); CK(make(e)); c.side_stream = std::move(s); c.ev_side = std::move(e); }
+      side = SIDE_FORKED; return 0;
+    }
+    int side_done() { if (side == SIDE_FORKED) { CK(msrt::event_record(c.ev_side.get(), c.side_stream.get())); side = SIDE_DONE; } return 0; }
+    int join_side() { if (side == SIDE_NONE) return 0; RQ(side_done()); side = SIDE_NONE; CK(msrt::stream_wait_event(c.stream, c.ev_side.get())); return 0; }
     template <class P> int attach(P& p) {   // (outside a stage nobody reads the slots: nothing is attached)
       if (!open) return 0;
       RQ(join_side());
@@ -275,8 +318,8 @@ template <class F> struct Ctx : CtxBase {
       return 0;
     }
     void abandon() {   // (the stage is leaving with an error of its own, or never asked: failures of the calls below are not reported)
-      if (side == SIDE_FORKED) msrt::event_record(c.ev_side, c.side_stream);
-      if (side != SIDE_NONE) msrt::stream_wait_event(c.stream, c.ev_side);
+      if (side == SIDE_FORKED) msrt::event_record(c.ev_side.get(), c.side_stream.get());
+      if (side != SIDE_NONE) msrt::stream_wait_event(c.stream, c.ev_side.get());
       side = SIDE_NONE;
       if (want && owns(want)) msrt::memset_dev(want, 0, 8, c.stream);
       open = attached = false; want = nullptr; seq_pending = seq_armed = 0;
@@ -291,8 +334,8 @@ template <class F> struct Ctx : CtxBase {
     else if (!prof_on) { e = go(); ran = !e; }
     else {
       ProfRec r; r.kid = kid; r.sub = next_sub; r.bytes = next_bytes; r.part = part_depth > 0; next_bytes = 0; next_sub = 0;
-      if (msrt::event_create(&r.a) || msrt::event_create(&r.b)) e = 1;
-      else { msrt::event_record(r.a, stream); e = go(); msrt::event_record(r.b, stream); prof_recs.push_back(r); ran = !e; }
+      if (make(r.a) || make(r.b)) e = 1;
+      else { msrt::event_record(r.a.get(), stream); e = go(); msrt::event_record(r.b.get(), stream); prof_recs.push_back(std::move(r)); ran = !e; }
     }
     res.launched(ran);
     return e;
@@ -316,7 +359,8 @@ template <class F> struct Ctx : CtxBase {
     T n_inv = 0;
     T root = 0;   // w_n the tables hold the powers of (host copy: the FRI fold's octet table is derived from it)
   };
-  std::map<int, Plan*> plans;  // key = (log_n*4 + log_pad)*2 + inverse
+  std::map<int, Plan> plans;  // key = (log_n*4 + log_pad)*2 + inverse; complete plans only (get_plan), and a map's elements stay where they are
+  int power_table(DevBuf& tab, T w, size_t count, const char* what);   // w^0 .. w^(count-1) in twiddle form -> device
   DevBuf ntt_scratch;
   int ntt_kmax = 9;            // largest tile (log2 rows) of a multi-pass plan; MS_NTT_KMAX overrides (tuning)
   int ntt_v2 = 1, ntt_v2_regpass = 1;   // MS_NTT_V2=0: round-1 kernels only (tests, A/B); MS_NTT_V2_REGPASS: the register-only last pass of 2^21..2^25-point transforms (0: off; 2: tests, on 2^7-row tiles)
@@ -353,11 +397,6 @@ template <class F> struct Ctx : CtxBase {
   // users ahead of the clear) — a proof needs ~50 such counters, i.e. one memset instead of ~50 four-microsecond fills.
   // CONTRACT: a piece is valid only until the next zero_alloc call on the context (that call may wipe the whole pool): its last reader must be enqueued before
   // then.  A word that has to live longer is one of res.word()'s.
-  // page-locked staging for the per-proof job tables (r03): uploads out of it are plain DMA, not the runtime's pageable-memory path (which pins or stages the
-  // caller's pages on the fly), and need no synchronisation of their own - the area is rewritten by the NEXT proof's same stage, behind that stage's final
-  // stream synchronisation
-  void* h_tabs = nullptr; size_t h_tabs_cap = 0;
-  int tabs_host(size_t bytes, u8** out);
   DevBuf d_zero; size_t zero_used = 0, zero_cap = 0;
   int zero_alloc(size_t bytes, void** out);
 
@@ -433,7 +472,7 @@ template <class F> struct Ctx : CtxBase {
     return (S >= 2 && !(S & 1)) ? S : 0;
   }
   DevBuf d_carry, d_lq, d_pack, d_fullpoly;
-  std::vector<Round*> rounds; size_t nrounds_done = 0, fri_rounds = 0, fri_blowup = 0;
+  std::vector<std::unique_ptr<Round>> rounds; size_t nrounds_done = 0, fri_rounds = 0, fri_blowup = 0;
   bool have_deep = false; XE cur_z; XE cur_B[2];
   DevBuf d_folded, d_sh, d_blob, d_tabs, d_targets, d_idx, d_ovf;
   size_t blob_size = 0;
@@ -441,32 +480,18 @@ template <class F> struct Ctx : CtxBase {
   int ensure_polys(size_t count);
 
   int init(int dev, u32 flags);
+  // Only what needs an order, in front of every member's own destructor: the communicator goes while its streams exist, and transfers still in flight read or write
+  // memory the members free - wait for them, however long it takes (a poisoned context got here exactly because one did not finish in time)
   ~Ctx() {
-    for (auto& kv : plans) { kv.second->tw_lo.release(); kv.second->tw_hi.release(); kv.second->vtw.release(); kv.second->w0.release(); for (auto& b : kv.second->w_r) b.release(); delete kv.second; }
     drop_rccl();
-    // transfers still in flight read or write memory freed below: wait for them, however long it takes (a poisoned context got here exactly because one did not finish in time)
-    if (sdma_pending) msrt::Sdma::get().wait(sdma_sig, -1.0);
-    else if (copy_pending) msrt::event_sync(ev_copy);
-    if (up.pending) msrt::Sdma::get().wait(sdma_up_sig, -1.0);
-    if (sdma_state == 1) { msrt::Sdma::get().signal_destroy(sdma_sig); msrt::Sdma::get().signal_destroy(sdma_up_sig); }
-    for (msrt::Event* e : ev_hash) msrt::event_destroy(e);
-    for (msrt::Event* e : ev_xchg) msrt::event_destroy(e);
-    if (comm_stream) msrt::stream_destroy(comm_stream);
-    if (side_stream) { msrt::sync(side_stream); msrt::stream_destroy(side_stream); }
-    if (ev_side) msrt::event_destroy(ev_side);
-    if (ev_blob) msrt::event_destroy(ev_blob);
-    if (ev_copy) msrt::event_destroy(ev_copy);
-    if (copy_stream) msrt::stream_destroy(copy_stream);
-    for (Round* r : rounds) { r->poly.release(); r->cw.release(); r->nodes.release(); delete r; }
-    DevBuf* bufs[] = {&ntt_scratch, &d_trace[0], &d_trace[1], &d_polys, &d_coef, &d_lde, &d_trace_nodes, &d_lde_nodes, &d_io, &d_partials, &d_small, &d_folded, &d_sh, &d_blob, &d_tabs, &d_targets, &d_idx, &d_ovf, &d_zero, &d_lin, &d_cubic, &d_carry, &d_lq, &d_pack, &d_fullpoly, &res.words, &d_air_inv, &d_aux};
-    for (DevBuf* b : bufs) b->release();
-    if (pinned) msrt::free_host(pinned);
-    if (h_tabs) msrt::free_host(h_tabs);
-    if (own_stream) msrt::stream_destroy(own_stream);
+    if (sdma_pending) msrt::Sdma::get().wait(sdma_sig.s, -1.0);
+    else if (copy_pending) msrt::event_sync(ev_copy.get());
+    if (up.pending) msrt::Sdma::get().wait(sdma_up_sig.s, -1.0);
+    if (side_stream) msrt::sync(side_stream.get());
   }
   int ext_degree() const override { return E; }
   void bind_device() const override { msrt::set_device(device); }
-  int set_stream(void* s) override { stream = s ? reinterpret_cast<msrt::Stream*>(s) : own_stream; zero_used = zero_cap; return 0; }
+  int set_stream(void* s) override { stream = s ? reinterpret_cast<msrt::Stream*>(s) : own_stream.get(); zero_used = zero_cap; return 0; }
   int synchronize() override { CK(msrt::sync(stream)); return 0; }
 
   static unsigned grid1(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
@@ -593,7 +618,7 @@ template <class F> struct Ctx : CtxBase {
   int eval_ext(const u64* z, int q, u64* out) override;
 
   // ------------------------------------------------------------------ FRI rounds (fri.rs:314-352)
-  Round* round_slot(size_t i) { while (rounds.size() <= i) rounds.push_back(new Round()); return rounds[i]; }
+  Round* round_slot(size_t i) { while (rounds.size() <= i) rounds.push_back(std::make_unique<Round>()); return rounds[i].get(); }
   // codeword + tree of rounds[i] from its coefficient limbs (ncoef_in valid coefficients)
   // `nonzero_limbs`: limbs >= this are identically zero (round 0: extend_poly embeds base coefficients), so their
   // transform is all zeros and is not computed
@@ -650,7 +675,7 @@ template <class F> struct Ctx : CtxBase {
   // while the evaluation side (pointwise codeword, leaf hashing, tree) runs on the context's stream - the two are independent (the codeword never reads the
   // quotient); the launch that forwards root and length word to the host waits for the side stream's event.  The fused tail rounds do the same inside one kernel.
   int fri_overlap = 0;   // MS_FLAG_LATENCY at ms_create (MS_FRI_OVERLAP=0/1 overrides: A/B)
-  msrt::Stream* side_stream = nullptr; msrt::Event* ev_side = nullptr;   // (forked and joined by `res`)
+  StreamOwner side_stream; EventOwner ev_side;   // (made together, forked and joined by `res`)
   struct StreamScope { Ctx* c; msrt::Stream* keep; StreamScope(Ctx* c_, msrt::Stream* s) : c(c_), keep(c_->stream) { c->stream = s; } ~StreamScope() { c->stream = keep; } };
   int fri_tail_round(Round* pr, Round* nr, const XE& a, bool* done);
   template <class DG> int fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done);   // DG: the kernel family of `digest` (msmerkle::with_digest, digest.hpp)
@@ -687,12 +712,12 @@ template <class F> struct Ctx : CtxBase {
   int fri_proof_read(u8* out) override;
   // The same copy on the context's COPY stream, ordered behind the query phase by an event: the call returns at once and the next proof's
   // stages run while the ~64 MiB travel; the next ms_fri_query waits (on the device, not on the host) for the copy before it rewrites the blob.
-  msrt::Stream* copy_stream = nullptr; msrt::Event* ev_blob = nullptr; msrt::Event* ev_copy = nullptr; bool copy_pending = false;
+  StreamOwner copy_stream; EventOwner ev_blob, ev_copy; bool copy_pending = false;   // (the three are made together: all or none)
   // r04: the read-back as an explicit SDMA copy through the HSA runtime (rt.hpp, msrt::Sdma) - queued on a copy engine whatever the engines' load, never a
   // blit kernel; completion is an HSA signal the host waits on (ms_fri_proof_wait, or the next ms_fri_query before it rewrites the blob).  MS_READBACK=hip keeps
   // hipMemcpyAsync on the copy stream (A/B); io_engine() reports which path the last read-back took.
   int readback_sdma = 2, sdma_gpu = -1, sdma_state = 0 /* 0 untried, 1 bound, 2 unavailable */, last_io_engine = 0;
-  msrt::Sdma::Signal sdma_sig{0}, sdma_up_sig{0}; bool sdma_pending = false; int upload_sdma = 1;
+  SdmaSignal sdma_sig, sdma_up_sig; bool sdma_pending = false; int upload_sdma = 1;   // (both or neither: sdma_state == 1 means both)
   u8* readback_dst = nullptr; size_t readback_bytes = 0;   // destination and size of the read-back in flight (a FAILED engine copy is redone through the HIP runtime)
   double sdma_timeout_s = 20.0;        // MS_SDMA_TIMEOUT_S: how long a stage waits for a copy engine before it poisons the context
   bool sdma_ready();

@@ -170,10 +170,10 @@ int Ctx<F>::fri_deep(const u64* z, u64* B) {
   if (nrounds_done == 0 || nrounds_done >= fri_rounds) return fail(MS_ERR_STATE, "fri_deep out of order");
   if (!z || !B) return fail(MS_ERR_ARG, "fri_deep");
   if (!load_ext(z, &cur_z)) return fail(MS_ERR_ARG, "z not canonical");
-  Round* r = rounds[nrounds_done - 1];
+  Round* r = rounds[nrounds_done - 1].get();
   auto stage = res.expect();
   size_t off[2] = {0, 1}, cnt[2] = {(r->ncoef + 1) / 2, r->ncoef / 2};
-  T* dst = reinterpret_cast<T*>(pinned);   // the last kernel of the evaluation stores its 2 E words straight into page-locked host memory
+  T* dst = pinned.as<T>();   // the last kernel of the evaluation stores its 2 E words straight into page-locked host memory
   if (r->dist) {   // even(z), odd(z) by coefficient range: partial sums over this rank's coefficients, one all-gather, combination with z^(S/2)
     const size_t lc = lcount(r, r->ncoef);
     cnt[0] = (lc + 1) / 2; cnt[1] = lc / 2;   // (the rank's first coefficient has an even index: S is even)
@@ -183,7 +183,7 @@ int Ctx<F>::fri_deep(const u64* z, u64* B) {
   } else
   RQ((eval_views<E>(r->poly.template as<T>(), 0, r->cap, 2, off, cnt, 2, cur_z, dst, true)));  // fri.rs:354-359
   RQ(res.collect());
-  const T* h = reinterpret_cast<const T*>(pinned);
+  const T* h = pinned.as<const T>();
   for (int s = 0; s < 2; s++) for (int l = 0; l < E; l++) { cur_B[s].c[l] = h[s * E + l]; B[s * E + l] = F::to_u64(h[s * E + l]); }
   have_deep = true;
   return MS_OK;
@@ -401,7 +401,7 @@ int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
   if (!have_deep) return fail(MS_ERR_STATE, "fri_fold_commit before fri_deep");
   XE a;
   if (!alpha || !root || !load_ext(alpha, &a)) return fail(MS_ERR_ARG, "alpha");
-  Round* pr = rounds[nrounds_done - 1];
+  Round* pr = rounds[nrounds_done - 1].get();
   if (pr->D < 4) return fail(MS_ERR_SHAPE, "FRI round domain too small to fold (merkle.rs:93-104 panics)");
   const size_t n = pr->ncoef, m = (n + 1) / 2;
   Round* nr = round_slot(nrounds_done);
@@ -424,7 +424,7 @@ int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
     // the coefficient side on the side stream (every stage ends with a synchronisation of the context's stream behind a join: the side stream starts on finished data)
     side = fri_overlap && !prof_on;   // (the per-kernel profile times launches one behind the other on ONE stream)
     if (side) RQ(res.fork_side());
-    StreamScope on_side(this, side ? side_stream : stream);
+    StreamScope on_side(this, side ? side_stream.get() : stream);
     typename mspoly::FoldKernel<F, E>::Params fp{pr->poly.template as<T>(), pr->cap, n, d_folded.as<T>(), m, a, nullptr};  // fri.rs:361-372
     CK(run<mspoly::FoldKernel<F, E>>(K_FOLD, grid1(m, mspoly::THREADS), 1, mspoly::THREADS, 0, fp));
     // (folded - B(alpha)) / (x - z): quotient coefficients are H_1.. of the suffix Horner in z (fri.rs:99-101)
@@ -440,7 +440,7 @@ int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
       CK(run<mspoly::DegreeKernel<F, E>>(K_DEGREE, grid1(lc, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
     }
   } else if (nq_coef) {
-    StreamScope on_side(this, side ? side_stream : stream);
+    StreamScope on_side(this, side ? side_stream.get() : stream);
     typename mspoly::DegreeKernel<F, E>::Params dp{nr->poly.template as<T>(), nr->cap, nq_coef, dres, 0};
     CK(run<mspoly::DegreeKernel<F, E>>(K_DEGREE, grid1(nq_coef, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
   }

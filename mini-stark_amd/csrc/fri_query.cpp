@@ -15,7 +15,7 @@ int Ctx<F>::query_layout(QueryPlan& q, int nq) {
   q.rec_off.assign(W * nq, 0); q.path_off.assign(W * nq * 2, 0); q.qlen.assign(W ? W : 1, 0);
   size_t pos = 0;
   for (size_t i = 0; i < W; i++) {
-    Round* pr = rounds[i];
+    Round* pr = rounds[i].get();
     if (pr->D / 2 != rounds[i + 1]->D) return fail(MS_ERR_SHAPE, "round domains do not halve (fri.rs:134-137)");
     q.qlen[i] = pr->ncoef >= 3 ? pr->ncoef - 2 : 0;
     const size_t nlev = pr->ts.levels - 1;
@@ -49,7 +49,7 @@ int Ctx<F>::query_build(QueryPlan& q, const u64* betas) {
   q.any_dist = false;
   for (size_t i = 0; i <= W; i++) q.any_dist = q.any_dist || rounds[i]->dist;
   for (size_t i = 0; i < W; i++) {
-    Round* pr = rounds[i];
+    Round* pr = rounds[i].get();
     if (!pr->dist) continue;
     const size_t Sh = pr->S / 2;
     for (size_t r = 0; r < Wr; r++) for (int j = 0; j < nq; j++) {
@@ -68,7 +68,7 @@ int Ctx<F>::query_build(QueryPlan& q, const u64* betas) {
     std::vector<SHPlan> shplans;
     T* scr = d_sh.as<T>();
     for (size_t i = 0; i <= W; i++) {
-      Round* pr = rounds[i];
+      Round* pr = rounds[i].get();
       const T gp = f_root_of_unity<F>(ctz64(pr->D));
       const size_t n = pr->ncoef, mm[2] = {(n + 1) / 2, n / 2};
       for (int j = 0; j < nq; j++) {
@@ -148,7 +148,7 @@ int Ctx<F>::query_build(QueryPlan& q, const u64* betas) {
   q.fjobs.resize(W);
   q.stage_bytes = 0;
   for (size_t i = 0; i < W; i++) {
-    Round* pr = rounds[i];
+    Round* pr = rounds[i].get();
     const size_t nlev = pr->ts.levels - 1, path_bytes = 8 + 2 * E * 8 + 8 + nlev * 2 * 32;
     if (pr->ts.sharded) {
       q.fjobs[i] = FJ{pr->cw.template as<T>(), 2 * pr->m, 2 * pr->m, d_tg + i * 2 * nq * E, 2 * nq, d_ix + i * 2 * nq, 2, (u32)sh_world, (u32)sh_rank, pr->m};
@@ -279,9 +279,9 @@ int Ctx<F>::query_openings(QueryPlan& q) {
     msmerkle::CopyJobsKernel::Params ck{reinterpret_cast<const msmerkle::CopyJob*>(dt + q.off_cj), (u32)q.cjobs.size()};
     CK(run<msmerkle::CopyJobsKernel>(K_PATH, (unsigned)q.cjobs.size(), 1, msmerkle::CopyJobsKernel::THREADS, 0, ck));
   }
-  CK(msrt::d2h(pinned, q.d_ix, W * nq * 2 * 8, stream));
+  CK(msrt::d2h(pinned.p, q.d_ix, W * nq * 2 * 8, stream));
   CK(msrt::sync(stream));
-  const unsigned long long* hidx = reinterpret_cast<const unsigned long long*>(pinned);
+  const unsigned long long* hidx = pinned.as<const unsigned long long>();
   for (size_t t = 0; t < W * nq * 2; t++) if (hidx[t] == ~0ULL) return fail(MS_ERR_LEAF_NOT_FOUND, "leaf is not included in the tree");
   return 0;
 }
@@ -306,7 +306,7 @@ int Ctx<F>::fri_query(const u64* betas, int nq, u8* ext_out, size_t ext_cap, siz
   for (size_t i = 0; i <= W; i++) sh_elems += (size_t)nq * (sh_scratch_elems((rounds[i]->ncoef + 1) / 2) + sh_scratch_elems(rounds[i]->ncoef / 2));
   const size_t n_h0 = (W + 1) * nq * 2 * E, n_tg = (W ? W : 1) * 2 * nq * E;
   if (copy_pending && !ext_out) {   // an asynchronous read-back of the previous proof: finish it before the blob moves, order it before the blob is rewritten
-    if (sdma_pending || pos + 8 > d_blob.cap) RQ(fri_proof_wait()); else CK(msrt::stream_wait_event(stream, ev_copy));   // (an SDMA copy is waited for on the host: it ended a whole proof ago)
+    if (sdma_pending || pos + 8 > d_blob.cap) RQ(fri_proof_wait()); else CK(msrt::stream_wait_event(stream, ev_copy.get()));   // (an SDMA copy is waited for on the host: it ended a whole proof ago)
   }
   if ((!ext_out && d_blob.ensure(pos + 8)) || d_sh.ensure(sh_elems * sizeof(T)) || d_targets.ensure((n_h0 + n_tg) * sizeof(T)) || d_idx.ensure((W ? W : 1) * nq * 2 * 8))
     return fail(MS_ERR_NOMEM, "query buffers");
@@ -337,37 +337,29 @@ int Ctx<F>::merkle_prove_t(const u64* leafs, size_t leaf_num, size_t lpn, const 
   typedef mspoly::FindJob<F, EL> FJ;
   typedef msmerkle::PathJob<F, EL> PJ;
   const size_t off_ix = 256, off_pj = 512, off_path = 1024;
-  int rc = 0;
-  if (ds.ensure(leaf_num * EL * sizeof(T)) || dw.ensure(off_path + plen) || d_io.ensure(leaf_num * EL * 8)) rc = fail(MS_ERR_NOMEM, "merkle_prove");
-  if (!rc) {
-    int e = msrt::h2d(d_io.p, leafs, leaf_num * EL * 8, stream);
-    if (e) rc = fail_rt(e, "leaf upload");
-    else rc = transpose_in(d_io.as<u64>(), ds.as<T>(), leaf_num, (size_t)EL, F::from_u64(1), 0, nullptr);
-  }
-  if (!rc) rc = tree_build<EL>(ds.as<T>(), 0, 1, leaf_num, 1, ts, dn);
-  if (!rc) {
-    T tgt[EL]; for (int l = 0; l < EL; l++) tgt[l] = F::from_u64(leaf[l]);
-    unsigned long long none = ~0ULL;
-    u8* base = dw.as<u8>();
-    PJ pj{ds.as<T>(), leaf_num, dn.as<u32>(), leaf_num, (u32)lpn, 2, (u32)(ts.levels - 1), reinterpret_cast<unsigned long long*>(base + off_ix), base + off_path};
-    int e = msrt::h2d(base, tgt, sizeof tgt, stream);
-    if (!e) e = msrt::h2d(base + off_ix, &none, 8, stream);
-    if (!e) e = msrt::h2d(base + off_pj, &pj, sizeof pj, stream);
-    if (!e) e = msrt::sync(stream);  // stack sources
-    typename mspoly::FindFirstKernel<F, EL>::Params fp; fp.jobs = nullptr;
-    fp.inline_job = FJ{ds.as<T>(), leaf_num, leaf_num, reinterpret_cast<const T*>(base), 1, reinterpret_cast<unsigned long long*>(base + off_ix)};
-    if (!e) e = run<mspoly::FindFirstKernel<F, EL>>(K_FIND_FIRST, grid1(leaf_num, mspoly::THREADS), 1, mspoly::THREADS, 0, fp);   // merkle.rs:216-225
-    typename msmerkle::PathKernel<F, EL>::Params pk{reinterpret_cast<const PJ*>(base + off_pj), 1};
-    if (!e) e = run<msmerkle::PathKernel<F, EL>>(K_PATH, 1, 1, 64, 0, pk);                                                          // merkle.rs:230-288
-    if (!e) e = msrt::d2h(pinned, base + off_ix, 8, stream);
-    if (!e) e = msrt::d2h(out, base + off_path, plen, stream);
-    if (!e) e = msrt::sync(stream);
-    if (e) rc = fail_rt(e, "merkle_prove");
-    else if (*reinterpret_cast<unsigned long long*>(pinned) == ~0ULL) rc = fail(MS_ERR_LEAF_NOT_FOUND, "leaf is not included in the tree");
-  }
-  msrt::sync(stream);
-  ds.release(); dn.release(); dw.release();
-  return rc;
+  auto idle = scope_exit([&] { msrt::sync(stream); });   // (before ds, dn and dw go: a launch may still read them on an early exit; the stack sources below likewise)
+  if (ds.ensure(leaf_num * EL * sizeof(T)) || dw.ensure(off_path + plen) || d_io.ensure(leaf_num * EL * 8)) return fail(MS_ERR_NOMEM, "merkle_prove");
+  CK(msrt::h2d(d_io.p, leafs, leaf_num * EL * 8, stream));
+  RQ(transpose_in(d_io.as<u64>(), ds.as<T>(), leaf_num, (size_t)EL, F::from_u64(1), 0, nullptr));
+  RQ(tree_build<EL>(ds.as<T>(), 0, 1, leaf_num, 1, ts, dn));
+  T tgt[EL]; for (int l = 0; l < EL; l++) tgt[l] = F::from_u64(leaf[l]);
+  unsigned long long none = ~0ULL;
+  u8* base = dw.as<u8>();
+  PJ pj{ds.as<T>(), leaf_num, dn.as<u32>(), leaf_num, (u32)lpn, 2, (u32)(ts.levels - 1), reinterpret_cast<unsigned long long*>(base + off_ix), base + off_path};
+  CK(msrt::h2d(base, tgt, sizeof tgt, stream));
+  CK(msrt::h2d(base + off_ix, &none, 8, stream));
+  CK(msrt::h2d(base + off_pj, &pj, sizeof pj, stream));
+  CK(msrt::sync(stream));  // stack sources
+  typename mspoly::FindFirstKernel<F, EL>::Params fp; fp.jobs = nullptr;
+  fp.inline_job = FJ{ds.as<T>(), leaf_num, leaf_num, reinterpret_cast<const T*>(base), 1, reinterpret_cast<unsigned long long*>(base + off_ix)};
+  CK(run<mspoly::FindFirstKernel<F, EL>>(K_FIND_FIRST, grid1(leaf_num, mspoly::THREADS), 1, mspoly::THREADS, 0, fp));   // merkle.rs:216-225
+  typename msmerkle::PathKernel<F, EL>::Params pk{reinterpret_cast<const PJ*>(base + off_pj), 1};
+  CK(run<msmerkle::PathKernel<F, EL>>(K_PATH, 1, 1, 64, 0, pk));                                                          // merkle.rs:230-288
+  CK(msrt::d2h(pinned.p, base + off_ix, 8, stream));
+  CK(msrt::d2h(out, base + off_path, plen, stream));
+  CK(msrt::sync(stream));
+  if (*pinned.as<unsigned long long>() == ~0ULL) return fail(MS_ERR_LEAF_NOT_FOUND, "leaf is not included in the tree");
+  return MS_OK;
 }
 
 template <class F>

@@ -14,8 +14,11 @@ bool Ctx<F>::sdma_ready() {
   if (!readback_sdma) return false;
   if (sdma_state == 0) {
     msrt::Sdma& S = msrt::Sdma::get();
-    if (!S.bind_device(device, &sdma_gpu)) sdma_state = (!S.signal_create(&sdma_sig) && !S.signal_create(&sdma_up_sig)) ? 1 : 2;
-    else if (S.unavailable()) sdma_state = 2;   // no HSA runtime to bind: this context stays on the HIP runtime's copies.  (Engines merely busy: asked again at the next copy.)
+    if (!S.bind_device(device, &sdma_gpu)) {
+      SdmaSignal down, upl;   // (the second cannot be made: the first goes too)
+      if (!down.create() && !upl.create()) { sdma_sig = std::move(down); sdma_up_sig = std::move(upl); sdma_state = 1; }
+      else sdma_state = 2;
+    } else if (S.unavailable()) sdma_state = 2;   // no HSA runtime to bind: this context stays on the HIP runtime's copies.  (Engines merely busy: asked again at the next copy.)
   }
   return sdma_state == 1;
 }
@@ -31,7 +34,7 @@ int Ctx<F>::poison(const char* what) {
 template <class F>
 int Ctx<F>::upload_wait(const char* what) {
   if (!up.pending) return 0;
-  const int wv = msrt::Sdma::get().wait(sdma_up_sig, sdma_timeout_s);
+  const int wv = msrt::Sdma::get().wait(sdma_up_sig.s, sdma_timeout_s);
   if (wv == 1) return poison(what);          // (up.pending stays set: the destructor waits for it)
   up.pending = false;
   if (wv < 0) { sdma_state = 2; return 1; }  // the engine reported a failed copy: no more engine copies on this context; the caller redoes this one
@@ -51,7 +54,7 @@ int Ctx<F>::trace_upload_async(const u64* trace, size_t N_, size_t w_) {
   msrt::Sdma& S = msrt::Sdma::get();
   const unsigned eng = S.h2d_engine(sdma_gpu);
   // (the buffer is free: the transposing kernel that read it ran two ms_trace_commit's ago, and every ms_trace_commit ends with a stream synchronisation)
-  if (!eng || S.copy_h2d(sdma_gpu, d_trace[slot].p, trace, N_ * w_ * 8, sdma_up_sig, eng)) return MS_OK;   // engine busy / copy refused: no prefetch
+  if (!eng || S.copy_h2d(sdma_gpu, d_trace[slot].p, trace, N_ * w_ * 8, sdma_up_sig.s, eng)) return MS_OK;   // engine busy / copy refused: no prefetch
   up.src = trace; up.N = N_; up.w = w_; up.slot = slot; up.pending = true;
   return MS_OK;
 }
@@ -78,7 +81,7 @@ int Ctx<F>::trace_to_device(const u64* trace, const u64** dsrc) {
     msrt::Sdma& S = msrt::Sdma::get();
     CK(msrt::sync(stream));                                           // (the buffer may still be read by an earlier proof's transposing kernel if that stage left on an error path)
     const unsigned eng = S.h2d_engine(sdma_gpu);
-    if (eng && !S.copy_h2d(sdma_gpu, d_trace[slot].p, trace, bytes, sdma_up_sig, eng)) {
+    if (eng && !S.copy_h2d(sdma_gpu, d_trace[slot].p, trace, bytes, sdma_up_sig.s, eng)) {
       up.pending = true;
       const int e = upload_wait("SDMA upload did not complete within the time limit");
       if (e < 0) return e;
@@ -117,16 +120,20 @@ int Ctx<F>::fri_proof_read_async(u8* out) {
   if (sdma_ready() && msrt::is_pinned_host(out)) {     // ms_fri_query ended with a stream synchronisation: the blob is complete, the copy needs no dependency (the synchronisation here returns at once)
     CK(msrt::sync(stream));
     msrt::Sdma& S = msrt::Sdma::get();
-    const int e = S.copy_d2h(sdma_gpu, out, d_blob.p, blob_size, sdma_sig, S.d2h_engine(sdma_gpu));
+    const int e = S.copy_d2h(sdma_gpu, out, d_blob.p, blob_size, sdma_sig.s, S.d2h_engine(sdma_gpu));
     if (!e) { sdma_pending = true; copy_pending = true; readback_dst = out; readback_bytes = blob_size; last_io_engine = 1; return MS_OK; }
     sdma_state = 2;       // refused (engine id / access / a runtime that does not know the buffers): this context stays on the runtime's copy from here on
   }
   last_io_engine = 0;
-  if (!copy_stream) { CK(msrt::stream_create(&copy_stream)); CK(msrt::event_create(&ev_blob)); CK(msrt::event_create(&ev_copy)); }
-  CK(msrt::event_record(ev_blob, stream));
-  CK(msrt::stream_wait_event(copy_stream, ev_blob));
-  CK(msrt::d2h(out, d_blob.p, blob_size, copy_stream));
-  CK(msrt::event_record(ev_copy, copy_stream));
+  if (!copy_stream) {
+    StreamOwner s; EventOwner blob, copy;
+    CK(make(s)); CK(make(blob)); CK(make(copy));
+    copy_stream = std::move(s); ev_blob = std::move(blob); ev_copy = std::move(copy);
+  }
+  CK(msrt::event_record(ev_blob.get(), stream));
+  CK(msrt::stream_wait_event(copy_stream.get(), ev_blob.get()));
+  CK(msrt::d2h(out, d_blob.p, blob_size, copy_stream.get()));
+  CK(msrt::event_record(ev_copy.get(), copy_stream.get()));
   copy_pending = true;
   return MS_OK;
 }
@@ -134,7 +141,7 @@ int Ctx<F>::fri_proof_read_async(u8* out) {
 template <class F>
 int Ctx<F>::fri_proof_wait() {
   if (sdma_pending) {
-    const int wv = msrt::Sdma::get().wait(sdma_sig, sdma_timeout_s);
+    const int wv = msrt::Sdma::get().wait(sdma_sig.s, sdma_timeout_s);
     if (wv == 1) return poison("SDMA read-back did not complete within the time limit");   // sdma_pending stays set: neither the blob nor the signal is reused
     sdma_pending = false; copy_pending = false;
     if (wv < 0) {   // the engine reported a FAILED copy (negative completion signal): `out` holds garbage or nothing - once more through the HIP runtime
@@ -144,7 +151,7 @@ int Ctx<F>::fri_proof_wait() {
     }
     return MS_OK;
   }
-  if (copy_pending) { CK(msrt::event_sync(ev_copy)); copy_pending = false; }
+  if (copy_pending) { CK(msrt::event_sync(ev_copy.get())); copy_pending = false; }
   return MS_OK;
 }
 

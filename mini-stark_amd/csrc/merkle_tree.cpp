@@ -229,19 +229,19 @@ int Ctx<F>::merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn
   if (!canonical(leafs, leaf_num * ext)) return fail(MS_ERR_ARG, "leaf not canonical");
   DevBuf dl, dn;
   if (dl.ensure(leaf_num * ext * sizeof(T))) return fail(MS_ERR_NOMEM, "leafs");
+  auto idle = scope_exit([&] { msrt::sync(stream); });   // (before dl and dn go, behind whatever the stage's guard enqueues)
   auto stage = res.expect();
-  int rc = upload_narrow(leafs, leaf_num * ext, dl.as<T>());
+  RQ(upload_narrow(leafs, leaf_num * ext, dl.as<T>()));
   // AoS view: element f limb k at base + f*ext + k
-  if (!rc) rc = (ext == 1) ? tree_build<1>(dl.as<T>(), 0, 1, 0, 1, ts, dn) : tree_build<E>(dl.as<T>(), 0, (size_t)ext, 1, 1, ts, dn);
-  if (!rc && nn) *nn = ts.nodes;
-  if (!rc && nodes_out) {
-    if (cap < ts.nodes) rc = fail(MS_ERR_ARG, "nodes_out too small");
-    else { int e = msrt::d2h(nodes_out, dn.p, ts.nodes * 32, stream); if (!e) e = msrt::sync(stream); if (e) rc = fail_rt(e, "nodes d2h"); }
+  RQ((ext == 1) ? tree_build<1>(dl.as<T>(), 0, 1, 0, 1, ts, dn) : tree_build<E>(dl.as<T>(), 0, (size_t)ext, 1, 1, ts, dn));
+  if (nn) *nn = ts.nodes;
+  if (nodes_out) {
+    if (cap < ts.nodes) return fail(MS_ERR_ARG, "nodes_out too small");
+    CK(msrt::d2h(nodes_out, dn.p, ts.nodes * 32, stream));
+    CK(msrt::sync(stream));
   }
-  if (!rc && root) rc = read_root(dn, ts, root);
-  msrt::sync(stream);
-  dl.release(); dn.release();
-  return rc;
+  if (root) RQ(read_root(dn, ts, root));
+  return MS_OK;
 }
 
 // ------------------------------------------------------------------ build-defined: proof-of-work grinding (include/ministark.h; kernel: grind.hpp)

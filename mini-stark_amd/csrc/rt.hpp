@@ -26,25 +26,38 @@ MS_HD uint64_t ms_mulhi64(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned
 #define MS_RESTRICT
 namespace msrt {
 struct Stream { int dummy; };
-inline int malloc_dev(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? 0 : 1; }
-inline int free_dev(void* p) { std::free(p); return 0; }
-inline int malloc_host(void** p, size_t n) { *p = std::malloc(n ? n : 1); return *p ? 0 : 1; }
+// What the emulated runtime has handed out and not yet taken back, and its failure hooks (tests: ms_emu_live, ms_emu_fail_device_alloc_after,
+// ms_emu_fail_handle_after in abi.cpp).  A hook armed at k makes the k-th call from now fail, once.
+struct EmuLive {
+  enum { DEV, HOST, STREAM, EVENT, SIGNAL, KINDS };
+  long live[KINDS] = {0, 0, 0, 0, 0};
+  long allocs = 0, fail_alloc_at = -1;     // device and page-locked allocations, counted together
+  long handles = 0, fail_handle_at = -1;   // streams, events and copy-engine signals, counted together
+  static EmuLive& get() { static EmuLive l; return l; }
+  static bool fails(long& count, long& at) { const long k = count++; if (at < 0 || k != at) return false; at = -1; return true; }
+  bool alloc_fails() { return fails(allocs, fail_alloc_at); }
+  bool handle_fails() { return fails(handles, fail_handle_at); }
+};
+inline int emu_malloc(void** p, size_t n, int kind) { EmuLive& l = EmuLive::get(); *p = l.alloc_fails() ? nullptr : std::malloc(n ? n : 1); if (!*p) return 1; l.live[kind]++; return 0; }
+inline int malloc_dev(void** p, size_t n) { return emu_malloc(p, n, EmuLive::DEV); }
+inline int free_dev(void* p) { std::free(p); EmuLive::get().live[EmuLive::DEV]--; return 0; }
+inline int malloc_host(void** p, size_t n) { return emu_malloc(p, n, EmuLive::HOST); }
 inline int malloc_host_coherent(void** p, size_t n) { return malloc_host(p, n); }
-inline int free_host(void* p) { std::free(p); return 0; }
+inline int free_host(void* p) { std::free(p); EmuLive::get().live[EmuLive::HOST]--; return 0; }
 inline int h2d(void* d, const void* h, size_t n, Stream*) { std::memcpy(d, h, n); return 0; }
 inline int d2h(void* h, const void* d, size_t n, Stream*) { std::memcpy(h, d, n); return 0; }
 inline int d2d(void* d, const void* s, size_t n, Stream*) { std::memmove(d, s, n); return 0; }
 inline int memset_dev(void* d, int v, size_t n, Stream*) { std::memset(d, v, n); return 0; }
 inline int sync(Stream*) { return 0; }
 inline int sync_flag(Stream*, const unsigned long long* f, unsigned long long v) { return *f == v ? 0 : 999; }   // emulated launches are synchronous: the flag is up or it never will be
-inline int stream_create(Stream** s) { *s = new Stream(); return 0; }
-inline int stream_destroy(Stream* s) { delete s; return 0; }
+inline int stream_create(Stream** s) { if (EmuLive::get().handle_fails()) return 1; *s = new Stream(); EmuLive::get().live[EmuLive::STREAM]++; return 0; }
+inline int stream_destroy(Stream* s) { delete s; EmuLive::get().live[EmuLive::STREAM]--; return 0; }
 inline int set_device(int) { return 0; }
 inline int cu_count(int, int* n) { *n = 4; return 0; }   // (a persistent grid sized by it stays small: every emulated thread is a fiber)
 inline const char* last_error_string() { return "emu"; }
 struct Event { int dummy; };
-inline int event_create(Event** e) { *e = new Event(); return 0; }
-inline int event_destroy(Event* e) { delete e; return 0; }
+inline int event_create(Event** e) { if (EmuLive::get().handle_fails()) return 1; *e = new Event(); EmuLive::get().live[EmuLive::EVENT]++; return 0; }
+inline int event_destroy(Event* e) { delete e; EmuLive::get().live[EmuLive::EVENT]--; return 0; }
 inline int event_record(Event*, Stream*) { return 0; }
 inline int event_elapsed_ms(float* ms, Event*, Event*) { *ms = 0.f; return 0; }
 inline int stream_wait_event(Stream*, Event*) { return 0; }
@@ -84,8 +97,8 @@ struct Sdma {
   static bool is(const char* m) { const char* e = mode(); return e && !std::strcmp(e, m); }
   int load() { return mode() ? 0 : 1; }
   int bind_device(int, int* g) { if (!mode()) return 1; *g = 0; return 0; }
-  int signal_create(Signal* s) { if (!mode()) return 1; s->handle = 1 + (nsig++ & 7); return 0; }
-  void signal_destroy(Signal) {}
+  int signal_create(Signal* s) { if (!mode() || EmuLive::get().handle_fails()) return 1; s->handle = 1 + (nsig++ & 7); EmuLive::get().live[EmuLive::SIGNAL]++; return 0; }
+  void signal_destroy(Signal s) { if (s.handle) EmuLive::get().live[EmuLive::SIGNAL]--; }
   int copy_d2h(int, void* d, const void* s_, size_t n, Signal sg, unsigned) {
     if (!mode()) return 1;
     if (is("hang")) { sig_val[sg.handle - 1] = 1; return 0; }

@@ -13,11 +13,10 @@ int Ctx<F>::profile_end(char* out, size_t cap) {
   double ms[K_COUNT] = {0}, by[K_COUNT] = {0}, ms_part = 0, ms_repl = 0, repl_by[K_COUNT] = {0}; unsigned long long cnt[K_COUNT] = {0};
   std::map<int, double> sub_ms, sub_by; std::map<int, unsigned long long> sub_cnt;
   for (auto& r : prof_recs) {
-    float t = 0.f; msrt::event_elapsed_ms(&t, r.a, r.b);
+    float t = 0.f; msrt::event_elapsed_ms(&t, r.a.get(), r.b.get());
     ms[r.kid] += t; by[r.kid] += r.bytes; cnt[r.kid]++;
     if (r.part) ms_part += t; else { ms_repl += t; repl_by[r.kid] += t; }
     if (r.kid == K_NTT_PASS) { sub_ms[r.sub] += t; sub_by[r.sub] += r.bytes; sub_cnt[r.sub]++; }
-    msrt::event_destroy(r.a); msrt::event_destroy(r.b);
   }
   prof_recs.clear(); prof_on = false;
   std::string j = "{";
@@ -47,14 +46,8 @@ int Ctx<F>::profile_end(char* out, size_t cap) {
 template <class F>
 int Ctx<F>::tabs_host(size_t bytes, u8** out) {
   CK(msrt::sync(stream));                         // an upload out of the area may still be in flight if the stage that issued it left on an error path; free otherwise: the stream is idle here
-  if (bytes > h_tabs_cap) {
-    if (h_tabs) msrt::free_host(h_tabs);
-    h_tabs = nullptr; h_tabs_cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (msrt::malloc_host(&h_tabs, want)) { h_tabs = nullptr; return fail(MS_ERR_NOMEM, "page-locked table staging"); }
-    h_tabs_cap = want;
-  }
-  *out = reinterpret_cast<u8*>(h_tabs);
+  if (bytes > h_tabs.cap && h_tabs.alloc(bytes + bytes / 4 + 4096)) return fail(MS_ERR_NOMEM, "page-locked table staging");
+  *out = h_tabs.as<u8>();
   return 0;
 }
 
@@ -88,8 +81,7 @@ int Ctx<F>::ensure_polys(size_t count) {
   // what is live moves along: the polynomials, or - between ms_trace_commit and ms_interpolate - the trace columns and the running columns behind them
   const size_t live = have_polys ? (size_t)npolys : (have_trace ? w + (size_t)naux : 0);
   if (d_polys.p && live > 0) { CK(msrt::d2d(nb.p, d_polys.p, live * N * sizeof(T), stream)); CK(msrt::sync(stream)); }
-  d_polys.release();
-  d_polys = nb; polys_cap = ncap;
+  d_polys = std::move(nb); polys_cap = ncap;
   return 0;
 }
 
@@ -136,10 +128,10 @@ int Ctx<F>::init(int dev, u32 flags) {
   if (const char* e = getenv("MS_SHARD_SLICE_MIN")) { long v = atol(e); if (v >= 1) shard_slice_min = (size_t)v; }
   if (const char* e = getenv("MS_RCCL_MAX_PIECE")) { long long v = atoll(e); if (v >= 64 && v <= ((long long)1 << 30)) rccl_max_piece = (size_t)v & ~(size_t)63; }
   CK(msrt::set_device(dev));
-  CK(msrt::stream_create(&own_stream));
-  stream = own_stream;
+  CK(make(own_stream));
+  stream = own_stream.get();
   pinned_cap = 1 << 16;
-  CK(msrt::malloc_host_coherent(&pinned, pinned_cap + Results::SLOT_BYTES));   // (+ the slots of the stage results: polled sequence number, word, root)
+  CK(pinned.alloc(pinned_cap + Results::SLOT_BYTES, true));   // (+ the slots of the stage results: polled sequence number, word, root)
   *res.seq_slot() = 0;
   if (d_small.ensure(4096) || res.words.ensure(Results::WORD_BYTES)) return fail(MS_ERR_NOMEM, "small");
   CK(msrt::memset_dev(res.words.p, 0, Results::WORD_BYTES, stream));
@@ -376,20 +368,18 @@ int Ctx<F>::arith_selftest(int op_word, const u64* a, const u64* b, u64* out, si
   if (op != 12 && (!canonical(a, n) || ((op < 6 || op == 15 || op >= 32) && !canonical(b, n)))) return fail(MS_ERR_ARG, "operand not canonical");
   DevBuf d;
   if (d.ensure(3 * n * 8)) return fail(MS_ERR_NOMEM, "arith_selftest");
-  int e = msrt::h2d(d.p, a, n * 8, stream);
-  if (!e) e = msrt::h2d(d.as<u64>() + n, b, n * 8, stream);
-  if (!e) e = msrt::sync(stream);
-  if (!e) {
-    if constexpr (F::ID == 0) {
-      if (cls == 1) e = arith_launch<GL>(op, d.as<u64>(), n);
-      else if (cls == 2) e = arith_launch<GLT>(op, d.as<u64>(), n);
-      else e = arith_launch<GLM>(op, d.as<u64>(), n);
-    } else e = arith_launch<F>(op, d.as<u64>(), n);
-  }
-  if (!e) e = msrt::d2h(out, d.as<u64>() + 2 * n, n * 8, stream);
-  if (!e) e = msrt::sync(stream);
-  d.release();
-  return e ? fail_rt(e, "arith_selftest") : MS_OK;
+  auto idle = scope_exit([&] { msrt::sync(stream); });   // (before d goes: a launch may still read it on an early exit)
+  CK(msrt::h2d(d.p, a, n * 8, stream));
+  CK(msrt::h2d(d.as<u64>() + n, b, n * 8, stream));
+  CK(msrt::sync(stream));
+  if constexpr (F::ID == 0) {
+    if (cls == 1) CK(arith_launch<GL>(op, d.as<u64>(), n));
+    else if (cls == 2) CK(arith_launch<GLT>(op, d.as<u64>(), n));
+    else CK(arith_launch<GLM>(op, d.as<u64>(), n));
+  } else CK(arith_launch<F>(op, d.as<u64>(), n));
+  CK(msrt::d2h(out, d.as<u64>() + 2 * n, n * 8, stream));
+  CK(msrt::sync(stream));
+  return MS_OK;
 }
 
 template <class F> template <class A>

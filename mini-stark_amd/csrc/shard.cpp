@@ -69,22 +69,23 @@ int Ctx<F>::exchange_slice(size_t off, size_t stride, size_t bytes, int sl, int 
   xstat[4] += bytes * (size_t)(sh_world - 1);
   if (rccl_comm) {
     msrt::Rccl& R = msrt::Rccl::get();
-    if (!comm_stream) CK(msrt::stream_create(&comm_stream));
-    while ((int)ev_hash.size() < S) { msrt::Event* a; msrt::Event* b; CK(msrt::event_create(&a)); CK(msrt::event_create(&b)); ev_hash.push_back(a); ev_xchg.push_back(b); }
-    CK(msrt::event_record(ev_hash[sl], stream));                 // slice hashed (incl. its deferred pad-only blocks)
-    CK(msrt::stream_wait_event(comm_stream, ev_hash[sl]));
+    if (!comm_stream) CK(make(comm_stream));
+    while ((int)ev_slice.size() < S) { SliceEvents ev; CK(make(ev.hashed)); CK(make(ev.exchanged)); ev_slice.push_back(std::move(ev)); }
+    msrt::Stream* const cs = comm_stream.get();
+    CK(msrt::event_record(ev_slice[sl].hashed.get(), stream));                 // slice hashed (incl. its deferred pad-only blocks)
+    CK(msrt::stream_wait_event(cs, ev_slice[sl].hashed.get()));
     int e = R.group_start();
     for (int r = 0; r < sh_world && !e; r++)
       for (size_t o = 0; o < bytes && !e; o += rccl_max_piece) {   // (pieces: see exchange)
         const size_t len = bytes - o < rccl_max_piece ? bytes - o : rccl_max_piece;
-        e = R.send(xs + off + (size_t)r * stride + o, len, 1 /* ncclUint8 */, r, rccl_comm, comm_stream);
-        if (!e) e = R.recv(xr + off + (size_t)r * stride + o, len, 1, r, rccl_comm, comm_stream);
+        e = R.send(xs + off + (size_t)r * stride + o, len, 1 /* ncclUint8 */, r, rccl_comm, cs);
+        if (!e) e = R.recv(xr + off + (size_t)r * stride + o, len, 1, r, rccl_comm, cs);
       }
     const int e2 = R.group_end();
     if (!e) e = e2;
     if (e) { err = std::string("RCCL error ") + std::to_string(e) + (R.err_string ? std::string(": ") + R.err_string(e) : std::string()); return MS_ERR_HIP; }
-    CK(msrt::event_record(ev_xchg[sl], comm_stream));
-    if (sl == S - 1) CK(msrt::stream_wait_event(stream, ev_xchg[sl]));   // the communication stream runs in order: the last slice's event covers all of them
+    CK(msrt::event_record(ev_slice[sl].exchanged.get(), cs));
+    if (sl == S - 1) CK(msrt::stream_wait_event(stream, ev_slice[sl].exchanged.get()));   // the communication stream runs in order: the last slice's event covers all of them
     return 0;
   }
   if (!xfn) { for (int r = 0; r < sh_world; r++) CK(msrt::d2d(xr + off + (size_t)r * stride, xs + off + (size_t)r * stride, bytes, stream)); return 0; }   // (stub world: see exchange)
@@ -96,7 +97,7 @@ int Ctx<F>::exchange_slice(size_t off, size_t stride, size_t bytes, int sl, int 
 
 template <class F>
 void Ctx<F>::drop_rccl() {
-  if (rccl_comm) { msrt::sync(stream); if (comm_stream) msrt::sync(comm_stream); msrt::Rccl::get().comm_destroy(rccl_comm); rccl_comm = nullptr; }   // (work may be queued on either stream)
+  if (rccl_comm) { msrt::sync(stream); if (comm_stream) msrt::sync(comm_stream.get()); msrt::Rccl::get().comm_destroy(rccl_comm); rccl_comm = nullptr; }   // (work may be queued on either stream)
   rccl_send.release(); rccl_recv.release();
 }
 
@@ -135,55 +136,46 @@ int Ctx<F>::rccl_selftest() {
   int e = R.comm_init_rank(&comm, 1, id, 0);
   if (e || !comm) return fail(MS_ERR_HIP, "ncclCommInitRank(1 rank) failed");
   DevBuf a, b;
-  int rc = MS_OK;
-  if (a.ensure(4096) || b.ensure(4096)) rc = fail(MS_ERR_NOMEM, "selftest buffers");
+  StreamOwner cs; EventOwner e1, e2;
+  // every way out, before buffers, stream and events go: both streams idle, then the communicator
+  auto done = scope_exit([&] { msrt::sync(stream); if (cs) msrt::sync(cs.get()); R.comm_destroy(comm); });
+  if (a.ensure(4096) || b.ensure(4096)) return fail(MS_ERR_NOMEM, "selftest buffers");
   u64 h[64], g[64];
   for (int i = 0; i < 64; i++) h[i] = 0x0123456789ABCDEFull * (u64)(i + 1);
-  if (!rc && (msrt::h2d(a.p, h, sizeof h, stream) || msrt::memset_dev(b.p, 0, 4096, stream))) rc = fail(MS_ERR_HIP, "selftest upload");
-  if (!rc) {
-    e = R.group_start();
-    if (!e) e = R.send(a.p, 256, 1, 0, comm, stream);
-    if (!e) e = R.recv(b.p, 256, 1, 0, comm, stream);
-    const int e2 = R.group_end(); if (!e) e = e2;
-    if (!e) e = R.all_gather(a.as<u8>() + 256, b.as<u8>() + 256, 128, 1, comm, stream);
-    if (!e) e = R.all_reduce(a.p, a.p, 8, 5, 3, comm, stream);        // MIN over one rank: unchanged
-    if (!e) e = R.all_reduce(a.p, a.p, 64, 1, 0, comm, stream);       // SUM over one rank: unchanged
-    if (e) rc = fail(MS_ERR_HIP, "RCCL collective failed in the self test");
-  }
-  if (!rc && (msrt::d2h(g, b.p, sizeof g, stream) || msrt::sync(stream))) rc = fail(MS_ERR_HIP, "selftest download");
-  if (!rc) for (int i = 0; i < 48; i++) if (g[i] != h[i]) { rc = fail(MS_ERR_HIP, "RCCL self test: payload mismatch"); break; }
+  if (msrt::h2d(a.p, h, sizeof h, stream) || msrt::memset_dev(b.p, 0, 4096, stream)) return fail(MS_ERR_HIP, "selftest upload");
+  e = R.group_start();
+  if (!e) e = R.send(a.p, 256, 1, 0, comm, stream);
+  if (!e) e = R.recv(b.p, 256, 1, 0, comm, stream);
+  { const int e2 = R.group_end(); if (!e) e = e2; }
+  if (!e) e = R.all_gather(a.as<u8>() + 256, b.as<u8>() + 256, 128, 1, comm, stream);
+  if (!e) e = R.all_reduce(a.p, a.p, 8, 5, 3, comm, stream);        // MIN over one rank: unchanged
+  if (!e) e = R.all_reduce(a.p, a.p, 64, 1, 0, comm, stream);       // SUM over one rank: unchanged
+  if (e) return fail(MS_ERR_HIP, "RCCL collective failed in the self test");
+  if (msrt::d2h(g, b.p, sizeof g, stream) || msrt::sync(stream)) return fail(MS_ERR_HIP, "selftest download");
+  for (int i = 0; i < 48; i++) if (g[i] != h[i]) return fail(MS_ERR_HIP, "RCCL self test: payload mismatch");
   // the choreography of a sliced digest exchange (exchange_slice): payload produced on the prover's stream, grouped send / recv on a SECOND stream behind an
   // event, the prover's stream waiting for the exchange's event before it reads the result
-  if (!rc) {
-    msrt::Stream* cs = nullptr; msrt::Event* e1 = nullptr; msrt::Event* e2 = nullptr;
-    u64 h2[32], g2[32];
-    for (int i = 0; i < 32; i++) h2[i] = 0xA5A5A5A5DEADBEEFull + (u64)i * 0x1000193ull;
-    int er = msrt::stream_create(&cs) || msrt::event_create(&e1) || msrt::event_create(&e2);
-    if (!er) er = msrt::h2d(a.as<u8>() + 1024, h2, sizeof h2, stream) || msrt::memset_dev(b.as<u8>() + 1024, 0, sizeof h2, stream);
-    if (!er) er = msrt::event_record(e1, stream) || msrt::stream_wait_event(cs, e1);
-    if (!er) {
-      e = R.group_start();
-      if (!e) e = R.send(a.as<u8>() + 1024, 128, 1, 0, comm, cs);
-      if (!e) e = R.recv(b.as<u8>() + 1024, 128, 1, 0, comm, cs);
-      if (!e) e = R.send(a.as<u8>() + 1024 + 128, 128, 1, 0, comm, cs);     // a second, strided piece in the same group, as a slice of several peers' chunks would be
-      if (!e) e = R.recv(b.as<u8>() + 1024 + 128, 128, 1, 0, comm, cs);
-      const int e3 = R.group_end(); if (!e) e = e3;
-      er = e;
-    }
-    if (!er) er = msrt::event_record(e2, cs) || msrt::stream_wait_event(stream, e2);
-    if (!er) er = msrt::d2h(g2, b.as<u8>() + 1024, sizeof g2, stream) || msrt::sync(stream);
-    if (er) rc = fail(MS_ERR_HIP, "RCCL self test: exchange on the communication stream failed");
-    else for (int i = 0; i < 32; i++) if (g2[i] != h2[i]) { rc = fail(MS_ERR_HIP, "RCCL self test: payload mismatch on the communication stream"); break; }
-    if (cs) { msrt::sync(cs); msrt::stream_destroy(cs); }
-    if (e1) msrt::event_destroy(e1);
-    if (e2) msrt::event_destroy(e2);
+  u64 h2[32], g2[32];
+  for (int i = 0; i < 32; i++) h2[i] = 0xA5A5A5A5DEADBEEFull + (u64)i * 0x1000193ull;
+  int er = make(cs) || make(e1) || make(e2);
+  if (!er) er = msrt::h2d(a.as<u8>() + 1024, h2, sizeof h2, stream) || msrt::memset_dev(b.as<u8>() + 1024, 0, sizeof h2, stream);
+  if (!er) er = msrt::event_record(e1.get(), stream) || msrt::stream_wait_event(cs.get(), e1.get());
+  if (!er) {
+    e = R.group_start();
+    if (!e) e = R.send(a.as<u8>() + 1024, 128, 1, 0, comm, cs.get());
+    if (!e) e = R.recv(b.as<u8>() + 1024, 128, 1, 0, comm, cs.get());
+    if (!e) e = R.send(a.as<u8>() + 1024 + 128, 128, 1, 0, comm, cs.get());     // a second, strided piece in the same group, as a slice of several peers' chunks would be
+    if (!e) e = R.recv(b.as<u8>() + 1024 + 128, 128, 1, 0, comm, cs.get());
+    const int e3 = R.group_end(); if (!e) e = e3;
+    er = e;
   }
-  if (!rc && (msrt::d2h(g, a.p, sizeof g, stream) || msrt::sync(stream))) rc = fail(MS_ERR_HIP, "selftest download");
-  if (!rc) for (int i = 0; i < 64; i++) if (g[i] != h[i]) { rc = fail(MS_ERR_HIP, "RCCL self test: all-reduce changed a one-rank payload"); break; }
-  msrt::sync(stream);
-  R.comm_destroy(comm);
-  a.release(); b.release();
-  return rc;
+  if (!er) er = msrt::event_record(e2.get(), cs.get()) || msrt::stream_wait_event(stream, e2.get());
+  if (!er) er = msrt::d2h(g2, b.as<u8>() + 1024, sizeof g2, stream) || msrt::sync(stream);
+  if (er) return fail(MS_ERR_HIP, "RCCL self test: exchange on the communication stream failed");
+  for (int i = 0; i < 32; i++) if (g2[i] != h2[i]) return fail(MS_ERR_HIP, "RCCL self test: payload mismatch on the communication stream");
+  if (msrt::d2h(g, a.p, sizeof g, stream) || msrt::sync(stream)) return fail(MS_ERR_HIP, "selftest download");
+  for (int i = 0; i < 64; i++) if (g[i] != h[i]) return fail(MS_ERR_HIP, "RCCL self test: all-reduce changed a one-rank payload");
+  return MS_OK;
 }
 
 template <class F>

@@ -318,59 +318,14 @@ def test_c_abi_never_unwinds(field, flags):
     """SURVEY 8(b) "never unwind" (VERDICT r3 #5): every entry point of libministark runs inside a guard that turns std::bad_alloc into MS_ERR_NOMEM (anything else
     into MS_ERR_HIP).  The emulation build's operator new (hidden: this library's allocations only) can be armed to fail on its N-th call: a whole proof is driven
     with the failure placed at EVERY allocation it makes, one after the other - the stage that hits it must return a negative code (never abort the process, never
-    unwind into ctypes), the stages before it succeed, and after EVERY injected failure the same context proves once more with outputs identical to a clean run's (r05)."""
+    unwind into ctypes), the stages before it succeed, and after EVERY injected failure the same context proves once more with outputs identical to a clean run's (r05).
+    The failures leave no resource behind either: the emulated runtime counts what it has handed out (ms_emu_live) - the same after every failure plus recovery proof
+    as after a clean proof, and after ms_destroy what it was before ms_create, for the clean context, for a refused ms_create and for the context of the whole sweep."""
     import ctypes as C
-    import numpy as np
-    from common import MODULUS, EXT, SplitMix64, fibonacci_trace, fibonacci_closures
-    from oracle import oracle as orc
-    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu")], stdout=subprocess.DEVNULL)
-    L = C.CDLL(EMU)
-    L.ms_emu_alloc_count.restype = C.c_long
-    L.ms_emu_fail_alloc_after.argtypes = [C.c_long]
-    p, e = MODULUS[field], EXT[field]
-    N, blowup = 16, 4
-    trace = fibonacci_trace(field, N)
-    omega = orc.root_of_unity(field, N)
-    rounds = 6
-    u64p = C.POINTER(C.c_uint64)
-
-    def stages(h, outs=None):
-        """the reference's prove sequence as raw C calls: yields (name, rc); `outs` (a list) collects every output of the proof"""
-        rng = SplitMix64(5)
-        root = (C.c_uint8 * 32)()
-        t = np.ascontiguousarray(trace)
-
-        def keep(*vals):
-            if outs is not None:
-                outs.extend(bytes(v) for v in vals)
-        yield "trace_commit", L.ms_trace_commit(h, t.ctypes.data_as(u64p), C.c_size_t(N), C.c_size_t(3), C.c_size_t(6), root)
-        keep(root)
-        yield "interpolate", L.ms_interpolate(h)
-        for sc, idx in fibonacci_closures(field, N, omega):
-            yield "polys_lincomb", L.ms_polys_lincomb(h, (C.c_uint64 * len(sc))(*sc), (C.c_int * len(idx))(*idx), len(sc))
-        yield "lde_commit", L.ms_lde_commit(h, C.c_size_t(blowup), C.c_uint64(rng.nonzero(p)), C.c_size_t(6), root)
-        keep(root)
-        yield "mix", L.ms_mix(h, C.c_uint64(rng.field(p)))
-        out = (C.c_uint64 * (7 * e))()
-        yield "eval_ext", L.ms_eval_ext(h, (C.c_uint64 * e)(*[rng.field(p) for _ in range(e)]), 1, out)
-        keep(out)
-        yield "fri_begin", L.ms_fri_begin(h, C.c_size_t(blowup), C.c_size_t(rounds), root)
-        keep(root)
-        B = (C.c_uint64 * (2 * e))()
-        for _ in range(1, rounds):
-            yield "fri_deep", L.ms_fri_deep(h, (C.c_uint64 * e)(*[rng.field(p) for _ in range(e)]), B)
-            yield "fri_fold_commit", L.ms_fri_fold_commit(h, (C.c_uint64 * e)(*[rng.field(p) for _ in range(e)]), root)
-            keep(B, root)
-        yield "fri_query", L.ms_fri_query(h, (C.c_uint64 * 2)(3, 77), 2)
-        if outs is not None:
-            L.ms_fri_proof_size.restype = C.c_size_t
-            L.ms_fri_proof_size.argtypes = [C.c_void_p]
-            blob = (C.c_uint8 * L.ms_fri_proof_size(h))()
-            yield "fri_proof_read", L.ms_fri_proof_read(h, blob)
-            keep(blob)
-        yield "ntt", L.ms_ntt(h, (C.c_uint64 * 64)(*range(64)), C.c_size_t(64), C.c_size_t(1), 0)
-        yield "merkle_commit", L.ms_merkle_commit(h, (C.c_uint64 * 16)(*range(16)), C.c_size_t(16), 1, C.c_size_t(2), C.c_size_t(2), None, C.c_size_t(0), None, root)
-        keep(root)
+    import ownership_cases as oc
+    L = oc.load()
+    stages = lambda h, outs=None: oc.stages(L, h, field, outs)
+    base = oc.live(L)
 
     # ms_create itself under allocation failure: a negative code, no context
     for k in range(6):
@@ -383,13 +338,20 @@ def test_c_abi_never_unwinds(field, flags):
             L.ms_destroy(h)
         else:
             assert not h.value
+        assert oc.live(L) == base, (k, rc)
     h = C.c_void_p()
     assert L.ms_create(C.byref(h), 0, field, flags) == 0
     want = []
     assert all(rc == 0 for _, rc in stages(h, want))   # (the first proof also builds the NTT plans, which later proofs reuse)
+    L.ms_destroy(h)
+    assert oc.live(L) == base                          # one clean proof, then destroy: nothing is left
+    assert L.ms_create(C.byref(h), 0, field, flags) == 0
+    got = []
+    assert all(rc == 0 for _, rc in stages(h, got)) and got == want
     n0 = L.ms_emu_alloc_count()
     assert all(rc == 0 for _, rc in stages(h))
     total = L.ms_emu_alloc_count() - n0
+    steady = oc.live(L)                                # what a context that has proved holds
     assert total > 50            # the job tables, plans and error texts do allocate: the guard has something to catch
     hit = 0
     step = 1 if field == 0 else 3          # every allocation of the Goldilocks proof; every third of the BabyBear one (same code paths, twice the extension limbs)
@@ -397,24 +359,21 @@ def test_c_abi_never_unwinds(field, flags):
     for k in range(0, total + 3, step):
         tried += k < total
         L.ms_emu_fail_alloc_after(k)
-        failed = None
-        for name, rc in stages(h):
-            if rc != 0:
-                failed = (name, rc)
-                break
+        failed = oc.first_failure(stages(h))
         L.ms_emu_fail_alloc_after(-1)
         if failed is not None:
             hit += 1
             assert failed[1] in (ms.ERR_NOMEM, ms.ERR_HIP), (k, failed)
-            L.ms_last_error.restype = C.c_char_p
             assert L.ms_last_error(h)            # readable, no allocation needed
             # a failure caught by the guard must leave no state behind (pending words of the next tree launch, a swapped knob, a half-counted scope) -
             # the SAME context proves again, and every output of that proof is the clean run's
             got = []
             assert all(rc == 0 for _, rc in stages(h, got)), (k, failed)
             assert got == want, (k, failed, "a proof on the same context after the injected failure differs")
+            assert oc.live(L) == steady, (k, failed, "the failed call left a buffer, stream or event behind")
     assert hit == tried, (hit, tried, total)   # every single allocation of a proof, when it fails, surfaces as a negative status of the stage that made it
     L.ms_destroy(h)
+    assert oc.live(L) == base
     # after all that the library still proves: same bytes as the oracle
     pc.case_prove(lambda f, fresh=False: ms.Context(f, lib_path=EMU), field, 4, 4, read_big=False)
 
