@@ -30,12 +30,10 @@ def case_flag_selects_blake2s(make):
 
 
 def _special_leafs(field, n, seed):
-    """random canonical values with zeros, small values, p - 1 and every digit-count boundary sprinkled in (parity_cases.case_merkle)"""
-    p = MODULUS[field]
+    """random canonical values with the directed values of parity_cases.directed_values (zeros, small values, p - 1, every digit-count boundary, the chunk
+    fix-up grid) sprinkled in"""
     leafs = pc.rand_field(field, (n,), seed=seed)
-    vals = [0, 1, p - 1, 2**32 % p, 12345678901234567890 % p, 0, 0, 1000100010001 % p, 10203040506070809 % p]
-    vals += [v % p for k in range(1, 20) for v in (10**k - 1, 10**k, 10**k + 1, 7 * 10**k)]
-    for i, v in enumerate(vals):
+    for i, v in enumerate(pc.directed_values(field)):
         leafs[(i * 5) % n] = v
     return leafs
 

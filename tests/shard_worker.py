@@ -40,6 +40,9 @@ if "low-degree" in modes:   # trace columns of degree N/2 + 2: the validity poly
         coef[: N // 2 + 3] = pc.rand_field(field, (N // 2 + 3,), seed=40 + c)
         cols.append(orc.ntt(field, coef))
     trace = np.ascontiguousarray(np.stack(cols, axis=1))
+if "directed" in modes:   # zeros, short texts, digit-count boundaries and the chunk fix-up values in every column (tests/view_cases.py)
+    import view_cases as vc
+    trace = vc.directed_matrix(field, N, 3, seed=9)
 if log_n >= 16:  # full-size comparisons: OpenMP over the oracle's independent loops (every rank runs its own oracle)
     orc.set_threads(max(1, min(8, len(os.sched_getaffinity(0)) // grp.world)))
 root_only = "root-only" in modes        # ms_shard_proof_on_root: only rank 0 ends up with the FRI proof
