@@ -47,6 +47,31 @@ extern "C" void ms_emu_live(long out[7]) {
 }
 extern "C" void ms_emu_fail_device_alloc_after(long n) { msrt::EmuLive& l = msrt::EmuLive::get(); l.fail_alloc_at = n < 0 ? -1 : l.allocs + n; }
 extern "C" void ms_emu_fail_handle_after(long n) { msrt::EmuLive& l = msrt::EmuLive::get(); l.fail_handle_at = n < 0 ? -1 : l.handles + n; }
+// ---- the NTT plan this context would build for 2^log_n points whose input is zero beyond n >> log_pad, as JSON: the shape and the kernel instance of every pass; for a
+// pass with a shared-table alternative also which of the two a call with `batch` transforms launches.  The shape only (Ctx::plan_shape): no table, nothing on the device
+template <class F> static int emu_ntt_plan(Ctx<F>* c, int log_n, int log_pad, bool inverse, size_t batch, char* out, size_t cap) {
+  if (log_n < 1 || log_pad < 0 || log_pad > msntt::MAX_LOG_PAD || !out || !cap) return c->fail(MS_ERR_ARG, "ms_emu_ntt_plan");
+  typename Ctx<F>::Plan pl;
+  RQ(c->plan_shape(log_n, log_pad, inverse, &pl));
+  char buf[400];
+  snprintf(buf, sizeof buf, "{\"log_r0\": %d, \"log_rho\": %d, \"passes\": [", pl.log_r0, pl.log_rho);
+  std::string j = buf;
+  for (int k = 0; k < pl.npass; k++) {
+    const auto& ps = pl.pass[k];
+    snprintf(buf, sizeof buf, "%s{\"K\": %d, \"LC\": %d, \"instance\": \"%s\"", k ? ", " : "", ps.K, ps.LC, ps.inst.name);
+    j += buf;
+    if (ps.shared) { snprintf(buf, sizeof buf, ", \"shared\": \"%s\", \"launches\": \"%s\"", ps.shared.name, c->pick(pl, k, batch).name); j += buf; }
+    j += "}";
+  }
+  j += "]}";
+  if (j.size() + 1 > cap) return c->fail(MS_ERR_ARG, "ms_emu_ntt_plan: buffer too small");
+  memcpy(out, j.c_str(), j.size() + 1);
+  return MS_OK;
+}
+extern "C" int ms_emu_ntt_plan(ms_ctx* ctx, int log_n, int log_pad, int inverse, size_t batch, char* out, size_t cap) {
+  if (auto* g = dynamic_cast<Ctx<GL>*>(B(ctx))) MS_ENTRY(ctx, emu_ntt_plan(g, log_n, log_pad, inverse != 0, batch, out, cap));
+  MS_ENTRY(ctx, emu_ntt_plan(dynamic_cast<Ctx<BB>*>(B(ctx)), log_n, log_pad, inverse != 0, batch, out, cap));
+}
 #endif
 
 extern "C" {

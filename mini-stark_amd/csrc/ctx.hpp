@@ -5,7 +5,7 @@
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
 //   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels)
 //                    one host pipeline, a compose kernel each), DEEP-ALI evaluations
-//   ntt_plan.cpp     NTT plans and pass dispatch, coset evaluation, ms_ntt / ms_coset_lde                           (every NTT pass instance)
+//   ntt_plan.cpp     NTT plans (shape, instances, tables), coset evaluation, ms_ntt / ms_coset_lde                        (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
 //   fri_query.cpp    FRI query phase, proof read-back, ms_merkle_prove                                              (find-first, path, copy kernels)
@@ -245,14 +245,11 @@ template <class F> struct Ctx : CtxBase {
   double next_bytes = 0;  // algorithmic bytes attributed to the next launch
   int next_sub = 0;       // NTT pass template instance of the next launch: index into ntt_names (the kernel names rocprofv3 reports)
   std::vector<std::string> ntt_names{std::string("?")};
-  void name_next(const char* fmt, ...) __attribute__((format(printf, 2, 3))) {
+  void name_next(const char* name) {
     if (!prof_on) return;
-    char buf[200]; va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    for (size_t i = 0; i < ntt_names.size(); i++) if (ntt_names[i] == buf) { next_sub = (int)i; return; }
-    ntt_names.push_back(buf); next_sub = (int)ntt_names.size() - 1;
+    for (size_t i = 0; i < ntt_names.size(); i++) if (ntt_names[i] == name) { next_sub = (int)i; return; }
+    ntt_names.push_back(name); next_sub = (int)ntt_names.size() - 1;
   }
-  static const char* fname() { return F::ID == 0 ? "GL" : "BB"; }
-  template <class A> static const char* aname() { return std::is_same<A, GLM>::value ? "GLM" : (std::is_same<A, GLT>::value ? "GLT" : (std::is_same<A, GL>::value ? "GL" : "BB")); }
   // ------------------------------------------------------------------ stage results: ONE owner of what a stage brings home
   // Every stage that ends in a host round trip brings home a Merkle root, one 8-byte device word, or just the news that it is done.  The stage's LAST launch stores
   // them in page-locked memory (the host_root / aux_src -> aux_dst / flag fields of its Params) and, under MS_FLAG_LATENCY, raises a sequence number behind them
@@ -350,14 +347,35 @@ template <class F> struct Ctx : CtxBase {
   int profile_end(char* out, size_t cap) override;
 
   // ------------------------------------------------------------------ NTT plans
+  // A transform is decided ONCE, when its plan is built: the shape (passes, tile rows and columns, the virtual pass) and the kernel instance of every pass
+  typedef msntt::PassParams<F> PassParams;
+  // One instantiated pass kernel of ntt.hpp (ntt_plan.cpp, pass_instance: the one map from a pass's shape to its instance).  Empty: there is no such instance
+  struct Instance {
+    char name[96] = "";                                    // the kernel name a profiler reports, from the instance's own constants: the key of the profile's ntt_pass_variants
+    bool coop = false; int per_cu = 0;                     // grid: cooperative -> coop_grid(tiles * batch, per_cu) x 1; else own_grid(pp) x batch where set (register pass), tiles x batch
+    unsigned (*own_grid)(const PassParams&) = nullptr; bool (*applicable)(const PassParams&) = nullptr;   // applicable: the kernel's own precondition
+    int (*launch)(Ctx&, unsigned gx, unsigned gy, const PassParams&) = nullptr;   // run / run_coop of the instance, with its threads and LDS bytes
+    explicit operator bool() const { return launch != nullptr; }
+  };
+  enum Gen { GEN_TILE, GEN_FAST, GEN_COOP, GEN_REG };   // generic round-1 tiles (PassKernel) | compile-time specialised ones (PassKernelK) | PassKernel2 | RegPassKernel (last pass, radix <= 32, registers only)
+  static Instance pass_instance(Gen gen, bool inverse, int K, int log_C, int mode);
+  struct Pass {
+    int K = 0, LC = msntt::TILE_LOG_C; Gen gen = GEN_TILE;   // log2 tile rows and tile columns; the kernel generation
+    int log_Rp = 0, log_C = 0;           // log2 of the points done before the pass; the columns its tiles really have (LC, or all that is left outside the rows)
+    Instance inst, shared;               // shared: the shared-table instance (MODE 3) a first pass behind the virtual pass may run as instead (pick)
+    DevBuf w_r;
+  };
   struct Plan {
-    int log_n = 0, log_r0 = 0, log_rho = 0, npass = 0, K[4] = {0, 0, 0, 0}, lo_bits = 0;
-    int LC[4] = {msntt::TILE_LOG_C, msntt::TILE_LOG_C, msntt::TILE_LOG_C, msntt::TILE_LOG_C};   // log2 tile columns of every pass
-    bool v2[4] = {false, false, false, false};                                                   // pass runs on msntt::PassKernel2
-    bool regp[4] = {false, false, false, false};                                                 // pass runs on msntt::RegPassKernel (last pass, radix <= 32, registers only)
-    DevBuf tw_lo, tw_hi, w_r[4], vtw, w0;
-    T n_inv = 0;
-    T root = 0;   // w_n the tables hold the powers of (host copy: the FRI fold's octet table is derived from it)
+    int log_n = 0, log_pad = 0, log_r0 = 0, log_rho = 0, npass = 0, lo_bits = 0;
+    static constexpr int MAX_PASSES = 7; Pass pass[MAX_PASSES];   // (the smallest MS_NTT_KMAX, 5, at the largest two-adicity, 32)
+    DevBuf tw_lo, tw_hi, vtw, w0;
+    T n_inv = 0, root = 0;   // root: w_n the tables hold the powers of (host copy: the FRI fold's octet table is derived from it)
+    size_t tiles(int k) const { return (size_t)1 << (log_n - pass[k].K - pass[k].log_C); }
+    // what the plan alone says about the PassParams of pass k (the caller adds buffers, strides, n_in, batch and scale)
+    PassParams params(int k) const {
+      PassParams pp{}; pp.log_n = log_n; pp.log_r = pass[k].K; pp.log_Rp = pass[k].log_Rp; pp.log_C = pass[k].log_C; pp.lo_bits = lo_bits;
+      pp.log_r0 = k == 0 ? log_r0 : 0; pp.log_rho = k == 0 ? log_rho : 0; pp.last = k == npass - 1; return pp;
+    }
   };
   std::map<int, Plan> plans;  // key = (log_n*4 + log_pad)*2 + inverse; complete plans only (get_plan), and a map's elements stay where they are
   int power_table(DevBuf& tab, T w, size_t count, const char* what);   // w^0 .. w^(count-1) in twiddle form -> device
@@ -365,27 +383,17 @@ template <class F> struct Ctx : CtxBase {
   int ntt_kmax = 9;            // largest tile (log2 rows) of a multi-pass plan; MS_NTT_KMAX overrides (tuning)
   int ntt_v2 = 1, ntt_v2_regpass = 1;   // MS_NTT_V2=0: round-1 kernels only (tests, A/B); MS_NTT_V2_REGPASS: the register-only last pass of 2^21..2^25-point transforms (0: off; 2: tests, on 2^7-row tiles)
   int ntt_fast = 1;            // MS_NTT_FAST=0: no compile-time specialised round-1 tiles (tests)
-
-  // log_pad: the input is zero beyond n >> log_pad
-  int get_plan(int log_n, int log_pad, bool inverse, Plan** out);
-
-  template <bool INV, int K, int TH>
-  int launch_fast(const msntt::PassParams<F>& pp, size_t tiles, size_t batch);
-  // PassKernel2 instance for a pass of 2^K rows x 2^LC columns in MODE (ntt.hpp): tile shape -> threads, sub-rounds, arithmetic class
-  template <class KK> int launch_v2i(const msntt::PassParams<F>& pp, unsigned grid, int nsub, int mode, int k, int lc);
-  template <bool INV, int K, int LC, int MODE>
-  int launch_v2m(const msntt::PassParams<F>& pp, size_t tiles, size_t batch);
   // persistent grid of the cooperative pass kernels: two workgroups per CU (their 72-80 KiB of LDS), a multiple of 8 (XCD-aware tile walk)
   int ntt_coop_wgs = 512, ntt_share = 1;   // MS_NTT_SHARE=0: never the shared-table instance (A/B)
   unsigned coop_grid(size_t work_items, int per_cu = 2) const { const size_t g = (size_t)ntt_coop_wgs * per_cu / 2; return (unsigned)(work_items < g ? work_items : g); }
-  template <bool INV, int K, int LC>
-  int launch_v2(const msntt::PassParams<F>& pp, size_t tiles, size_t batch);
-  template <bool INV, int LC>
-  int launch_v2k(const msntt::PassParams<F>& pp, size_t tiles, size_t batch);
-  template <bool INV, int K>
-  int launch_reg(const msntt::PassParams<F>& pp, size_t batch);
-  template <bool INV>
-  int launch_pass(const msntt::PassParams<F>& pp, size_t tiles, size_t batch, bool v2 = false, bool regp = false);
+  // log_pad: the input is zero beyond n >> log_pad.  plan_shape: everything but the tables - no device memory, no stream; get_plan: shape, then tables, then publish
+  int plan_shape(int log_n, int log_pad, bool inverse, Plan* pl); int get_plan(int log_n, int log_pad, bool inverse, Plan** out);
+  // the instance pass k launches for `batch` transforms.  Goldilocks, several columns, enough tiles to feed the persistent grid one tile at a time: the instance that
+  // builds the per-tile twiddle tables once per tile for all columns (measured r03: six-column LDE 0.560 -> 0.555 ms; BabyBear 0.333 -> 0.375 ms, so it has none)
+  const Instance& pick(const Plan& pl, int k, size_t batch) const {
+    const Pass& ps = pl.pass[k]; const size_t tiles = pl.tiles(k);
+    return (ps.shared && ntt_share && batch > 1 && tiles >= (size_t)coop_grid(tiles * batch) && (tiles & 7) == 0) ? ps.shared : ps.inst;
+  }
 
   // batch transforms of size 2^log_n: src (n_in valid elements per entry, zero padded) -> dst
   int ntt_run(int log_n, bool inverse, const T* src, size_t src_bstride, size_t n_in, T* dst, size_t dst_bstride, size_t batch);
