@@ -107,6 +107,8 @@ extern "C" {
     pub fn ms_mix_terms(ctx: *mut ms_ctx, r: u64, ncons: c_int, term_begin: *const u32, coef: *const u64, fac_begin: *const u32, fac_poly: *const u32,
                         fac_row: *const u32, nexempt: c_int) -> c_int;
     pub fn ms_mix_air(ctx: *mut ms_ctx, r: u64, air: *const MsAir) -> c_int;
+    pub fn ms_mix_air_ext(ctx: *mut ms_ctx, r: *const u64, air: *const MsAir) -> c_int;
+    pub fn ms_validity_ext(ctx: *const ms_ctx) -> c_int;
     pub fn ms_validity_len(ctx: *const ms_ctx) -> usize;
     pub fn ms_eval_ext(ctx: *mut ms_ctx, z: *const u64, q: c_int, out: *mut u64) -> c_int;
     // ---- Fri::prove stages (src/fri.rs:53-189)

@@ -110,6 +110,16 @@ impl Gpu {
         })?;
         Ok(unsafe { ms_validity_len(self.ctx) })
     }
+    /// BUILD-DEFINED (no reference counterpart): the AIR composition of `ms_mix_air` with the combiner `r` drawn from the extension field (`self.ext` canonical
+    /// limbs), so that the combination of the constraint quotients is |K|-sound, not |Fp|-sound.  `air` borrows its arrays for the call.  Returns the length of the
+    /// validity polynomial in coefficients; each has `self.ext` limbs afterwards (`validity_ext`), and `eval_ext` / `fri_begin` work on that polynomial.
+    pub fn mix_air_ext(&mut self, r: &[u64], air: &MsAir) -> Result<usize, GpuError> {
+        assert_eq!(r.len(), self.ext);
+        self.check(unsafe { ms_mix_air_ext(self.ctx, r.as_ptr(), air) })?;
+        Ok(unsafe { ms_validity_len(self.ctx) })
+    }
+    /// limbs per coefficient of the validity polynomial: 0 none, 1 after `mix` / `mix_terms`, `self.ext` after `mix_air_ext`
+    pub fn validity_ext(&self) -> i32 { unsafe { ms_validity_ext(self.ctx) } }
     /// starks.rs:124-151: out[t] = (f_0(z_t), .., f_{c-1}(z_t), validity(z_t)), E limbs each
     pub fn eval_ext(&mut self, z_limbs: &[u64], c: usize) -> Result<Vec<u64>, GpuError> {
         let q = z_limbs.len() / self.ext;

@@ -184,7 +184,7 @@ int ms_trace_upload_async(ms_ctx* ctx, const uint64_t* trace_rowmajor, size_t N,
  * The recurrence and z_0 are ordinary constraints of ms_mix_air (mini_stark_amd.aux_constraints writes them out); msh_air_expected_validity checks them on the
  * verifying side.
  * SOUNDNESS.  ext = 1 puts the challenges in Fp: the argument is then only |Fp|-sound - what the base-field `r` of the mix stages gives today - which for BabyBear
- * is 31 bits: use ext = 4 there.  Binding the trace columns of the LDE tree to the trace root stays the caller's linking step, as before.
+ * is 31 bits: use ext = 4 there, and draw the composition challenge from the extension as well (ms_mix_air_ext below).  Binding the trace columns of the LDE tree to the trace root stays the caller's linking step, as before.
  *   MS_ERR_STATE  no committed trace; ms_interpolate already called for this trace; a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1).
  *   MS_ERR_ARG    a null argument (column_out may be null, final_out may not); op > 1; ext not in {1, ms_ext_degree}; nfrac outside 1..4; form_begin not starting at 0 or
  *                 decreasing; more than 16 terms in a form; a column >= w; a non-canonical limb; more than 16 limb columns in all.
@@ -220,7 +220,7 @@ int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_
 int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c */);
 /* 1.3  validity = sum_i r^i f_i (remainder of divide_by_vanishing_poly; quirk Q1).  starks.rs:108-119. */
 int ms_mix(ms_ctx* ctx, uint64_t r);
-int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms / ms_mix_air */);
+int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms / ms_mix_air; times ms_validity_ext(ctx) limbs after ms_mix_air_ext */);
 /* BUILD-DEFINED, no reference counterpart (BASELINE configs[4] "degree-3 constraints"; the reference cannot express them: its validity polynomial is the
  * remainder of divide_by_vanishing_poly, starks.rs:118-119, quirk Q1).  In place of ms_mix, with the TRUE quotient:
  *   C_t(x) = P_j(w x) - P_a(x) P_b(x) P_c(x) - s_t P_d(x)         spec[t] = {j, a, b, c, d} (polynomial indices), w = the trace domain's generator
@@ -294,6 +294,24 @@ typedef struct ms_air {
   const uint64_t* bnd_val;             /* canonical */
 } ms_air;
 int ms_mix_air(ms_ctx* ctx, uint64_t r, const ms_air* air);
+/* BUILD-DEFINED: ms_mix_air with the combiner r in the extension K (Fp2 for Goldilocks, Fp4 for BabyBear): r = E = ms_ext_degree canonical limbs.  Same program,
+ * same formula, the powers of r taken in K:
+ *   validity(x) = sum_t r^t C_t(x) Z_t(x) / (x^N - 1)  +  sum_b r^(ncons+b) (P_j(x) - v_b) / (x - w^rho_b)
+ * a polynomial with coefficients in K; limb l of coefficient k is sum_t (r^t)_l * q_{t,k}, q_t the base-field quotient of constraint t.  A trace that breaks a
+ * constraint passes the combination with probability about (ncons + nbound) / |K| instead of / |Fp| (31 bits for BabyBear).  VL, the MS_ERR_ARG and the MS_ERR_SHAPE
+ * conditions are ms_mix_air's ("the division is exact": every limb plane of the size-L interpolant has at most VL coefficients); additionally
+ *   MS_ERR_ARG    r null or a limb >= p.
+ *   MS_ERR_STATE  a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1), as for ms_aux_running.
+ * After any refusal the context is as if the call had not been made.  Afterwards ms_validity_len is VL (in coefficients) and ms_validity_ext is E:
+ *   ms_validity_read  writes VL * E limbs, the limbs of one coefficient consecutive (as ms_fri_round_poly_read);
+ *   ms_eval_ext       out[t][c] = validity(z_t) = sum_k v_k z_t^k with v_k in K, the output shape unchanged;
+ *   ms_fri_begin      round 0's polynomial is the validity polynomial itself, all E limbs live (no extend_poly zero-fill), trimmed to the longest limb; the
+ *                     domain rule (deg + 1) * blowup is unchanged, and so is everything behind ms_fri_begin.
+ * r = (r0, 0, ..) gives ms_mix_air(r0)'s polynomial in limb 0 and zero limbs above it, and the same DEEP-ALI values, FRI roots and MSFP bytes.  A later ms_mix,
+ * ms_mix_cubic, ms_mix_terms or ms_mix_air replaces the polynomial and ms_validity_ext is 1 again; ms_polys_* and ms_trace_commit clear it.
+ * msh_air_expected_validity_ext (ministark_host.h) is the verifying side.  Tests: tests/test_air_ext_*.py. */
+int ms_mix_air_ext(ms_ctx* ctx, const uint64_t* r /* E limbs */, const ms_air* air);
+int ms_validity_ext(const ms_ctx* ctx);   /* limbs per validity coefficient: 0 no validity polynomial, 1 after ms_mix / _cubic / _terms / _air, E after ms_mix_air_ext */
 size_t ms_validity_len(const ms_ctx* ctx);
 /* 2.   DEEP-ALI: out[t][i] = f_i(z_t) for the c constraint polys, out[t][c] = validity(z_t);
  *      z: q*E limbs, out: q*(c+1)*E limbs.  starks.rs:124-151, field.rs:23-32. */

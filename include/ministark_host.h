@@ -105,6 +105,10 @@ int msh_terms_expected_validity(int field, uint64_t r, int ncons, const uint32_t
  * does not list (row 0 included when nbound > 0); MS_ERR_SHAPE when z^N = 1. */
 int msh_air_expected_validity(int field, uint64_t r, const ms_air* air, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows, const uint64_t* opened,
                               size_t row_stride, uint32_t npolys, uint64_t* out);
+/* The verifying side of ms_mix_air_ext: the same value with r in the extension (E canonical limbs), its powers taken there.  Everything else as above; a null r
+ * or a limb >= p is MS_ERR_ARG.  r = (r0, 0, ..) gives msh_air_expected_validity(r0). */
+int msh_air_expected_validity_ext(int field, const uint64_t* r /* E limbs */, const ms_air* air, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows,
+                                  const uint64_t* opened, size_t row_stride, uint32_t npolys, uint64_t* out);
 /* synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic): col_j[i+1] = col_j[i] col_{j+1}[i] col_{j+2}[i] + s_j col_{j+3}[i]; length x w row-major, w scalars */
 int msh_cubic_rows(uint64_t p, size_t length, size_t w, uint64_t seed, uint64_t* out, uint64_t* scalars);
 /* synthetic Fibonacci-AIR trace of the benchmark workload (N x 3 row-major) */

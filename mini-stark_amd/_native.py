@@ -540,11 +540,28 @@ class Context:
         s, _keep = air_struct(air)
         return self.L.ms_mix_air(self.h, C.c_uint64(r), C.byref(s))
 
+    def mix_air_ext(self, r, constraints, exempt=None, periodic=(), boundary=()):
+        """ms_mix_air_ext: mix_air with the combiner in the extension field, r = a sequence of E = ext_degree limbs (None passes a null pointer).  Afterwards
+        validity_ext() is E and validity_read() has the shape (VL, E)."""
+        air = constraints if isinstance(constraints, dict) else flatten_air(constraints, exempt, periodic, boundary)
+        s, _keep = air_struct(air)
+        if r is None:
+            return self.L.ms_mix_air_ext(self.h, None, C.byref(s))
+        rr, rp = _u64(r)
+        if rr.size != self.e:
+            raise ValueError(f"mix_air_ext: r has {rr.size} limbs, the extension has {self.e}")
+        return self.L.ms_mix_air_ext(self.h, rp, C.byref(s))
+
+    def validity_ext(self):
+        """ms_validity_ext: limbs per coefficient of the validity polynomial (0: none; 1; E after mix_air_ext)."""
+        return int(self.L.ms_validity_ext(self.h))
+
     def validity_read(self):
         self.L.ms_validity_len.restype = C.c_size_t
-        out = np.zeros(int(self.L.ms_validity_len(self.h)) or self.N, dtype=np.uint64)
+        vl, ve = int(self.L.ms_validity_len(self.h)) or self.N, max(1, self.validity_ext())
+        out = np.zeros(vl * ve, dtype=np.uint64)
         self.check(self.L.ms_validity_read(self.h, out.ctypes.data_as(_u64p)))
-        return out
+        return out.reshape(vl, ve) if ve > 1 else out
 
     def eval_ext(self, z):
         z, zp = _u64(z)

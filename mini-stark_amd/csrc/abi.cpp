@@ -183,6 +183,8 @@ int ms_mix_cubic(ms_ctx* ctx, uint64_t r, const int* spec, const uint64_t* s, in
 int ms_mix_terms(ms_ctx* ctx, uint64_t r, int ncons, const uint32_t* term_begin, const uint64_t* coef, const uint32_t* fac_begin, const uint32_t* fac_poly,
                  const uint32_t* fac_row, int nexempt) { MS_ENTRY(ctx, B(ctx)->mix_terms(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt)); }
 int ms_mix_air(ms_ctx* ctx, uint64_t r, const ms_air* air) { MS_ENTRY(ctx, B(ctx)->mix_air(r, air)); }
+int ms_mix_air_ext(ms_ctx* ctx, const uint64_t* r, const ms_air* air) { MS_ENTRY(ctx, B(ctx)->mix_air_ext(r, air)); }
+int ms_validity_ext(const ms_ctx* ctx) { return ctx ? B(ctx)->validity_ext_() : 0; }
 size_t ms_validity_len(const ms_ctx* ctx) { return ctx ? B(ctx)->validity_len_() : 0; }
 int ms_eval_ext(ms_ctx* ctx, const uint64_t* z, int q, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->eval_ext(z, q, out)); }
 int ms_fri_begin(ms_ctx* ctx, size_t blowup, size_t rounds, uint8_t root0[32]) { MS_ENTRY(ctx, B(ctx)->fri_begin(blowup, rounds, root0)); }

@@ -1,5 +1,5 @@
 // air_stages.cpp — constraint columns by linear provenance, coset LDE + commitment (starks.rs:80-95), constraint mixing (starks.rs:108-119; build-defined ms_mix_cubic,
-// ms_mix_terms and ms_mix_air: one host pipeline - gate, table, upload, compose launch, finish_mix - and a compose kernel each), DEEP-ALI evaluations (starks.rs:124-151).
+// ms_mix_terms, ms_mix_air and ms_mix_air_ext: one host pipeline - gate, table, upload, compose launch, finish_mix - and a compose kernel each), DEEP-ALI evaluations (starks.rs:124-151).
 #include "ctx.hpp"
 
 #include <algorithm>
@@ -217,7 +217,7 @@ int Ctx<F>::mix(u64 r) {
     CK(run<mspoly::DegreeKernel<F, 1>>(K_DEGREE, grid1(N, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
     validity_len_at = VLEN_DEVICE;
   }
-  have_validity = true; validity_len = N; nrounds_done = 0;
+  have_validity = true; validity_len = N; validity_ext = 1; nrounds_done = 0;
   return MS_OK;
 }
 
@@ -268,9 +268,9 @@ int Ctx<F>::check_term_program(const char* who, u32 ncons, const u32* term_begin
 }
 
 template <class F>
-int Ctx<F>::upload_mix_table(const char* who, const u8* tab, size_t bytes) {
+int Ctx<F>::upload_mix_table(const char* who, const u8* tab, size_t bytes, size_t ne) {
   if (lde_cols_virtual) { RQ(lincomb_linear_columns(d_lde.as<T>(), lde_col_stride, lde_col_len)); lde_cols_virtual = false; }
-  if (d_cubic.ensure(2 * L * sizeof(T)) || d_tabs.ensure(bytes + 64)) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
+  if (d_cubic.ensure(2 * L * ne * sizeof(T)) || d_tabs.ensure(bytes + 64)) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
   u8* ht;
   RQ(tabs_host(bytes + 64, &ht));     // (the previous user of the area, the last proof's query phase, ended with a stream synchronisation)
   memcpy(ht, tab, bytes);
@@ -281,19 +281,22 @@ int Ctx<F>::upload_mix_table(const char* who, const u8* tab, size_t bytes) {
 // evaluations on shift * <g_L> (d_cubic)  ->  coefficients of Q(shift y)  ->  q_k = coefficient_k * shift^-k.  The size-L interpolant I of the pointwise quotient satisfies
 // I (x^N - 1) = numerator on L points: with both sides of degree < L (the stages' SHAPE conditions), "I has at most VL coefficients" is "the division is exact" - the
 // reference's `assert_eq!(rest, zero)` of starks.rs:119, for the true quotient.  The stage's one stream synchronisation is here, for that answer.
+// ne limb planes (ms_mix_air_ext: the interpolation is Fp-linear, so a K-valued quotient is ne base-field ones): planes of L evaluations at d_cubic, their
+// coefficients behind them; exact means EVERY plane has at most VL coefficients (the scan takes the maximum over the limbs); limb l is stored at + l * VL.
 template <class F>
-int Ctx<F>::finish_mix(const char* refusal, size_t VL) {
-  T* cf = d_cubic.as<T>() + L;
-  RQ(ntt_run(ctz64(L), true, d_cubic.as<T>(), L, L, cf, L, 1));
-  if ((size_t)npolys + VL / N > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
-  RQ(ensure_polys(npolys + VL / N));
+int Ctx<F>::finish_mix(const char* refusal, size_t VL, int ne) {
+  T* cf = d_cubic.as<T>() + (size_t)ne * L;
+  RQ(ntt_run(ctz64(L), true, d_cubic.as<T>(), L, L, cf, L, (size_t)ne));
+  const size_t slots = (size_t)ne * (VL / N);
+  if ((size_t)npolys + slots > polys_cap) have_validity = false;   // (the polynomial store is about to move: an earlier validity polynomial behind the constraint polynomials does not move with it)
+  RQ(ensure_polys(npolys + slots));
   unsigned long long* dres, ncoef = 0;
-  RQ(degree_launch1(cf, L, &dres));
+  if (ne == 1) RQ(degree_launch1(cf, L, &dres)); else RQ(degree_launch(cf, L, L, &dres));
   { auto scan = res.expect(dres, false, false); RQ(res.collect(nullptr, nullptr, &ncoef)); }
   if (ncoef > VL) return fail(MS_ERR_SHAPE, refusal);
-  RQ(scale_pow(cf, 0, d_polys.as<T>() + (size_t)npolys * N, 0, VL, f_inv<F>(F::from_u64(lde_shift)), 1));
+  RQ(scale_pow(cf, L, d_polys.as<T>() + (size_t)npolys * N, VL, VL, f_inv<F>(F::from_u64(lde_shift)), (size_t)ne));
   validity_ncoef = (size_t)ncoef; validity_len_at = VLEN_HOST;   // (scaling by shift^-k keeps the trimmed length)
-  have_validity = true; validity_len = VL; nrounds_done = 0;
+  have_validity = true; validity_len = VL; validity_ext = ne; nrounds_done = 0;
   return MS_OK;
 }
 
@@ -458,7 +461,7 @@ void Ctx<F>::air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLa
   AG* hg = reinterpret_cast<AG*>(tab); mspoly::TermRec<F>* ht = reinterpret_cast<mspoly::TermRec<F>*>(tab + lay.off_t); AF* hf = reinterpret_cast<AF*>(tab + lay.off_f);
   T* hx = reinterpret_cast<T*>(tab + lay.off_x); T* hp = reinterpret_cast<T*>(tab + lay.off_p);
   const u32 ncons = a.ncons;
-  const T gL = f_root_of_unity<F>(ctz64(L)), wN = f_root_of_unity<F>(ctz64(N)), wi = f_inv<F>(wN), sh = F::from_u64(lde_shift), one = F::from_u64(1);
+  const T wN = f_root_of_unity<F>(ctz64(N)), wi = f_inv<F>(wN), one = F::from_u64(1);
   std::vector<T> rpow((size_t)ncons + a.nbound);
   { T rp = one; for (auto& v : rpow) { v = rp; rp = F::mul(rp, F::from_u64(r)); } }
   size_t m_out = 0, f_out = 0, x_out = 0;
@@ -494,7 +497,14 @@ void Ctx<F>::air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLa
     AG& gr = hg[pg.sets.size() + k];
     gr.nterms = (u32)(m_out - m_first); gr.nroots = 0; gr.kind = 1; gr.moff = (u32)(((N - pg.brows[k]) % N) * blowup);
   }
-  // periodic column k on the domain: K_k(x_i) = Q_k(x_i^(N/q)) takes blowup * q values, tab[u] = Q_k(shift^(N/q) g_L^(u N/q))
+  air_periodic_tables(a, pg, hp);
+  memcpy(tab + lay.off_d, dinv.data(), dinv.size() * sizeof(T));
+}
+
+// periodic column k on the domain: K_k(x_i) = Q_k(x_i^(N/q)) takes blowup * q values, tab[u] = Q_k(shift^(N/q) g_L^(u N/q))
+template <class F>
+void Ctx<F>::air_periodic_tables(const ms_air& a, const AirProgram& pg, T* hp) {
+  const T gL = f_root_of_unity<F>(ctz64(L)), wi = f_inv<F>(f_root_of_unity<F>(ctz64(N))), sh = F::from_u64(lde_shift), one = F::from_u64(1);
   for (u32 k = 0; k < a.nperiodic; k++) {
     const size_t q = a.per_begin[k + 1] - a.per_begin[k], step = N / q;
     const u64* val = a.per_val + a.per_begin[k];
@@ -506,7 +516,67 @@ void Ctx<F>::air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLa
     T x = f_pow<F>(sh, (u64)step);
     for (size_t u = 0; u < q * blowup; u++) { T v = 0; for (size_t m = q; m-- > 0;) v = F::add(F::mul(v, x), Q[m]); hp[pg.per_off[k] + u] = v; x = F::mul(x, zq); }
   }
-  memcpy(tab + lay.off_d, dinv.data(), dinv.size() * sizeof(T));
+}
+
+// ---- ms_mix_air_ext: the table of mspoly::ComposeAirExtKernel.  The groups are air_table's (one per exemption set, one per boundary row); inside a group every
+// constraint is a segment of its own with the K weight r^t (r^(ncons+b)) beside it, its term coefficients as the caller gave them
+template <class F>
+typename Ctx<F>::AirLayoutExt Ctx<F>::air_layout_ext(const ms_air& a, const AirProgram& pg, const AirLayout& lay) const {
+  AirLayoutExt lx;
+  lx.nsegs = (size_t)a.ncons + a.nbound; lx.tterms = (size_t)pg.nterms + 2 * (size_t)a.nbound; lx.tfacs = (size_t)pg.nfacs + a.nbound;
+  size_t nroots = 0; for (auto& s : pg.sets) nroots += s.size();
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  lx.off_s = up16(lay.ngroups * sizeof(mspoly::AirGroupExt)); lx.off_t = up16(lx.off_s + lx.nsegs * sizeof(mspoly::AirSeg<F, E>));
+  lx.off_f = up16(lx.off_t + lx.tterms * sizeof(mspoly::TermRec<F>)); lx.off_x = up16(lx.off_f + lx.tfacs * sizeof(mspoly::AirFac));
+  lx.off_p = up16(lx.off_x + nroots * sizeof(T)); lx.off_d = up16(lx.off_p + (size_t)pg.per_off[a.nperiodic] * sizeof(T)); lx.bytes = lx.off_d + blowup * sizeof(T);
+  return lx;
+}
+
+template <class F>
+void Ctx<F>::air_table_ext(const XE& r, const ms_air& a, const AirProgram& pg, const AirLayoutExt& lx, const std::vector<T>& dinv, u8* tab) {
+  typedef mspoly::AirFac AF; typedef mspoly::AirGroupExt AG; typedef mspoly::AirSeg<F, E> AS;
+  AG* hg = reinterpret_cast<AG*>(tab); AS* hs = reinterpret_cast<AS*>(tab + lx.off_s); mspoly::TermRec<F>* ht = reinterpret_cast<mspoly::TermRec<F>*>(tab + lx.off_t);
+  AF* hf = reinterpret_cast<AF*>(tab + lx.off_f); T* hx = reinterpret_cast<T*>(tab + lx.off_x);
+  const u32 ncons = a.ncons;
+  const T wN = f_root_of_unity<F>(ctz64(N)), wi = f_inv<F>(wN);
+  std::vector<XE> rpow((size_t)ncons + a.nbound);
+  { XE rp = e_one<F, E>(); for (auto& v : rpow) { v = rp; rp = e_mul<F>(rp, r); } }
+  size_t s_out = 0, m_out = 0, f_out = 0, x_out = 0;
+  for (size_t g = 0; g < pg.sets.size(); g++) {      // transition groups: the group's constraints in the caller's order, a segment each
+    const size_t s_first = s_out;
+    for (u32 t = 0; t < ncons; t++) {
+      if (pg.set_of[t] != g) continue;
+      for (int l = 0; l < E; l++) hs[s_out].w[l] = rpow[t].c[l];
+      hs[s_out].nterms = a.term_begin[t + 1] - a.term_begin[t]; s_out++;
+      for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++, m_out++) {
+        ht[m_out].coef = F::from_u64(a.coef[m]); ht[m_out].nfac = a.fac_begin[m + 1] - a.fac_begin[m];
+        for (u32 f = a.fac_begin[m]; f < a.fac_begin[m + 1]; f++, f_out++) {
+          const u32 fp = a.fac_poly[f];
+          hf[f_out].rowoff = (u32)((size_t)a.fac_row[f] * blowup);
+          if (fp & MS_AIR_PERIODIC) { const u32 k = fp & ~MS_AIR_PERIODIC; hf[f_out].src = pg.per_off[k]; hf[f_out].mask = pg.per_off[k + 1] - pg.per_off[k] - 1; hf[f_out].kind = 1; }
+          else { hf[f_out].src = fp; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; }
+        }
+      }
+    }
+    for (u32 rho : pg.sets[g]) hx[x_out++] = f_pow<F>(wN, (u64)rho);
+    hg[g].nsegs = (u32)(s_out - s_first); hg[g].nroots = (u32)pg.sets[g].size(); hg[g].kind = 0; hg[g].moff = 0;
+  }
+  for (size_t k = 0; k < pg.brows.size(); k++) {     // boundary groups: (sum_b r^(ncons+b) (w^-rho P_j - w^-rho v_b)) * D[i - rho blowup]
+    const size_t s_first = s_out;
+    const T wr = f_pow<F>(wi, (u64)pg.brows[k]);
+    for (u32 b = 0; b < a.nbound; b++) {
+      if (pg.brow_of[b] != k) continue;
+      for (int l = 0; l < E; l++) hs[s_out].w[l] = rpow[(size_t)ncons + b].c[l];
+      hs[s_out].nterms = 2; s_out++;
+      ht[m_out].coef = wr; ht[m_out].nfac = 1; m_out++;
+      hf[f_out].src = a.bnd_poly[b]; hf[f_out].rowoff = 0; hf[f_out].mask = (u32)(L - 1); hf[f_out].kind = 0; f_out++;
+      ht[m_out].coef = F::neg(F::mul(wr, F::from_u64(a.bnd_val[b]))); ht[m_out].nfac = 0; m_out++;
+    }
+    AG& gr = hg[pg.sets.size() + k];
+    gr.nsegs = (u32)(s_out - s_first); gr.nroots = 0; gr.kind = 1; gr.moff = (u32)(((N - pg.brows[k]) % N) * blowup);
+  }
+  air_periodic_tables(a, pg, reinterpret_cast<T*>(tab + lx.off_p));
+  memcpy(tab + lx.off_d, dinv.data(), dinv.size() * sizeof(T));
 }
 
 // D[i] = 1 / (x_i - 1) over the LDE domain: one table for every boundary row, kept while (N, blowup, shift) stay what it was built for
@@ -550,6 +620,39 @@ int Ctx<F>::mix_air(u64 r, const ms_air* air) {
   return finish_mix("mix_air: a transition constraint fails on a non-exempt row or a boundary value is wrong (the pointwise quotients do not interpolate to a polynomial of VL coefficients)", lay.VL);
 }
 
+template <class F>
+int Ctx<F>::mix_air_ext(const u64* r, const ms_air* air) {
+  RQ(mix_gate("mix_air_ext", 0));
+  if (sh_on) return fail(MS_ERR_STATE, "mix_air_ext: not available on a context with sharding on");
+  XE rr;
+  if (!r || !load_ext(r, &rr)) return fail(MS_ERR_ARG, "mix_air_ext: r null or a limb not canonical");
+  if (!air) return fail(MS_ERR_ARG, "mix_air_ext: null program");
+  const ms_air& a = *air;
+  AirProgram pg; AirLayout lay; std::vector<T> dinv;
+  RQ(air_validate(a, pg));
+  RQ(air_layout(a, pg, lay));
+  RQ(coset_vanishing_inv("mix_air_ext", dinv));
+  const AirLayoutExt lx = air_layout_ext(a, pg, lay);
+  std::vector<u8> tab(lx.bytes, 0);
+  air_table_ext(rr, a, pg, lx, dinv, tab.data());
+  typedef mspoly::ComposeAirExtKernel<F, E> CK_;
+  static_assert(CK_::THREADS == mspoly::CosetInvKernel<F>::THREADS, "gL_step is shared");
+  const T gL = f_root_of_unity<F>(ctz64(L)), gstep = f_pow<F>(gL, (u64)CK_::THREADS);
+  RQ(upload_mix_table("mix_air_ext", tab.data(), lx.bytes, (size_t)E));
+  if (a.nbound) RQ(air_inv_table(gstep));
+  const u8* dt = d_tabs.as<u8>();
+  typename CK_::Params cp;
+  cp.lde = d_lde.as<T>(); cp.L = L; cp.blowup = (u32)blowup; cp.ngroups = (u32)lay.ngroups;
+  cp.groups = reinterpret_cast<const mspoly::AirGroupExt*>(dt); cp.segs = reinterpret_cast<const mspoly::AirSeg<F, E>*>(dt + lx.off_s);
+  cp.terms = reinterpret_cast<const mspoly::TermRec<F>*>(dt + lx.off_t); cp.facs = reinterpret_cast<const mspoly::AirFac*>(dt + lx.off_f);
+  cp.roots = reinterpret_cast<const T*>(dt + lx.off_x); cp.ptab = reinterpret_cast<const T*>(dt + lx.off_p);
+  cp.den_inv = reinterpret_cast<const T*>(dt + lx.off_d); cp.inv = a.nbound ? d_air_inv.as<T>() : nullptr;
+  cp.shift = F::from_u64(lde_shift); cp.gL = gL; cp.gL_step = gstep; cp.out = d_cubic.as<T>();
+  next_bytes = (double)(lx.tfacs + lay.ngroups + E) * L * sizeof(T);
+  CK(run<CK_>(K_MIX_AIR_EXT, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
+  return finish_mix("mix_air_ext: a transition constraint fails on a non-exempt row or a boundary value is wrong (a limb of the pointwise quotients does not interpolate to a polynomial of VL coefficients)", lay.VL, E);
+}
+
 // trimmed length of a base-field coefficient vector
 template <class F>
 int Ctx<F>::degree_launch1(const T* poly, size_t n, unsigned long long** dres_out) {
@@ -564,7 +667,7 @@ int Ctx<F>::degree_launch1(const T* poly, size_t n, unsigned long long** dres_ou
 template <class F>
 int Ctx<F>::validity_read(u64* out) {
   if (!have_validity || !out) return fail(MS_ERR_STATE, "validity_read");
-  return download_widen(d_polys.as<T>() + (size_t)npolys * N, validity_len, 0, 1, out);
+  return download_widen(d_polys.as<T>() + (size_t)npolys * N, validity_len, validity_len, (u32)validity_ext, out);   // (the limbs of a coefficient consecutive)
 }
 
 // evaluate `npoly` polynomials (views) at ext point z into dst as [npoly][E] T
@@ -671,9 +774,11 @@ template <class F>
 int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   if (!have_validity) return fail(MS_ERR_STATE, "eval_ext before mix");
   if (!z || !out || q < 0) return fail(MS_ERR_ARG, "eval_ext");
+  const bool vx = validity_ext > 1;   // K-valued validity polynomial (ms_mix_air_ext): out of the base-coefficient batches, one launch of its own per point
+  if (vx && sh_on) return fail(MS_ERR_STATE, "eval_ext: a validity polynomial over the extension on a context with sharding on");   // (sharding switched on behind the stage)
   if (dist_eval()) return eval_ext_sharded(z, q, out);
   const std::vector<int> ev = eval_set();
-  const int nev = (int)ev.size();
+  const int nev = (int)ev.size(), nb1 = vx ? nev - 1 : nev;   // (the validity polynomial is the set's last entry)
   const size_t tot = (size_t)q * nev * E;
   if (d_small.ensure(tot * sizeof(T) + 4096)) return fail(MS_ERR_NOMEM, "small");
   if (tot * sizeof(T) > pinned_cap) return fail(MS_ERR_ARG, "too many evaluation points");
@@ -686,11 +791,15 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   for (int t = 0; t < q; t++) {
     XE zz;
     if (!load_ext(z + (size_t)t * E, &zz)) return fail(MS_ERR_ARG, "query point not canonical");
-    for (int i0 = 0; i0 < nev; i0 += mspoly::MAX_POLYS) {
-      const int nb = (nev - i0 < mspoly::MAX_POLYS) ? nev - i0 : mspoly::MAX_POLYS;
+    for (int i0 = 0; i0 < nb1; i0 += mspoly::MAX_POLYS) {
+      const int nb = (nb1 - i0 < mspoly::MAX_POLYS) ? nb1 - i0 : mspoly::MAX_POLYS;
       size_t off[mspoly::MAX_POLYS], cnt[mspoly::MAX_POLYS];
       for (int i = 0; i < nb; i++) { const int pi = ev[i0 + i]; off[i] = (size_t)pi * N; cnt[i] = (pi == npolys) ? validity_len : N; }   // the validity polynomial has 2N coefficients after ms_mix_cubic
-      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, pinned.as<T>() + ((size_t)t * nev + i0) * E, t == q - 1 && i0 + mspoly::MAX_POLYS >= nev)));   // results land in page-locked host memory
+      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, zz, pinned.as<T>() + ((size_t)t * nev + i0) * E, !vx && t == q - 1 && i0 + mspoly::MAX_POLYS >= nb1)));   // results land in page-locked host memory
+    }
+    if (vx) {
+      const size_t off = 0, cnt = validity_len;
+      RQ((eval_views<E>(d_polys.as<T>() + (size_t)npolys * N, 0, validity_len, 1, &off, &cnt, 1, zz, pinned.as<T>() + ((size_t)t * nev + nb1) * E, t == q - 1)));
     }
   }
   RQ(res.collect(nullptr, nullptr, &vlen));
@@ -712,6 +821,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   template int Ctx<FF>::mix_cubic(u64 r, const int* spec, const u64* sc, int ncons); \
   template int Ctx<FF>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt); \
   template int Ctx<FF>::mix_air(u64 r, const ms_air* air); \
+  template int Ctx<FF>::mix_air_ext(const u64* r, const ms_air* air); \
   template int Ctx<FF>::degree_launch1(const Ctx<FF>::T* poly, size_t n, unsigned long long** dres_out); \
   template int Ctx<FF>::validity_read(u64* out); \
   template int Ctx<FF>::shard_combine_launch(size_t off, size_t rank_stride, u32 n, const Ctx<FF>::XE& zstep, Ctx<FF>::T* out); \

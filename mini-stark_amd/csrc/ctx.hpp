@@ -131,6 +131,8 @@ struct CtxBase {
   virtual int mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) = 0;
   virtual int mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) = 0;
   virtual int mix_air(u64 r, const ms_air* air) = 0;
+  virtual int mix_air_ext(const u64* r, const ms_air* air) = 0;
+  virtual int validity_ext_() const = 0;
   virtual size_t validity_len_() const = 0;
   virtual int validity_read(u64* out) = 0;
   virtual int eval_ext(const u64* z, int q, u64* out) = 0;
@@ -233,7 +235,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_MIX_AIR_EXT, K_COUNT };
   struct ProfRec { int kid, sub; EventOwner a, b; double bytes; bool part; };   // (the records of a profile never ended go with the context)
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -566,6 +568,9 @@ template <class F> struct Ctx : CtxBase {
   // build-defined degree-3 composition with the true quotient (include/ministark.h; kernel: mspoly::CubicComposeKernel)
   size_t validity_len = 0; u64 lde_shift = 0; DevBuf d_cubic;
   size_t validity_len_() const override { return have_validity ? validity_len : 0; }
+  // limbs per coefficient of the validity polynomial: 1 (base field: every mix stage but ms_mix_air_ext) or E, limb l of the coefficients at + l * validity_len
+  int validity_ext = 1;
+  int validity_ext_() const override { return have_validity ? validity_ext : 0; }
   int mix_cubic(u64 r, const int* spec, const u64* sc, int ncons) override;
   // build-defined composition of any degree: constraints as sums of monomials over the polynomials, in CSR arrays (include/ministark.h; kernel: mspoly::ComposeTermsKernel)
   int mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) override;
@@ -574,6 +579,8 @@ template <class F> struct Ctx : CtxBase {
   // constraints and kept while (N, blowup, shift) stay what it was built for
   DevBuf d_air_inv; bool air_inv_valid = false; size_t air_inv_N = 0, air_inv_blowup = 0; u64 air_inv_shift = 0;
   int mix_air(u64 r, const ms_air* air) override;
+  // ms_mix_air with r in the extension (kernel: mspoly::ComposeAirExtKernel): the same gate, checks, sizes and tables, the program as segments with K weights
+  int mix_air_ext(const u64* r, const ms_air* air) override;
   // ms_mix_air's program regrouped for ComposeAirKernel: filled by air_validate, read by air_layout and air_table
   struct AirProgram {
     u32 nterms = 0, nfacs = 0;
@@ -587,6 +594,11 @@ template <class F> struct Ctx : CtxBase {
   int air_validate(const ms_air& a, AirProgram& pg);
   int air_layout(const ms_air& a, const AirProgram& pg, AirLayout& lay);
   void air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLayout& lay, const std::vector<T>& dinv, u8* tab);
+  // the table of ComposeAirExtKernel: [groups | segments | terms | factors | exemption roots | periodic tables | den_inv]; the last three as air_table writes them
+  struct AirLayoutExt { size_t nsegs, tterms, tfacs, off_s, off_t, off_f, off_x, off_p, off_d, bytes; };
+  AirLayoutExt air_layout_ext(const ms_air& a, const AirProgram& pg, const AirLayout& lay) const;
+  void air_table_ext(const XE& r, const ms_air& a, const AirProgram& pg, const AirLayoutExt& lx, const std::vector<T>& dinv, u8* tab);
+  void air_periodic_tables(const ms_air& a, const AirProgram& pg, T* hp);   // periodic column k on the domain, at hp + pg.per_off[k] (both tables)
   int air_inv_table(T gL_step);
   // ---- the pipeline the three build-defined mix stages share (air_stages.cpp): gate, [the stage's own checks and host table], upload, [its compose launch], finish.
   // `who` is the entry point, for the messages
@@ -596,9 +608,10 @@ template <class F> struct Ctx : CtxBase {
   // what ms_mix_terms and ms_mix_air ask of the CSR term arrays; *d = the most factors of any term (deg_per_constraint, when given and zeroed: the same per constraint)
   int check_term_program(const char* who, u32 ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, u32* deg_per_constraint, u32* d);
   // virtual LDE columns written out, d_cubic / d_tabs sized, the host table staged and copied to d_tabs
-  int upload_mix_table(const char* who, const u8* tab, size_t bytes);
-  // d_cubic's evaluations -> the validity polynomial of VL coefficients behind the constraint polynomials, or MS_ERR_SHAPE with `refusal` when the division was not exact
-  int finish_mix(const char* refusal, size_t VL);
+  int upload_mix_table(const char* who, const u8* tab, size_t bytes, size_t ne = 1);
+  // d_cubic's evaluations (ne limb planes of L) -> the validity polynomial of VL coefficients behind the constraint polynomials (limb l at + l * VL), or MS_ERR_SHAPE
+  // with `refusal` when the division was not exact
+  int finish_mix(const char* refusal, size_t VL, int ne = 1);
   // trimmed length of a base-field coefficient vector
   int degree_launch1(const T* poly, size_t n, unsigned long long** dres_out);
   int validity_read(u64* out) override;

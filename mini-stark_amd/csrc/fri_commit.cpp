@@ -141,9 +141,14 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   const size_t VL = validity_len;   // N (ms_mix) or 2N (ms_mix_cubic)
   r->cap = VL;
   if (r->poly.ensure(VL * E * sizeof(T))) return fail(MS_ERR_NOMEM, "round poly");
+  const bool vx = validity_ext > 1;   // ms_mix_air_ext: the validity polynomial has its E limbs already, VL apart as the round's are
+  if (vx && sh_on) return fail(MS_ERR_STATE, "fri_begin: a validity polynomial over the extension on a context with sharding on");
+  if (vx) CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * E * sizeof(T), stream));
+  else {
   // field.rs:23-32 extend_poly: limb 0 = validity, higher limbs zero
   CK(msrt::memset_dev(r->poly.p, 0, VL * E * sizeof(T), stream));
   CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * sizeof(T), stream));
+  }
   unsigned long long nc = validity_ncoef;   // (came to the host with DEEP-ALI's values: ms_mix scans, ms_eval_ext forwards)
   if (validity_len_at != VLEN_HOST) {   // a scan of its own and a copy behind it
     unsigned long long* dres;
@@ -158,7 +163,7 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   r->D = D;
   r->S = dist_chunk(D); r->dist = r->S != 0; r->local_store = false;   // the validity polynomial is replicated: a distributed round 0 means every rank WORKS on its range of it
   auto stage = res.expect();
-  RQ(round_commit(r, (size_t)nc, 1));
+  RQ(round_commit(r, (size_t)nc, vx ? E : 1));
   RQ(read_root(r->nodes, r->ts, root0));
   nrounds_done = 1;
   return MS_OK;

@@ -1108,6 +1108,102 @@ template <class F> struct ComposeAirKernel {
   }
 };
 
+// ---------------------------------------------------------------- ms_mix_air with the combiner r in the extension K (ms_mix_air_ext)
+// The same formula with the powers of r taken in K: the validity polynomial has coefficients in K, limb l of it is sum_t (r^t)_l * (quotient of constraint t).
+// The constraint values stay in Fp - the column loads and factor products are those of ComposeAirKernel - so r^t is NOT folded into the term coefficients (E
+// multiplications per term); the program gets one more level instead, group -> SEGMENT -> term -> factor:
+// * a segment is one transition constraint, or one boundary constraint as the two terms w^-rho P_j and - w^-rho v_b; its value is accumulated in Fp and enters
+//   the group's K accumulator as weight * value (E multiplications per segment and point), weight = r^t or r^(ncons+b);
+// * the group multiplier M_g(x_i) of ComposeAirKernel is formed in Fp (den_inv or D, times the exemption roots) and applied once per group: E multiplications.
+// Field arithmetic is exact: limb 0 for r = (r0, 0, ..) is ComposeAirKernel's output, element for element.  Output: E planes of L points, limb l at out + l L.
+// Thread shape, masking and the store-behind-the-walk rule are ComposeAirKernel's; the accumulators are 2 ITEMS E words.
+template <class F, int E> struct AirSeg { typename F::T w[E]; u32 nterms; };
+struct AirGroupExt { u32 nsegs, nroots, kind, moff; };
+template <class F, int E> struct ComposeAirExtKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int ITEMS = 8;
+  struct Params { const T* lde; size_t L; u32 blowup, ngroups; const AirGroupExt* groups; const AirSeg<F, E>* segs; const TermRec<F>* terms; const AirFac* facs;
+                  const T* roots /* w^rho, group by group */; const T* ptab; const T* den_inv; const T* inv /* D, L entries; unused without boundary groups */;
+                  T shift, gL, gL_step /* gL^THREADS */; T* out /* E planes of L */; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
+    const size_t i0 = (size_t)bx * (THREADS * ITEMS) + tid;
+    if (i0 >= p.L) return;
+    const size_t mask = p.L - 1;
+    const T x0 = F::mul(p.shift, f_pow<F>(p.gL, i0));
+    T total[E][ITEMS];
+#pragma unroll
+    for (int l = 0; l < E; l++)
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) total[l][it] = 0;
+    u32 s = 0, m = 0, f = 0, rk = 0;
+    for (u32 g = 0; g < p.ngroups; g++) {
+      const AirGroupExt gr = p.groups[g];
+      T gacc[E][ITEMS];
+#pragma unroll
+      for (int l = 0; l < E; l++)
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) gacc[l][it] = 0;
+      for (u32 sg = 0; sg < gr.nsegs; sg++, s++) {
+        const AirSeg<F, E> seg = p.segs[s];
+        T sv[ITEMS];
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) sv[it] = 0;
+        for (u32 ms = 0; ms < seg.nterms; ms++, m++) {
+          const TermRec<F> tr = p.terms[m];
+          T v[ITEMS];
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) v[it] = tr.coef;
+          for (u32 k = 0; k < tr.nfac; k++, f++) {
+            const AirFac fc = p.facs[f];
+            const T* col = fc.kind ? p.ptab + fc.src : p.lde + (size_t)fc.src * p.L;
+            T c[ITEMS];                                 // (loaded first, multiplied behind, as in ComposeAirKernel)
+#pragma unroll
+            for (int it = 0; it < ITEMS; it++) c[it] = col[(i0 + (size_t)it * THREADS + fc.rowoff) & (size_t)fc.mask];
+#pragma unroll
+            for (int it = 0; it < ITEMS; it++) v[it] = F::mul(v[it], c[it]);
+          }
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) sv[it] = F::add(sv[it], v[it]);
+        }
+#pragma unroll
+        for (int l = 0; l < E; l++)
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) gacc[l][it] = F::add(gacc[l][it], F::mul(seg.w[l], sv[it]));
+      }
+      const T* mt = gr.kind ? p.inv : p.den_inv;
+      const size_t mm = gr.kind ? mask : (size_t)(p.blowup - 1);   // (blowup is a power of two: ms_lde_commit)
+      T mv[ITEMS];                                      // the group multiplier, in Fp
+#pragma unroll
+      for (int it = 0; it < ITEMS; it++) mv[it] = mt[(i0 + (size_t)it * THREADS + gr.moff) & mm];
+      if (gr.nroots) {
+        T x[ITEMS];
+        x[0] = x0;
+#pragma unroll
+        for (int it = 1; it < ITEMS; it++) x[it] = F::mul(x[it - 1], p.gL_step);
+        for (u32 k = 0; k < gr.nroots; k++, rk++) {
+          const T root = p.roots[rk];
+#pragma unroll
+          for (int it = 0; it < ITEMS; it++) mv[it] = F::mul(mv[it], F::sub(x[it], root));
+        }
+      }
+#pragma unroll
+      for (int l = 0; l < E; l++)
+#pragma unroll
+        for (int it = 0; it < ITEMS; it++) total[l][it] = F::add(total[l][it], F::mul(gacc[l][it], mv[it]));
+    }
+#pragma unroll
+    for (int it = 0; it < ITEMS; it++) {
+      const size_t i = i0 + (size_t)it * THREADS;
+      if (i < p.L) {
+#pragma unroll
+        for (int l = 0; l < E; l++) p.out[(size_t)l * p.L + i] = total[l][it];
+      }
+    }
+  }
+};
+
 // D[i] = 1 / (x_i - 1) over the LDE domain x_i = shift gL^i, for the boundary groups of ComposeAirKernel: a thread owns ITEMS strided points and inverts their
 // product once (Montgomery's trick).  No x_i is 1: the stage has refused a coset that meets the trace domain, and the points past L of a short domain are
 // points of the same coset again (computed, not stored).

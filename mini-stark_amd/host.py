@@ -109,6 +109,28 @@ def air_expected_validity(field, r, air, N, z, rows, opened, npolys=None):
     return rc, out
 
 
+def air_expected_validity_ext(field, r, air, N, z, rows, opened, npolys=None):
+    """msh_air_expected_validity_ext: air_expected_validity after ms_mix_air_ext, r = the E limbs of the combiner."""
+    if not isinstance(air, dict):
+        air = flatten_air(*air)
+    s, _keep = air_struct(air)
+    zz = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1)
+    e = zz.size
+    rr = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1)
+    if rr.size != e:
+        raise ValueError(f"air_expected_validity_ext: r has {rr.size} limbs, z has {e}")
+    op = np.ascontiguousarray(opened, dtype=np.uint64)
+    rw = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    op = op.reshape(max(1, rw.size), -1)
+    if npolys is None:
+        npolys = op.shape[1] // e - 1          # the last entry of an ms_eval_ext row is the validity polynomial's value
+    out = np.zeros(e, dtype=np.uint64)
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    rc = _host().msh_air_expected_validity_ext(C.c_int(field), rr.ctypes.data_as(u64p), C.byref(s), C.c_uint64(N), zz.ctypes.data_as(u64p), C.c_int(rw.size),
+                                               rw.ctypes.data_as(u32p), op.ctypes.data_as(u64p), C.c_size_t(op.shape[1]), C.c_uint32(npolys), out.ctypes.data_as(u64p))
+    return rc, out
+
+
 class HostStark:
     """StarkConfig::new + Stark::new + Stark::prove + Stark::verify (src/starks.rs:268-310, 40-57, 59-169, 171-235) in C++."""
 

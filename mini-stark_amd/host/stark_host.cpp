@@ -605,12 +605,13 @@ template <class F, int E> static int terms_expected(u64 r, int ncons, const u32*
 }
 // The verifying side of ms_mix_air: the same program in the extension field from the opened values, the periodic columns evaluated here, the boundary quotients
 // from the row-0 opening:  sum_t r^t C_t(z) Z_t(z) / (z^N - 1)  +  sum_b r^(ncons+b) (opened[row 0][j_b] - v_b) / (z - w^rho_b)
-template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+// r: E limbs, the powers taken in the extension (ms_mix_air_ext); ms_mix_air's base-field r is (r, 0, ..)
+template <class F, int E> static int air_expected(const u64* r, const ms_air& a, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
   typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
   typedef typename F::T T;
   const u32 ncons = a.ncons;
-  if (r >= F::P || !V::canon(z, E) || term_program_degree<F>(ncons, a.term_begin, a.coef, a.fac_begin) <= 0 || a.ex_begin[0] != 0) return MS_ERR_ARG;   // (d = 0 too)
+  if (!V::canon(r, E) || !V::canon(z, E) || term_program_degree<F>(ncons, a.term_begin, a.coef, a.fac_begin) <= 0 || a.ex_begin[0] != 0) return MS_ERR_ARG;   // (d = 0 too)
   for (u32 t = 0; t < ncons; t++) if (a.ex_begin[t + 1] < a.ex_begin[t] || a.ex_begin[t + 1] - a.ex_begin[t] > 16) return MS_ERR_ARG;
   const u32 nterms = a.term_begin[ncons];
   if (a.ex_begin[ncons] && !a.ex_row) return MS_ERR_ARG;
@@ -660,7 +661,8 @@ template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N,
   const X den = e_sub<F, E>(e_pow<F, E>(zz, N), e_one<F, E>());
   if (e_is_zero<F, E>(den)) return MS_ERR_SHAPE;                       // z lies in the trace domain
   X acc = e_zero<F, E>();
-  T rp = one;
+  const X rr = V::load(r);
+  X rp = e_one<F, E>();
   for (u32 t = 0; t < ncons; t++) {
     X ct = e_zero<F, E>();
     for (u32 m = a.term_begin[t]; m < a.term_begin[t + 1]; m++) {
@@ -678,15 +680,15 @@ template <class F, int E> static int air_expected(u64 r, const ms_air& a, u64 N,
       ct = e_add<F, E>(ct, v);
     }
     for (u32 k = a.ex_begin[t]; k < a.ex_begin[t + 1]; k++) ct = e_mul<F>(ct, e_sub<F, E>(zz, e_from_base<F, E>(f_pow<F>(wN, (u64)a.ex_row[k]))));
-    acc = e_add<F, E>(acc, e_mul_base<F, E>(ct, rp));
-    rp = F::mul(rp, F::from_u64(r));
+    acc = e_add<F, E>(acc, e_mul<F>(ct, rp));
+    rp = e_mul<F>(rp, rr);
   }
   acc = e_mul<F>(acc, e_inv<F>(den));
   for (u32 b = 0; b < a.nbound; b++) {
     const X num = e_sub<F, E>(V::load(opened + (size_t)slot0 * row_stride + (size_t)a.bnd_poly[b] * E), e_from_base<F, E>(F::from_u64(a.bnd_val[b])));
     const X dn = e_sub<F, E>(zz, e_from_base<F, E>(f_pow<F>(wN, (u64)a.bnd_row[b])));   // (non-zero: z^N != 1)
-    acc = e_add<F, E>(acc, e_mul_base<F, E>(e_mul<F>(num, e_inv<F>(dn)), rp));
-    rp = F::mul(rp, F::from_u64(r));
+    acc = e_add<F, E>(acc, e_mul<F>(e_mul<F>(num, e_inv<F>(dn)), rp));
+    rp = e_mul<F>(rp, rr);
   }
   for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
   return MS_OK;
@@ -897,7 +899,11 @@ int msh_terms_expected_validity(int field, u64 r, int ncons, const u32* term_beg
   } catch (...) { return MS_ERR_NOMEM; }   // nothing unwinds through the C boundary
 }
 int msh_air_expected_validity(int field, u64 r, const ms_air* air, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
-  if (!air || !z || !opened || !out || (nrows && !rows)) return MS_ERR_ARG;
+  const u64 rk[4] = {r, 0, 0, 0};
+  return msh_air_expected_validity_ext(field, rk, air, N, z, nrows, rows, opened, row_stride, npolys, out);
+}
+int msh_air_expected_validity_ext(int field, const u64* r, const ms_air* air, u64 N, const u64* z, int nrows, const u32* rows, const u64* opened, size_t row_stride, u32 npolys, u64* out) {
+  if (!r || !air || !z || !opened || !out || (nrows && !rows)) return MS_ERR_ARG;
   const ms_air& a = *air;
   if (!a.term_begin || !a.coef || !a.fac_begin || !a.fac_poly || !a.fac_row || !a.ex_begin || (a.nperiodic && (!a.per_begin || !a.per_val)) || (a.nbound && (!a.bnd_poly || !a.bnd_row || !a.bnd_val))) return MS_ERR_ARG;
   if ((field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) || a.ncons < 1 || a.ncons > 4096 || a.nperiodic > 64 || a.nbound > 4096 || nrows < 0 || !N || (N & (N - 1))) return MS_ERR_ARG;
