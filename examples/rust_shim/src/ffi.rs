@@ -108,6 +108,8 @@ extern "C" {
                         fac_row: *const u32, nexempt: c_int) -> c_int;
     pub fn ms_mix_air(ctx: *mut ms_ctx, r: u64, air: *const MsAir) -> c_int;
     pub fn ms_mix_air_ext(ctx: *mut ms_ctx, r: *const u64, air: *const MsAir) -> c_int;
+    /// diagnostic: which constraints of `air` the trace violates and on which rows (every out-pointer but `nfail` may be null)
+    pub fn ms_air_check(ctx: *mut ms_ctx, air: *const MsAir, nfail: *mut u64, cons_count: *mut u64, cons_first_row: *mut u64, bnd_got: *mut u64) -> c_int;
     pub fn ms_validity_ext(ctx: *const ms_ctx) -> c_int;
     pub fn ms_validity_len(ctx: *const ms_ctx) -> usize;
     pub fn ms_eval_ext(ctx: *mut ms_ctx, z: *const u64, q: c_int, out: *mut u64) -> c_int;

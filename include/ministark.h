@@ -312,6 +312,27 @@ int ms_mix_air(ms_ctx* ctx, uint64_t r, const ms_air* air);
  * msh_air_expected_validity_ext (ministark_host.h) is the verifying side.  Tests: tests/test_air_ext_*.py. */
 int ms_mix_air_ext(ms_ctx* ctx, const uint64_t* r /* E limbs */, const ms_air* air);
 int ms_validity_ext(const ms_ctx* ctx);   /* limbs per validity coefficient: 0 no validity polynomial, 1 after ms_mix / _cubic / _terms / _air, E after ms_mix_air_ext */
+/* BUILD-DEFINED, diagnostic: WHY a trace is refused.  The ms_air program of ms_mix_air evaluated on the N rows of the trace domain (not on the LDE), one streaming
+ * launch.  T_j[i] = P_j(w^i) is the value of column / polynomial j on row i; the factor (j, row) is T_j[(i + row) mod N], the factor (MS_AIR_PERIODIC | k, row) is
+ * per_val[per_begin[k] + ((i + row) mod q_k)]; C_t(i) = sum_m coef_m prod_f factor_f(i) in Fp.  Row i VIOLATES constraint t when C_t(i) != 0 and i is not in X_t.
+ *   cons_count[t]      the number of violating rows of constraint t                       (ncons words, or NULL)
+ *   cons_first_row[t]  the smallest violating row, N when there is none                   (ncons words, or NULL)
+ *   bnd_got[b]         T_{bnd_poly[b]}[bnd_row[b]], the value the trace really has: boundary constraint b fails when it differs from bnd_val[b]   (nbound words, or NULL)
+ *   *nfail             the transition constraints with cons_count > 0 plus the failing boundary constraints
+ * Returns MS_OK whenever the check ran; the verdict is *nfail.  *nfail == 0: the same program goes through ms_mix_air / ms_mix_air_ext on this trace (their
+ * domain-size conditions provided); *nfail > 0 is what those stages report as MS_ERR_SHAPE.  Counts and minima do not depend on grid, wave order or launches.
+ * Valid from ms_trace_commit[_device] until the next one:
+ *   before ms_interpolate  the columns are the w trace columns and the ms_aux_count running columns behind them (indices < c = w + ms_aux_count), read as they stand;
+ *   after it (at any later stage: after ms_lde_commit, a refused mix stage, a finished FRI) c = ms_polys_count as it is now, ms_polys_lincomb / ms_polys_append
+ *                          polynomials included (lazily defined ones are written out as by ms_poly_read); the c polynomials are evaluated on the trace domain by
+ *                          one forward transform into a scratch buffer of c * N elements, which the same kernel reads.
+ *   MS_ERR_STATE  no committed trace; a context with sharding on (as for ms_aux_running and ms_mix_air_ext).
+ *   MS_ERR_ARG    air or nfail null; every MS_ERR_ARG condition of ms_mix_air, with c as above.  It needs no LDE: there is no MS_ERR_SHAPE.
+ * Everything is decided before anything is launched.  The context is unchanged whether the call succeeds, refuses or fails: polynomials, LDE, tree, validity
+ * polynomial, ms_validity_ext and the FRI state are untouched, and a proof with checks inserted anywhere is byte-identical to one without.
+ * Tests: tests/test_air_check_*.py (tests/pyref_air_check.py restates the definitions). */
+int ms_air_check(ms_ctx* ctx, const ms_air* air, uint64_t* nfail, uint64_t* cons_count /* ncons, or NULL */, uint64_t* cons_first_row /* ncons, or NULL */,
+                 uint64_t* bnd_got /* nbound, or NULL */);
 size_t ms_validity_len(const ms_ctx* ctx);
 /* 2.   DEEP-ALI: out[t][i] = f_i(z_t) for the c constraint polys, out[t][c] = validity(z_t);
  *      z: q*E limbs, out: q*(c+1)*E limbs.  starks.rs:124-151, field.rs:23-32. */

@@ -552,6 +552,24 @@ class Context:
             raise ValueError(f"mix_air_ext: r has {rr.size} limbs, the extension has {self.e}")
         return self.L.ms_mix_air_ext(self.h, rp, C.byref(s))
 
+    def air_check(self, constraints, exempt=None, periodic=(), boundary=()):
+        """ms_air_check (BUILD-DEFINED, diagnostic; include/ministark.h): the program of mix_air - same arguments, or a flatten_air dict - evaluated on the rows of the
+        trace domain, valid from trace_commit on.  Returns (rc, report); report (None when rc != 0) is a dict: nfail; count and first_row (uint64 arrays of ncons:
+        violating rows per constraint, the smallest one or N); bnd_got (the value the trace has at every boundary cell); bnd_fail (indices of the boundary constraints whose
+        value differs); first (the (row, constraint) pair smallest by row, then by constraint, or None); ok (nfail == 0)."""
+        air = constraints if isinstance(constraints, dict) else flatten_air(constraints, exempt, periodic, boundary)
+        s, keep = air_struct(air)
+        ncons, nbound = int(air["ncons"]), int(air["nbound"])
+        nfail = C.c_uint64(0)
+        count, first_row, got = (np.zeros(max(1, n), dtype=np.uint64) for n in (ncons, ncons, nbound))
+        rc = self.L.ms_air_check(self.h, C.byref(s), C.byref(nfail), count.ctypes.data_as(_u64p), first_row.ctypes.data_as(_u64p), got.ctypes.data_as(_u64p))
+        if rc != 0:
+            return rc, None
+        count, first_row, got = count[:ncons], first_row[:ncons], got[:nbound]
+        bad = [(int(first_row[t]), t) for t in range(ncons) if count[t]]
+        return 0, {"nfail": int(nfail.value), "count": count, "first_row": first_row, "bnd_got": got,
+                   "bnd_fail": [b for b in range(nbound) if int(got[b]) != int(keep["bnd_val"][b])], "first": min(bad) if bad else None, "ok": nfail.value == 0}
+
     def validity_ext(self):
         """ms_validity_ext: limbs per coefficient of the validity polynomial (0: none; 1; E after mix_air_ext)."""
         return int(self.L.ms_validity_ext(self.h))

@@ -184,6 +184,7 @@ int ms_mix_terms(ms_ctx* ctx, uint64_t r, int ncons, const uint32_t* term_begin,
                  const uint32_t* fac_row, int nexempt) { MS_ENTRY(ctx, B(ctx)->mix_terms(r, ncons, term_begin, coef, fac_begin, fac_poly, fac_row, nexempt)); }
 int ms_mix_air(ms_ctx* ctx, uint64_t r, const ms_air* air) { MS_ENTRY(ctx, B(ctx)->mix_air(r, air)); }
 int ms_mix_air_ext(ms_ctx* ctx, const uint64_t* r, const ms_air* air) { MS_ENTRY(ctx, B(ctx)->mix_air_ext(r, air)); }
+int ms_air_check(ms_ctx* ctx, const ms_air* air, uint64_t* nfail, uint64_t* cons_count, uint64_t* cons_first_row, uint64_t* bnd_got) { MS_ENTRY(ctx, B(ctx)->air_check(air, nfail, cons_count, cons_first_row, bnd_got)); }
 int ms_validity_ext(const ms_ctx* ctx) { return ctx ? B(ctx)->validity_ext_() : 0; }
 size_t ms_validity_len(const ms_ctx* ctx) { return ctx ? B(ctx)->validity_len_() : 0; }
 int ms_eval_ext(ms_ctx* ctx, const uint64_t* z, int q, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->eval_ext(z, q, out)); }

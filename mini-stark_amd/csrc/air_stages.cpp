@@ -1,6 +1,7 @@
 // air_stages.cpp — constraint columns by linear provenance, coset LDE + commitment (starks.rs:80-95), constraint mixing (starks.rs:108-119; build-defined ms_mix_cubic,
 // ms_mix_terms, ms_mix_air and ms_mix_air_ext: one host pipeline - gate, table, upload, compose launch, finish_mix - and a compose kernel each), DEEP-ALI evaluations (starks.rs:124-151).
 #include "ctx.hpp"
+#include "air_check.hpp"
 
 #include <algorithm>
 
@@ -375,14 +376,13 @@ int Ctx<F>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, 
 
 // ---- ms_mix_air: ms_mix_terms with an exemption set per constraint, periodic columns and boundary constraints, the program regrouped for mspoly::ComposeAirKernel -
 // the constraints that share an exemption set form one group, the boundary constraints at one row another.
-// Every MS_ERR_ARG refusal of the stage; fills pg
+// Every MS_ERR_ARG refusal of the stage (and of ms_air_check, whose c is not the LDE's); fills pg
 template <class F>
-int Ctx<F>::air_validate(const ms_air& a, AirProgram& pg) {
+int Ctx<F>::air_validate(const ms_air& a, AirProgram& pg, size_t c) {
   if (!a.term_begin || !a.coef || !a.fac_begin || !a.fac_poly || !a.fac_row || !a.ex_begin) return fail(MS_ERR_ARG, "mix_air: null array");
   if (a.ncons < 1 || a.ncons > 4096 || a.nperiodic > (u32)mspoly::AIR_MAX_PERIODIC || a.nbound > 4096) return fail(MS_ERR_ARG, "mix_air arguments");
   if ((a.nperiodic && (!a.per_begin || !a.per_val)) || (a.nbound && (!a.bnd_poly || !a.bnd_row || !a.bnd_val))) return fail(MS_ERR_ARG, "mix_air: null array");
   const u32 ncons = a.ncons;
-  const size_t c = lde_c;
   u32 d;                                     // ---- the term program: the conditions of mix_terms, the degree per constraint
   pg.deg.assign(ncons, 0);
   RQ(check_term_program("mix_air", ncons, a.term_begin, a.coef, a.fac_begin, pg.deg.data(), &d));
@@ -600,7 +600,7 @@ int Ctx<F>::mix_air(u64 r, const ms_air* air) {
   if (!air) return fail(MS_ERR_ARG, "mix_air: null program");
   const ms_air& a = *air;
   AirProgram pg; AirLayout lay; std::vector<T> dinv;
-  RQ(air_validate(a, pg));
+  RQ(air_validate(a, pg, lde_c));
   RQ(air_layout(a, pg, lay));
   RQ(coset_vanishing_inv("mix_air", dinv));
   std::vector<u8> tab(lay.bytes, 0);
@@ -629,7 +629,7 @@ int Ctx<F>::mix_air_ext(const u64* r, const ms_air* air) {
   if (!air) return fail(MS_ERR_ARG, "mix_air_ext: null program");
   const ms_air& a = *air;
   AirProgram pg; AirLayout lay; std::vector<T> dinv;
-  RQ(air_validate(a, pg));
+  RQ(air_validate(a, pg, lde_c));
   RQ(air_layout(a, pg, lay));
   RQ(coset_vanishing_inv("mix_air_ext", dinv));
   const AirLayoutExt lx = air_layout_ext(a, pg, lay);
@@ -651,6 +651,72 @@ int Ctx<F>::mix_air_ext(const u64* r, const ms_air* air) {
   next_bytes = (double)(lx.tfacs + lay.ngroups + E) * L * sizeof(T);
   CK(run<CK_>(K_MIX_AIR_EXT, grid1(L, CK_::THREADS * CK_::ITEMS), 1, CK_::THREADS, 0, cp));
   return finish_mix("mix_air_ext: a transition constraint fails on a non-exempt row or a boundary value is wrong (a limb of the pointwise quotients does not interpolate to a polynomial of VL coefficients)", lay.VL, E);
+}
+
+// ---- ms_air_check: the program of ms_mix_air on the rows of the trace domain (mspoly::AirCheckKernel).  Diagnostic: it writes buffers of its own only (d_chk_eval,
+// d_chk_tab, the table staging area) and changes nothing a later stage reads - apart from writing out lazily defined polynomials, as ms_poly_read does.
+// The device table: [constraints | terms | factors | exempt rows | periodic values | boundary (poly, row) | results: count[ncons], first row[ncons], value[nbound]],
+// uploaded in one copy that also sets the results to (0, N, 0); the results come back with one copy behind the launch.
+template <class F>
+int Ctx<F>::air_check(const ms_air* air, u64* nfail, u64* cons_count, u64* cons_first_row, u64* bnd_got) {
+  if (!have_trace) return fail(MS_ERR_STATE, "air_check before trace_commit");
+  if (sh_on) return fail(MS_ERR_STATE, "air_check: not available on a context with sharding on");
+  if (!air || !nfail) return fail(MS_ERR_ARG, "air_check: null program or null nfail");
+  const ms_air& a = *air;
+  const size_t c = have_polys ? (size_t)npolys : w + (size_t)naux;   // before ms_interpolate: the trace columns and the running columns behind them
+  AirProgram pg;
+  if (const int e = air_validate(a, pg, c)) { if (err.compare(0, 7, "mix_air") == 0) err.replace(0, 7, "air_check"); return e; }
+  typedef mspoly::AirCheckKernel<F> CKn; typedef mspoly::AirCheckCons AC; typedef mspoly::TermRec<F> TR; typedef mspoly::AirFac AF;
+  const u32 ncons = a.ncons, nex = a.ex_begin[ncons], nper = a.nperiodic ? a.per_begin[a.nperiodic] : 0;
+  const size_t nres = 2 * (size_t)ncons + a.nbound;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t off_t = up16((size_t)ncons * sizeof(AC)), off_f = up16(off_t + (size_t)pg.nterms * sizeof(TR)), off_x = up16(off_f + (size_t)pg.nfacs * sizeof(AF));
+  const size_t off_p = up16(off_x + (size_t)nex * sizeof(u32)), off_b = up16(off_p + (size_t)nper * sizeof(T)), off_r = up16(off_b + (size_t)a.nbound * 2 * sizeof(u32));
+  const size_t bytes = off_r + nres * sizeof(u64);
+  if (d_chk_tab.ensure(bytes) || (have_polys && d_chk_eval.ensure(c * N * sizeof(T)))) return fail(MS_ERR_NOMEM, "air_check buffers");
+  std::vector<u64> out(nres);
+  u8* tab;
+  RQ(tabs_host(bytes, &tab));
+  memset(tab, 0, bytes);
+  { AC* hc = reinterpret_cast<AC*>(tab); TR* ht = reinterpret_cast<TR*>(tab + off_t); AF* hf = reinterpret_cast<AF*>(tab + off_f);
+    u32* hx = reinterpret_cast<u32*>(tab + off_x); T* hp = reinterpret_cast<T*>(tab + off_p); u32* hb = reinterpret_cast<u32*>(tab + off_b); u64* hr = reinterpret_cast<u64*>(tab + off_r);
+    for (u32 t = 0; t < ncons; t++) { hc[t].nterms = a.term_begin[t + 1] - a.term_begin[t]; hc[t].nex = a.ex_begin[t + 1] - a.ex_begin[t]; hr[ncons + t] = (u64)N; }
+    for (u32 m = 0; m < pg.nterms; m++) { ht[m].coef = F::from_u64(a.coef[m]); ht[m].nfac = a.fac_begin[m + 1] - a.fac_begin[m]; }
+    for (u32 f = 0; f < pg.nfacs; f++) {
+      const u32 fp = a.fac_poly[f];
+      hf[f].rowoff = a.fac_row[f];
+      if (fp & MS_AIR_PERIODIC) { const u32 k = fp & ~MS_AIR_PERIODIC; hf[f].src = a.per_begin[k]; hf[f].mask = a.per_begin[k + 1] - a.per_begin[k] - 1; hf[f].kind = 1; }
+      else { hf[f].src = fp; hf[f].mask = (u32)(N - 1); hf[f].kind = 0; }
+    }
+    for (u32 k = 0; k < nex; k++) hx[k] = a.ex_row[k];
+    for (u32 k = 0; k < nper; k++) hp[k] = F::from_u64(a.per_val[k]);
+    for (u32 b = 0; b < a.nbound; b++) { hb[2 * b] = a.bnd_poly[b]; hb[2 * b + 1] = a.bnd_row[b]; } }
+  // everything is decided: from here on only the runtime can fail
+  const T* cols = d_polys.as<T>();
+  if (have_polys) {   // the polynomials' values on the trace domain: ONE forward transform of all of them, out of place
+    for (size_t i = 0; i < c; i++) RQ(materialize((int)i));
+    RQ(ntt_run(ctz64(N), false, d_polys.as<T>(), N, N, d_chk_eval.as<T>(), N, c));
+    cols = d_chk_eval.as<T>();
+  }
+  CK(msrt::h2d(d_chk_tab.p, tab, bytes, stream));
+  const u8* dt = d_chk_tab.as<u8>();
+  typename CKn::Params cp;
+  cp.cols = cols; cp.N = N; cp.ncons = ncons; cp.nbound = a.nbound;
+  cp.cons = reinterpret_cast<const AC*>(dt); cp.terms = reinterpret_cast<const TR*>(dt + off_t); cp.facs = reinterpret_cast<const AF*>(dt + off_f);
+  cp.ex_rows = reinterpret_cast<const u32*>(dt + off_x); cp.ptab = reinterpret_cast<const T*>(dt + off_p); cp.bnd = reinterpret_cast<const u32*>(dt + off_b);
+  cp.count = reinterpret_cast<unsigned long long*>(d_chk_tab.as<u8>() + off_r); cp.first = cp.count + ncons; cp.bnd_got = cp.first + ncons;
+  next_bytes = (double)pg.nfacs * N * sizeof(T);
+  CK(run_coop<CKn>(K_AIR_CHECK, grid1(N, CKn::THREADS * CKn::ITEMS), CKn::THREADS, CKn::lds_bytes(), cp));
+  CK(msrt::d2h(out.data(), cp.count, nres * sizeof(u64), stream));
+  CK(msrt::sync(stream));
+  u64 nf = 0;
+  for (u32 t = 0; t < ncons; t++) if (out[t]) nf++;
+  for (u32 b = 0; b < a.nbound; b++) if (out[2 * (size_t)ncons + b] != a.bnd_val[b]) nf++;
+  if (cons_count) memcpy(cons_count, out.data(), (size_t)ncons * sizeof(u64));
+  if (cons_first_row) memcpy(cons_first_row, out.data() + ncons, (size_t)ncons * sizeof(u64));
+  if (bnd_got && a.nbound) memcpy(bnd_got, out.data() + 2 * (size_t)ncons, (size_t)a.nbound * sizeof(u64));
+  *nfail = nf;
+  return MS_OK;
 }
 
 // trimmed length of a base-field coefficient vector
@@ -822,6 +888,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   template int Ctx<FF>::mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt); \
   template int Ctx<FF>::mix_air(u64 r, const ms_air* air); \
   template int Ctx<FF>::mix_air_ext(const u64* r, const ms_air* air); \
+  template int Ctx<FF>::air_check(const ms_air* air, u64* nfail, u64* cons_count, u64* cons_first_row, u64* bnd_got); \
   template int Ctx<FF>::degree_launch1(const Ctx<FF>::T* poly, size_t n, unsigned long long** dres_out); \
   template int Ctx<FF>::validity_read(u64* out); \
   template int Ctx<FF>::shard_combine_launch(size_t off, size_t rank_stride, u32 n, const Ctx<FF>::XE& zstep, Ctx<FF>::T* out); \

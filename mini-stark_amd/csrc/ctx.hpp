@@ -3,8 +3,8 @@
 // instantiated - and its device code generated - in the unit that launches it, so the units also partition the device code:
 //   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / aux_running / interpolate / polys_*  (transpose, narrow / widen, running-column kernels)
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
-//   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels)
-//                    one host pipeline, a compose kernel each), DEEP-ALI evaluations
+//   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels,
+//                    one host pipeline, a compose kernel each), the trace-domain check of their program, DEEP-ALI evaluations     the check kernel of air_check.hpp)
 //   ntt_plan.cpp     NTT plans (shape, instances, tables), coset evaluation, ms_ntt / ms_coset_lde                        (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
@@ -132,6 +132,7 @@ struct CtxBase {
   virtual int mix_terms(u64 r, int ncons, const u32* term_begin, const u64* coef, const u32* fac_begin, const u32* fac_poly, const u32* fac_row, int nexempt) = 0;
   virtual int mix_air(u64 r, const ms_air* air) = 0;
   virtual int mix_air_ext(const u64* r, const ms_air* air) = 0;
+  virtual int air_check(const ms_air* air, u64* nfail, u64* cons_count, u64* cons_first_row, u64* bnd_got) = 0;
   virtual int validity_ext_() const = 0;
   virtual size_t validity_len_() const = 0;
   virtual int validity_read(u64* out) = 0;
@@ -235,7 +236,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_MIX_AIR_EXT, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_MIX_AIR_EXT, K_AIR_CHECK, K_COUNT };
   struct ProfRec { int kid, sub; EventOwner a, b; double bytes; bool part; };   // (the records of a profile never ended go with the context)
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -591,7 +592,7 @@ template <class F> struct Ctx : CtxBase {
     std::vector<u32> brows, brow_of;         // the distinct boundary rows (one boundary group each); per boundary constraint: its row's index
   };
   struct AirLayout { size_t VL, ngroups, tterms, tfacs, off_t, off_f, off_x, off_p, off_d, bytes; };   // [groups | terms | factors | exemption roots | periodic tables | den_inv]
-  int air_validate(const ms_air& a, AirProgram& pg);
+  int air_validate(const ms_air& a, AirProgram& pg, size_t c);   // c: the polynomials (columns) an index may name
   int air_layout(const ms_air& a, const AirProgram& pg, AirLayout& lay);
   void air_table(u64 r, const ms_air& a, const AirProgram& pg, const AirLayout& lay, const std::vector<T>& dinv, u8* tab);
   // the table of ComposeAirExtKernel: [groups | segments | terms | factors | exemption roots | periodic tables | den_inv]; the last three as air_table writes them
@@ -600,6 +601,11 @@ template <class F> struct Ctx : CtxBase {
   void air_table_ext(const XE& r, const ms_air& a, const AirProgram& pg, const AirLayoutExt& lx, const std::vector<T>& dinv, u8* tab);
   void air_periodic_tables(const ms_air& a, const AirProgram& pg, T* hp);   // periodic column k on the domain, at hp + pg.per_off[k] (both tables)
   int air_inv_table(T gL_step);
+  // build-defined, diagnostic: the same program on the ROWS of the trace domain (include/ministark.h; kernel: mspoly::AirCheckKernel, air_check.hpp) - per constraint the
+  // number of violating rows and the first one, per boundary constraint the value the trace has.  Before ms_interpolate the kernel reads the columns of d_polys as
+  // they stand; afterwards one forward transform of all polynomials into d_chk_eval first.  Buffers of its own: nothing another stage reads is written
+  DevBuf d_chk_eval, d_chk_tab;
+  int air_check(const ms_air* air, u64* nfail, u64* cons_count, u64* cons_first_row, u64* bnd_got) override;
   // ---- the pipeline the three build-defined mix stages share (air_stages.cpp): gate, [the stage's own checks and host table], upload, [its compose launch], finish.
   // `who` is the entry point, for the messages
   int mix_gate(const char* who, u64 r);

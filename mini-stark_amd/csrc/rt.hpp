@@ -246,6 +246,15 @@ inline int launch_coop(Stream*, unsigned gx, unsigned gy, int threads, size_t ld
 MS_DEV void atomic_min_u64(unsigned long long* a, unsigned long long v) { if (v < *a) *a = v; }
 MS_DEV void atomic_max_u64(unsigned long long* a, unsigned long long v) { if (v > *a) *a = v; }
 MS_DEV unsigned atomic_add_u32(unsigned* a, unsigned v) { unsigned o = *a; *a = o + v; return o; }
+MS_DEV void atomic_add_u64(unsigned long long* a, unsigned long long v) { *a += v; }
+template <class U> MS_DEV U load_uniform(const U* p) { return *p; }   // (the HIP half reads such a record with a scalar load)
+// true if the predicate holds on any lane of the caller's 64-lane wave, in a COOPERATIVE kernel whose wave takes the vote as a whole (every lane that has not returned
+// calls it, like an exchange): an OR butterfly over wave_shfl_xor - the lanes of a wave get the same answer, so a branch on it keeps their exchanges in step
+inline bool wave_vote_any(bool pred) {
+  unsigned long long v = pred ? 1u : 0u;
+  for (int s = 1; s < 64; s <<= 1) v |= wave_shfl_xor(v, s);
+  return v != 0;
+}
 // one slot of a device list per lane that wants one (call from all live lanes)
 MS_DEV unsigned wave_alloc_slot(unsigned* counter, bool want) { if (!want) return 0; unsigned o = *counter; *counter = o + 1; return o; }
 // true if the predicate holds on any live lane of the wave (emulation: a wave of one lane — results must not depend on it)
@@ -595,8 +604,28 @@ MS_DEV int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 MS_DEV void atomic_min_u64(unsigned long long* a, unsigned long long v) { atomicMin(a, v); }
 MS_DEV void atomic_max_u64(unsigned long long* a, unsigned long long v) { atomicMax(a, v); }
 MS_DEV unsigned atomic_add_u32(unsigned* a, unsigned v) { return atomicAdd(a, v); }
+MS_DEV void atomic_add_u64(unsigned long long* a, unsigned long long v) { atomicAdd(a, v); }
 // true if the predicate holds on any live lane of the wave
 MS_DEV bool wave_any(bool pred) { return __any(pred) != 0; }
+// ... the same as a vote the whole wave takes (the emulation's form is a lane exchange): uniform over the wave, a branch on it is a scalar branch
+MS_DEV bool wave_vote_any(bool pred) { return __any(pred) != 0; }
+// A record of a table that NO launch writes, at an address every lane holds alike, read through the constant address space: a scalar load even where the kernel has
+// stores or atomics in front of it (behind those the compiler reads plain global memory lane by lane, since they might have changed it)
+template <class U> MS_DEV U load_uniform(const U* p) {
+  static_assert(sizeof(U) % 4 == 0 && alignof(U) >= 4, "whole dwords");
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) unsigned CW;
+  CW* q = (CW*)p;
+  unsigned w[sizeof(U) / 4];
+#pragma unroll
+  for (unsigned k = 0; k < sizeof(U) / 4; k++) w[k] = q[k];
+  U r;
+  __builtin_memcpy(&r, w, sizeof(U));
+  return r;
+#else
+  return *p;
+#endif
+}
 // one slot of a device list per lane that wants one (call from all live lanes): ONE atomic per wave, not per lane
 MS_DEV unsigned wave_alloc_slot(unsigned* counter, bool want) {
   const unsigned long long mask = __ballot(want);
