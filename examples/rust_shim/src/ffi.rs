@@ -128,6 +128,10 @@ extern "C" {
     pub fn ms_fri_proof_wait(ctx: *mut ms_ctx) -> c_int;
     pub fn ms_io_engine(ctx: *const ms_ctx) -> c_int;
     pub fn ms_io_runtime_path() -> *const c_char;
+    // ---- Merkle openings by index (build-defined): tree 0 trace / 1 LDE / 2 FRI round `round`; MerklePaths of the leaf groups `index`, concatenated.  out = null, cap = 0: size query
+    pub fn ms_tree_open(ctx: *mut ms_ctx, tree: c_int, round: c_int, index: *const u64, n: usize, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    // ---- the compact query phase (build-defined): the MSFI blob - openings by position, the last round's polynomial in the clear
+    pub fn ms_fri_query_index(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- proof-of-work grinding (build-defined): the smallest nonce of [start, start + limit) whose digest D(seed || nonce LE) starts with `bits` zero bits
     pub fn ms_grind(ctx: *mut ms_ctx, seed: *const u8 /* [32] */, bits: u32, start: u64, limit: u64, nonce: *mut u64) -> c_int;
     // ---- Tree trait (src/merkle.rs:8-30) on its own

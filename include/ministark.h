@@ -384,6 +384,47 @@ int ms_fri_query_into(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, 
  * MerklePath = u64 leaf_index | lpn*E u64 leaf_neighbours | u64 nlevels | nlevels*ic*32 bytes
  *              (merkle.rs:272-298; leaf located BY VALUE, first match, quirk Q7). */
 
+/* ---- Merkle openings BY INDEX (BUILD-DEFINED; the reference opens by value only and never opens the trace or the LDE tree) ------------------------------------
+ * ms_tree_open writes the MerklePaths (layout above, ic = 2) of n leaf groups of one of the trees the context holds, concatenated in request order, to `out`.
+ * index[k] is a LEAF-GROUP index: the tree's leaf k hashes the lpn consecutive elements [index * lpn, (index + 1) * lpn) of the committed vector (for the trace and
+ * the LDE tree committed with lpn = the number of columns that is row `index`; for a FRI round tree, lpn = 2, it is the codeword positions 2 index and 2 index + 1).
+ * The path's leaf_index word is index[k] * lpn, its leaf_neighbours are the group's lpn elements (E limbs each for a FRI tree, one otherwise).  A linear LDE column
+ * that is never written to memory is opened with the value that was hashed.  Duplicate and unsorted indices are allowed.  Every path of one call has the same size;
+ * *len receives n times that.  out = NULL with cap = 0 is a size query (MS_OK, nothing launched); cap < *len returns MS_ERR_ARG and computes nothing.
+ *   MS_TREE_TRACE  valid from ms_trace_commit[_device] until ms_interpolate: the rows are transformed in place there, afterwards the call returns MS_ERR_STATE
+ *                  (the tree covers the w trace columns; running columns of ms_aux_running are not in it).
+ *   MS_TREE_LDE    valid from ms_lde_commit until the next ms_trace_commit, ms_polys_lincomb / ms_polys_append, ms_bench_lde or ms_lde_commit.
+ *   MS_TREE_FRI    round < the rounds committed so far, from ms_fri_begin on (until the next mix stage or trace).  `round` is 0 for the other trees.
+ * Errors, all decided before anything is launched (ONE launch per call, on the context's stream; the call returns with the bytes in `out`):
+ *   MS_ERR_ARG           null index or len; n outside 1..65536; an unknown tree id; round out of range; out = NULL with cap != 0; cap too small.
+ *   MS_ERR_OUT_OF_RANGE  an index at or above the number of leaf groups.
+ *   MS_ERR_STATE         the tree does not exist (yet, or any more); a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1), as ms_aux_running.
+ * The context is unchanged: a proof with such calls between its stages comes out byte for byte as without them. */
+typedef enum { MS_TREE_TRACE = 0, MS_TREE_LDE = 1, MS_TREE_FRI = 2 } ms_tree_id;
+int ms_tree_open(ms_ctx* ctx, int tree, int round /* MS_TREE_FRI only, else 0 */, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len);
+/* The COMPACT query phase: what ms_fri_query opens by value, opened by position, and nothing else.  Valid wherever ms_fri_query is (after the commit phase, before or
+ * after ms_fri_query, any number of times); it leaves the FRI state, the MSFP blob and a later ms_fri_query's bytes untouched.  MS_ERR_STATE on a context with sharding
+ * on.  With R rounds and D_i the domain size of round i (ms_fri_round_info; D_(i+1) = D_i / 2):
+ *   b_(0,j) = betas[j] mod D_0 - a plain modulus: quirk Q6's `>` (a beta equal to D_0 stays D_0 in ms_fri_query) is NOT carried over - and b_(i+1,j) = b_(i,j) mod D_(i+1).
+ *   Window i (0 <= i < R - 1), query j opens the positions b = b_(i,j) and (b + D_i / 2) mod D_i of round i's codeword in round i's tree.
+ *   x1 = g_i^b, x2 = -x1, x3 = x1^2 are the verifier's to compute; they are not shipped.
+ * MSFI layout, u64 little-endian words:
+ *   'MSFI' (0x4946534D) | E | R | nq | D_0 | nfinal            nfinal = the last round's ncoef
+ *   nfinal * E limbs                                            the last round's polynomial, in the clear
+ *   for each window in order, for each beta in order:  MerklePath(first position), MerklePath(second position)
+ * A path's leaf_index word is the opened POSITION (as in MSFP, where it is the position found by value: for a codeword of distinct values the two blobs' paths are
+ * the same bytes); its group is position / 2 and the opened value y is leaf_neighbours[position & 1].  y3 of window i is not shipped: it is window i + 1's y1 of the
+ * same query, and for the last window the final polynomial at x3.  No points, no quotients.  R = 1: header and final polynomial only.
+ * What it binds (msh_fri_index_verify, ministark_host.h): every opened value to its position under the round's root, each window's fold to the next window's opened
+ * value, the last fold to the final polynomial, and the final polynomial's length to D_(R-1) / blowup.  Not bound here, as in MSFP: round 0's root to the LDE tree
+ * (whole-proof integration is a follow-up: DESIGN.md).
+ * One launch whatever R and nq (openings and final polynomial together); no pass over any codeword or polynomial.  nq outside 1..4096: MS_ERR_ARG.  Size query and
+ * cap rule as ms_tree_open.
+ * Measured (tools/fri_index_bench.py, profiles/fri_index.json; one paired run on one MI355X, Goldilocks, 2^20 rows, blowup 8, 23 rounds, 2 queries, both phases behind
+ * the same commit phase): ms_fri_query 0.370 ms per call with the blob left in HBM - 14 launches, 0.346 ms of kernel time, 67 180 512 bytes (22.2 ms with the read-back);
+ * ms_fri_query_index 0.052 ms per call with the bytes at the caller - 1 launch, 0.0062 ms of kernel time, 69 040 bytes; one ms_tree_open of 64 LDE rows 0.039 ms. */
+int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
+
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
  * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI
  * queries (ms_num_queries_grind).  The transcript stays with the caller: the library is given a seed and returns the nonce.

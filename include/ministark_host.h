@@ -86,6 +86,22 @@ int msh_stark_verify_mssp(const msh_stark* h, const uint64_t* constrains, size_t
 /* FriProof (fri.rs:17-22) from its MSFP bytes: the compiled twin of the Rust shim's FriProof::from_msfp.  windows = rounds - 1; returns the
  * number of (window, query) records (windows * nq; the first `cap` are written to `out`) or -1 if the bytes do not parse exactly. */
 int msh_fri_proof_parse(const uint8_t* blob, size_t len, uint32_t e, uint32_t windows, uint32_t nq, msh_fri_query_view* out, size_t cap);
+/* The verifying side of the openings by index (ministark.h: ms_tree_open, ms_fri_query_index; build-defined, no reference counterpart).
+ * msh_merkle_path_check_index is check_proof made POSITIONAL, on one serialised MerklePath (ic = 2, any lpn, ext in {1, E} limbs per element) of at most `avail`
+ * bytes: the path's leaf_index word must be expect_leaf_group * lpn, its leaf_neighbours canonical; at level l the running digest must sit in slot
+ * (expect_leaf_group >> l) & 1 - "either half" is not accepted -, the path must be as high as the position needs and end at `root`.  *used receives the path's
+ * bytes.  1 accepted, 0 rejected, < 0 a null argument, an unknown digest id or field, ext or lpn out of range. */
+int msh_merkle_path_check_index(int digest_id, int field, int ext, size_t lpn, int zero_display_empty, const uint8_t root[32], const uint8_t* path, size_t avail,
+                                uint64_t expect_leaf_group, size_t* used);
+/* The MSFI blob of ms_fri_query_index against the commit phase: roots rounds * 32 bytes (round 0 first), z (rounds - 1) * E limbs, B (rounds - 1) * 2 * E limbs,
+ * alpha (rounds - 1) * E limbs - what ms_fri_deep / ms_fri_fold_commit took and returned -, and the nq betas.  It parses the blob exactly (a header that is not the
+ * verifier's E, rounds and nq or names no domain that can be halved rounds - 1 times, a non-canonical limb, a path of another height than its round's, trailing
+ * bytes: rejected), checks nfinal <= max(1, D_(R-1) / blowup), checks every path at ITS position (leaf_index = the position, group = position / 2) under its
+ * round's root, and per (window, query) the DEEP-adjusted linearity check of Stark::verify's FRI step with y3 = the next window's opened value, for the last window
+ * the final polynomial at x3: the line through (x1, y1), (x2, y2) at alpha_i equals y3 (x3 - z_i) + B_i0 + B_i1 alpha_i.  1 accepted, 0 rejected (reason in `why`),
+ * < 0 malformed arguments. */
+int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, uint64_t blowup, const uint8_t* roots, size_t rounds, const uint64_t* z, const uint64_t* B,
+                         const uint64_t* alpha, const uint64_t* betas, size_t nq, const uint8_t* blob, size_t len, char* why, size_t why_cap);
 /* D(data) by this library's own host implementation of an ms_digest_id (SHA-256, BLAKE2s-256, BLAKE3 with its chunk tree, Keccak-256, SHA3-256: any length): 0, -1 for an unknown id (3 is unassigned) */
 int msh_hash(int digest_id, const uint8_t* data, size_t len, uint8_t out[32]);
 /* The verifying side of ms_mix_terms (ministark.h; build-defined, no reference counterpart): the value validity(z) must have at an extension point z (E limbs),

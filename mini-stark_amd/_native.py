@@ -21,6 +21,7 @@ FLAG_DIGEST_KECCAK256 = 0x20   # D = Keccak-256 (original padding: Ethereum's); 
 FLAG_DIGEST_SHA3_256 = 0x40   # D = SHA3-256 (FIPS 202)
 DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3 = 0, 1, 2   # ms_digest_id
 DIGEST_KECCAK256, DIGEST_SHA3_256 = 4, 5   # (3 is unassigned)
+TREE_TRACE, TREE_LDE, TREE_FRI = 0, 1, 2   # ms_tree_id
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -641,6 +642,25 @@ class Context:
         buf = np.zeros(max(1, n), dtype=np.uint8)
         self.check(self.L.ms_fri_proof_read(self.h, buf.ctypes.data_as(_u8p)))
         return buf[:n].tobytes()
+
+    # ---- openings by index (BUILD-DEFINED; include/ministark.h) -----------------------
+    def _sized_bytes(self, call):
+        """the size query of an entry point with (out, cap, len) arguments, then the call itself: bytes, or MsError"""
+        n = C.c_size_t(0)
+        self.check(call(None, C.c_size_t(0), C.byref(n)))
+        buf = np.zeros(max(1, n.value), dtype=np.uint8)
+        self.check(call(buf.ctypes.data_as(_u8p), C.c_size_t(n.value), C.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def tree_open(self, tree, indices, round=0) -> bytes:
+        """ms_tree_open: the MerklePaths of the leaf groups `indices` of TREE_TRACE / TREE_LDE / TREE_FRI (round `round`), concatenated in request order."""
+        ix, ip = _u64(indices)
+        return self._sized_bytes(lambda out, cap, n: self.L.ms_tree_open(self.h, C.c_int(tree), C.c_int(round), ip, C.c_size_t(ix.size), out, cap, n))
+
+    def fri_query_index(self, betas) -> bytes:
+        """ms_fri_query_index: the compact query phase, the MSFI blob (openings by position, the last round's polynomial in the clear)."""
+        b, bp = _u64(betas)
+        return self._sized_bytes(lambda out, cap, n: self.L.ms_fri_query_index(self.h, bp, C.c_int(b.size), out, cap, n))
 
     # ---- standalone ----------------------------------------------------------------
     def merkle_commit(self, leafs, ext=1, lpn=2, ic=2):

@@ -212,6 +212,8 @@ int ms_merkle_commit(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ex
 int ms_merkle_prove(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext, size_t lpn, const uint64_t* leaf, uint8_t* out, size_t cap, size_t* len) {
   MS_ENTRY(ctx, B(ctx)->merkle_prove(leafs, leaf_num, ext, lpn, leaf, out, cap, len));
 }
+int ms_tree_open(ms_ctx* ctx, int tree, int round, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->tree_open(tree, round, index, n, out, cap, len)); }
+int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_index(betas, nq, out, cap, len)); }
 int ms_grind(ms_ctx* ctx, const uint8_t seed[32], uint32_t bits, uint64_t start, uint64_t limit, uint64_t* nonce) { MS_ENTRY(ctx, B(ctx)->grind(seed, bits, start, limit, nonce)); }
 int ms_ntt(ms_ctx* ctx, uint64_t* data, size_t n, size_t batch, int inverse) { MS_ENTRY(ctx, B(ctx)->ntt(data, n, batch, inverse)); }
 int ms_coset_lde(ms_ctx* ctx, const uint64_t* c, size_t ncoef, size_t batch, uint64_t shift, uint64_t* out, size_t L) { MS_ENTRY(ctx, B(ctx)->coset_lde(c, ncoef, batch, shift, out, L)); }

@@ -8,7 +8,7 @@
 //   ntt_plan.cpp     NTT plans (shape, instances, tables), coset evaluation, ms_ntt / ms_coset_lde                        (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
-//   fri_query.cpp    FRI query phase, proof read-back, ms_merkle_prove                                              (find-first, path, copy kernels)
+//   fri_query.cpp    FRI query phase, ms_merkle_prove, openings by index (ms_tree_open, ms_fri_query_index)        (find-first, path, open, copy kernels)
 //   shard.cpp        one proof over several ranks: exchange (RCCL or callback), ms_set_shard*
 //   abi.cpp          the extern "C" entry points and their never-unwind guard
 // Built with hipcc for gfx950 into libministark.so (csrc/Makefile).  There is no CPU fallback.
@@ -151,6 +151,8 @@ struct CtxBase {
   virtual int io_engine() const = 0;
   virtual int merkle_commit(const u64* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, u8* nodes_out, size_t cap, size_t* nn, u8* root) = 0;
   virtual int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) = 0;
+  virtual int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) = 0;
+  virtual int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
   virtual int grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce) = 0;
   virtual int ntt(u64* data, size_t n, size_t batch, int inverse) = 0;
   virtual int coset_lde(const u64* coeffs, size_t ncoef, size_t batch, u64 shift, u64* out, size_t L) = 0;
@@ -767,6 +769,16 @@ template <class F> struct Ctx : CtxBase {
   template <int EL>
   int merkle_prove_t(const u64* leafs, size_t leaf_num, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len);
   int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) override;
+  // ------------------------------------------------------------------ build-defined: Merkle openings by index (include/ministark.h; kernel: msmerkle::OpenKernel, host side: fri_query.cpp)
+  // ms_tree_open and ms_fri_query_index: a host-built job table through the page-locked staging area, ONE launch, the bytes copied to the caller.  Buffers of their own
+  // (d_open: job table | output), nothing another stage reads is written.  `view`: the leaf view and the nodes of a tree this context holds, or why there is none
+  DevBuf d_open;
+  struct OpenView { const T* base = nullptr; size_t col_stride = 0, row_stride = 0, limb_stride = 0; const msmerkle::LinColSpec* lin = nullptr; const u32* nodes = nullptr;
+                    size_t ngroups = 0; u32 width = 1, lpn = 1, nlevels = 0; int el = 1; };
+  int open_view(int tree, int round, OpenView* v);
+  template <int EL> int open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_t out_bytes, const Round* fin, size_t fin_off, u8* out);
+  int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) override;
+  int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
   // ------------------------------------------------------------------ build-defined: proof-of-work grinding (include/ministark.h; kernel: grind.hpp, host side: merkle_tree.cpp)
   u64 grind_launch_max = (u64)1 << 30;   // MS_GRIND_LAUNCH_MAX: most nonces of one launch
   unsigned grind_grid = 0;               // MS_GRIND_GRID: workgroups of a launch (0: by the device's compute units at the kernel's occupancy)

@@ -1,4 +1,5 @@
-// fri_query.cpp — the FRI query phase (fri.rs:115-189, merkle.rs:216-288) as a handful of batched launches over device job tables, and the standalone ms_merkle_prove.  (The proof's way to the host: io.cpp.)
+// fri_query.cpp — the FRI query phase (fri.rs:115-189, merkle.rs:216-288) as a handful of batched launches over device job tables, the standalone ms_merkle_prove,
+// and the build-defined openings by index (ms_tree_open, ms_fri_query_index).  (The proof's way to the host: io.cpp.)
 #include "ctx.hpp"
 
 namespace msctx {
@@ -323,6 +324,132 @@ int Ctx<F>::fri_query(const u64* betas, int nq, u8* ext_out, size_t ext_cap, siz
   return MS_OK;
 }
 
+// ------------------------------------------------------------------ build-defined: Merkle openings by index (include/ministark.h)
+// The view LeafHashKernel hashed and the node array of one of the context's trees; MS_ERR_STATE with the reason when the tree is not there (any more)
+template <class F>
+int Ctx<F>::open_view(int tree, int round, OpenView* v) {
+  OpenView o;
+  const TreeShape* ts = nullptr;
+  if (tree == MS_TREE_TRACE) {
+    if (!have_trace) return fail(MS_ERR_STATE, "tree_open: no committed trace");
+    if (have_polys) return fail(MS_ERR_STATE, "tree_open: ms_interpolate has transformed the trace rows in place");
+    ts = &trace_ts;
+    o.base = d_polys.template as<T>(); o.col_stride = N; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)w; o.nodes = d_trace_nodes.template as<u32>();
+  } else if (tree == MS_TREE_LDE) {
+    if (!have_lde) return fail(MS_ERR_STATE, "tree_open: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+    ts = &lde_ts;
+    o.base = d_lde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)lde_c; o.lin = lde_lin(); o.nodes = d_lde_nodes.template as<u32>();
+  } else if (tree == MS_TREE_FRI) {
+    if (nrounds_done == 0) return fail(MS_ERR_STATE, "tree_open: no FRI round committed (ms_fri_begin)");
+    if (round < 0 || (size_t)round >= nrounds_done) return fail(MS_ERR_ARG, "tree_open: round index");
+    const Round* r = rounds[round].get();
+    ts = &r->ts;
+    o.base = r->cw.template as<T>(); o.col_stride = 0; o.row_stride = 1; o.limb_stride = r->D; o.width = 1; o.nodes = r->nodes.template as<u32>(); o.el = E;
+  } else return fail(MS_ERR_ARG, "tree_open: unknown tree id");
+  if (ts->sharded || ts->ic != 2) return fail(MS_ERR_STATE, "tree_open: the tree is distributed over the ranks");
+  o.lpn = (u32)ts->lpn; o.ngroups = ts->leaf_num / ts->lpn; o.nlevels = (u32)(ts->levels - 1);
+  *v = o;
+  return 0;
+}
+
+// The one launch of both entry points.  jobs[k].out holds the OFFSET of the path in the output; `fin` (ms_fri_query_index): the round whose polynomial goes to
+// offset 0 of the output in the same launch.  Ends with the copy to the caller and the stream synchronisation.
+template <class F> template <int EL>
+int Ctx<F>::open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_t out_bytes, const Round* fin, size_t fin_off, u8* out) {
+  typedef msmerkle::OpenJob<F, EL> OJ;
+  typedef msmerkle::OpenKernel<F, EL> OKn;
+  const size_t tab_bytes = (jobs.size() * sizeof(OJ) + 255) & ~(size_t)255;
+  if (d_open.ensure(tab_bytes + out_bytes + 8)) return fail(MS_ERR_NOMEM, "opening buffers");
+  RQ(res.join_side());   // (MS_FLAG_LATENCY: nothing of a round's side stream is still writing what is read here)
+  u8* tab;
+  RQ(tabs_host(tab_bytes + 8, &tab));
+  u8* dout = d_open.template as<u8>() + tab_bytes;
+  if (!jobs.empty()) {
+    memcpy(tab, jobs.data(), jobs.size() * sizeof(OJ));
+    OJ* hj = reinterpret_cast<OJ*>(tab);
+    for (size_t k = 0; k < jobs.size(); k++) hj[k].out = dout + reinterpret_cast<size_t>(jobs[k].out);
+    CK(msrt::h2d(d_open.p, tab, jobs.size() * sizeof(OJ), stream));   // page-locked source; the stage ends with a synchronisation
+  }
+  typename OKn::Params pk{d_open.template as<const OJ>(), (u32)jobs.size(), nullptr, 0, 0, nullptr};
+  size_t fin_wgs = 0;
+  if (fin && fin->ncoef) {
+    pk.fin = fin->poly.template as<T>(); pk.fin_stride = fin->cap; pk.fin_n = fin->ncoef; pk.fin_out = reinterpret_cast<u64*>(dout + fin_off);
+    fin_wgs = (fin->ncoef * (size_t)EL + OKn::FIN_WORDS - 1) / OKn::FIN_WORDS;
+  }
+  CK(run<OKn>(K_PATH, (unsigned)(jobs.size() + fin_wgs), 1, OKn::THREADS, 0, pk));   // one wave per opening
+  if (out_bytes) CK(msrt::d2h(out, dout, out_bytes, stream));
+  CK(msrt::sync(stream));
+  return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) {
+  if (!index || !len || (!out && cap)) return fail(MS_ERR_ARG, "tree_open: null argument");
+  if (n < 1 || n > 65536) return fail(MS_ERR_ARG, "tree_open: n outside 1..65536");
+  if (tree != MS_TREE_TRACE && tree != MS_TREE_LDE && tree != MS_TREE_FRI) return fail(MS_ERR_ARG, "tree_open: unknown tree id");
+  if (sh_on) return fail(MS_ERR_STATE, "tree_open: not available on a context with sharding on");
+  OpenView v;
+  RQ(open_view(tree, round, &v));
+  const size_t pb = 8 + (size_t)v.lpn * v.el * 8 + 8 + (size_t)v.nlevels * 64, total = n * pb;
+  *len = total;
+  if (!out) return MS_OK;   // size query
+  if (cap < total) return fail(MS_ERR_ARG, "tree_open: buffer too small (the size needed is in *len)");
+  for (size_t k = 0; k < n; k++) if (index[k] >= v.ngroups) return fail(MS_ERR_OUT_OF_RANGE, "tree_open: leaf-group index out of range");
+  auto go = [&](auto el) -> int {
+    constexpr int EL = decltype(el)::value;
+    std::vector<msmerkle::OpenJob<F, EL>> jobs(n);
+    for (size_t k = 0; k < n; k++)
+      jobs[k] = msmerkle::OpenJob<F, EL>{v.base, v.col_stride, v.row_stride, v.limb_stride, v.lin, v.nodes, v.ngroups, (size_t)index[k], index[k] * v.lpn, v.width, v.lpn, v.nlevels, 0,
+                                         reinterpret_cast<unsigned char*>(k * pb)};
+    return open_launch<EL>(jobs, total, nullptr, 0, out);
+  };
+  return v.el == 1 ? go(std::integral_constant<int, 1>()) : go(std::integral_constant<int, E>());
+}
+
+// The compact query phase (MSFI, include/ministark.h): the positions ms_fri_query opens by value, opened by index, and the last round's polynomial
+template <class F>
+int Ctx<F>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  if (nrounds_done != fri_rounds || fri_rounds == 0) return fail(MS_ERR_STATE, "fri_query_index before the commit phase finished");
+  if (sh_on) return fail(MS_ERR_STATE, "fri_query_index: not available on a context with sharding on");
+  if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "fri_query_index: null argument");
+  if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "fri_query_index: nq outside 1..4096");
+  const size_t R = fri_rounds, W = R - 1;
+  std::vector<OpenView> views(W);
+  std::vector<size_t> pb(W);
+  for (size_t i = 0; i < W; i++) {
+    if (rounds[i]->D / 2 != rounds[i + 1]->D) return fail(MS_ERR_SHAPE, "round domains do not halve (fri.rs:134-137)");
+    RQ(open_view(MS_TREE_FRI, (int)i, &views[i]));
+    pb[i] = 8 + 2 * (size_t)E * 8 + 8 + (size_t)views[i].nlevels * 64;
+  }
+  const Round* last = rounds[W].get();
+  const size_t head = 6 * 8, fin_bytes = last->ncoef * (size_t)E * 8;
+  size_t pos = head + fin_bytes;
+  for (size_t i = 0; i < W; i++) pos += pb[i] * 2 * (size_t)nq;
+  *len = pos;
+  if (!out) return MS_OK;   // size query
+  if (cap < pos) return fail(MS_ERR_ARG, "fri_query_index: buffer too small (the size needed is in *len)");
+  std::vector<msmerkle::OpenJob<F, E>> jobs;
+  jobs.reserve(W * (size_t)nq * 2);
+  std::vector<u64> b(betas, betas + nq);
+  size_t off = fin_bytes;   // offsets in the device image of the blob, which starts behind the header
+  for (size_t i = 0; i < W; i++) {
+    const OpenView& v = views[i];
+    const u64 D = rounds[i]->D;
+    for (int j = 0; j < nq; j++) {
+      b[j] %= D;   // b_(0,j) = beta mod D_0, b_(i+1,j) = b_(i,j) mod D_(i+1): a plain modulus
+      for (int s = 0; s < 2; s++) {
+        const u64 position = s ? (b[j] + D / 2) % D : b[j];
+        jobs.push_back(msmerkle::OpenJob<F, E>{v.base, v.col_stride, v.row_stride, v.limb_stride, v.lin, v.nodes, v.ngroups, (size_t)(position / 2), position, v.width, v.lpn, v.nlevels, 0,
+                                               reinterpret_cast<unsigned char*>(off)});
+        off += pb[i];
+      }
+    }
+  }
+  const u64 hd[6] = {0x4946534DULL /* 'MSFI' */, (u64)E, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)last->ncoef};
+  memcpy(out, hd, head);
+  return open_launch<E>(jobs, pos - head, last, 0, out + head);
+}
+
 // src/merkle.rs:272-288 on a standalone binary tree: leaves de-interleaved to SoA limbs, then the same
 // LeafHash / InnerHash / FindFirst / MerklePath kernels the FRI query phase uses
 template <class F> template <int EL>
@@ -378,7 +505,10 @@ int Ctx<F>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn,
   template int Ctx<FF>::query_shard_assembly(Ctx<FF>::QueryPlan& q); \
   template int Ctx<FF>::query_openings(Ctx<FF>::QueryPlan& q); \
   template int Ctx<FF>::fri_query(const u64* betas, int nq, u8* ext_out, size_t ext_cap, size_t* ext_len); \
-  template int Ctx<FF>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len);
+  template int Ctx<FF>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len); \
+  template int Ctx<FF>::open_view(int tree, int round, Ctx<FF>::OpenView* v); \
+  template int Ctx<FF>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len); \
+  template int Ctx<FF>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -856,6 +856,69 @@ template <class F, int E> struct PathKernel {
   }
 };
 
+// MerklePath BY INDEX (build-defined: ms_tree_open, ms_fri_query_index), the same layout as PathKernel's.  What differs: the leaf group comes from the job record
+// (the host has checked it against ngroups: no device index word, no lookup by value), the group is read through the general view LeafHashKernel hashes
+// (element f of the committed vector: column f % width, row f / width), and a VIRTUAL column (LinColSpec) is opened with the value LeafHashKernel hashed for that
+// row, from the same specification.  Binary trees only (ic = 2).  `leaf_index` is the word the path carries: group * lpn for ms_tree_open, the opened position for
+// ms_fri_query_index.
+template <class F, int EL> struct OpenJob {
+  const typename F::T* base; size_t col_stride, row_stride, limb_stride;
+  const LinColSpec* lin;   // per column, or nullptr
+  const u32* nodes;        // level-major, 2 * ngroups - 1 digests
+  size_t ngroups, group;
+  unsigned long long leaf_index;
+  u32 width, lpn, nlevels /* log2(ngroups) */, pad_;
+  unsigned char* out;
+};
+template <class F, int EL> struct OpenKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = 64;
+  static constexpr u32 FIN_WORDS = 1024;   // words of the final polynomial per workgroup
+  // workgroups [0, njobs): one opening each; behind them (ms_fri_query_index) ceil(fin_n * EL / FIN_WORDS) workgroups that write the last round's polynomial - limb k
+  // of coefficient c at fin[k * fin_stride + c] - as fin_n * EL u64 words, so that the query phase is ONE launch
+  struct Params { const OpenJob<F, EL>* jobs; u32 njobs; const T* fin; size_t fin_stride, fin_n; u64* fin_out; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  // One WAVE per opening, a lane per word, as PathKernel: every address follows from the job record alone, so the loads of the leaf group and of all levels are in
+  // flight together (a virtual column's specification is the one load in front of its sources).
+  static MS_DEV void phase(int, const Params& pp, int bx, int, int tid, int nthreads, unsigned char*) {
+    if ((u32)bx >= pp.njobs) {
+      const size_t nw = pp.fin_n * (size_t)EL, w0 = (size_t)((u32)bx - pp.njobs) * FIN_WORDS;
+      for (size_t w = w0 + (size_t)tid; w < w0 + FIN_WORDS && w < nw; w += (size_t)nthreads)
+        pp.fin_out[w] = F::to_u64(pp.fin[(w % EL) * pp.fin_stride + w / EL]);
+      return;
+    }
+    const OpenJob<F, EL>& p = pp.jobs[bx];
+    u64* o = reinterpret_cast<u64*>(p.out);
+    const u32 nval = p.lpn * (u32)EL;
+    if (tid == 0) { o[0] = p.leaf_index; o[1 + nval] = p.nlevels; }
+    const size_t f0 = p.group * p.lpn;
+    for (u32 v = (u32)tid; v < nval; v += (u32)nthreads) {
+      const size_t f = f0 + v / EL;
+      const size_t row = f / p.width; const u32 col = (u32)(f - row * p.width);
+      const T* rowp = p.base + row * p.row_stride + (size_t)(v % EL) * p.limb_stride;
+      T x;
+      if (p.lin && p.lin[col].n) {   // LeafHashKernel's evaluation of the column, term by term in the same order: the same field element
+        const LinColSpec& lc = p.lin[col];
+        x = 0;
+        for (u32 t = 0; t < lc.n; t++) {
+          const T s = rowp[(size_t)lc.src[t] * p.col_stride];
+          if (lc.s[t] == 1) x = F::add(x, s);
+          else if (lc.s[t] == F::P - 1) x = F::sub(x, s);
+          else x = F::add(x, F::mul(s, F::from_u64(lc.s[t])));
+        }
+      } else x = rowp[(size_t)col * p.col_stride];
+      o[1 + v] = F::to_u64(x);
+    }
+    u32* o32 = reinterpret_cast<u32*>(o + 2 + nval);
+    const u32 total = p.nlevels * 16;
+    for (u32 w = (u32)tid; w < total; w += (u32)nthreads) {   // level l: the pair of siblings that holds the path's node (merkle.rs:241-265)
+      const u32 l = w / 16, i = w % 16;
+      const size_t cur = p.group >> l, level_off = 2 * p.ngroups - ((2 * p.ngroups) >> l);   // sum_{q<l} ngroups / 2^q
+      o32[w] = p.nodes[(level_off + (cur & ~(size_t)1)) * 8 + i];
+    }
+  }
+};
+
 // ---------------------------------------------------------------------------------------------
 // Sharded trees (ms_set_shard).  After the all-to-all, recv chunk k holds the digests of the leaves
 // p = k + W*q (q < per) of this rank's contiguous range: interleave them into subtree leaf order.

@@ -68,6 +68,33 @@ def pow_check(digest_id: int, seed: bytes, nonce: int, bits: int) -> bool:
     return rc == 1
 
 
+def merkle_path_check_index(digest_id, field, ext, lpn, zero_display_empty, root, path, expect_leaf_group):
+    """msh_merkle_path_check_index: the positional check of ONE serialised MerklePath at the head of `path` (ms_tree_open / ms_fri_query_index; ministark_host.h).
+    Returns (rc, bytes used): rc 1 accepted, 0 rejected, < 0 malformed arguments."""
+    H = _host()
+    H.msh_merkle_path_check_index.argtypes = [C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_size_t)]
+    used = C.c_size_t(0)
+    rc = H.msh_merkle_path_check_index(int(digest_id), int(field), int(ext), int(lpn), 1 if zero_display_empty else 0, bytes(root), bytes(path), len(path),
+                                       int(expect_leaf_group), C.byref(used))
+    return rc, int(used.value)
+
+
+def fri_index_verify(digest_id, field, zero_display_empty, blowup, roots, z, B, alpha, betas, blob):
+    """msh_fri_index_verify: the MSFI blob of Context.fri_query_index against the commit phase.  roots: the R round roots (32 bytes each); z, alpha: R - 1 elements of E
+    limbs; B: R - 1 pairs of elements; betas: the query values.  Returns (rc, why): rc 1 accepted, 0 rejected, < 0 malformed arguments."""
+    H = _host()
+    u64p = C.POINTER(C.c_uint64)
+    H.msh_fri_index_verify.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_char_p, C.c_size_t, u64p, u64p, u64p, u64p, C.c_size_t, C.c_char_p, C.c_size_t,
+                                       C.c_char_p, C.c_size_t]
+    arr = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))   # noqa: E731
+    zz, bb, aa, be = arr(z), arr(B), arr(alpha), arr(betas)
+    ptr = lambda a: a.ctypes.data_as(u64p) if a.size else None   # noqa: E731
+    why = C.create_string_buffer(512)
+    rc = H.msh_fri_index_verify(int(digest_id), int(field), 1 if zero_display_empty else 0, int(blowup), b"".join(bytes(r) for r in roots), len(roots), ptr(zz), ptr(bb),
+                                ptr(aa), ptr(be), be.size, bytes(blob), len(blob), why, 512)
+    return rc, why.value.decode()
+
+
 def terms_expected_validity(field, r, constraints, nexempt, N, z, rows, opened, npolys=None):
     """msh_terms_expected_validity: the value validity(z) must have after ms_mix_terms, from the opened values.  `constraints` as for Context.mix_terms (or the CSR
     5-tuple); `rows` the row offsets opened, `opened[k]` = the ms_eval_ext output at w^rows[k] z ([c + 1][E], or [c][E] with npolys = c).  Returns (status, E limbs)."""
