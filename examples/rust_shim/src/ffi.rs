@@ -44,6 +44,15 @@ pub struct MsAir {
     pub bnd_row: *const u32,
     pub bnd_val: *const u64,
 }
+pub const MS_TREE_VALIDITY: c_int = 4; // ms_tree_open: the tree of ms_validity_commit (0 trace, 1 LDE, 2 FRI round; 3 is unassigned)
+/// `ms_deep` of include/ministark.h: the openings of the DEEP stage.  Every pointer borrows from the caller for the duration of the call.
+#[repr(C)]
+pub struct MsDeep {
+    pub npts: u32,              // 1..8 points
+    pub z: *const u64,          // npts * E limbs: the verifier's z and its shifts z * w^row
+    pub pt_begin: *const u32,   // npts + 1
+    pub pt_poly: *const u32,    // entry n: j < c polynomial j of the LDE tree, c + j' chunk column j' of the validity tree
+}
 pub const MS_AUX_SUM: u32 = 0; // z_{i+1} = z_i + s_i, z_0 = 0 (LogUp)
 pub const MS_AUX_PRODUCT: u32 = 1; // z_{i+1} = z_i * s_i, z_0 = 1 (grand product)
 /// `ms_aux` of include/ministark.h: the program of ms_aux_running.  Every pointer borrows from the caller for the duration of the call.
@@ -132,6 +141,12 @@ extern "C" {
     pub fn ms_tree_open(ctx: *mut ms_ctx, tree: c_int, round: c_int, index: *const u64, n: usize, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- the compact query phase (build-defined): the MSFI blob - openings by position, the last round's polynomial in the clear
     pub fn ms_fri_query_index(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    // ---- the composition commitment and the DEEP stage (build-defined): the tree over the validity polynomial's chunk columns on the LDE coset; the claimed evaluations;
+    // D' = sum_t (A_t - A_t(z_t)) / (x - z_t) on the coset's own variable, which ms_fri_begin then starts from
+    pub fn ms_validity_commit(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;
+    pub fn ms_deep_evals(ctx: *mut ms_ctx, deep: *const MsDeep, evals: *mut u64) -> c_int;
+    pub fn ms_deep_compose(ctx: *mut ms_ctx, deep: *const MsDeep, gamma: *const u64) -> c_int;
+    pub fn ms_deep_len(ctx: *const ms_ctx) -> c_int;
     // ---- proof-of-work grinding (build-defined): the smallest nonce of [start, start + limit) whose digest D(seed || nonce LE) starts with `bits` zero bits
     pub fn ms_grind(ctx: *mut ms_ctx, seed: *const u8 /* [32] */, bits: u32, start: u64, limit: u64, nonce: *mut u64) -> c_int;
     // ---- Tree trait (src/merkle.rs:8-30) on its own

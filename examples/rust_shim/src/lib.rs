@@ -127,6 +127,25 @@ impl Gpu {
         self.check(unsafe { ms_eval_ext(self.ctx, z_limbs.as_ptr(), q as i32, out.as_mut_ptr()) })?;
         Ok(out)
     }
+    /// BUILD-DEFINED: commits to the validity polynomial before z is drawn - the tree over its m = validity_ext * validity_len / N chunk columns on the LDE coset
+    pub fn validity_commit(&mut self, lpn: usize) -> Result<Digest, GpuError> {
+        let mut root = [0u8; 32];
+        self.check(unsafe { ms_validity_commit(self.ctx, lpn, root.as_mut_ptr()) })?;
+        Ok(root)
+    }
+    /// BUILD-DEFINED: the claimed evaluations F_{pt_poly[n]}(z_t) of the openings `deep`, `entries` of them, E limbs each, in entry order
+    pub fn deep_evals(&mut self, deep: &MsDeep, entries: usize) -> Result<Vec<u64>, GpuError> {
+        let mut out = vec![0u64; entries * self.ext];
+        self.check(unsafe { ms_deep_evals(self.ctx, deep, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// BUILD-DEFINED: installs the DEEP polynomial of the openings `deep` under the challenge `gamma` (E limbs); `fri_begin` then starts round 0 from it.
+    /// Returns its length in coefficients (N).
+    pub fn deep_compose(&mut self, deep: &MsDeep, gamma: &[u64]) -> Result<usize, GpuError> {
+        assert_eq!(gamma.len(), self.ext);
+        self.check(unsafe { ms_deep_compose(self.ctx, deep, gamma.as_ptr()) })?;
+        Ok(unsafe { ms_deep_len(self.ctx) } as usize)
+    }
     /// fri.rs:73-82
     pub fn fri_begin(&mut self, blowup: usize, rounds: usize) -> Result<Digest, GpuError> {
         let mut root = [0u8; 32];

@@ -394,13 +394,14 @@ int ms_fri_query_into(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, 
  *   MS_TREE_TRACE  valid from ms_trace_commit[_device] until ms_interpolate: the rows are transformed in place there, afterwards the call returns MS_ERR_STATE
  *                  (the tree covers the w trace columns; running columns of ms_aux_running are not in it).
  *   MS_TREE_LDE    valid from ms_lde_commit until the next ms_trace_commit, ms_polys_lincomb / ms_polys_append, ms_bench_lde or ms_lde_commit.
+ *   MS_TREE_VALIDITY  the tree of ms_validity_commit (below), opened exactly as MS_TREE_LDE: row `index`, m one-limb neighbours.  Valid while that tree lives.
  *   MS_TREE_FRI    round < the rounds committed so far, from ms_fri_begin on (until the next mix stage or trace).  `round` is 0 for the other trees.
  * Errors, all decided before anything is launched (ONE launch per call, on the context's stream; the call returns with the bytes in `out`):
  *   MS_ERR_ARG           null index or len; n outside 1..65536; an unknown tree id; round out of range; out = NULL with cap != 0; cap too small.
  *   MS_ERR_OUT_OF_RANGE  an index at or above the number of leaf groups.
  *   MS_ERR_STATE         the tree does not exist (yet, or any more); a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1), as ms_aux_running.
  * The context is unchanged: a proof with such calls between its stages comes out byte for byte as without them. */
-typedef enum { MS_TREE_TRACE = 0, MS_TREE_LDE = 1, MS_TREE_FRI = 2 } ms_tree_id;
+typedef enum { MS_TREE_TRACE = 0, MS_TREE_LDE = 1, MS_TREE_FRI = 2, MS_TREE_VALIDITY = 4 } ms_tree_id;   /* 3 stays unassigned: it has always been refused as an unknown id (MS_ERR_ARG), and callers may rely on that */
 int ms_tree_open(ms_ctx* ctx, int tree, int round /* MS_TREE_FRI only, else 0 */, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len);
 /* The COMPACT query phase: what ms_fri_query opens by value, opened by position, and nothing else.  Valid wherever ms_fri_query is (after the commit phase, before or
  * after ms_fri_query, any number of times); it leaves the FRI state, the MSFP blob and a later ms_fri_query's bytes untouched.  MS_ERR_STATE on a context with sharding
@@ -416,14 +417,68 @@ int ms_tree_open(ms_ctx* ctx, int tree, int round /* MS_TREE_FRI only, else 0 */
  * the same bytes); its group is position / 2 and the opened value y is leaf_neighbours[position & 1].  y3 of window i is not shipped: it is window i + 1's y1 of the
  * same query, and for the last window the final polynomial at x3.  No points, no quotients.  R = 1: header and final polynomial only.
  * What it binds (msh_fri_index_verify, ministark_host.h): every opened value to its position under the round's root, each window's fold to the next window's opened
- * value, the last fold to the final polynomial, and the final polynomial's length to D_(R-1) / blowup.  Not bound here, as in MSFP: round 0's root to the LDE tree
- * (whole-proof integration is a follow-up: DESIGN.md).
+ * value, the last fold to the final polynomial, and the final polynomial's length to D_(R-1) / blowup.  Not bound here, as in MSFP: round 0's root to the LDE tree -
+ * that is the DEEP stage's part (ms_validity_commit / ms_deep_compose below, msh_deep_link_verify on the verifying side).
  * One launch whatever R and nq (openings and final polynomial together); no pass over any codeword or polynomial.  nq outside 1..4096: MS_ERR_ARG.  Size query and
  * cap rule as ms_tree_open.
  * Measured (tools/fri_index_bench.py, profiles/fri_index.json; one paired run on one MI355X, Goldilocks, 2^20 rows, blowup 8, 23 rounds, 2 queries, both phases behind
  * the same commit phase): ms_fri_query 0.370 ms per call with the blob left in HBM - 14 launches, 0.346 ms of kernel time, 67 180 512 bytes (22.2 ms with the read-back);
  * ms_fri_query_index 0.052 ms per call with the bytes at the caller - 1 launch, 0.0062 ms of kernel time, 69 040 bytes; one ms_tree_open of 64 LDE rows 0.039 ms. */
 int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
+
+/* ---- the composition commitment and the DEEP stage (BUILD-DEFINED; the reference runs FRI on the validity polynomial alone and ties it to nothing) -----------------
+ * Notation: N rows, c = ms_polys_count at the preceding ms_lde_commit, L = blowup * N, shift and g_L the LDE coset's shift and generator, K the context's extension of
+ * E limbs, ve = ms_validity_ext and VL = ms_validity_len after the mix stage, m = ve * VL / N.  All four entry points run on the context's stream and return
+ * MS_ERR_STATE on a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1), as ms_aux_running and ms_tree_open do.
+ *
+ * ms_validity_commit commits to the validity polynomial BEFORE the caller draws z.  The polynomial's ve limb planes of VL base-field coefficients are cut into VL / N
+ * chunks of N coefficients each: chunk column k * ve + l holds the coefficients [kN, (k+1)N) of plane l, so that
+ *   V(x) = sum_k x^(kN) sum_l u_l V_(k,l)(x)            u_l the l-th basis element of K in this header's limb order
+ * (msh_validity_from_chunks, ministark_host.h, is this identity on the verifying side).  The stage evaluates the m chunk columns on the coset the LDE tree covers (L
+ * points each), builds a Merkle tree with the context's digest over the L x m row-major matrix (lpn must equal m, one row per leaf group as for the LDE tree; ic = 2)
+ * and returns the root.  The chunk LDE and the nodes stay in HBM; ms_tree_open(MS_TREE_VALIDITY) opens rows of it.  Valid after any mix stage (ms_mix .. ms_mix_air_ext)
+ * on a context with a committed LDE; the tree lives until the next mix stage, ms_polys_*, ms_lde_commit or ms_trace_commit.
+ *   MS_ERR_STATE  before a mix stage; no committed LDE.      MS_ERR_ARG  a null root; lpn != m; under BLAKE3 a row whose message may exceed 16 KiB (as everywhere).
+ * The validity polynomial, ms_validity_*, ms_eval_ext and a following ms_fri_begin are unchanged by the call.
+ *
+ * ms_deep describes the openings: npts points (the verifier's z and its shifts z * w^row, computed by the caller) and, per point, the committed polynomials opened
+ * there.  F_j for j < c is polynomial j of the LDE tree, F_(c + j') for j' < m chunk column j' of the validity tree.  Entry n is position n of pt_poly; point t owns
+ * the entries pt_begin[t] .. pt_begin[t+1] - 1.  Both functions below are valid from ms_validity_commit until that tree dies.
+ * ms_deep_evals writes F_(pt_poly[n])(z_t) in entry order, E limbs each: what the caller sends to the verifier.  It is the evaluation path of ms_eval_ext over views
+ * of the coefficient storage and changes nothing in the context (a polynomial ms_polys_lincomb defined lazily is written out first, as by ms_poly_read).
+ * ms_deep_compose builds, with gamma^n the n-th power in K,
+ *   A_t(x) = sum_(n in point t) gamma^n F_(pt_poly[n])(x)          N coefficients in K
+ *   D(x)   = sum_t (A_t(x) - A_t(z_t)) / (x - z_t)                 degree <= N - 2
+ *   D'(y)  = D(shift * y)                                          coefficient k times shift^k
+ * and installs D' as the context's DEEP polynomial: N coefficients of E limbs, zero above its degree, in a buffer of its own (ms_deep_len: N while it is installed, else
+ * 0).  The library needs no claimed evaluations: the remainders A_t(z_t) fall out of the divisions.  Launches: ONE streaming pass forms every A_t (each column
+ * coefficient loaded once, however many points name the column), the divisions are the synthetic-division scans of the FRI quotient with the npts jobs of a level
+ * in one launch (2 levels - 1 launches: levels = 1 up to 2048 coefficients, 2 up to 2^22, 3 beyond), one launch sums the quotients and scales by shift^k:
+ * 1 + (2 levels - 1) + 1 launches, 3 / 5 / 7.  A second ms_deep_compose replaces the polynomial; whatever kills the validity tree clears it.
+ * While a DEEP polynomial is installed, ms_fri_begin starts round 0 from D' in place of the validity polynomial (all E limbs live, trimmed by the usual degree scan,
+ * the domain rule (deg + 1) * blowup unchanged).  Everything behind it - ms_fri_deep, ms_fri_fold_commit, ms_fri_query, ms_fri_query_index, ms_tree_open(MS_TREE_FRI),
+ * ms_grind - is untouched, and without ms_deep_compose ms_fri_begin and every blob are byte for byte what they were.  With the FRI blowup equal to the LDE's,
+ * D_0 = next_pow2(ncoef * blowup) <= L and round-0 position b is LDE row b * (L / D_0): D'(g_0^b) = D(shift * g_L^(b L / D_0)).
+ *   MS_ERR_STATE  no validity tree.
+ *   MS_ERR_ARG    a null argument; npts outside 1..8; pt_begin not starting at 0 or decreasing; a point without entries; more than 8192 entries; an index >= c + m;
+ *                 a limb >= p.
+ *   MS_ERR_SHAPE  some z_t lies in the LDE coset (z_t^L = shift^L): the verifier would divide by zero at one of its rows.
+ * All decided before anything is launched; after any refusal the context is as if the call had not been made.
+ * WHAT THIS BINDS (msh_deep_link_verify, ministark_host.h): at every FRI query position, the value round 0's tree opens to the rows the LDE tree and the validity tree
+ * open there and to the claimed evaluations - so the low-degree test speaks about the committed polynomials, the claimed evaluations are theirs, and V was fixed
+ * before z.  WHAT IT LEAVES TO THE CALLER: the transcript order (trace root, LDE root, r, validity root, z, evaluations, gamma, the FRI rounds - each challenge drawn
+ * after what it must not depend on); the AIR identity at z (msh_air_expected_validity[_ext] against msh_validity_from_chunks); msh_fri_index_verify on the same MSFI;
+ * and linking the trace tree to the LDE tree's trace columns, as before.  Tests: tests/test_deep_*.py (tests/pyref_deep.py restates the definitions). */
+typedef struct ms_deep {
+  uint32_t npts;              /* 1..8 points */
+  const uint64_t* z;          /* npts * E limbs, canonical: the verifier's z and its shifts z*w^row, computed by the caller */
+  const uint32_t* pt_begin;   /* npts + 1, starts at 0, does not decrease, at most 8192 entries in all */
+  const uint32_t* pt_poly;    /* entry n: F index. j < c: polynomial j of the LDE tree; c + j', j' < m: chunk column j' of the validity tree */
+} ms_deep;
+int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]);
+int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals /* entries * E limbs: F_{pt_poly[n]}(z_t), entry order */);
+int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma /* E limbs */);
+int ms_deep_len(const ms_ctx* ctx);   /* 0, or N once a DEEP polynomial is installed */
 
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
  * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI

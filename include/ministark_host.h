@@ -102,6 +102,24 @@ int msh_merkle_path_check_index(int digest_id, int field, int ext, size_t lpn, i
  * < 0 malformed arguments. */
 int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, uint64_t blowup, const uint8_t* roots, size_t rounds, const uint64_t* z, const uint64_t* B,
                          const uint64_t* alpha, const uint64_t* betas, size_t nq, const uint8_t* blob, size_t len, char* why, size_t why_cap);
+/* The verifying side of the DEEP stage (ministark.h: ms_validity_commit, ms_deep_evals, ms_deep_compose; build-defined, no reference counterpart): the link between
+ * FRI's round 0 and the two committed trees.  N rows, L = blowup * N (the FRI blowup is the LDE's), c LDE columns, m chunk columns, `deep` / evals / gamma what the
+ * prover's ms_deep_evals / ms_deep_compose took and returned, msfi the blob of ms_fri_query_index for `betas`.  With D_0 from the MSFI header (required: a power of two
+ * that divides L, D_0 <= L) and b_j = betas[j] mod D_0, lde_open and val_open are the ms_tree_open outputs of MS_TREE_LDE and MS_TREE_VALIDITY for the 2 nq rows
+ * p_j = b_j (L / D_0) and (p_j + L / 2) mod L, in that order per query: the rows under window 0's two positions b_j and (b_j + D_0 / 2) mod D_0.
+ * It checks every path positionally under its root (msh_merkle_path_check_index's rule: leaf_index = row * lpn), both blobs consumed exactly; for each row computes
+ *   sum_n gamma^n (F_(pt_poly[n])(x) - evals[n]) / (x - z_t(n))   at x = shift g_L^p, F from the opened rows,
+ * and requires it to equal the value window 0 of the MSFI opened at the matching position (leaf_neighbours[position & 1] of the query's first or second path); for
+ * R = 1 there is no window and it compares with the final polynomial at g_0^position.  It does NOT repeat msh_fri_index_verify (run it on the same MSFI, with the
+ * round roots from the transcript) nor the AIR identity at z (msh_air_expected_validity[_ext] against msh_validity_from_chunks): the caller runs those.
+ * 1 accepted, 0 rejected (reason in `why`, naming the step: "LDE opening: ..", "validity opening: ..", "DEEP link: ..", "MSFI .."), < 0 malformed arguments. */
+int msh_deep_link_verify(int digest_id, int field, int zero_display_empty, uint64_t N, uint64_t blowup, uint64_t shift, uint32_t c, uint32_t m,
+                         const uint8_t lde_root[32], const uint8_t val_root[32], const ms_deep* deep, const uint64_t* evals, const uint64_t* gamma,
+                         const uint64_t* betas, size_t nq, const uint8_t* msfi, size_t msfi_len, const uint8_t* lde_open, size_t lde_len,
+                         const uint8_t* val_open, size_t val_len, char* why, size_t why_cap);
+/* V(z) from the m = ve * nchunks chunk evaluations (chunk column k * ve + l at chunk_evals + (k * ve + l) * E, E limbs each) by the identity of ms_validity_commit,
+ *   V(z) = sum_k z^(kN) sum_l u_l V_(k,l)(z):  the value to compare with msh_air_expected_validity[_ext].  ve in {1, E}.  MS_OK, or MS_ERR_ARG (null, ve, a limb >= p). */
+int msh_validity_from_chunks(int field, uint32_t ve, uint32_t nchunks, uint64_t N, const uint64_t* z, const uint64_t* chunk_evals, uint64_t* out);
 /* D(data) by this library's own host implementation of an ms_digest_id (SHA-256, BLAKE2s-256, BLAKE3 with its chunk tree, Keccak-256, SHA3-256: any length): 0, -1 for an unknown id (3 is unassigned) */
 int msh_hash(int digest_id, const uint8_t* data, size_t len, uint8_t out[32]);
 /* The verifying side of ms_mix_terms (ministark.h; build-defined, no reference counterpart): the value validity(z) must have at an extension point z (E limbs),

@@ -21,7 +21,7 @@ FLAG_DIGEST_KECCAK256 = 0x20   # D = Keccak-256 (original padding: Ethereum's); 
 FLAG_DIGEST_SHA3_256 = 0x40   # D = SHA3-256 (FIPS 202)
 DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3 = 0, 1, 2   # ms_digest_id
 DIGEST_KECCAK256, DIGEST_SHA3_256 = 4, 5   # (3 is unassigned)
-TREE_TRACE, TREE_LDE, TREE_FRI = 0, 1, 2   # ms_tree_id
+TREE_TRACE, TREE_LDE, TREE_FRI, TREE_VALIDITY = 0, 1, 2, 4   # ms_tree_id (3 is unassigned)
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -153,6 +153,35 @@ def air_rows(constraints, boundary=()):
     if len(boundary):
         rows.add(0)
     return sorted(rows)
+
+
+class MsDeep(C.Structure):
+    """ms_deep (include/ministark.h)"""
+    _fields_ = [("npts", C.c_uint32), ("z", _u64p), ("pt_begin", C.POINTER(C.c_uint32)), ("pt_poly", C.POINTER(C.c_uint32))]
+
+
+def deep_struct(z, lists, npts=None):
+    """(MsDeep, the arrays it points into - keep them alive while the struct is in use): z = the points' limbs (npts * E of them, any nesting), lists = one list of F
+    indices per point (F index j < c: polynomial j of the LDE tree; c + j': chunk column j' of the validity tree).  A list entry that is None leaves that array NULL;
+    `lists` may also be the (pt_begin, pt_poly) arrays themselves; npts overrides the count (the refusal tests)."""
+    keep = {"z": None if z is None else np.ascontiguousarray(np.asarray(z, dtype=np.uint64).reshape(-1))}
+    if isinstance(lists, tuple):
+        pb, pp = lists
+        n = (len(pb) - 1) if pb is not None else 0
+    else:
+        n = len(lists)
+        pb = np.cumsum([0] + [len(x) for x in lists])
+        pp = [int(j) for x in lists for j in x]
+    keep["pt_begin"] = None if pb is None else np.ascontiguousarray(pb, dtype=np.uint32)
+    keep["pt_poly"] = None if pp is None else np.ascontiguousarray(pp, dtype=np.uint32)
+    s = MsDeep()
+    s.npts = int(n if npts is None else npts)
+    if keep["z"] is not None:
+        s.z = keep["z"].ctypes.data_as(_u64p)
+    for k in ("pt_begin", "pt_poly"):
+        if keep[k] is not None:
+            setattr(s, k, keep[k].ctypes.data_as(C.POINTER(C.c_uint32)))
+    return s, keep
 
 
 AUX_SUM, AUX_PRODUCT = 0, 1   # MS_AUX_SUM / MS_AUX_PRODUCT
@@ -661,6 +690,35 @@ class Context:
         """ms_fri_query_index: the compact query phase, the MSFI blob (openings by position, the last round's polynomial in the clear)."""
         b, bp = _u64(betas)
         return self._sized_bytes(lambda out, cap, n: self.L.ms_fri_query_index(self.h, bp, C.c_int(b.size), out, cap, n))
+
+    # ---- the composition commitment and the DEEP stage (BUILD-DEFINED; include/ministark.h) -----------------------
+    def validity_commit(self, lpn):
+        """ms_validity_commit: (rc, root) of the tree over the chunk columns of the validity polynomial on the LDE coset; lpn = validity_ext * validity_len / N."""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_validity_commit(self.h, C.c_size_t(lpn), root)
+        return rc, bytes(root)
+
+    def deep_evals(self, z, lists):
+        """ms_deep_evals: (rc, evals) with evals[n] = F_{pt_poly[n]}(z_t), E limbs each, in entry order (deep_struct describes z and lists)."""
+        s, keep = deep_struct(z, lists)
+        n = 0 if keep["pt_poly"] is None else keep["pt_poly"].size
+        out = np.zeros((max(1, n), self.e), dtype=np.uint64)
+        rc = self.L.ms_deep_evals(self.h, C.byref(s), out.ctypes.data_as(_u64p))
+        return rc, out[:n]
+
+    def deep_compose(self, z, lists, gamma):
+        """ms_deep_compose: installs the DEEP polynomial D' of the openings (z, lists) under the challenge gamma (E limbs; None passes a null pointer)."""
+        s, _keep = deep_struct(z, lists)
+        if gamma is None:
+            return self.L.ms_deep_compose(self.h, C.byref(s), None)
+        g, gp = _u64(gamma)
+        if g.size != self.e:
+            raise ValueError(f"deep_compose: gamma has {g.size} limbs, the extension has {self.e}")
+        return self.L.ms_deep_compose(self.h, C.byref(s), gp)
+
+    def deep_len(self):
+        """ms_deep_len: N while a DEEP polynomial is installed, else 0."""
+        return int(self.L.ms_deep_len(self.h))
 
     # ---- standalone ----------------------------------------------------------------
     def merkle_commit(self, leafs, ext=1, lpn=2, ic=2):

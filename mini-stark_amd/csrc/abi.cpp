@@ -214,6 +214,10 @@ int ms_merkle_prove(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext
 }
 int ms_tree_open(ms_ctx* ctx, int tree, int round, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->tree_open(tree, round, index, n, out, cap, len)); }
 int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_index(betas, nq, out, cap, len)); }
+int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->validity_commit(lpn, root)); }
+int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals) { MS_ENTRY(ctx, B(ctx)->deep_evals(deep, evals)); }
+int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma) { MS_ENTRY(ctx, B(ctx)->deep_compose(deep, gamma)); }
+int ms_deep_len(const ms_ctx* ctx) { return ctx ? B(ctx)->deep_len_() : 0; }
 int ms_grind(ms_ctx* ctx, const uint8_t seed[32], uint32_t bits, uint64_t start, uint64_t limit, uint64_t* nonce) { MS_ENTRY(ctx, B(ctx)->grind(seed, bits, start, limit, nonce)); }
 int ms_ntt(ms_ctx* ctx, uint64_t* data, size_t n, size_t batch, int inverse) { MS_ENTRY(ctx, B(ctx)->ntt(data, n, batch, inverse)); }
 int ms_coset_lde(ms_ctx* ctx, const uint64_t* c, size_t ncoef, size_t batch, uint64_t shift, uint64_t* out, size_t L) { MS_ENTRY(ctx, B(ctx)->coset_lde(c, ncoef, batch, shift, out, L)); }

@@ -149,7 +149,7 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
   const size_t c = (size_t)npolys;
   TreeShape ts;
   RQ(tree_shape(L_ * c, lpn, 2, &ts));
-  L = L_; blowup = blowup_; lde_c = c; lde_shift = shift;
+  L = L_; blowup = blowup_; lde_c = c; lde_shift = shift; drop_vtree();
   auto stage = res.expect();
   if (lpn == c && shardable(L_)) {  // one LDE row per leaf group: rank k evaluates and hashes the rows k (mod world)
     RQ(lde_compute_sharded(blowup_, shift));
@@ -218,7 +218,7 @@ int Ctx<F>::mix(u64 r) {
     CK(run<mspoly::DegreeKernel<F, 1>>(K_DEGREE, grid1(N, mspoly::THREADS), 1, mspoly::THREADS, 0, dp));
     validity_len_at = VLEN_DEVICE;
   }
-  have_validity = true; validity_len = N; validity_ext = 1; nrounds_done = 0;
+  have_validity = true; validity_len = N; validity_ext = 1; nrounds_done = 0; drop_vtree();
   return MS_OK;
 }
 
@@ -297,7 +297,7 @@ int Ctx<F>::finish_mix(const char* refusal, size_t VL, int ne) {
   if (ncoef > VL) return fail(MS_ERR_SHAPE, refusal);
   RQ(scale_pow(cf, L, d_polys.as<T>() + (size_t)npolys * N, VL, VL, f_inv<F>(F::from_u64(lde_shift)), (size_t)ne));
   validity_ncoef = (size_t)ncoef; validity_len_at = VLEN_HOST;   // (scaling by shift^-k keeps the trimmed length)
-  have_validity = true; validity_len = VL; validity_ext = ne; nrounds_done = 0;
+  have_validity = true; validity_len = VL; validity_ext = ne; nrounds_done = 0; drop_vtree();
   return MS_OK;
 }
 
@@ -873,6 +873,164 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   return eval_finish(q, ev, out);
 }
 
+// ------------------------------------------------------------------ build-defined: the composition commitment and the DEEP stage (include/ministark.h)
+// ms_validity_commit: the m chunk columns of the validity polynomial evaluated on the LDE's coset - the LDE commit's own path, scale by shift^k and one size-L
+// transform, a limb plane's VL / N chunks per batch - and the tree over the L x m row-major matrix.  Reads the validity polynomial, writes d_coef (scratch), d_vlde
+// and d_vlde_nodes only: the polynomial, its trimmed length and a following ms_fri_begin are what they were.
+template <class F>
+int Ctx<F>::validity_commit(size_t lpn, u8* root) {
+  if (sh_on) return fail(MS_ERR_STATE, "validity_commit: not available on a context with sharding on");
+  if (!have_validity) return fail(MS_ERR_STATE, "validity_commit before a mix stage");
+  if (!have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "validity_commit: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+  const size_t ve = (size_t)validity_ext, nch = validity_len / N, m = ve * nch;
+  if (!root || lpn != m) return fail(MS_ERR_ARG, "validity_commit: null root, or lpn is not the number of chunk columns (ms_validity_ext * ms_validity_len / N)");
+  TreeShape ts;
+  RQ(tree_shape(L * m, lpn, 2, &ts));
+  drop_vtree();   // (the buffers are rewritten from here on)
+  if (d_coef.ensure(nch * N * sizeof(T)) || d_vlde.ensure(m * L * sizeof(T))) return fail(MS_ERR_NOMEM, "validity_commit buffers");
+  auto stage = res.expect();
+  const T* v = d_polys.as<T>() + (size_t)npolys * N;
+  for (size_t l = 0; l < ve; l++) {   // chunk column k * ve + l = coefficients [kN, (k+1)N) of plane l
+    RQ(scale_pow(v + l * validity_len, N, d_coef.as<T>(), N, N, F::from_u64(lde_shift), nch));
+    RQ(ntt_run(ctz64(L), false, d_coef.as<T>(), N, N, d_vlde.as<T>() + l * L, ve * L, nch));
+  }
+  RQ((tree_build<1>(d_vlde.as<T>(), L, 1, 0, (u32)m, ts, d_vlde_nodes)));
+  RQ(read_root(d_vlde_nodes, ts, root));
+  vtree_ts = ts; vtree_m = m; have_vtree = true;
+  return MS_OK;
+}
+
+// what ms_deep_evals and ms_deep_compose ask of a ms_deep, all of it before anything is launched; the points come back in pl.z
+template <class F>
+int Ctx<F>::deep_check(const char* who, const ms_deep* d, DeepPlan& pl) {
+  auto bad = [&](int code, const char* what) { return fail(code, std::string(who) + what); };
+  if (sh_on) return bad(MS_ERR_STATE, ": not available on a context with sharding on");
+  if (!vtree_live()) return bad(MS_ERR_STATE, ": no validity tree (ms_validity_commit, and no mix stage, ms_polys_*, ms_lde_commit or ms_trace_commit since)");
+  if (!d || !d->z || !d->pt_begin || !d->pt_poly) return bad(MS_ERR_ARG, ": null argument");
+  if (d->npts < 1 || d->npts > (u32)mspoly::DEEP_MAX_POINTS) return bad(MS_ERR_ARG, ": npts outside 1..8");
+  if (d->pt_begin[0] != 0) return bad(MS_ERR_ARG, ": pt_begin[0] must be 0");
+  for (u32 t = 0; t < d->npts; t++) {
+    if (d->pt_begin[t + 1] < d->pt_begin[t]) return bad(MS_ERR_ARG, ": pt_begin decreases");
+    if (d->pt_begin[t + 1] == d->pt_begin[t]) return bad(MS_ERR_ARG, ": a point without entries");
+    if (d->pt_begin[t + 1] > (u32)mspoly::DEEP_MAX_ENTRIES) return bad(MS_ERR_ARG, ": more than 8192 entries");
+  }
+  pl.entries = d->pt_begin[d->npts];
+  const size_t nf = lde_c + vtree_m;
+  for (size_t n = 0; n < pl.entries; n++) if (d->pt_poly[n] >= nf) return bad(MS_ERR_ARG, ": an index at or above c + m");
+  pl.z.resize(d->npts);
+  for (u32 t = 0; t < d->npts; t++) if (!load_ext(d->z + (size_t)t * E, &pl.z[t])) return bad(MS_ERR_ARG, ": a point is not canonical");
+  const T shL = f_pow<F>(F::from_u64(lde_shift), (u64)L);
+  for (u32 t = 0; t < d->npts; t++) {   // z^L = shift^L: z lies in the LDE coset, where the verifier's (x - z) vanishes for some row x
+    XE zL = e_pow<F, E>(pl.z[t], (u64)L);
+    bool in_coset = zL.c[0] == shL;
+    for (int l = 1; l < E; l++) in_coset = in_coset && zL.c[l] == 0;
+    if (in_coset) return bad(MS_ERR_SHAPE, ": a point lies in the LDE coset (z^L = shift^L)");
+  }
+  pl.pt_of.resize(pl.entries);
+  for (u32 t = 0; t < d->npts; t++) for (u32 n = d->pt_begin[t]; n < d->pt_begin[t + 1]; n++) pl.pt_of[n] = t;
+  return 0;
+}
+
+// ms_deep_evals: F_{pt_poly[n]}(z_t) in entry order - the DEEP-ALI evaluation path over views of the coefficient storage, MAX_POLYS views per launch
+template <class F>
+int Ctx<F>::deep_evals(const ms_deep* deep, u64* evals) {
+  DeepPlan pl;
+  RQ(deep_check("deep_evals", deep, pl));
+  if (!evals) return fail(MS_ERR_ARG, "deep_evals: null argument");
+  if (d_small.ensure(pl.entries * E * sizeof(T) + 4096)) return fail(MS_ERR_NOMEM, "deep_evals results");
+  for (size_t n = 0; n < pl.entries; n++) if (deep->pt_poly[n] < lde_c) RQ(materialize((int)deep->pt_poly[n]));   // (lazily defined polynomials are written out, as by ms_poly_read)
+  for (u32 t = 0; t < deep->npts; t++)
+    for (u32 n0 = deep->pt_begin[t]; n0 < deep->pt_begin[t + 1]; n0 += mspoly::MAX_POLYS) {
+      const int nb = (int)(deep->pt_begin[t + 1] - n0 < (u32)mspoly::MAX_POLYS ? deep->pt_begin[t + 1] - n0 : (u32)mspoly::MAX_POLYS);
+      size_t off[mspoly::MAX_POLYS], cnt[mspoly::MAX_POLYS];
+      for (int i = 0; i < nb; i++) { const size_t j = deep->pt_poly[n0 + i]; off[i] = j < lde_c ? j * N : chunk_off(j - lde_c); cnt[i] = N; }
+      RQ((eval_views<1>(d_polys.as<T>(), 0, 0, 1, off, cnt, nb, pl.z[t], d_small.as<T>() + (size_t)n0 * E)));
+    }
+  std::vector<T> h(pl.entries * E);
+  CK(msrt::d2h(h.data(), d_small.p, h.size() * sizeof(T), stream));
+  CK(msrt::sync(stream));
+  for (size_t i = 0; i < h.size(); i++) evals[i] = F::to_u64(h[i]);
+  return MS_OK;
+}
+
+// ms_deep_compose: A_t = sum_n gamma^n F_n over the entries of point t (DeepCombineKernel, one pass over the columns), Q_t = (A_t - A_t(z_t)) / (x - z_t) by synthetic
+// division (the suffix-Horner scan, the npts jobs of a level in one launch), D'_k = shift^k sum_t Q_t[k] (DeepSumScaleKernel).  Launches: 1 + (2 levels - 1) + 1, with
+// levels = 1 up to SH_BS = 2048 coefficients, 2 up to 2048^2, 3 beyond.  d_deep_w: [A_t | Q_t], npts * E planes of N each; d_deep_tab: [column records | weights | job tables].
+template <class F>
+int Ctx<F>::deep_compose(const ms_deep* deep, const u64* gamma) {
+  DeepPlan pl;
+  RQ(deep_check("deep_compose", deep, pl));
+  XE g;
+  if (!gamma || !load_ext(gamma, &g)) return fail(MS_ERR_ARG, "deep_compose: gamma null or not canonical");
+  const u32 npts = deep->npts;
+  const size_t nf = lde_c + vtree_m;
+  // the weight table (host, as air_table_ext): per named column the points that name it and, for each, the sum of gamma^n over its entries there
+  std::vector<u32> mask(nf, 0);
+  std::vector<XE> wsum(nf * npts, e_zero<F, E>());
+  { XE gp = e_one<F, E>();
+    for (size_t n = 0; n < pl.entries; n++, gp = e_mul<F>(gp, g)) {
+      const size_t j = deep->pt_poly[n]; const u32 t = pl.pt_of[n];
+      mask[j] |= 1u << t; wsum[j * npts + t] = e_add<F, E>(wsum[j * npts + t], gp);
+    } }
+  std::vector<mspoly::DeepCol> cols; std::vector<T> wtab;
+  for (size_t j = 0; j < nf; j++) {
+    if (!mask[j]) continue;
+    cols.push_back(mspoly::DeepCol{(unsigned long long)(j < lde_c ? j * N : chunk_off(j - lde_c)), mask[j], (u32)(wtab.size() / E)});
+    for (u32 t = 0; t < npts; t++) if (mask[j] & (1u << t)) for (int l = 0; l < E; l++) wtab.push_back(wsum[j * npts + t].c[l]);
+  }
+  const size_t plane = (size_t)E * N, scr = sh_scratch_elems(N);
+  if (d_deep.ensure(plane * sizeof(T)) || d_deep_w.ensure(2 * npts * plane * sizeof(T)) || d_sh.ensure(npts * scr * sizeof(T))) return fail(MS_ERR_NOMEM, "deep_compose buffers");
+  T* A = d_deep_w.as<T>(); T* Q = A + npts * plane;
+  std::vector<SHPlan> sp;
+  for (u32 t = 0; t < npts; t++) sp.push_back(sh_plan(A + t * plane, N, 0, 1, N, pl.z[t], Q + t * plane, false, N, 0, 1, nullptr, d_sh.as<T>() + t * scr));
+  const int nl = sp[0].nl;   // (every job has N elements: the same levels)
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t off_w = up16(cols.size() * sizeof(mspoly::DeepCol)), off_j = up16(off_w + wtab.size() * sizeof(T)), jtab = (size_t)npts * sizeof(SHJ);
+  const size_t bytes = off_j + (size_t)(2 * nl - 1) * jtab;
+  if (d_deep_tab.ensure(bytes)) return fail(MS_ERR_NOMEM, "deep_compose tables");
+  u8* ht;
+  RQ(tabs_host(bytes, &ht));
+  memset(ht, 0, bytes);
+  memcpy(ht, cols.data(), cols.size() * sizeof(mspoly::DeepCol));
+  memcpy(ht + off_w, wtab.data(), wtab.size() * sizeof(T));
+  // launch order of the scans: the aggregate launches bottom-up, then the final launches top-down
+  for (int k = 0; k < 2 * nl - 1; k++) {
+    SHJ* hj = reinterpret_cast<SHJ*>(ht + off_j + (size_t)k * jtab);
+    for (u32 t = 0; t < npts; t++) hj[t] = k < nl - 1 ? sp[t].agg[k] : sp[t].fin[2 * nl - 2 - k];
+  }
+  // everything is decided: from here on only the runtime can fail
+  have_dpoly = false;
+  for (size_t n = 0; n < pl.entries; n++) if (deep->pt_poly[n] < lde_c) RQ(materialize((int)deep->pt_poly[n]));
+  CK(msrt::h2d(d_deep_tab.p, ht, bytes, stream));
+  const u8* dt = d_deep_tab.as<u8>();
+  auto combine = [&](auto np) -> int {
+    typedef mspoly::DeepCombineKernel<F, E, decltype(np)::value> DK;
+    typename DK::Params cp{d_polys.as<T>(), reinterpret_cast<const mspoly::DeepCol*>(dt), reinterpret_cast<const T*>(dt + off_w), (u32)cols.size(), npts, N, A};
+    next_bytes = (double)(cols.size() + (size_t)npts * E) * N * sizeof(T);
+    CK(run<DK>(K_DEEP_COMBINE, grid1((N + DK::VEC - 1) / DK::VEC, DK::THREADS), 1, DK::THREADS, 0, cp));
+    return 0;
+  };
+  if (npts == 1) RQ(combine(std::integral_constant<int, 1>()));
+  else if (npts == 2) RQ(combine(std::integral_constant<int, 2>()));
+  else if (npts <= 4) RQ(combine(std::integral_constant<int, 4>()));
+  else RQ(combine(std::integral_constant<int, 8>()));
+  const size_t maxnb = (N + mspoly::SH_BS - 1) / mspoly::SH_BS;
+  for (int k = 0; k < 2 * nl - 1; k++) {
+    size_t nb = maxnb;
+    const int lvl = k < nl - 1 ? k : 2 * nl - 2 - k;
+    for (int i = 0; i < lvl; i++) nb = (nb + mspoly::SH_BS - 1) / mspoly::SH_BS;
+    RQ(sh_launch_table(reinterpret_cast<const SHJ*>(dt + off_j + (size_t)k * jtab), npts, nb ? nb : 1, k < nl - 1 ? 0 : 1));
+  }
+  typedef mspoly::DeepSumScaleKernel<F, E> SK;
+  const T sh = F::from_u64(lde_shift);
+  typename SK::Params kp{Q, npts, N, sh, f_pow<F>(sh, (u64)SK::THREADS), d_deep.as<T>()};
+  next_bytes = (double)((size_t)npts + 1) * plane * sizeof(T);
+  CK(run<SK>(K_DEEP_SCALE, grid1(N, SK::THREADS * SK::ITEMS), 1, SK::THREADS, 0, kp));
+  CK(msrt::sync(stream));   // (the staged tables are free again; the caller's arrays are no longer read)
+  have_dpoly = true;
+  return MS_OK;
+}
+
 // the members this unit defines, for both fields (the other units see declarations only; the mix stages' shared steps are called from here alone and come with them)
 #define MS_INSTANTIATE(FF) \
   template int Ctx<FF>::lincomb_into(const Ctx<FF>::T* base, size_t stride, size_t n, const u64* sc, const int* idx, int k, int self_index, Ctx<FF>::T* dst); \
@@ -894,7 +1052,11 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
   template int Ctx<FF>::shard_combine_launch(size_t off, size_t rank_stride, u32 n, const Ctx<FF>::XE& zstep, Ctx<FF>::T* out); \
   template int Ctx<FF>::eval_finish(int q, const std::vector<int>& ev, u64* out); \
   template int Ctx<FF>::eval_ext_sharded(const u64* z, int q, u64* out); \
-  template int Ctx<FF>::eval_ext(const u64* z, int q, u64* out);
+  template int Ctx<FF>::eval_ext(const u64* z, int q, u64* out); \
+  template int Ctx<FF>::deep_check(const char* who, const ms_deep* d, Ctx<FF>::DeepPlan& pl); \
+  template int Ctx<FF>::validity_commit(size_t lpn, u8* root); \
+  template int Ctx<FF>::deep_evals(const ms_deep* deep, u64* evals); \
+  template int Ctx<FF>::deep_compose(const ms_deep* deep, const u64* gamma);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -153,6 +153,10 @@ struct CtxBase {
   virtual int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) = 0;
   virtual int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) = 0;
   virtual int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
+  virtual int validity_commit(size_t lpn, u8* root) = 0;
+  virtual int deep_evals(const ms_deep* deep, u64* evals) = 0;
+  virtual int deep_compose(const ms_deep* deep, const u64* gamma) = 0;
+  virtual int deep_len_() const = 0;
   virtual int grind(const u8* seed, u32 bits, u64 start, u64 limit, u64* nonce) = 0;
   virtual int ntt(u64* data, size_t n, size_t batch, int inverse) = 0;
   virtual int coset_lde(const u64* coeffs, size_t ncoef, size_t batch, u64 shift, u64* out, size_t L) = 0;
@@ -238,7 +242,7 @@ template <class F> struct Ctx : CtxBase {
 
   // ---- optional per-kernel timing with HIP events on the launching stream (bench.py roofline leg)
   enum { K_NTT_PASS, K_SCALE_POW, K_LEAF_HASH, K_INNER_HASH, K_TRANSPOSE, K_IO, K_LINCOMB, K_MIX, K_EVAL, K_EVAL_REDUCE, K_FOLD,
-         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_MIX_AIR_EXT, K_AIR_CHECK, K_COUNT };
+         K_SUFFIX_HORNER, K_DEGREE, K_FIND_FIRST, K_PATH, K_QUERY_POINTS, K_FRI_TAIL, K_MIX_TERMS, K_MIX_AIR, K_AIR_INV, K_AUX, K_GRIND, K_MIX_AIR_EXT, K_AIR_CHECK, K_DEEP_COMBINE, K_DEEP_SCALE, K_COUNT };
   struct ProfRec { int kid, sub; EventOwner a, b; double bytes; bool part; };   // (the records of a profile never ended go with the context)
   // sharded proofs: launches inside a PartScope work on this rank's PART of the proof (1 / world of it); everything else is replicated on every rank.
   // ms_profile_end reports both sums: the replicated one bounds the strong scaling (bench.py: sharded.replicated_ms_estimate)
@@ -779,6 +783,24 @@ template <class F> struct Ctx : CtxBase {
   template <int EL> int open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_t out_bytes, const Round* fin, size_t fin_off, u8* out);
   int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) override;
   int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
+  // ------------------------------------------------------------------ build-defined: the composition commitment and the DEEP stage (include/ministark.h; kernels:
+  // mspoly::DeepCombineKernel, mspoly::DeepSumScaleKernel; host side: air_stages.cpp).  The validity polynomial's ve limb planes of VL coefficients are m = ve * VL / N
+  // chunk columns of N coefficients, column k * ve + l = coefficients [kN, (k+1)N) of plane l: views of the polynomial where it lies, behind the constraint polynomials.
+  // d_vlde holds their evaluations on the LDE coset (column j' at + j' * L), d_vlde_nodes the tree over its rows.  The tree lives while have_validity and have_lde
+  // do and no mix stage has run since (vtree_live); the DEEP polynomial D' (d_deep: limb l at + l * N) lives at most as long.
+  bool have_vtree = false, have_dpoly = false;
+  DevBuf d_vlde, d_vlde_nodes, d_deep, d_deep_w, d_deep_tab;
+  TreeShape vtree_ts; size_t vtree_m = 0;
+  bool vtree_live() const { return have_vtree && have_validity && have_lde; }
+  bool dpoly_live() const { return have_dpoly && vtree_live(); }
+  void drop_vtree() { have_vtree = have_dpoly = false; }
+  size_t chunk_off(size_t j) const { const size_t ve = (size_t)validity_ext; return (size_t)npolys * N + (j % ve) * validity_len + (j / ve) * N; }   // chunk column j in d_polys
+  struct DeepPlan { std::vector<XE> z; std::vector<u32> pt_of; size_t entries = 0; };
+  int deep_check(const char* who, const ms_deep* d, DeepPlan& pl);
+  int validity_commit(size_t lpn, u8* root) override;
+  int deep_evals(const ms_deep* deep, u64* evals) override;
+  int deep_compose(const ms_deep* deep, const u64* gamma) override;
+  int deep_len_() const override { return dpoly_live() ? (int)N : 0; }
   // ------------------------------------------------------------------ build-defined: proof-of-work grinding (include/ministark.h; kernel: grind.hpp, host side: merkle_tree.cpp)
   u64 grind_launch_max = (u64)1 << 30;   // MS_GRIND_LAUNCH_MAX: most nonces of one launch
   unsigned grind_grid = 0;               // MS_GRIND_GRID: workgroups of a launch (0: by the device's compute units at the kernel's occupancy)

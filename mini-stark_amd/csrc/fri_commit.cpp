@@ -138,19 +138,21 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   static_assert(Results::TAIL_DONE == Results::FRI_LEN + 128, "one fill clears both lines");
   CK(msrt::memset_dev(res.word(Results::FRI_LEN), 0, 256, stream));
   Round* r = round_slot(0);
-  const size_t VL = validity_len;   // N (ms_mix) or 2N (ms_mix_cubic)
+  const bool dp = dpoly_live();       // ms_deep_compose: round 0 starts from the DEEP polynomial D' (N coefficients, E limbs N apart) in place of the validity polynomial
+  const size_t VL = dp ? N : validity_len;   // N (ms_mix) or 2N (ms_mix_cubic)
   r->cap = VL;
   if (r->poly.ensure(VL * E * sizeof(T))) return fail(MS_ERR_NOMEM, "round poly");
-  const bool vx = validity_ext > 1;   // ms_mix_air_ext: the validity polynomial has its E limbs already, VL apart as the round's are
+  const bool vx = dp || validity_ext > 1;   // ms_mix_air_ext: the validity polynomial has its E limbs already, VL apart as the round's are
   if (vx && sh_on) return fail(MS_ERR_STATE, "fri_begin: a validity polynomial over the extension on a context with sharding on");
-  if (vx) CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * E * sizeof(T), stream));
+  if (dp) CK(msrt::d2d(r->poly.p, d_deep.p, VL * E * sizeof(T), stream));
+  else if (vx) CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * E * sizeof(T), stream));
   else {
   // field.rs:23-32 extend_poly: limb 0 = validity, higher limbs zero
   CK(msrt::memset_dev(r->poly.p, 0, VL * E * sizeof(T), stream));
   CK(msrt::d2d(r->poly.p, d_polys.as<T>() + (size_t)npolys * N, VL * sizeof(T), stream));
   }
   unsigned long long nc = validity_ncoef;   // (came to the host with DEEP-ALI's values: ms_mix scans, ms_eval_ext forwards)
-  if (validity_len_at != VLEN_HOST) {   // a scan of its own and a copy behind it
+  if (dp || validity_len_at != VLEN_HOST) {   // a scan of its own and a copy behind it (the validity polynomial's length, where known, is not D''s)
     unsigned long long* dres;
     RQ(degree_launch(r->poly.template as<T>(), r->cap, VL, &dres));
     auto scan = res.expect(dres, false, false);

@@ -339,6 +339,10 @@ int Ctx<F>::open_view(int tree, int round, OpenView* v) {
     if (!have_lde) return fail(MS_ERR_STATE, "tree_open: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
     ts = &lde_ts;
     o.base = d_lde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)lde_c; o.lin = lde_lin(); o.nodes = d_lde_nodes.template as<u32>();
+  } else if (tree == MS_TREE_VALIDITY) {
+    if (!vtree_live()) return fail(MS_ERR_STATE, "tree_open: no validity tree (ms_validity_commit, and no mix stage, ms_polys_*, ms_lde_commit or ms_trace_commit since)");
+    ts = &vtree_ts;
+    o.base = d_vlde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)vtree_m; o.nodes = d_vlde_nodes.template as<u32>();
   } else if (tree == MS_TREE_FRI) {
     if (nrounds_done == 0) return fail(MS_ERR_STATE, "tree_open: no FRI round committed (ms_fri_begin)");
     if (round < 0 || (size_t)round >= nrounds_done) return fail(MS_ERR_ARG, "tree_open: round index");
@@ -386,7 +390,7 @@ template <class F>
 int Ctx<F>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) {
   if (!index || !len || (!out && cap)) return fail(MS_ERR_ARG, "tree_open: null argument");
   if (n < 1 || n > 65536) return fail(MS_ERR_ARG, "tree_open: n outside 1..65536");
-  if (tree != MS_TREE_TRACE && tree != MS_TREE_LDE && tree != MS_TREE_FRI) return fail(MS_ERR_ARG, "tree_open: unknown tree id");
+  if (tree != MS_TREE_TRACE && tree != MS_TREE_LDE && tree != MS_TREE_FRI && tree != MS_TREE_VALIDITY) return fail(MS_ERR_ARG, "tree_open: unknown tree id");
   if (sh_on) return fail(MS_ERR_STATE, "tree_open: not available on a context with sharding on");
   OpenView v;
   RQ(open_view(tree, round, &v));

@@ -934,6 +934,105 @@ template <class F, int E> struct GatherPolyKernel {
   }
 };
 
+// ---------------------------------------------------------------- DEEP composition (ms_deep_compose)
+// The gamma-weighted combinations of the committed columns, one per opened point, in ONE streaming pass:
+//   A_t[k] = sum_{columns j that point t names} w_(j,t) * col_j[k]        w_(j,t) = the sum of gamma^n over the entries n of point t that name column j (host table)
+// A thread owns 16 bytes of consecutive coefficients (VEC = 2 Goldilocks / 4 BabyBear elements).  It walks the column records - wave-uniform table reads: the record,
+// then one weight of E limbs for every point in the record's mask - loads the column's coefficients ONCE, however many points name the column, and spends one
+// base-by-extension multiply-add (e_mul_base) per coefficient and naming point.  The NP x VEC accumulators (NP = the number of points rounded up to a power of two)
+// stay in registers; no LDS, no scratch, no atomics.  Four columns' loads are issued before the first of them is used.  Limb l of A_t goes to out[(t * E + l) * n ..).
+// A vector access needs n to be a multiple of VEC (columns lie n apart): a shorter vector (n < VEC) takes the element-wise path.
+struct DeepCol { unsigned long long off; u32 mask, wbase; };   // the column's coefficients at base + off | the points that name it | its first weight in the weight table (in elements of E limbs)
+constexpr int DEEP_MAX_POINTS = 8, DEEP_MAX_ENTRIES = 8192;
+template <class F, int E, int NP> struct DeepCombineKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int VEC = 16 / (int)sizeof(T), AHEAD = 4;
+  typedef T V16 __attribute__((vector_size(16)));
+  struct Params { const T* base; const DeepCol* cols; const T* w; u32 ncols, npts; size_t n; T* out; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
+    const size_t j = ((size_t)bx * nthreads + tid) * VEC;
+    if (j >= p.n) return;
+    const bool whole = j + VEC <= p.n && (p.n % VEC) == 0;
+    Ext<F, E> acc[NP][VEC];
+#pragma unroll
+    for (int t = 0; t < NP; t++)
+#pragma unroll
+      for (int i = 0; i < VEC; i++) acc[t][i] = e_zero<F, E>();
+    for (u32 c0 = 0; c0 < p.ncols; c0 += AHEAD) {
+      V16 v[AHEAD];
+#pragma unroll
+      for (int u = 0; u < AHEAD; u++) {
+        if (c0 + u < p.ncols) {
+          const T* src = p.base + p.cols[c0 + u].off + j;
+          if (whole) v[u] = *reinterpret_cast<const V16*>(src);
+          else
+#pragma unroll
+            for (int i = 0; i < VEC; i++) v[u][i] = (j + i < p.n) ? src[i] : (T)0;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < AHEAD; u++) {
+        if (c0 + u < p.ncols) {
+          const u32 mask = p.cols[c0 + u].mask;
+          const T* w = p.w + (size_t)p.cols[c0 + u].wbase * E;
+#pragma unroll
+          for (int t = 0; t < NP; t++) {
+            if (mask & (1u << t)) {
+              Ext<F, E> wt;
+#pragma unroll
+              for (int l = 0; l < E; l++) wt.c[l] = w[l];
+              w += E;
+#pragma unroll
+              for (int i = 0; i < VEC; i++) acc[t][i] = e_add<F, E>(acc[t][i], e_mul_base<F, E>(wt, v[u][i]));
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < NP; t++) {
+      if ((u32)t < p.npts) {
+#pragma unroll
+        for (int l = 0; l < E; l++) {
+          T* dst = p.out + ((size_t)t * E + l) * p.n + j;
+          if (whole) {
+            V16 o;
+#pragma unroll
+            for (int i = 0; i < VEC; i++) o[i] = acc[t][i].c[l];
+            *reinterpret_cast<V16*>(dst) = o;
+          } else
+#pragma unroll
+            for (int i = 0; i < VEC; i++) if (j + i < p.n) dst[i] = acc[t][i].c[l];
+        }
+      }
+    }
+  }
+};
+// D'_k = shift^k * sum_t Q_t[k] for k < n - 1, 0 at k = n - 1: the sum of the npts synthetic-division quotients (limb l of Q_t at q[(t * E + l) * n ..), written by the
+// scans for k < n - 1 only) moved to the coset's own variable, D'(y) = D(shift y).  dst: limb l at dst[l * n ..).
+template <class F, int E> struct DeepSumScaleKernel {
+  typedef typename F::T T;
+  static constexpr int THREADS = mspoly::THREADS;
+  static constexpr int ITEMS = 4;
+  struct Params { const T* q; u32 npts; size_t n; T s, s_step /* s^THREADS */; T* dst; };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int, unsigned char*) {
+    size_t k = (size_t)bx * (THREADS * ITEMS) + tid;
+    if (k >= p.n) return;
+    T pw = f_pow<F>(p.s, k);
+    for (int it = 0; it < ITEMS && k < p.n; it++, k += THREADS) {
+      for (int l = 0; l < E; l++) {
+        T sum = 0;
+        if (k + 1 < p.n) for (u32 t = 0; t < p.npts; t++) sum = F::add(sum, p.q[((size_t)t * E + l) * p.n + k]);
+        p.dst[(size_t)l * p.n + k] = F::mul(sum, pw);
+      }
+      pw = F::mul(pw, p.s_step);
+    }
+  }
+};
+
 // ---------------------------------------------------------------- build-defined degree-3 composition (ms_mix_cubic)
 // BASELINE configs[4] names "degree-3 constraints", which the reference cannot express (quirk Q1: its `validity` polynomial is the REMAINDER of the division by
 // the vanishing polynomial, so any constraint polynomial with >= N coefficients panics).  The build-defined variant, with the TRUE quotient:

@@ -8,7 +8,7 @@ namespace msctx {
 template <class F>
 int Ctx<F>::profile_end(char* out, size_t cap) {
   static const char* names[K_COUNT] = {"ntt_pass", "scale_pow", "leaf_hash", "inner_hash", "transpose_in", "io_copy", "lincomb", "mix", "eval", "eval_reduce",
-                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv", "aux_running", "grind", "mix_air_ext", "air_check"};
+                                       "fold", "suffix_horner", "degree", "find_first", "merkle_path", "query_points", "fri_tail", "mix_terms", "mix_air", "air_inv", "aux_running", "grind", "mix_air_ext", "air_check", "deep_combine", "deep_scale"};
   msrt::sync(stream);
   double ms[K_COUNT] = {0}, by[K_COUNT] = {0}, ms_part = 0, ms_repl = 0, repl_by[K_COUNT] = {0}; unsigned long long cnt[K_COUNT] = {0};
   std::map<int, double> sub_ms, sub_by; std::map<int, unsigned long long> sub_cnt;

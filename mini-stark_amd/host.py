@@ -95,6 +95,38 @@ def fri_index_verify(digest_id, field, zero_display_empty, blowup, roots, z, B, 
     return rc, why.value.decode()
 
 
+def deep_link_verify(digest_id, field, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, z, lists, evals, gamma, betas, msfi, lde_open, val_open):
+    """msh_deep_link_verify: FRI's round 0 (the MSFI blob) against the LDE tree and the validity tree.  z / lists as for Context.deep_evals, evals its output, gamma the
+    challenge of Context.deep_compose; lde_open / val_open: Context.tree_open of TREE_LDE / TREE_VALIDITY at the rows of window 0's positions (ministark_host.h).
+    Returns (rc, why): rc 1 accepted, 0 rejected, < 0 malformed arguments."""
+    from ._native import deep_struct
+    H = _host()
+    u64p = C.POINTER(C.c_uint64)
+    H.msh_deep_link_verify.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, u64p, u64p,
+                                       u64p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+    arr = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))   # noqa: E731
+    s, _keep = deep_struct(z, lists)
+    ev, gg, be = arr(evals), arr(gamma), arr(betas)
+    why = C.create_string_buffer(512)
+    rc = H.msh_deep_link_verify(int(digest_id), int(field), 1 if zero_display_empty else 0, int(N), int(blowup), int(shift), int(c), int(m), bytes(lde_root), bytes(val_root),
+                                C.addressof(s), ev.ctypes.data_as(u64p), gg.ctypes.data_as(u64p), be.ctypes.data_as(u64p), be.size, bytes(msfi), len(msfi),
+                                bytes(lde_open), len(lde_open), bytes(val_open), len(val_open), why, 512)
+    return rc, why.value.decode()
+
+
+def validity_from_chunks(field, ve, N, z, chunk_evals):
+    """msh_validity_from_chunks: V(z) from the evaluations of the m = ve * nchunks chunk columns ([m][E] limbs, chunk column k * ve + l at index k * ve + l).
+    Returns (status, E limbs)."""
+    u64p = C.POINTER(C.c_uint64)
+    zz = np.ascontiguousarray(np.asarray(z, dtype=np.uint64).reshape(-1))
+    ce = np.ascontiguousarray(np.asarray(chunk_evals, dtype=np.uint64).reshape(-1))
+    out = np.zeros(zz.size, dtype=np.uint64)
+    nchunks = ce.size // (zz.size * int(ve))
+    rc = _host().msh_validity_from_chunks(C.c_int(field), C.c_uint32(int(ve)), C.c_uint32(nchunks), C.c_uint64(int(N)), zz.ctypes.data_as(u64p), ce.ctypes.data_as(u64p),
+                                          out.ctypes.data_as(u64p))
+    return rc, out
+
+
 def terms_expected_validity(field, r, constraints, nexempt, N, z, rows, opened, npolys=None):
     """msh_terms_expected_validity: the value validity(z) must have after ms_mix_terms, from the opened values.  `constraints` as for Context.mix_terms (or the CSR
     5-tuple); `rows` the row offsets opened, `opened[k]` = the ms_eval_ext output at w^rows[k] z ([c + 1][E], or [c][E] with npolys = c).  Returns (status, E limbs)."""

@@ -646,6 +646,112 @@ template <class F, int E> static int fri_index_verify(int digest, int zae, u64 b
   return 1;
 }
 
+// ---- the verifying side of the DEEP stage (ministark.h: ms_validity_commit, ms_deep_compose; build-defined) -------------------------------------------------------
+// V(z) = sum_k z^(kN) sum_l u_l V_(k,l)(z) from the m = ve * nchunks chunk evaluations (chunk column k * ve + l, E limbs each); u_l = the l-th basis element of K
+template <class F, int E> static void validity_from_chunks(u32 ve, u32 nchunks, u64 N, const u64* z, const u64* ev, u64* out) {
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  const X zz = V::load(z), zN = e_pow<F, E>(zz, N);
+  X acc = e_zero<F, E>();
+  for (u32 k = nchunks; k-- > 0;) {   // Horner in z^N
+    X inner = e_zero<F, E>();
+    for (u32 l = 0; l < ve; l++) { X u = e_zero<F, E>(); u.c[l] = F::from_u64(1); inner = e_add<F, E>(inner, e_mul<F>(u, V::load(ev + ((size_t)k * ve + l) * E))); }
+    acc = e_add<F, E>(e_mul<F>(acc, zN), inner);
+  }
+  for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
+}
+
+// the link between FRI's round 0 and the two committed trees: 1 accepted, 0 rejected (reason in *why), < 0 malformed arguments
+template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N, u64 blowup, u64 shift, u32 c, u32 m, const u8* lde_root, const u8* val_root, const ms_deep& d,
+                                                      const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msfi, size_t msfi_len,
+                                                      const u8* lde_open, size_t lde_len, const u8* val_open, size_t val_len, std::string* why) {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  const u64 L = N * blowup;
+  if (shift == 0 || shift >= F::P || L > ((u64)1 << F::TWO_ADICITY)) { *why = "shift or domain size out of range"; return MS_ERR_ARG; }
+  if (d.npts < 1 || d.npts > 8 || d.pt_begin[0] != 0) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+  for (u32 t = 0; t < d.npts; t++) if (d.pt_begin[t + 1] <= d.pt_begin[t] || d.pt_begin[t + 1] > 8192) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+  const size_t ne = d.pt_begin[d.npts];
+  for (size_t n = 0; n < ne; n++) if (d.pt_poly[n] >= c + m) { *why = "malformed ms_deep: an index at or above c + m"; return MS_ERR_ARG; }
+  if (!V::canon(d.z, (size_t)d.npts * E) || !V::canon(gamma, E)) { *why = "a point or gamma is not canonical"; return MS_ERR_ARG; }
+  if (!V::canon(evals, ne * E)) { *why = "claimed evaluation not canonical"; return 0; }
+  int lgL = 0; while (((u64)1 << lgL) < L) lgL++;
+  const T sh = F::from_u64(shift), gL = f_root_of_unity<F>(lgL), shL = f_pow<F>(sh, L);
+  std::vector<X> z(d.npts);
+  for (u32 t = 0; t < d.npts; t++) {
+    z[t] = V::load(d.z + (size_t)t * E);
+    if (e_eq<F, E>(e_pow<F, E>(z[t], L), e_from_base<F, E>(shL))) { *why = "a point lies in the LDE coset: the quotient by (x - z) is undefined at one of its rows"; return 0; }
+  }
+  // the MSFI header, the final polynomial, and window 0's openings (the whole blob is msh_fri_index_verify's to check)
+  if (msfi_len < 48) { *why = "MSFI blob shorter than its header"; return 0; }
+  u64 hd[6]; memcpy(hd, msfi, 48);
+  if (hd[0] != 0x4946534DULL) { *why = "not an MSFI blob (magic)"; return 0; }
+  if (hd[1] != (u64)E || hd[3] != (u64)nq || hd[2] < 1 || hd[2] > 64) { *why = "MSFI header: E, rounds or queries are not the verifier's"; return 0; }
+  const u64 R = hd[2], D0 = hd[4], nfinal = hd[5];
+  if (D0 < 1 || (D0 & (D0 - 1)) || D0 > L || L % D0) { *why = "MSFI header: D_0 does not divide the LDE domain"; return 0; }
+  if (R > 1 && D0 < 2) { *why = "MSFI header: D_0 cannot be halved"; return 0; }
+  const u8* bp = msfi + 48; size_t left = msfi_len - 48;
+  if (left / 8 < nfinal * E || nfinal > D0) { *why = "MSFI blob truncated in the final polynomial"; return 0; }
+  const u64* fin = (const u64*)bp;
+  if (!V::canon(fin, (size_t)nfinal * E)) { *why = "final polynomial coefficient not canonical"; return 0; }
+  bp += nfinal * E * 8; left -= nfinal * E * 8;
+  const u64 step = L / D0;
+  int lg0 = 0; while (((u64)1 << lg0) < D0) lg0++;
+  const T g0 = f_root_of_unity<F>(lg0);
+  X gp = e_one<F, E>();
+  const X g = V::load(gamma);
+  std::vector<X> gpow(ne), ev(ne);
+  std::vector<u32> pt_of(ne);
+  for (u32 t = 0; t < d.npts; t++) for (u32 n = d.pt_begin[t]; n < d.pt_begin[t + 1]; n++) pt_of[n] = t;
+  for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
+  const u8* lp = lde_open; size_t lleft = lde_len;
+  const u8* vp = val_open; size_t vleft = val_len;
+  for (size_t j = 0; j < nq; j++) {
+    const u64 b = betas[j] % D0;
+    for (int s = 0; s < 2; s++) {
+      const u64 pos = s ? (b + D0 / 2) % D0 : b, row = pos * step;
+      size_t used = 0;
+      std::string w;
+      if (!check_path_at<F>(digest, 1, c, zae, lde_root, lp, lleft, row * c, &used, &w)) { *why = "LDE opening: " + w; return 0; }
+      const u64* lrow = (const u64*)(lp + 8);
+      lp += used; lleft -= used;
+      if (!check_path_at<F>(digest, 1, m, zae, val_root, vp, vleft, row * m, &used, &w)) { *why = "validity opening: " + w; return 0; }
+      const u64* vrow = (const u64*)(vp + 8);
+      vp += used; vleft -= used;
+      // D(x) at x = shift * g_L^row from the opened rows and the claimed evaluations
+      const T x = F::mul(sh, f_pow<F>(gL, row));
+      std::vector<X> inv(d.npts);
+      for (u32 t = 0; t < d.npts; t++) inv[t] = e_inv<F>(e_sub<F, E>(e_from_base<F, E>(x), z[t]));
+      X Dx = e_zero<F, E>();
+      for (size_t n = 0; n < ne; n++) {
+        const u32 fi = d.pt_poly[n];
+        const T fx = F::from_u64(fi < c ? lrow[fi] : vrow[fi - c]);
+        Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
+      }
+      X y;
+      if (R > 1) {   // what window 0 opened at this position
+        const size_t head = 8 + 2 * (size_t)E * 8 + 8;
+        if (left < head) { *why = "MSFI blob truncated in window 0"; return 0; }
+        u64 li, nlev; memcpy(&li, bp, 8); memcpy(&nlev, bp + head - 8, 8);
+        if (nlev > 64 || left - head < (size_t)nlev * 64) { *why = "MSFI blob truncated in window 0"; return 0; }
+        if (li != pos) { *why = "MSFI: a window-0 path is not at the query's position"; return 0; }
+        if (!V::canon((const u64*)(bp + 8), 2 * E)) { *why = "MSFI: opened value not canonical"; return 0; }
+        y = V::load((const u64*)(bp + 8) + (pos & 1) * E);
+        bp += head + (size_t)nlev * 64; left -= head + (size_t)nlev * 64;
+      } else {       // no window: the final polynomial IS round 0's, in the clear
+        const X xb = e_from_base<F, E>(f_pow<F>(g0, pos));
+        y = e_zero<F, E>();
+        for (size_t k = nfinal; k-- > 0;) y = e_add<F, E>(e_mul<F>(y, xb), V::load(fin + k * E));
+      }
+      if (!e_eq<F, E>(Dx, y)) { *why = R > 1 ? "DEEP link: the composition recomputed from the opened rows and the claimed evaluations is not the value round 0 opened" : "DEEP link: the composition recomputed from the opened rows and the claimed evaluations is not the final polynomial's value"; return 0; }
+    }
+  }
+  if (lleft != 0) { *why = "LDE opening: trailing bytes"; return 0; }
+  if (vleft != 0) { *why = "validity opening: trailing bytes"; return 0; }
+  return 1;
+}
+
 }  // namespace ministark
 
 // ---- C entry points for the Python test / bench harness ---------------------------------------
@@ -1057,6 +1163,31 @@ int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, u64 b
     std::string w;
     const int rc = field == MS_FIELD_GOLDILOCKS ? fri_index_verify<GL, 2>(digest_id, zero_display_empty, blowup, roots, rounds, z, B, alpha, betas, nq, blob, len, &w)
                                                 : fri_index_verify<BB, 4>(digest_id, zero_display_empty, blowup, roots, rounds, z, B, alpha, betas, nq, blob, len, &w);
+    return set_why(why, why_cap, w.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+int msh_validity_from_chunks(int field, uint32_t ve, uint32_t nchunks, u64 N, const u64* z, const u64* chunk_evals, u64* out) {
+  if ((field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) || !z || !chunk_evals || !out || !nchunks || !N) return MS_ERR_ARG;
+  const u32 E = field == MS_FIELD_GOLDILOCKS ? 2 : 4;
+  if ((ve != 1 && ve != E) || nchunks > 4096) return MS_ERR_ARG;
+  const bool ok = field == MS_FIELD_GOLDILOCKS ? Verifier<GL, 2>::canon(z, E) && Verifier<GL, 2>::canon(chunk_evals, (size_t)ve * nchunks * E)
+                                               : Verifier<BB, 4>::canon(z, E) && Verifier<BB, 4>::canon(chunk_evals, (size_t)ve * nchunks * E);
+  if (!ok) return MS_ERR_ARG;
+  if (field == MS_FIELD_GOLDILOCKS) validity_from_chunks<GL, 2>(ve, nchunks, N, z, chunk_evals, out); else validity_from_chunks<BB, 4>(ve, nchunks, N, z, chunk_evals, out);
+  return MS_OK;
+}
+int msh_deep_link_verify(int digest_id, int field, int zero_display_empty, u64 N, u64 blowup, u64 shift, uint32_t c, uint32_t m, const u8 lde_root[32], const u8 val_root[32],
+                         const ms_deep* deep, const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msfi, size_t msfi_len,
+                         const u8* lde_open, size_t lde_len, const u8* val_open, size_t val_len, char* why, size_t why_cap) {
+  if (!known_digest(digest_id) || (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR)) return set_why(why, why_cap, "unknown digest or field", MS_ERR_ARG);
+  if (!lde_root || !val_root || !deep || !deep->z || !deep->pt_begin || !deep->pt_poly || !evals || !gamma || !betas || !msfi || !lde_open || !val_open || nq < 1 || nq > 4096 ||
+      !N || (N & (N - 1)) || !blowup || (blowup & (blowup - 1)) || N > ((u64)1 << 32) || blowup > ((u64)1 << 16) || c < 1 || m < 1 || c > (1u << 24) || m > (1u << 24))
+    return set_why(why, why_cap, "null argument, or N, blowup, c, m or queries out of range", MS_ERR_ARG);
+  try {
+    std::string w;
+    const int rc = field == MS_FIELD_GOLDILOCKS
+      ? deep_link_verify<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, val_open, val_len, &w)
+      : deep_link_verify<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, val_open, val_len, &w);
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }

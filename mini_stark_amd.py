@@ -10,6 +10,6 @@ from mini_stark_amd._native import (  # noqa: E402,F401
     AUX_SUM, AUX_PRODUCT, MsAux, flatten_aux, aux_struct, aux_constraints,
     GOLDILOCKS, BABYBEAR, FLAG_ZERO_DISPLAY_EMPTY, FLAG_TRACE_MONT64, FLAG_LATENCY, FLAG_DIGEST_BLAKE2S, FLAG_DIGEST_BLAKE3, FLAG_DIGEST_KECCAK256, FLAG_DIGEST_SHA3_256,
     DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256,
-    TREE_TRACE, TREE_LDE, TREE_FRI,
+    TREE_TRACE, TREE_LDE, TREE_FRI, TREE_VALIDITY, MsDeep, deep_struct,
     OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM,
 )
