@@ -141,6 +141,7 @@ extern "C" {
     pub fn ms_tree_open(ctx: *mut ms_ctx, tree: c_int, round: c_int, index: *const u64, n: usize, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- the compact query phase (build-defined): the MSFI blob - openings by position, the last round's polynomial in the clear
     pub fn ms_fri_query_index(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn ms_query_linked(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- the composition commitment and the DEEP stage (build-defined): the tree over the validity polynomial's chunk columns on the LDE coset; the claimed evaluations;
     // D' = sum_t (A_t - A_t(z_t)) / (x - z_t) on the coset's own variable, which ms_fri_begin then starts from
     pub fn ms_validity_commit(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;

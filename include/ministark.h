@@ -479,6 +479,22 @@ int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]);
 int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals /* entries * E limbs: F_{pt_poly[n]}(z_t), entry order */);
 int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma /* E limbs */);
 int ms_deep_len(const ms_ctx* ctx);   /* 0, or N once a DEEP polynomial is installed */
+/* The WHOLE query phase of a linked proof in one call and ONE launch: what ms_fri_query_index(betas), ms_tree_open(MS_TREE_LDE) and ms_tree_open(MS_TREE_VALIDITY) at
+ * the rows under round 0's positions return, in one blob - one job upload, one launch, one read-back, one stream synchronisation in place of three of each.
+ * Valid when the FRI commit phase is finished, a DEEP polynomial is installed (ms_deep_len != 0, so the validity tree lives), both row trees hold one row per leaf
+ * group, and round 0's domain satisfies D_0 | L, D_0 <= L (ms_fri_begin with the LDE's blowup); otherwise MS_ERR_STATE.  MS_ERR_STATE on a context with sharding on, as
+ * ms_tree_open.  MS_ERR_ARG, the size query (out = NULL, cap = 0) and the cap rule as ms_fri_query_index: null betas or len, out = NULL with cap != 0, nq outside
+ * 1..4096, cap too small (*len is set).  Everything is decided before anything is launched, and the context is unchanged: a later ms_fri_query, ms_fri_query_index or
+ * ms_tree_open returns the bytes it returns without the call.
+ * MSLQ layout, u64 little-endian words:
+ *   'MSLQ' (0x514C534D) | len_msfi | len_lde | len_val          the three sections' lengths in bytes
+ *   MSFI blob           exactly the bytes ms_fri_query_index(betas) returns (its own header included)
+ *   LDE openings        exactly the bytes ms_tree_open(MS_TREE_LDE, 0, rows) returns
+ *   validity openings   exactly the bytes ms_tree_open(MS_TREE_VALIDITY, 0, rows) returns
+ * rows: the 2 * nq rows msh_deep_link_verify expects - with b_j = betas[j] mod D_0 and p_j = b_j * (L / D_0), query j contributes p_j, then (p_j + L / 2) mod L, in
+ * query order.  The equality with the three calls is the definition (tests/test_linked_*.py hold the bytes to it).  A virtual linear LDE column opens with the value
+ * that was hashed, as in ms_tree_open.  Not measured on the device yet (tools/linked_bench.py, profiles/linked.json). */
+int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
 
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
  * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI

@@ -143,6 +143,61 @@ int msh_air_expected_validity(int field, uint64_t r, const ms_air* air, uint64_t
  * or a limb >= p is MS_ERR_ARG.  r = (r0, 0, ..) gives msh_air_expected_validity(r0). */
 int msh_air_expected_validity_ext(int field, const uint64_t* r /* E limbs */, const ms_air* air, uint64_t N, const uint64_t* z, int nrows, const uint32_t* rows,
                                   const uint64_t* opened, size_t row_stride, uint32_t npolys, uint64_t* out);
+/* ---- LINKED PROOFS: MSLP v1 (build-defined; the sound counterpart of msh_stark_prove / MSSP, which keep the reference's unlinked flow byte for byte) ----------------
+ * THE STATEMENT a linked proof claims: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air` - its transition constraints,
+ * exemption sets, periodic columns and boundary values are the public input.  The constraint polynomials are the trace columns (c = w; no ms_polys_lincomb
+ * transitions).  Running columns (ms_aux_running) are not part of the flow: their challenges would have to follow a commitment to the main columns' LDE, a staged
+ * commitment that does not exist yet.  The raw-trace root is computed because ms_trace_commit is how the trace gets in; it is absorbed first
+ * and BINDS NOTHING - no opening of that tree is part of the proof.
+ * The handle's configuration supplies field, digest, blowup, the rounds (fri_rounds = 0), fri_queries and the grinding bits (msh_stark_set_grinding).  The linked proof
+ * lives in a slot of its own: msh_stark_prove, MSSP and the two MSFP slots are untouched.
+ *
+ * msh_air_encode: the canonical bytes of an AIR program, little-endian: u32 'MSAR' (0x5241534D) | u32 version 1 | u32 ncons, nterms, nfacs, nexempt, nperiodic,
+ * nperval, nbound, array_bytes (the eight counts: nterms = term_begin[ncons], nfacs = fac_begin[nterms], nexempt = ex_begin[ncons], nperval = per_begin[nperiodic],
+ * array_bytes = the bytes that follow) | the arrays in the order of the ms_air struct: term_begin, coef, fac_begin, fac_poly, fac_row, ex_begin, ex_row, per_begin
+ * (the single word 0 when nperiodic = 0), per_val, bnd_poly, bnd_row, bnd_val - u32 arrays as u32, u64 arrays as u64.  The counts fix every array's length, so two
+ * programs that differ in any entry encode differently.  Returns the size (writes when cap suffices), 0 for a null or malformed program (a needed array missing, CSR
+ * offsets not starting at 0 or decreasing, a limit of ms_mix_air on the counts exceeded).
+ * msh_air_rows: the row offsets the verifying side needs opened - those of the program's factors, and row 0 when there are boundary constraints - ascending, the C
+ * twin of mini_stark_amd.air_rows.  Returns their number (the first `cap` are written), MS_ERR_ARG for a malformed program.
+ *
+ * TRANSCRIPT: the Transcript hash chain with the domain separator domsep + "/linked/v1" (a linked and an unlinked transcript never coincide), in this order:
+ *   1. absorb the statement: the u64 words field, digest id, N, w, blowup, R, nq, grinding bits; then msh_air_encode(air).  (The statement does not travel.)
+ *   2. absorb the trace root; draw shift (one base-field scalar), REDRAWN while msh_linked_shift_ok is 0: shift == 0 or shift^L == 1, the coset meeting the trace
+ *      domain - probability about 2^-8 for BabyBear at the headline size, so the redraw is part of the protocol on both sides, not an error path.
+ *   3. ms_interpolate, ms_lde_commit(blowup, shift, lpn = w); absorb the LDE root.
+ *   4. draw r (E limbs); ms_mix_air_ext.  MS_ERR_SHAPE comes back as is: the trace violates the AIR.
+ *   5. ms_validity_commit(m), m = E * VL / N; absorb the validity root.
+ *   6. draw z (E limbs), REDRAWN while msh_linked_z_ok is 0: every limb above limb 0 zero, z in the base field (this makes ms_deep_compose's MS_ERR_SHAPE
+ *      unreachable).  The points are z * w^row for row in msh_air_rows(air), row 0 first (added if the program does not name it); more than 8: MS_ERR_ARG.  Every
+ *      point opens all c columns, the point of row 0 the m chunk columns too.  ms_deep_evals; absorb the evaluations.
+ *   7. draw gamma (E limbs); ms_deep_compose.
+ *   8. ms_fri_begin(blowup, R); absorb round 0's root (the unlinked flow never does).  Per round: draw z_i, ms_fri_deep, absorb B, draw alpha_i,
+ *      ms_fri_fold_commit, absorb the root.
+ *   9. grind exactly as msh_stark_prove: 32 challenge bytes as seed, the nonce's 8 little-endian bytes absorbed.
+ *  10. draw nq = fri_queries betas, 8 challenge bytes each; ms_query_linked.
+ * MSLP v1, little-endian:
+ *   u32 'MSLP' (0x504C534D) | u32 version 1 | u32 E | u32 c | u32 m | u32 npts | u32 R | u32 nq | u32 grinding bits | u64 N | u64 blowup | u64 len(arthur) | u64 len(MSLQ)
+ *   arthur   everything the prover absorbed after the statement, in order: trace root, LDE root, validity root, evaluations, round 0's root, per round B and root, nonce
+ *   MSLQ     the blob of ms_query_linked (ministark.h)
+ * msh_stark_prove_linked returns the stage's code on failure (MS_ERR_ARG for a malformed program or shape, MS_ERR_SHAPE for a trace that violates the AIR) and leaves
+ * the slot empty; msh_linked_proof returns the size of the last linked proof (0: none) and writes it when cap suffices.
+ * msh_stark_verify_linked compares EVERY header field with what it computes from its own configuration, air, N, w and fri_rounds (none is trusted), requires the
+ * lengths to fit exactly with no trailing bytes and every limb canonical, replays the transcript from the arthur bytes with both redraw rules, then runs in this order
+ * the proof of work, the AIR identity at z (msh_air_expected_validity_ext on the opened evaluations against msh_validity_from_chunks), msh_fri_index_verify on the
+ * MSFI section with the roots, z_i, B_i, alpha_i of the replay and its own betas, and msh_deep_link_verify on the three sections.  1 accepted; 0 rejected, `why`
+ * naming the step: "header: ..", "transcript: ..", "proof of work: ..", "AIR identity: ..", "FRI: .." (msh_fri_index_verify's reason behind it), or
+ * msh_deep_link_verify's own "LDE opening: ..", "validity opening: ..", "DEEP link: ..", "MSFI .."; < 0 malformed arguments.
+ * The Python mirror writes the same bytes (mini_stark_amd.stark.Stark.prove_air). */
+int msh_stark_prove_linked(msh_stark* h, const uint64_t* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, uint32_t fri_rounds /* 0: the configuration's */);
+size_t msh_linked_proof(const msh_stark* h, uint8_t* out, size_t cap);
+int msh_stark_verify_linked(const msh_stark* h, const ms_air* air, size_t N, size_t w, uint32_t fri_rounds, const uint8_t* data, size_t len, int zero_display_empty,
+                            char* why, size_t why_cap);
+size_t msh_air_encode(const ms_air* air, uint8_t* out, size_t cap);
+int msh_air_rows(const ms_air* air, uint32_t* rows, int cap);
+/* the two redraw rules, for a caller that keeps its own transcript: 1 the draw stands, 0 draw again, < 0 an unknown field or a null z */
+int msh_linked_shift_ok(int field, uint64_t L, uint64_t shift);
+int msh_linked_z_ok(int field, const uint64_t* z /* E limbs */);
 /* synthetic trace of the build-defined degree-3 wide AIR (ms_mix_cubic): col_j[i+1] = col_j[i] col_{j+1}[i] col_{j+2}[i] + s_j col_{j+3}[i]; length x w row-major, w scalars */
 int msh_cubic_rows(uint64_t p, size_t length, size_t w, uint64_t seed, uint64_t* out, uint64_t* scalars);
 /* synthetic Fibonacci-AIR trace of the benchmark workload (N x 3 row-major) */

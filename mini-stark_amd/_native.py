@@ -604,6 +604,11 @@ class Context:
         """ms_validity_ext: limbs per coefficient of the validity polynomial (0: none; 1; E after mix_air_ext)."""
         return int(self.L.ms_validity_ext(self.h))
 
+    def validity_len(self):
+        """ms_validity_len: coefficients of the validity polynomial after the mix stage (VL)."""
+        self.L.ms_validity_len.restype = C.c_size_t
+        return int(self.L.ms_validity_len(self.h))
+
     def validity_read(self):
         self.L.ms_validity_len.restype = C.c_size_t
         vl, ve = int(self.L.ms_validity_len(self.h)) or self.N, max(1, self.validity_ext())
@@ -719,6 +724,11 @@ class Context:
     def deep_len(self):
         """ms_deep_len: N while a DEEP polynomial is installed, else 0."""
         return int(self.L.ms_deep_len(self.h))
+
+    def query_linked(self, betas) -> bytes:
+        """ms_query_linked: the whole query phase of a linked proof in one launch, the MSLQ blob (MSFI, then the LDE and validity rows under round 0's positions)."""
+        b, bp = _u64(betas)
+        return self._sized_bytes(lambda out, cap, n: self.L.ms_query_linked(self.h, bp, C.c_int(b.size), out, cap, n))
 
     # ---- standalone ----------------------------------------------------------------
     def merkle_commit(self, leafs, ext=1, lpn=2, ic=2):

@@ -214,6 +214,7 @@ int ms_merkle_prove(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext
 }
 int ms_tree_open(ms_ctx* ctx, int tree, int round, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->tree_open(tree, round, index, n, out, cap, len)); }
 int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_index(betas, nq, out, cap, len)); }
+int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->query_linked(betas, nq, out, cap, len)); }
 int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->validity_commit(lpn, root)); }
 int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals) { MS_ENTRY(ctx, B(ctx)->deep_evals(deep, evals)); }
 int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma) { MS_ENTRY(ctx, B(ctx)->deep_compose(deep, gamma)); }

@@ -8,7 +8,7 @@
 //   ntt_plan.cpp     NTT plans (shape, instances, tables), coset evaluation, ms_ntt / ms_coset_lde                        (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
 //   fri_commit.cpp   FRI commit phase: round commitments, DEEP evaluations, fold, suffix-Horner planning             (fold, scan, degree kernels)
-//   fri_query.cpp    FRI query phase, ms_merkle_prove, openings by index (ms_tree_open, ms_fri_query_index)        (find-first, path, open, copy kernels)
+//   fri_query.cpp    FRI query phase, ms_merkle_prove, openings by index (ms_tree_open, ms_fri_query_index, ms_query_linked)   (find-first, path, open, copy kernels)
 //   shard.cpp        one proof over several ranks: exchange (RCCL or callback), ms_set_shard*
 //   abi.cpp          the extern "C" entry points and their never-unwind guard
 // Built with hipcc for gfx950 into libministark.so (csrc/Makefile).  There is no CPU fallback.
@@ -153,6 +153,7 @@ struct CtxBase {
   virtual int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) = 0;
   virtual int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) = 0;
   virtual int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
+  virtual int query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
   virtual int validity_commit(size_t lpn, u8* root) = 0;
   virtual int deep_evals(const ms_deep* deep, u64* evals) = 0;
   virtual int deep_compose(const ms_deep* deep, const u64* gamma) = 0;
@@ -774,15 +775,19 @@ template <class F> struct Ctx : CtxBase {
   int merkle_prove_t(const u64* leafs, size_t leaf_num, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len);
   int merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len) override;
   // ------------------------------------------------------------------ build-defined: Merkle openings by index (include/ministark.h; kernel: msmerkle::OpenKernel, host side: fri_query.cpp)
-  // ms_tree_open and ms_fri_query_index: a host-built job table through the page-locked staging area, ONE launch, the bytes copied to the caller.  Buffers of their own
+  // ms_tree_open, ms_fri_query_index and ms_query_linked: a host-built job table through the page-locked staging area, ONE launch, the bytes copied to the caller.  Buffers of their own
   // (d_open: job table | output), nothing another stage reads is written.  `view`: the leaf view and the nodes of a tree this context holds, or why there is none
   DevBuf d_open;
   struct OpenView { const T* base = nullptr; size_t col_stride = 0, row_stride = 0, limb_stride = 0; const msmerkle::LinColSpec* lin = nullptr; const u32* nodes = nullptr;
-                    size_t ngroups = 0; u32 width = 1, lpn = 1, nlevels = 0; int el = 1; };
+                    size_t ngroups = 0; u32 width = 1, lpn = 1, nlevels = 0; int el = 1;
+                    size_t path_bytes() const { return 8 + (size_t)lpn * el * 8 + 8 + (size_t)nlevels * 64; } };
   int open_view(int tree, int round, OpenView* v);
-  template <int EL> int open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_t out_bytes, const Round* fin, size_t fin_off, u8* out);
+  void open_jobs(const OpenView& v, const u64* index, size_t n, bool positions, size_t off, std::vector<msmerkle::OpenJob<F>>& jobs) const;
+  int open_launch(const std::vector<msmerkle::OpenJob<F>>& jobs, size_t out_bytes, const Round* fin, u8* out);
+  int msfi_plan(const u64* betas, int nq, u64 hd[6], size_t* body, std::vector<msmerkle::OpenJob<F>>* jobs);
   int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) override;
   int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
+  int query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
   // ------------------------------------------------------------------ build-defined: the composition commitment and the DEEP stage (include/ministark.h; kernels:
   // mspoly::DeepCombineKernel, mspoly::DeepSumScaleKernel; host side: air_stages.cpp).  The validity polynomial's ve limb planes of VL coefficients are m = ve * VL / N
   // chunk columns of N coefficients, column k * ve + l = coefficients [kN, (k+1)N) of plane l: views of the polynomial where it lies, behind the constraint polynomials.

@@ -1,5 +1,5 @@
 // fri_query.cpp — the FRI query phase (fri.rs:115-189, merkle.rs:216-288) as a handful of batched launches over device job tables, the standalone ms_merkle_prove,
-// and the build-defined openings by index (ms_tree_open, ms_fri_query_index).  (The proof's way to the host: io.cpp.)
+// and the build-defined openings by index (ms_tree_open, ms_fri_query_index, ms_query_linked).  (The proof's way to the host: io.cpp.)
 #include "ctx.hpp"
 
 namespace msctx {
@@ -356,12 +356,12 @@ int Ctx<F>::open_view(int tree, int round, OpenView* v) {
   return 0;
 }
 
-// The one launch of both entry points.  jobs[k].out holds the OFFSET of the path in the output; `fin` (ms_fri_query_index): the round whose polynomial goes to
-// offset 0 of the output in the same launch.  Ends with the copy to the caller and the stream synchronisation.
-template <class F> template <int EL>
-int Ctx<F>::open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_t out_bytes, const Round* fin, size_t fin_off, u8* out) {
-  typedef msmerkle::OpenJob<F, EL> OJ;
-  typedef msmerkle::OpenKernel<F, EL> OKn;
+// The one launch of the three entry points.  jobs[k].out holds the OFFSET of the path in the output; `fin` (ms_fri_query_index, ms_query_linked): the round whose
+// polynomial goes to offset 0 of the output in the same launch.  Ends with the copy to the caller and the stream synchronisation.
+template <class F>
+int Ctx<F>::open_launch(const std::vector<msmerkle::OpenJob<F>>& jobs, size_t out_bytes, const Round* fin, u8* out) {
+  typedef msmerkle::OpenJob<F> OJ;
+  typedef msmerkle::OpenKernel<F, E> OKn;
   const size_t tab_bytes = (jobs.size() * sizeof(OJ) + 255) & ~(size_t)255;
   if (d_open.ensure(tab_bytes + out_bytes + 8)) return fail(MS_ERR_NOMEM, "opening buffers");
   RQ(res.join_side());   // (MS_FLAG_LATENCY: nothing of a round's side stream is still writing what is read here)
@@ -377,13 +377,23 @@ int Ctx<F>::open_launch(const std::vector<msmerkle::OpenJob<F, EL>>& jobs, size_
   typename OKn::Params pk{d_open.template as<const OJ>(), (u32)jobs.size(), nullptr, 0, 0, nullptr};
   size_t fin_wgs = 0;
   if (fin && fin->ncoef) {
-    pk.fin = fin->poly.template as<T>(); pk.fin_stride = fin->cap; pk.fin_n = fin->ncoef; pk.fin_out = reinterpret_cast<u64*>(dout + fin_off);
-    fin_wgs = (fin->ncoef * (size_t)EL + OKn::FIN_WORDS - 1) / OKn::FIN_WORDS;
+    pk.fin = fin->poly.template as<T>(); pk.fin_stride = fin->cap; pk.fin_n = fin->ncoef; pk.fin_out = reinterpret_cast<u64*>(dout);
+    fin_wgs = (fin->ncoef * (size_t)E + OKn::FIN_WORDS - 1) / OKn::FIN_WORDS;
   }
   CK(run<OKn>(K_PATH, (unsigned)(jobs.size() + fin_wgs), 1, OKn::THREADS, 0, pk));   // one wave per opening
   if (out_bytes) CK(msrt::d2h(out, dout, out_bytes, stream));
   CK(msrt::sync(stream));
   return MS_OK;
+}
+
+// n openings of one view, path k at offset off + k * path_bytes of the output: group index[k], or (`positions`: a FRI window) group index[k] / 2 with the position
+// index[k] as the word the path carries
+template <class F>
+void Ctx<F>::open_jobs(const OpenView& v, const u64* index, size_t n, bool positions, size_t off, std::vector<msmerkle::OpenJob<F>>& jobs) const {
+  const size_t pb = v.path_bytes();
+  for (size_t k = 0; k < n; k++)
+    jobs.push_back(msmerkle::OpenJob<F>{v.base, v.col_stride, v.row_stride, v.limb_stride, v.lin, v.nodes, v.ngroups, (size_t)(positions ? index[k] / 2 : index[k]),
+                                        positions ? index[k] : index[k] * v.lpn, v.width, v.lpn, v.nlevels, (u32)v.el, reinterpret_cast<unsigned char*>(off + k * pb)});
 }
 
 template <class F>
@@ -394,20 +404,40 @@ int Ctx<F>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, 
   if (sh_on) return fail(MS_ERR_STATE, "tree_open: not available on a context with sharding on");
   OpenView v;
   RQ(open_view(tree, round, &v));
-  const size_t pb = 8 + (size_t)v.lpn * v.el * 8 + 8 + (size_t)v.nlevels * 64, total = n * pb;
+  const size_t total = n * v.path_bytes();
   *len = total;
   if (!out) return MS_OK;   // size query
   if (cap < total) return fail(MS_ERR_ARG, "tree_open: buffer too small (the size needed is in *len)");
   for (size_t k = 0; k < n; k++) if (index[k] >= v.ngroups) return fail(MS_ERR_OUT_OF_RANGE, "tree_open: leaf-group index out of range");
-  auto go = [&](auto el) -> int {
-    constexpr int EL = decltype(el)::value;
-    std::vector<msmerkle::OpenJob<F, EL>> jobs(n);
-    for (size_t k = 0; k < n; k++)
-      jobs[k] = msmerkle::OpenJob<F, EL>{v.base, v.col_stride, v.row_stride, v.limb_stride, v.lin, v.nodes, v.ngroups, (size_t)index[k], index[k] * v.lpn, v.width, v.lpn, v.nlevels, 0,
-                                         reinterpret_cast<unsigned char*>(k * pb)};
-    return open_launch<EL>(jobs, total, nullptr, 0, out);
-  };
-  return v.el == 1 ? go(std::integral_constant<int, 1>()) : go(std::integral_constant<int, E>());
+  std::vector<msmerkle::OpenJob<F>> jobs;
+  jobs.reserve(n);
+  open_jobs(v, index, n, false, 0, jobs);
+  return open_launch(jobs, total, nullptr, out);
+}
+
+// The FRI part of both query phases by index: the MSFI header into hd, the size of the blob behind it into *body (the final polynomial, then the windows' paths), and
+// (jobs != nullptr) the openings, their offsets counted from the final polynomial's first byte.  MSFI: b_(0,j) = beta mod D_0, b_(i+1,j) = b_(i,j) mod D_(i+1), a plain modulus
+template <class F>
+int Ctx<F>::msfi_plan(const u64* betas, int nq, u64 hd[6], size_t* body, std::vector<msmerkle::OpenJob<F>>* jobs) {
+  const size_t R = fri_rounds, W = R - 1;
+  std::vector<OpenView> views(W);
+  const Round* last = rounds[W].get();
+  size_t pos = last->ncoef * (size_t)E * 8;
+  for (size_t i = 0; i < W; i++) {
+    if (rounds[i]->D / 2 != rounds[i + 1]->D) return fail(MS_ERR_SHAPE, "round domains do not halve (fri.rs:134-137)");
+    RQ(open_view(MS_TREE_FRI, (int)i, &views[i]));
+  }
+  std::vector<u64> b(betas, betas + nq), position(2 * (size_t)nq);
+  for (size_t i = 0; i < W; i++) {
+    const u64 D = rounds[i]->D;
+    for (int j = 0; j < nq; j++) { b[j] %= D; position[2 * j] = b[j]; position[2 * j + 1] = (b[j] + D / 2) % D; }
+    if (jobs) open_jobs(views[i], position.data(), position.size(), true, pos, *jobs);
+    pos += views[i].path_bytes() * position.size();
+  }
+  const u64 h[6] = {0x4946534DULL /* 'MSFI' */, (u64)E, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)last->ncoef};
+  memcpy(hd, h, sizeof h);
+  *body = pos;
+  return 0;
 }
 
 // The compact query phase (MSFI, include/ministark.h): the positions ms_fri_query opens by value, opened by index, and the last round's polynomial
@@ -417,41 +447,49 @@ int Ctx<F>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_
   if (sh_on) return fail(MS_ERR_STATE, "fri_query_index: not available on a context with sharding on");
   if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "fri_query_index: null argument");
   if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "fri_query_index: nq outside 1..4096");
-  const size_t R = fri_rounds, W = R - 1;
-  std::vector<OpenView> views(W);
-  std::vector<size_t> pb(W);
-  for (size_t i = 0; i < W; i++) {
-    if (rounds[i]->D / 2 != rounds[i + 1]->D) return fail(MS_ERR_SHAPE, "round domains do not halve (fri.rs:134-137)");
-    RQ(open_view(MS_TREE_FRI, (int)i, &views[i]));
-    pb[i] = 8 + 2 * (size_t)E * 8 + 8 + (size_t)views[i].nlevels * 64;
-  }
-  const Round* last = rounds[W].get();
-  const size_t head = 6 * 8, fin_bytes = last->ncoef * (size_t)E * 8;
-  size_t pos = head + fin_bytes;
-  for (size_t i = 0; i < W; i++) pos += pb[i] * 2 * (size_t)nq;
-  *len = pos;
+  u64 hd[6]; size_t body;
+  RQ(msfi_plan(betas, nq, hd, &body, nullptr));
+  *len = sizeof hd + body;
   if (!out) return MS_OK;   // size query
-  if (cap < pos) return fail(MS_ERR_ARG, "fri_query_index: buffer too small (the size needed is in *len)");
-  std::vector<msmerkle::OpenJob<F, E>> jobs;
-  jobs.reserve(W * (size_t)nq * 2);
-  std::vector<u64> b(betas, betas + nq);
-  size_t off = fin_bytes;   // offsets in the device image of the blob, which starts behind the header
-  for (size_t i = 0; i < W; i++) {
-    const OpenView& v = views[i];
-    const u64 D = rounds[i]->D;
-    for (int j = 0; j < nq; j++) {
-      b[j] %= D;   // b_(0,j) = beta mod D_0, b_(i+1,j) = b_(i,j) mod D_(i+1): a plain modulus
-      for (int s = 0; s < 2; s++) {
-        const u64 position = s ? (b[j] + D / 2) % D : b[j];
-        jobs.push_back(msmerkle::OpenJob<F, E>{v.base, v.col_stride, v.row_stride, v.limb_stride, v.lin, v.nodes, v.ngroups, (size_t)(position / 2), position, v.width, v.lpn, v.nlevels, 0,
-                                               reinterpret_cast<unsigned char*>(off)});
-        off += pb[i];
-      }
-    }
-  }
-  const u64 hd[6] = {0x4946534DULL /* 'MSFI' */, (u64)E, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)last->ncoef};
-  memcpy(out, hd, head);
-  return open_launch<E>(jobs, pos - head, last, 0, out + head);
+  if (cap < *len) return fail(MS_ERR_ARG, "fri_query_index: buffer too small (the size needed is in *len)");
+  std::vector<msmerkle::OpenJob<F>> jobs;
+  jobs.reserve((fri_rounds - 1) * (size_t)nq * 2);
+  RQ(msfi_plan(betas, nq, hd, &body, &jobs));
+  memcpy(out, hd, sizeof hd);
+  return open_launch(jobs, body, rounds[fri_rounds - 1].get(), out + sizeof hd);
+}
+
+// The whole query phase of a linked proof (MSLQ, include/ministark.h): MSFI, then the rows of the LDE tree and of the validity tree that lie under round 0's positions,
+// every opening and the last round's polynomial in ONE launch.  The device image is the blob behind both headers: final polynomial | FRI paths | LDE paths | validity paths
+template <class F>
+int Ctx<F>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  if (sh_on) return fail(MS_ERR_STATE, "query_linked: not available on a context with sharding on");
+  if (nrounds_done != fri_rounds || fri_rounds == 0) return fail(MS_ERR_STATE, "query_linked before the commit phase finished");
+  if (!dpoly_live()) return fail(MS_ERR_STATE, "query_linked: no DEEP polynomial installed (ms_validity_commit, ms_deep_compose, and nothing that kills the validity tree since)");
+  const u64 D0 = rounds[0]->D;
+  if (D0 > L || L % D0) return fail(MS_ERR_STATE, "query_linked: round 0's domain does not divide the LDE domain (ms_fri_begin with the LDE's blowup)");
+  if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "query_linked: null argument");
+  if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "query_linked: nq outside 1..4096");
+  OpenView lde, val;
+  RQ(open_view(MS_TREE_LDE, 0, &lde));
+  RQ(open_view(MS_TREE_VALIDITY, 0, &val));
+  if (lde.ngroups != L || val.ngroups != L) return fail(MS_ERR_STATE, "query_linked: the LDE tree does not hold one row per leaf group (ms_lde_commit with lpn = the number of polynomials)");
+  u64 hd[4 + 6]; size_t body;
+  RQ(msfi_plan(betas, nq, hd + 4, &body, nullptr));
+  const size_t nrows = 2 * (size_t)nq, len_lde = nrows * lde.path_bytes(), len_val = nrows * val.path_bytes();
+  hd[0] = 0x514C534DULL /* 'MSLQ' */; hd[1] = 6 * 8 + body; hd[2] = len_lde; hd[3] = len_val;
+  *len = sizeof hd + body + len_lde + len_val;
+  if (!out) return MS_OK;   // size query
+  if (cap < *len) return fail(MS_ERR_ARG, "query_linked: buffer too small (the size needed is in *len)");
+  std::vector<msmerkle::OpenJob<F>> jobs;
+  jobs.reserve(((fri_rounds - 1) + 2) * nrows);
+  RQ(msfi_plan(betas, nq, hd + 4, &body, &jobs));
+  std::vector<u64> rows(nrows);   // round-0 position b is LDE row b * (L / D_0); its partner b + D_0 / 2 is row + L / 2
+  for (int j = 0; j < nq; j++) { rows[2 * j] = betas[j] % D0 * (L / D0); rows[2 * j + 1] = (rows[2 * j] + L / 2) % L; }
+  open_jobs(lde, rows.data(), nrows, false, body, jobs);
+  open_jobs(val, rows.data(), nrows, false, body + len_lde, jobs);
+  memcpy(out, hd, sizeof hd);
+  return open_launch(jobs, body + len_lde + len_val, rounds[fri_rounds - 1].get(), out + sizeof hd);
 }
 
 // src/merkle.rs:272-288 on a standalone binary tree: leaves de-interleaved to SoA limbs, then the same
@@ -512,7 +550,8 @@ int Ctx<F>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn,
   template int Ctx<FF>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn, const u64* leaf, u8* out, size_t cap, size_t* len); \
   template int Ctx<FF>::open_view(int tree, int round, Ctx<FF>::OpenView* v); \
   template int Ctx<FF>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len); \
-  template int Ctx<FF>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
+  template int Ctx<FF>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
+  template int Ctx<FF>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -856,46 +856,49 @@ template <class F, int E> struct PathKernel {
   }
 };
 
-// MerklePath BY INDEX (build-defined: ms_tree_open, ms_fri_query_index), the same layout as PathKernel's.  What differs: the leaf group comes from the job record
-// (the host has checked it against ngroups: no device index word, no lookup by value), the group is read through the general view LeafHashKernel hashes
+// MerklePath BY INDEX (build-defined: ms_tree_open, ms_fri_query_index, ms_query_linked), the same layout as PathKernel's.  What differs: the leaf group comes from
+// the job record (the host has checked it against ngroups: no device index word, no lookup by value), the group is read through the general view LeafHashKernel hashes
 // (element f of the committed vector: column f % width, row f / width), and a VIRTUAL column (LinColSpec) is opened with the value LeafHashKernel hashed for that
 // row, from the same specification.  Binary trees only (ic = 2).  `leaf_index` is the word the path carries: group * lpn for ms_tree_open, the opened position for
-// ms_fri_query_index.
-template <class F, int EL> struct OpenJob {
+// ms_fri_query_index.  The element width travels IN THE RECORD - el = 1 limb for the row trees (trace, LDE, validity), E for the FRI round trees - so that one launch
+// can open trees of both kinds (ms_query_linked: every FRI window, the LDE rows and the validity rows).
+template <class F> struct OpenJob {
   const typename F::T* base; size_t col_stride, row_stride, limb_stride;
   const LinColSpec* lin;   // per column, or nullptr
   const u32* nodes;        // level-major, 2 * ngroups - 1 digests
   size_t ngroups, group;
   unsigned long long leaf_index;
-  u32 width, lpn, nlevels /* log2(ngroups) */, pad_;
+  u32 width, lpn, nlevels /* log2(ngroups) */, el /* limbs per element: 1 or E */;
   unsigned char* out;
 };
-template <class F, int EL> struct OpenKernel {
+template <class F, int E> struct OpenKernel {
   typedef typename F::T T;
   static constexpr int THREADS = 64;
   static constexpr u32 FIN_WORDS = 1024;   // words of the final polynomial per workgroup
-  // workgroups [0, njobs): one opening each; behind them (ms_fri_query_index) ceil(fin_n * EL / FIN_WORDS) workgroups that write the last round's polynomial - limb k
-  // of coefficient c at fin[k * fin_stride + c] - as fin_n * EL u64 words, so that the query phase is ONE launch
-  struct Params { const OpenJob<F, EL>* jobs; u32 njobs; const T* fin; size_t fin_stride, fin_n; u64* fin_out; };
+  // workgroups [0, njobs): one opening each; behind them (ms_fri_query_index, ms_query_linked) ceil(fin_n * E / FIN_WORDS) workgroups that write the last round's
+  // polynomial - limb k of coefficient c at fin[k * fin_stride + c] - as fin_n * E u64 words, so that the query phase is ONE launch
+  struct Params { const OpenJob<F>* jobs; u32 njobs; const T* fin; size_t fin_stride, fin_n; u64* fin_out; };
   static MS_HD int nphases(const Params&) { return 1; }
   // One WAVE per opening, a lane per word, as PathKernel: every address follows from the job record alone, so the loads of the leaf group and of all levels are in
   // flight together (a virtual column's specification is the one load in front of its sources).
   static MS_DEV void phase(int, const Params& pp, int bx, int, int tid, int nthreads, unsigned char*) {
     if ((u32)bx >= pp.njobs) {
-      const size_t nw = pp.fin_n * (size_t)EL, w0 = (size_t)((u32)bx - pp.njobs) * FIN_WORDS;
+      const size_t nw = pp.fin_n * (size_t)E, w0 = (size_t)((u32)bx - pp.njobs) * FIN_WORDS;
       for (size_t w = w0 + (size_t)tid; w < w0 + FIN_WORDS && w < nw; w += (size_t)nthreads)
-        pp.fin_out[w] = F::to_u64(pp.fin[(w % EL) * pp.fin_stride + w / EL]);
+        pp.fin_out[w] = F::to_u64(pp.fin[(w % E) * pp.fin_stride + w / E]);
       return;
     }
-    const OpenJob<F, EL>& p = pp.jobs[bx];
+    const OpenJob<F>& p = pp.jobs[bx];
     u64* o = reinterpret_cast<u64*>(p.out);
-    const u32 nval = p.lpn * (u32)EL;
+    const bool one = p.el == 1;   // (wave-uniform; E is a constant: no division by a run-time width)
+    const u32 nval = one ? p.lpn : p.lpn * (u32)E;
     if (tid == 0) { o[0] = p.leaf_index; o[1 + nval] = p.nlevels; }
     const size_t f0 = p.group * p.lpn;
     for (u32 v = (u32)tid; v < nval; v += (u32)nthreads) {
-      const size_t f = f0 + v / EL;
+      const u32 elem = one ? v : v / (u32)E, limb = one ? 0 : v % (u32)E;
+      const size_t f = f0 + elem;
       const size_t row = f / p.width; const u32 col = (u32)(f - row * p.width);
-      const T* rowp = p.base + row * p.row_stride + (size_t)(v % EL) * p.limb_stride;
+      const T* rowp = p.base + row * p.row_stride + (size_t)limb * p.limb_stride;
       T x;
       if (p.lin && p.lin[col].n) {   // LeafHashKernel's evaluation of the column, term by term in the same order: the same field element
         const LinColSpec& lc = p.lin[col];

@@ -40,6 +40,7 @@ def _host():
         L = C.CDLL(path, mode=C.RTLD_GLOBAL)
         L.msh_stark_new.restype = C.c_void_p
         for n in ("msh_proof_arthur", "msh_proof_evals", "msh_proof_fri_roots", "msh_proof_fri_blob", "msh_proof_challenges", "msh_proof_num_polys", "msh_proof_serialize",
+                  "msh_linked_proof", "msh_air_encode",
                   "msh_prev_proof_arthur", "msh_prev_proof_fri_roots", "msh_prev_proof_fri_blob"):
             getattr(L, n).restype = C.c_size_t
         L.msh_proof_blob_checksum.restype = C.c_uint64
@@ -188,6 +189,42 @@ def air_expected_validity_ext(field, r, air, N, z, rows, opened, npolys=None):
     rc = _host().msh_air_expected_validity_ext(C.c_int(field), rr.ctypes.data_as(u64p), C.byref(s), C.c_uint64(N), zz.ctypes.data_as(u64p), C.c_int(rw.size),
                                                rw.ctypes.data_as(u32p), op.ctypes.data_as(u64p), C.c_size_t(op.shape[1]), C.c_uint32(npolys), out.ctypes.data_as(u64p))
     return rc, out
+
+
+def _air(air):
+    """(MsAir, keep-alive arrays) from a flatten_air dict or the tuple (constraints, exempt, periodic, boundary)"""
+    return air_struct(air if isinstance(air, dict) else flatten_air(*air))
+
+
+def air_encode(air) -> bytes:
+    """msh_air_encode: the canonical bytes of an AIR program (what a linked proof's statement absorbs); b"" for a malformed program."""
+    H = _host()
+    s, _keep = _air(air)
+    n = H.msh_air_encode(C.byref(s), None, C.c_size_t(0))
+    buf = (C.c_uint8 * max(1, n))()
+    H.msh_air_encode(C.byref(s), buf, C.c_size_t(n))
+    return bytes(buf[:n])
+
+
+def air_rows_native(air):
+    """msh_air_rows: the row offsets the verifying side of an AIR program needs opened, ascending - the C twin of mini_stark_amd.air_rows."""
+    s, _keep = _air(air)
+    rows = (C.c_uint32 * 65536)()
+    n = _host().msh_air_rows(C.byref(s), rows, C.c_int(65536))
+    if n < 0:
+        raise MsError(n, "msh_air_rows: malformed program")
+    return [int(rows[k]) for k in range(n)]
+
+
+def linked_shift_ok(field, L, shift) -> bool:
+    """msh_linked_shift_ok: the linked transcript keeps a drawn shift unless it is 0 or shift^L == 1 (then it draws again)."""
+    return _host().msh_linked_shift_ok(C.c_int(field), C.c_uint64(L), C.c_uint64(shift)) == 1
+
+
+def linked_z_ok(field, z) -> bool:
+    """msh_linked_z_ok: the linked transcript keeps a drawn z unless every limb above limb 0 is zero (then it draws again)."""
+    zz = np.ascontiguousarray(z, dtype=np.uint64)
+    return _host().msh_linked_z_ok(C.c_int(field), zz.ctypes.data_as(C.POINTER(C.c_uint64))) == 1
 
 
 class HostStark:
@@ -345,6 +382,33 @@ class HostStark:
     def prove(self, trace, trace_device_ptr=None, read_fri_proof=True) -> StarkProof:
         self.ctx.check(self.prove_raw(trace, trace_device_ptr, read_fri_proof))
         return self.last_proof(read_fri_proof)
+
+    # ---- linked proofs (MSLP v1; include/ministark_host.h) ----
+    def prove_linked(self, trace, air, fri_rounds=0, trace_device_ptr=None) -> int:
+        """msh_stark_prove_linked: the status code (ERR_SHAPE: the trace violates the program).  trace: the N x w matrix (or its shape (N, w) with
+        trace_device_ptr); air: a flatten_air dict or the tuple (constraints, exempt, periodic, boundary)."""
+        s, _keep = _air(air)
+        if trace_device_ptr is not None:
+            N, w = trace
+            host_ptr = None
+        else:
+            t = np.ascontiguousarray(trace, dtype=np.uint64)
+            N, w = t.shape
+            host_ptr = t.ctypes.data_as(C.POINTER(C.c_uint64))
+        return self.H.msh_stark_prove_linked(self.h, host_ptr, C.c_void_p(trace_device_ptr), C.c_size_t(N), C.c_size_t(w), C.byref(s), C.c_uint32(fri_rounds))
+
+    def linked_proof(self) -> bytes:
+        """msh_linked_proof: the MSLP bytes of the last linked proof (b"": none)."""
+        return self._bytes(self.H.msh_linked_proof)
+
+    def verify_linked(self, data, air, N, w, fri_rounds=0, zero_display_empty=True):
+        """msh_stark_verify_linked: (rc, why) - 1 accepted, 0 rejected with `why` naming the step, < 0 malformed arguments."""
+        s, _keep = _air(air)
+        why = C.create_string_buffer(512)
+        data = bytes(data)
+        rc = self.H.msh_stark_verify_linked(self.h, C.byref(s), C.c_size_t(N), C.c_size_t(w), C.c_uint32(fri_rounds), data, C.c_size_t(len(data)),
+                                            C.c_int(1 if zero_display_empty else 0), why, C.c_size_t(512))
+        return rc, why.value.decode()
 
 
 def fibonacci_rows_native(p, length, steps, secret_b=2, pad_seed=0x5EED):

@@ -308,6 +308,7 @@ struct Stark {
   // TWO proof slots: prove() k + 1 fills the slot proof k - 1 lived in, so that proof k - transcript, values, and its page-locked
   // FRI blob, possibly still arriving on the copy stream - stays whole and readable (`prev`, msh_prev_proof_*) while proof k + 1 is computed.
   StarkConfig cfg; StarkProof proof, prev;
+  std::vector<u8> linked;   // the MSLP bytes of the last linked proof (msh_stark_prove_linked): a slot of its own, the two MSFP slots are untouched
   // src/starks.rs:59-169
   // read_fri_proof: 0 the FRI proof stays in HBM; 1 read back before returning; 2 read back ASYNCHRONOUSLY (ms_fri_proof_read_async: the bytes
   // land in the slot's page-locked buffer while the caller goes on - e.g. into the next prove; wait_proof() / any accessor of the blob completes
@@ -894,6 +895,283 @@ template <class F, int E> static int air_expected(const u64* r, const ms_air& a,
   for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
   return MS_OK;
 }
+
+// ---- linked proofs: MSLP v1 (ministark_host.h) -----------------------------------------------------------------------------------------------------------------
+// The shape of an ms_air: every array that is needed is there, the CSR offsets start at 0 and do not decrease, the stages' own limits hold.  The counts the encoding carries
+struct AirShape { u32 ncons, nterms, nfacs, nex, nperiodic, nperval, nbound; };
+static bool air_shape(const ms_air* a, AirShape* s) {
+  if (!a || a->ncons < 1 || a->ncons > 4096 || a->nperiodic > 64 || a->nbound > 4096 || !a->term_begin || !a->coef || !a->fac_begin || !a->ex_begin) return false;
+  if (a->term_begin[0] != 0 || a->fac_begin[0] != 0 || a->ex_begin[0] != 0) return false;
+  for (u32 t = 0; t < a->ncons; t++) {
+    if (a->term_begin[t + 1] < a->term_begin[t] || a->term_begin[t + 1] > 65536) return false;
+    if (a->ex_begin[t + 1] < a->ex_begin[t] || a->ex_begin[t + 1] - a->ex_begin[t] > 16) return false;
+  }
+  const u32 nterms = a->term_begin[a->ncons];
+  for (u32 m = 0; m < nterms; m++) if (a->fac_begin[m + 1] < a->fac_begin[m] || a->fac_begin[m + 1] - a->fac_begin[m] > 8) return false;
+  const u32 nfacs = a->fac_begin[nterms], nex = a->ex_begin[a->ncons];
+  if ((nfacs && (!a->fac_poly || !a->fac_row)) || (nex && !a->ex_row)) return false;
+  u32 nperval = 0;
+  if (a->nperiodic) {
+    if (!a->per_begin || !a->per_val || a->per_begin[0] != 0) return false;
+    for (u32 k = 0; k < a->nperiodic; k++) if (a->per_begin[k + 1] <= a->per_begin[k] || a->per_begin[k + 1] > 4096) return false;
+    nperval = a->per_begin[a->nperiodic];
+  }
+  if (a->nbound && (!a->bnd_poly || !a->bnd_row || !a->bnd_val)) return false;
+  *s = AirShape{a->ncons, nterms, nfacs, nex, a->nperiodic, nperval, a->nbound};
+  return true;
+}
+// msh_air_encode: 'MSAR' | version 1 | ncons nterms nfacs nexempt nperiodic nperval nbound array_bytes (u32 each), then the arrays in the order of the struct
+static const u32 AIR_MAGIC = 0x5241534Du;   // 'MSAR'
+static bool air_encode(const ms_air* a, std::vector<u8>* out) {
+  AirShape sh;
+  if (!air_shape(a, &sh)) return false;
+  out->clear();
+  auto put = [&](const void* src, size_t n) { const u8* b = (const u8*)src; out->insert(out->end(), b, b + n); };   // little-endian host
+  const u32 zero = 0;
+  const size_t arrays = 4 * ((size_t)sh.ncons + 1) * 2 + 8 * (size_t)sh.nterms + 4 * ((size_t)sh.nterms + 1) + 8 * (size_t)sh.nfacs + 4 * (size_t)sh.nex + 4 * ((size_t)sh.nperiodic + 1) +
+                        8 * (size_t)sh.nperval + 16 * (size_t)sh.nbound;
+  const u32 head[10] = {AIR_MAGIC, 1, sh.ncons, sh.nterms, sh.nfacs, sh.nex, sh.nperiodic, sh.nperval, sh.nbound, (u32)arrays};
+  put(head, sizeof head);
+  put(a->term_begin, 4 * ((size_t)sh.ncons + 1)); put(a->coef, 8 * (size_t)sh.nterms); put(a->fac_begin, 4 * ((size_t)sh.nterms + 1));
+  put(a->fac_poly, 4 * (size_t)sh.nfacs); put(a->fac_row, 4 * (size_t)sh.nfacs);
+  put(a->ex_begin, 4 * ((size_t)sh.ncons + 1)); put(a->ex_row, 4 * (size_t)sh.nex);
+  if (sh.nperiodic) { put(a->per_begin, 4 * ((size_t)sh.nperiodic + 1)); put(a->per_val, 8 * (size_t)sh.nperval); } else put(&zero, 4);
+  put(a->bnd_poly, 4 * (size_t)sh.nbound); put(a->bnd_row, 4 * (size_t)sh.nbound); put(a->bnd_val, 8 * (size_t)sh.nbound);
+  return out->size() == sizeof head + arrays;
+}
+// msh_air_rows: the row offsets of the program's factors, and row 0 when there are boundary constraints, ascending (mini_stark_amd.air_rows)
+static bool air_rows(const ms_air* a, std::vector<u32>* rows) {
+  AirShape sh;
+  if (!air_shape(a, &sh)) return false;
+  rows->assign(a->fac_row, a->fac_row + sh.nfacs);
+  if (sh.nbound) rows->push_back(0);
+  std::sort(rows->begin(), rows->end());
+  rows->erase(std::unique(rows->begin(), rows->end()), rows->end());
+  return true;
+}
+// the redraw rules of the linked transcript (ministark_host.h: msh_linked_shift_ok, msh_linked_z_ok)
+template <class F> static bool linked_shift_ok(u64 shift, u64 L) { return shift != 0 && shift < F::P && F::to_u64(f_pow<F>(F::from_u64(shift), L)) != 1; }
+static bool linked_z_ok(const u64* z, int e) { for (int l = 1; l < e; l++) if (z[l]) return true; return false; }
+template <class F> static u64 draw_shift(Transcript& t, u64 L) { u64 s; do t.challenge_scalars(&s, 1, F::P); while (!linked_shift_ok<F>(s, L)); return s; }
+static void draw_z(Transcript& t, u64* z, int e, u64 p) { do t.challenge_scalars(z, e, p); while (!linked_z_ok(z, e)); }
+
+// What prover and verifier derive from the configuration, the AIR, N, w and fri_rounds alone: the statement they absorb and every count of the MSLP header
+struct LinkedShape {
+  u32 c = 0, m = 0, npts = 0, R = 0, nq = 0, gb = 0; u64 N = 0, blowup = 0, L = 0;
+  std::vector<u32> rows;          // the points are z * w^rows[t]; row 0 first
+  std::vector<u32> pt_begin, pt_poly; size_t ne = 0;   // every point opens the c columns, the point of row 0 the m chunk columns too
+  std::vector<u8> statement;
+  size_t arthur_len(int e) const { return 3 * 32 + ne * e * 8 + 32 + (size_t)(R - 1) * (2 * e * 8 + 32) + (gb ? 8 : 0); }
+};
+template <class F> static int linked_shape(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
+  const int e = c.e;
+  AirShape sh;
+  if (!air_shape(air, &sh) || N < 2 || (N & (N - 1)) || w < 1 || w > (1u << 16) || !c.blowup_factor || (c.blowup_factor & (c.blowup_factor - 1))) return MS_ERR_ARG;
+  if (N > ((u64)1 << F::TWO_ADICITY) / c.blowup_factor) return MS_ERR_ARG;
+  o->c = (u32)w; o->N = N; o->blowup = c.blowup_factor; o->L = N * c.blowup_factor; o->gb = c.grinding_bits;
+  o->R = fri_rounds ? fri_rounds : (u32)c.rounds; o->nq = (u32)c.fri_queries;
+  if (o->R < 1 || o->R > 64 || o->nq < 1 || o->nq > 4096) return MS_ERR_ARG;
+  // m = E * VL / N, VL by ms_mix_air's rule (ministark.h): nq = max(max_t (d_t (N - 1) + e_t - N + 1), N - 1 if nbound > 0, 1), VL = N * next_pow2(ceil(nq / N))
+  u64 nqv = sh.nbound ? N - 1 : 1;
+  if (nqv < 1) nqv = 1;
+  for (u32 t = 0; t < sh.ncons; t++) {
+    u64 d = 0;
+    for (u32 k = air->term_begin[t]; k < air->term_begin[t + 1]; k++) d = std::max<u64>(d, air->fac_begin[k + 1] - air->fac_begin[k]);
+    const u64 et = air->ex_begin[t + 1] - air->ex_begin[t], deg = d * (N - 1) + et;
+    if (air->term_begin[t + 1] > air->term_begin[t] && deg + 1 > N && deg - N + 1 > nqv) nqv = deg - N + 1;
+  }
+  u64 slots = 1; while (slots * N < nqv) slots *= 2;
+  o->m = (u32)(slots * e);
+  if (!air_rows(air, &o->rows)) return MS_ERR_ARG;
+  if (o->rows.empty() || o->rows[0] != 0) o->rows.insert(o->rows.begin(), 0);
+  for (u32 r : o->rows) if (r >= N) return MS_ERR_ARG;
+  if (o->rows.size() > 8) return MS_ERR_ARG;   // ms_deep_compose takes at most 8 points
+  o->npts = (u32)o->rows.size();
+  o->pt_begin.assign(1, 0); o->pt_poly.clear();
+  for (u32 t = 0; t < o->npts; t++) {
+    for (u32 j = 0; j < o->c + (t == 0 ? o->m : 0); j++) o->pt_poly.push_back(j);
+    o->pt_begin.push_back((u32)o->pt_poly.size());
+  }
+  o->ne = o->pt_poly.size();
+  if (o->ne > 8192) return MS_ERR_ARG;
+  const u64 words[8] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)o->R, (u64)o->nq, (u64)o->gb};
+  std::vector<u8> enc;
+  if (!air_encode(air, &enc)) return MS_ERR_ARG;
+  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
+  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
+  return MS_OK;
+}
+// z * w^row for every point, E limbs each (an element of K times a base-field scalar: limb by limb)
+template <class F> static std::vector<u64> linked_points(const LinkedShape& sh, const u64* z, int e) {
+  const typename F::T w = trace_root<F>(sh.N);
+  std::vector<u64> pts((size_t)sh.npts * e);
+  for (u32 t = 0; t < sh.npts; t++) {
+    const typename F::T s = f_pow<F>(w, (u64)sh.rows[t]);
+    for (int l = 0; l < e; l++) pts[(size_t)t * e + l] = F::to_u64(F::mul(F::from_u64(z[l]), s));
+  }
+  return pts;
+}
+static Transcript linked_transcript(const StarkConfig& c, const LinkedShape& sh) {
+  Transcript t(c.domsep + "/linked/v1", c.digest);
+  t.add_bytes(sh.statement.data(), 64);                                      // field, digest, N, w, blowup, R, nq, grinding bits
+  t.add_bytes(sh.statement.data() + 64, sh.statement.size() - 64);           // msh_air_encode(air)
+  t.prover_bytes.clear();                                                    // the statement is the verifier's own: it does not travel
+  return t;
+}
+static const size_t MSLP_HEAD = 9 * 4 + 4 * 8;
+static const u32 MSLP_MAGIC = 0x504C534Du;   // 'MSLP'
+
+// the prover's driver: transcript order and redraw rules of ministark_host.h
+template <class F> static int prove_linked(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, u32 fri_rounds) {
+  const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = c.e; const u64 p = c.p;
+  s.linked.clear();
+  if (!ctx || (!trace_host && !trace_dev)) return MS_ERR_ARG;
+  LinkedShape sh;
+  int rc = linked_shape<F>(c, air, N, w, fri_rounds, &sh);
+  if (rc) return rc;
+  Transcript t = linked_transcript(c, sh);
+  u8 root[32];
+  // the raw-trace root: ms_trace_commit is how the trace gets in.  It is absorbed first and binds nothing
+  rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
+  if (rc) return rc;
+  t.add_bytes(root, 32);
+  const u64 shift = draw_shift<F>(t, sh.L);
+  if ((rc = ms_interpolate(ctx))) return rc;
+  if ((rc = ms_lde_commit(ctx, sh.blowup, shift, w, root))) return rc;
+  t.add_bytes(root, 32);
+  std::vector<u64> r(e), z(e), gamma(e);
+  t.challenge_scalars(r.data(), e, p);
+  if ((rc = ms_mix_air_ext(ctx, r.data(), air))) return rc;                  // MS_ERR_SHAPE: the trace violates the AIR
+  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;        // (the stage's VL is the header's rule)
+  if ((rc = ms_validity_commit(ctx, sh.m, root))) return rc;
+  t.add_bytes(root, 32);
+  draw_z(t, z.data(), e, p);
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  std::vector<u64> evals(sh.ne * e);
+  if ((rc = ms_deep_evals(ctx, &deep, evals.data()))) return rc;
+  t.add_scalars(evals.data(), evals.size());
+  t.challenge_scalars(gamma.data(), e, p);
+  if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
+  if ((rc = ms_fri_begin(ctx, sh.blowup, sh.R, root))) return rc;
+  t.add_bytes(root, 32);                                                     // round 0's root is in the transcript
+  std::vector<u64> zq(e), B(2 * e), alpha(e);
+  for (u32 i = 1; i < sh.R; i++) {
+    t.challenge_scalars(zq.data(), e, p);
+    if ((rc = ms_fri_deep(ctx, zq.data(), B.data()))) return rc;
+    t.add_scalars(B.data(), 2 * e);
+    t.challenge_scalars(alpha.data(), e, p);
+    if ((rc = ms_fri_fold_commit(ctx, alpha.data(), root))) return rc;
+    t.add_bytes(root, 32);
+  }
+  if (sh.gb) {                                                               // the proof of work, exactly as Stark::prove
+    u8 seed[32]; t.challenge_bytes(seed, 32);
+    u64 nonce = 0;
+    if (!ms_grind) return MS_ERR_ARG;
+    if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
+    u8 le[8]; for (int k = 0; k < 8; k++) le[k] = (u8)(nonce >> (8 * k));
+    t.add_bytes(le, 8);
+  }
+  std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
+  std::vector<u64> betas(sh.nq);
+  memcpy(betas.data(), raw.data(), raw.size());
+  size_t lq = 0;
+  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
+  const size_t la = t.prover_bytes.size();
+  if (la != sh.arthur_len(e)) return MS_ERR_STATE;
+  std::vector<u8> out(MSLP_HEAD + la + lq);
+  const u32 h32[9] = {MSLP_MAGIC, 1, (u32)e, sh.c, sh.m, sh.npts, sh.R, sh.nq, sh.gb};
+  const u64 h64[4] = {sh.N, sh.blowup, (u64)la, (u64)lq};
+  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
+  memcpy(out.data() + MSLP_HEAD, t.prover_bytes.data(), la);
+  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, out.data() + MSLP_HEAD + la, lq, &lq))) return rc;
+  s.linked.swap(out);
+  return MS_OK;
+}
+
+// the verifier: 1 accepted, 0 rejected (*why names the step), < 0 malformed arguments.  Nothing of the proof is trusted: every header field is the verifier's own
+template <class F, int E> static int verify_linked(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, const u8* data, size_t len, int zae, std::string* why) {
+  typedef Verifier<F, E> V;
+  const u64 p = c.p;
+  LinkedShape sh;
+  if (c.e != E || linked_shape<F>(c, air, N, w, fri_rounds, &sh)) { *why = "malformed arguments: the AIR program, N, w, the rounds or the configuration"; return MS_ERR_ARG; }
+  // ---- header: MSLP's and MSLQ's, lengths exact
+  if (len < MSLP_HEAD) { *why = "header: the proof is shorter than the MSLP header"; return 0; }
+  u32 h32[9]; u64 h64[4];
+  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
+  const u32 want32[9] = {MSLP_MAGIC, 1, (u32)E, sh.c, sh.m, sh.npts, sh.R, sh.nq, sh.gb};
+  static const char* const name32[9] = {"magic", "version", "E", "c", "m", "npts", "R", "nq", "grinding bits"};
+  for (int k = 0; k < 9; k++) if (h32[k] != want32[k]) { *why = std::string("header: ") + name32[k] + " is not the verifier's"; return 0; }
+  if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
+  if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
+  const size_t la = sh.arthur_len(E);
+  if (h64[2] != (u64)la) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
+  if (len - MSLP_HEAD < la || h64[3] != (u64)(len - MSLP_HEAD - la)) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
+  const size_t lq = len - MSLP_HEAD - la;
+  std::vector<u64> q((lq + 7) / 8 + 4, 0);            // the MSLQ blob, aligned for the section verifiers
+  memcpy(q.data(), data + MSLP_HEAD + la, lq);
+  if (lq < 32 || q[0] != 0x514C534DULL) { *why = "header: no MSLQ blob behind arthur"; return 0; }
+  const u64 l_msfi = q[1], l_lde = q[2], l_val = q[3];
+  if (l_msfi > lq - 32 || l_lde > lq - 32 - l_msfi || l_val != lq - 32 - l_msfi - l_lde) { *why = "header: the MSLQ section lengths do not fit the blob exactly"; return 0; }
+  if ((l_msfi | l_lde | l_val) & 7) { *why = "header: an MSLQ section length is no multiple of 8"; return 0; }
+  const u8* msfi = (const u8*)q.data() + 32; const u8* lde_open = msfi + l_msfi; const u8* val_open = lde_open + l_lde;
+  // ---- transcript: replayed from arthur, both redraw rules included
+  Arthur a(c.domsep, c.digest, data + MSLP_HEAD, la);
+  a.t = linked_transcript(c, sh);
+  u8 troot[32], lroot[32], vroot[32];
+  std::vector<u8> roots((size_t)sh.R * 32);
+  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), zs((size_t)(sh.R - 1) * E), Bs((size_t)(sh.R - 1) * 2 * E), alphas((size_t)(sh.R - 1) * E), betas(sh.nq);
+  const char* cut = "transcript: arthur ends early";
+  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
+  const u64 shift = draw_shift<F>(a.t, sh.L);
+  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
+  a.t.challenge_scalars(r.data(), E, p);
+  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
+  draw_z(a.t, z.data(), E, p);
+  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
+  if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
+  a.t.challenge_scalars(gamma.data(), E, p);
+  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
+  for (u32 i = 1; i < sh.R; i++) {
+    a.t.challenge_scalars(zs.data() + (size_t)(i - 1) * E, E, p);
+    if (!a.next_scalars(Bs.data() + (size_t)(i - 1) * 2 * E, 2 * E)) { *why = cut; return 0; }
+    a.t.challenge_scalars(alphas.data() + (size_t)(i - 1) * E, E, p);
+    if (!a.next_bytes(roots.data() + (size_t)i * 32, 32)) { *why = cut; return 0; }
+  }
+  if (!V::canon(Bs.data(), Bs.size())) { *why = "transcript: a round's B is not canonical"; return 0; }
+  u8 seed[32] = {0}; u64 nonce = 0;
+  if (sh.gb) {
+    a.t.challenge_bytes(seed, 32);
+    u8 le[8];
+    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
+    for (int k = 0; k < 8; k++) nonce |= (u64)le[k] << (8 * k);
+  }
+  if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
+  { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
+  // ---- 1. the proof of work
+  if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
+  // ---- 2. the AIR identity at z: the program on the opened evaluations against V(z) from the chunk evaluations
+  {
+    std::vector<u64> opened((size_t)sh.npts * sh.c * E);
+    for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
+    u64 want[E], got[E];
+    const int rc = air_expected<F, E>(r.data(), *air, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
+    if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
+    validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
+    if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
+  }
+  // ---- 3. FRI on the MSFI section, with the roots and challenges of the replay
+  std::string sub;
+  int rc = fri_index_verify<F, E>(c.digest, zae, sh.blowup, roots.data(), sh.R, zs.data(), Bs.data(), alphas.data(), betas.data(), sh.nq, msfi, l_msfi, &sub);
+  if (rc != 1) { *why = "FRI: " + sub; return rc; }
+  // ---- 4. round 0 against the two trees
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, sh.c, sh.m, lroot, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
+                              val_open, l_val, &sub);
+  if (rc != 1) { *why = sub; return rc; }
+  return 1;
+}
 static size_t copy_out(const void* src, size_t n, void* dst, size_t cap) { if (dst && cap >= n && n) memcpy(dst, src, n); return n; }
 
 extern "C" {
@@ -1190,6 +1468,46 @@ int msh_deep_link_verify(int digest_id, int field, int zero_display_empty, u64 N
       : deep_link_verify<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, val_open, val_len, &w);
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+// ---- linked proofs (MSLP v1)
+int msh_stark_prove_linked(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, uint32_t fri_rounds) {
+  if (!h) return MS_ERR_ARG;
+  try {
+    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked<GL>(h->s, trace_host, trace_dev, N, w, air, fri_rounds) : prove_linked<BB>(h->s, trace_host, trace_dev, N, w, air, fri_rounds);
+  } catch (...) { return MS_ERR_NOMEM; }
+}
+size_t msh_linked_proof(const msh_stark* h, u8* out, size_t cap) { return h ? copy_out(h->s.linked.data(), h->s.linked.size(), out, cap) : 0; }
+int msh_stark_verify_linked(const msh_stark* h, const ms_air* air, size_t N, size_t w, uint32_t fri_rounds, const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
+  if (!h || !data || !air) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
+  try {
+    std::string msg;
+    const StarkConfig& c = h->s.cfg;
+    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked<GL, 2>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg)
+                                                  : verify_linked<BB, 4>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg);
+    return set_why(why, why_cap, msg.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+size_t msh_air_encode(const ms_air* air, u8* out, size_t cap) {
+  try {
+    std::vector<u8> enc;
+    return air_encode(air, &enc) ? copy_out(enc.data(), enc.size(), out, cap) : 0;
+  } catch (...) { return 0; }
+}
+int msh_air_rows(const ms_air* air, uint32_t* rows, int cap) {
+  try {
+    std::vector<u32> r;
+    if (!air_rows(air, &r) || (cap > 0 && !rows)) return MS_ERR_ARG;
+    for (int k = 0; k < cap && k < (int)r.size(); k++) rows[k] = r[k];
+    return (int)r.size();
+  } catch (...) { return MS_ERR_NOMEM; }
+}
+int msh_linked_shift_ok(int field, uint64_t L, uint64_t shift) {
+  if (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) return MS_ERR_ARG;
+  return (field == MS_FIELD_GOLDILOCKS ? linked_shift_ok<GL>(shift, L) : linked_shift_ok<BB>(shift, L)) ? 1 : 0;
+}
+int msh_linked_z_ok(int field, const uint64_t* z) {
+  if ((field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) || !z) return MS_ERR_ARG;
+  return linked_z_ok(z, field == MS_FIELD_GOLDILOCKS ? 2 : 4) ? 1 : 0;
 }
 // the synthetic Fibonacci-AIR trace of the benchmark workload (tests/e2e_goldilocks.rs:20-63 rows + SplitMix64 padding; = mini_stark_amd.synthetic.fibonacci_rows)
 int msh_fibonacci_rows(u64 p, size_t length, size_t steps, u64 secret_b, u64 pad_seed, u64* out) {

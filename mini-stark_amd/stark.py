@@ -22,7 +22,7 @@ from typing import List
 
 import numpy as np
 
-from ._native import Context, MsError, GOLDILOCKS, BABYBEAR, ERR_SHAPE, ERR_ARG, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
+from ._native import Context, MsError, AIR_ARRAYS, air_rows, flatten_air, GOLDILOCKS, BABYBEAR, ERR_SHAPE, ERR_ARG, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
 
@@ -171,6 +171,54 @@ class StarkProof:  # src/starks.rs:21-28
         return StarkProof(arthur, tc, lc, cq, vq, FriProof(data[pos:pos + lb], device_resident=False), roots)
 
 
+def encode_air(air) -> bytes:
+    """msh_air_encode (include/ministark_host.h) in Python: the canonical bytes of an AIR program, from a flatten_air dict or the tuple (constraints, exempt,
+    periodic, boundary): 'MSAR' | version 1 | the eight counts | the arrays in the order of the ms_air struct, little-endian."""
+    if not isinstance(air, dict):
+        air = flatten_air(*air)
+    arr = {k: np.ascontiguousarray(air[k], dtype=t).astype("<u4" if t is np.uint32 else "<u8") for k, t in AIR_ARRAYS}
+    ncons, nperiodic, nbound = int(air["ncons"]), int(air["nperiodic"]), int(air["nbound"])
+    if nperiodic == 0:
+        arr["per_begin"], arr["per_val"] = np.zeros(1, dtype="<u4"), np.zeros(0, dtype="<u8")
+    body = b"".join(arr[k].tobytes() for k, _ in AIR_ARRAYS)
+    nterms, nfacs = int(arr["term_begin"][ncons]), arr["fac_poly"].size
+    return struct.pack("<10I", 0x5241534D, 1, ncons, nterms, nfacs, arr["ex_row"].size, nperiodic, arr["per_val"].size, nbound, len(body)) + body
+
+
+@dataclass
+class LinkedProof:
+    """A linked proof, MSLP v1 (include/ministark_host.h): the header's counts, the prover's transcript bytes and the MSLQ blob of Context.query_linked."""
+    e: int
+    c: int
+    m: int
+    npts: int
+    rounds: int
+    nq: int
+    grinding_bits: int
+    N: int
+    blowup: int
+    arthur: bytes
+    mslq: bytes
+
+    _HEAD = "<4s8I4Q"
+
+    def to_bytes(self) -> bytes:
+        return struct.pack(self._HEAD, b"MSLP", 1, self.e, self.c, self.m, self.npts, self.rounds, self.nq, self.grinding_bits, self.N, self.blowup,
+                           len(self.arthur), len(self.mslq)) + self.arthur + self.mslq
+
+    @staticmethod
+    def from_bytes(data: bytes) -> "LinkedProof":
+        hs = struct.calcsize(LinkedProof._HEAD)
+        if len(data) < hs:
+            raise ValueError("not an MSLP v1 proof")
+        magic, ver, e, c, m, npts, rounds, nq, gb, N, blowup, la, lq = struct.unpack_from(LinkedProof._HEAD, data, 0)
+        if magic != b"MSLP" or ver != 1:
+            raise ValueError("not an MSLP v1 proof")
+        if len(data) != hs + la + lq:
+            raise ValueError(f"MSLP proof has {len(data)} bytes, header says {hs + la + lq}")
+        return LinkedProof(e, c, m, npts, rounds, nq, gb, N, blowup, bytes(data[hs:hs + la]), bytes(data[hs + la:]))
+
+
 class StarkConfig:
     """src/starks.rs:238-333."""
 
@@ -258,6 +306,86 @@ class Stark:
         self.last_transcript_ops = list(t.ops)
         return StarkProof(bytes(t.prover_bytes), trace_commit, lde_commit, ev[:, :c, :], ev[:, c, :],
                           FriProof(blob or b"", device_resident=not read_fri_proof), roots)
+
+
+    # ---- linked proofs (build-defined; MSLP v1, transcript order and redraw rules: include/ministark_host.h) -----------------------
+    def prove_air(self, trace, air, fri_rounds: int = 0) -> LinkedProof:
+        """msh_stark_prove_linked driven from Python: the same stages, the same transcript, the same bytes.  trace: the N x w matrix; air: a flatten_air dict or the
+        tuple (constraints, exempt, periodic, boundary).  The statement: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air`.
+        Raises MsError(ERR_SHAPE) for a trace that violates the program."""
+        cfg, ctx = self.cfg, self.cfg.ctx
+        p, e = _MODULUS[ctx.field], ctx.e
+        if not isinstance(air, dict):
+            air = flatten_air(*air)
+        data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
+        N, w = data.shape
+        blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
+        R, nq, gb = fri_rounds or cfg.rounds, cfg.fri_queries, cfg.grinding_bits
+        t = Transcript(cfg.domsep + "/linked/v1", ctx.digest)
+        t.add_bytes(struct.pack("<8Q", ctx.field, ctx.digest, N, w, blowup, R, nq, gb))
+        t.add_bytes(encode_air(air))
+        t.prover_bytes = bytearray()                              # the statement is the verifier's own: it does not travel
+        rc, root = ctx.trace_commit(data, w)                      # the raw-trace root: absorbed first, binds nothing
+        ctx.check(rc)
+        t.add_bytes(root)
+        (shift,) = t.challenge_scalars(1, p)
+        while shift == 0 or pow(shift, L, p) == 1:                # the coset must not meet the trace domain: part of the protocol on both sides
+            (shift,) = t.challenge_scalars(1, p)
+        ctx.check(ctx.interpolate())
+        rc, root = ctx.lde_commit(blowup, shift, w)
+        ctx.check(rc)
+        t.add_bytes(root)
+        r = t.challenge_scalars(e, p)
+        ctx.check(ctx.mix_air_ext(r, air))
+        m = e * ctx.validity_len() // N
+        rc, root = ctx.validity_commit(m)
+        ctx.check(rc)
+        t.add_bytes(root)
+        z = t.challenge_scalars(e, p)
+        while not any(z[1:]):                                     # z outside the base field
+            z = t.challenge_scalars(e, p)
+        rows = sorted({0} | {int(x) for x in np.asarray(air["fac_row"]).reshape(-1)})
+        if len(rows) > 8:
+            raise MsError(ERR_ARG, "prove_air: the program touches more than 8 row offsets")
+        omega = ctx.root_of_unity(N)
+        pts = [[v * pow(omega, row, p) % p for v in z] for row in rows]
+        lists = [list(range(w)) + (list(range(w, w + m)) if k == 0 else []) for k in range(len(rows))]
+        rc, ev = ctx.deep_evals(pts, lists)
+        ctx.check(rc)
+        t.add_scalars(ev.reshape(-1))
+        gamma = t.challenge_scalars(e, p)
+        ctx.check(ctx.deep_compose(pts, lists, gamma))
+        rc, root = ctx.fri_begin(blowup, R)
+        ctx.check(rc)
+        t.add_bytes(root)                                         # round 0's root is in the transcript
+        for _ in range(1, R):
+            zq = t.challenge_scalars(e, p)
+            rc, B = ctx.fri_deep(zq)
+            ctx.check(rc)
+            t.add_scalars(B)
+            alpha = t.challenge_scalars(e, p)
+            rc, root = ctx.fri_fold_commit(alpha)
+            ctx.check(rc)
+            t.add_bytes(root)
+        if gb:
+            rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
+            ctx.check(rc)
+            t.add_bytes(struct.pack("<Q", nonce))
+        raw = t.challenge_bytes(8 * nq)
+        betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
+        self.last_challenges = dict(shift=shift, r=r, z=z, gamma=gamma, betas=betas)
+        return LinkedProof(e, w, m, len(rows), R, nq, gb, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
+
+    def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True) -> bool:
+        """msh_stark_verify_linked on MSLP bytes (or a LinkedProof) under this configuration.  True / False, the reason of a rejection - naming the step - in
+        `self.last_verify_error`; raises MsError on malformed arguments."""
+        from .host import HostStark   # (host.py imports this module)
+        cfg = self.cfg
+        hs = HostStark(cfg.ctx, cfg.security_bits, cfg.blowup_factor, cfg.steps, cfg.trace_columns, cfg.grinding_bits)
+        rc, self.last_verify_error = hs.verify_linked(data.to_bytes() if isinstance(data, LinkedProof) else data, air, N, w, fri_rounds, zero_display_empty)
+        if rc < 0:
+            raise MsError(rc, self.last_verify_error)
+        return rc == 1
 
 
 def fibonacci_air(ctx: Context, steps: int, secret_b: int = 2, pad_seed: int = 0x5EED) -> TraceTable:
