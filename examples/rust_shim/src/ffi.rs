@@ -103,12 +103,15 @@ extern "C" {
     pub fn ms_trace_upload_async(ctx: *mut ms_ctx, trace_rowmajor: *const u64, n: usize, w: usize) -> c_int;
     pub fn ms_aux_running(ctx: *mut ms_ctx, aux: *const MsAux, final_out: *mut u64, column_out: *mut u64) -> c_int;
     pub fn ms_aux_count(ctx: *const ms_ctx) -> c_int;
+    pub fn ms_aux_running_staged(ctx: *mut ms_ctx, aux: *const MsAux, final_out: *mut u64, column_out: *mut u64) -> c_int;
+    pub fn ms_aux_staged_count(ctx: *const ms_ctx) -> c_int;
     pub fn ms_interpolate(ctx: *mut ms_ctx) -> c_int;
     pub fn ms_polys_lincomb(ctx: *mut ms_ctx, scalars: *const u64, idx: *const c_int, k: c_int) -> c_int;
     pub fn ms_polys_append(ctx: *mut ms_ctx, coeffs: *const u64, n: usize) -> c_int;
     pub fn ms_polys_count(ctx: *const ms_ctx) -> c_int;
     pub fn ms_poly_read(ctx: *mut ms_ctx, i: c_int, out: *mut u64) -> c_int;
     pub fn ms_lde_commit(ctx: *mut ms_ctx, blowup: usize, shift: u64, lpn: usize, root: *mut u8) -> c_int;
+    pub fn ms_lde_commit_stage(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;
     pub fn ms_lde_read(ctx: *mut ms_ctx, out_rowmajor: *mut u64) -> c_int;
     pub fn ms_mix(ctx: *mut ms_ctx, r: u64) -> c_int;
     pub fn ms_validity_read(ctx: *mut ms_ctx, out: *mut u64) -> c_int;

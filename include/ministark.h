@@ -205,6 +205,24 @@ typedef struct ms_aux {
 } ms_aux;
 int ms_aux_running(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out /* ext limbs */, uint64_t* column_out /* NULL, or N*ext limbs, row-major */);
 int ms_aux_count(const ms_ctx* ctx);   /* limb columns appended since the last ms_trace_commit */
+/* BUILD-DEFINED: the same column, built AFTER the main columns are committed - the first half of the staged LDE commitment (ms_lde_commit_stage below).  In a proof
+ * whose statement is bound by the LDE root, the challenges of a permutation or lookup argument must be drawn behind that root; ms_aux_running is over by then.
+ * Same descriptor, same argument checks (term_col < w names TRACE columns: the polynomials 0 .. w-1; the limit of 16 limb columns counts the columns of both entry
+ * points since ms_trace_commit), same MS_ERR_SHAPE for a zero denominator.
+ *   valid        while an unsharded LDE tree is live (ms_lde_commit, and no ms_polys_* / ms_bench_lde since), before ms_lde_commit_stage for that tree, and while no
+ *                validity polynomial exists (no mix stage since ms_trace_commit: it lies behind the polynomials, where the new ones go).  Otherwise MS_ERR_STATE;
+ *                MS_ERR_STATE on a context with sharding on, as ms_tree_open.
+ *   definition   final_out and column_out are exactly what ms_aux_running returns for the same descriptor on the same trace, and the ext new polynomials - indices
+ *                ms_polys_count_before .. + ext - 1, materialised - are what ms_interpolate makes of that column.  ms_polys_count grows by ext, ms_aux_staged_count too.
+ *   how          the trace polynomials the forms name are evaluated on the trace domain again (one forward size-N transform per maximal run of named columns, into a
+ *                scratch buffer), ms_aux_running's launches run over that scratch, one inverse transform of the ext columns writes the polynomials.
+ * The LDE tree, the LDE matrix, MS_TREE_LDE openings and ms_lde_read of the c0 committed columns are untouched.  While ms_aux_staged_count != 0 the new polynomials are
+ * in no tree: ms_mix, ms_mix_cubic, ms_mix_terms, ms_mix_air, ms_mix_air_ext and ms_validity_commit return MS_ERR_STATE ("uncommitted staged columns");
+ * ms_air_check, ms_poly_read, ms_tree_open of the trees that exist, ms_polys_lincomb / ms_polys_append (which kill the LDE as always) and a full ms_lde_commit (all
+ * columns in one tree, as always; the stage is cleared) work.  After any refusal or failure the context is as if the call had not been made; everything but the zero
+ * denominator is decided before the first launch.  Tests: tests/test_staged_*.py. */
+int ms_aux_running_staged(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out /* ext limbs */, uint64_t* column_out /* NULL, or N*ext limbs, row-major */);
+int ms_aux_staged_count(const ms_ctx* ctx);   /* limb columns ms_aux_running_staged appended and no tree covers yet: 0 after ms_lde_commit_stage, ms_lde_commit, ms_trace_commit */
 /* 1.2a TraceTable::get_trace_polys: per-column INTT.  air.rs:147-160. */
 int ms_interpolate(ms_ctx* ctx);
 /* 1.2b constraint polynomial appended as sum_t scalars[t] * poly[idx[t]] (the
@@ -217,7 +235,15 @@ int ms_poly_read(ms_ctx* ctx, int i, uint64_t* out /* N */);
 /* 1.2c coset LDE of every constraint polynomial over Radix2(blowup*N).get_coset(shift)
  *      and MerkleTree::new over the L x c row-major LDE matrix.  starks.rs:80-95. */
 int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_t root[32]);
-int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c */);
+/* BUILD-DEFINED: the second half of the staged commitment.  With c0 = the columns of the live ms_lde_commit, c1 = ms_aux_staged_count > 0 (else MS_ERR_STATE): the c1
+ * pending polynomials are evaluated on the SAME coset (blowup, shift, L of that ms_lde_commit) into the columns c0 .. c0 + c1 - 1 of the LDE matrix, a SECOND tree is
+ * built over the L x c1 row-major matrix of those columns alone (lpn checked as by ms_lde_commit, against L * c1 leaves) and its root returned.  Afterwards the mix
+ * stages, ms_deep_*, ms_lde_read and ms_eval_ext see c0 + c1 columns; ms_tree_open(MS_TREE_LDE) goes on opening rows of c0 elements under the stage-0 root, and
+ * ms_tree_open(MS_TREE_LDE_STAGED) opens rows of c1.  One stage per ms_lde_commit: a second call, and ms_aux_running_staged after it, return MS_ERR_STATE.  Whatever
+ * kills the LDE tree kills the staged tree with it.  MS_ERR_STATE on a context with sharding on; MS_ERR_ARG for a null root; MS_ERR_SHAPE as ms_lde_commit for lpn.
+ * After a refusal or failure the context is as if the call had not been made (the LDE matrix may have moved to a larger buffer, with its columns). */
+int ms_lde_commit_stage(ms_ctx* ctx, size_t lpn, uint8_t root[32]);
+int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c; c = c0 + c1 once a stage is committed */);
 /* 1.3  validity = sum_i r^i f_i (remainder of divide_by_vanishing_poly; quirk Q1).  starks.rs:108-119. */
 int ms_mix(ms_ctx* ctx, uint64_t r);
 int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms / ms_mix_air; times ms_validity_ext(ctx) limbs after ms_mix_air_ext */);
@@ -395,13 +421,15 @@ int ms_fri_query_into(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, 
  *                  (the tree covers the w trace columns; running columns of ms_aux_running are not in it).
  *   MS_TREE_LDE    valid from ms_lde_commit until the next ms_trace_commit, ms_polys_lincomb / ms_polys_append, ms_bench_lde or ms_lde_commit.
  *   MS_TREE_VALIDITY  the tree of ms_validity_commit (below), opened exactly as MS_TREE_LDE: row `index`, m one-limb neighbours.  Valid while that tree lives.
+ *   MS_TREE_LDE_STAGED  the tree of ms_lde_commit_stage, opened exactly as MS_TREE_LDE: row `index`, c1 one-limb neighbours, leaf_index = index * lpn.  MS_ERR_STATE
+ *                  while no staged tree lives.
  *   MS_TREE_FRI    round < the rounds committed so far, from ms_fri_begin on (until the next mix stage or trace).  `round` is 0 for the other trees.
  * Errors, all decided before anything is launched (ONE launch per call, on the context's stream; the call returns with the bytes in `out`):
  *   MS_ERR_ARG           null index or len; n outside 1..65536; an unknown tree id; round out of range; out = NULL with cap != 0; cap too small.
  *   MS_ERR_OUT_OF_RANGE  an index at or above the number of leaf groups.
  *   MS_ERR_STATE         the tree does not exist (yet, or any more); a context with sharding on (ms_set_shard* with world > 1, or MS_SHARD_WORLD1), as ms_aux_running.
  * The context is unchanged: a proof with such calls between its stages comes out byte for byte as without them. */
-typedef enum { MS_TREE_TRACE = 0, MS_TREE_LDE = 1, MS_TREE_FRI = 2, MS_TREE_VALIDITY = 4 } ms_tree_id;   /* 3 stays unassigned: it has always been refused as an unknown id (MS_ERR_ARG), and callers may rely on that */
+typedef enum { MS_TREE_TRACE = 0, MS_TREE_LDE = 1, MS_TREE_FRI = 2, MS_TREE_VALIDITY = 4, MS_TREE_LDE_STAGED = 5 } ms_tree_id;   /* 3 stays unassigned: it has always been refused as an unknown id (MS_ERR_ARG), and callers may rely on that */
 int ms_tree_open(ms_ctx* ctx, int tree, int round /* MS_TREE_FRI only, else 0 */, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len);
 /* The COMPACT query phase: what ms_fri_query opens by value, opened by position, and nothing else.  Valid wherever ms_fri_query is (after the commit phase, before or
  * after ms_fri_query, any number of times); it leaves the FRI state, the MSFP blob and a later ms_fri_query's bytes untouched.  MS_ERR_STATE on a context with sharding
@@ -493,7 +521,11 @@ int ms_deep_len(const ms_ctx* ctx);   /* 0, or N once a DEEP polynomial is insta
  *   validity openings   exactly the bytes ms_tree_open(MS_TREE_VALIDITY, 0, rows) returns
  * rows: the 2 * nq rows msh_deep_link_verify expects - with b_j = betas[j] mod D_0 and p_j = b_j * (L / D_0), query j contributes p_j, then (p_j + L / 2) mod L, in
  * query order.  The equality with the three calls is the definition (tests/test_linked_*.py hold the bytes to it).  A virtual linear LDE column opens with the value
- * that was hashed, as in ms_tree_open.  Not measured on the device yet (tools/linked_bench.py, profiles/linked.json). */
+ * that was hashed, as in ms_tree_open.  Not measured on the device yet (tools/linked_bench.py, profiles/linked.json).
+ * With a live staged tree (ms_lde_commit_stage) the call writes the STAGED layout instead - still one job table, one launch, one read-back, one synchronisation; it
+ * also needs the staged tree to hold one row per leaf group (lpn = c1), else MS_ERR_STATE.  Without a staged tree the bytes are the ones above.
+ *   'MSLS' (0x534C534D) | len_msfi | len_lde | len_stg | len_val
+ *   MSFI blob | ms_tree_open(MS_TREE_LDE, 0, rows) | ms_tree_open(MS_TREE_LDE_STAGED, 0, rows) | ms_tree_open(MS_TREE_VALIDITY, 0, rows)       the same rows */
 int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
 
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------

@@ -146,8 +146,8 @@ int msh_air_expected_validity_ext(int field, const uint64_t* r /* E limbs */, co
 /* ---- LINKED PROOFS: MSLP v1 (build-defined; the sound counterpart of msh_stark_prove / MSSP, which keep the reference's unlinked flow byte for byte) ----------------
  * THE STATEMENT a linked proof claims: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air` - its transition constraints,
  * exemption sets, periodic columns and boundary values are the public input.  The constraint polynomials are the trace columns (c = w; no ms_polys_lincomb
- * transitions).  Running columns (ms_aux_running) are not part of the flow: their challenges would have to follow a commitment to the main columns' LDE, a staged
- * commitment that does not exist yet.  The raw-trace root is computed because ms_trace_commit is how the trace gets in; it is absorbed first
+ * transitions).  Running columns are not part of THIS flow: their challenges have to follow a commitment to the main columns' LDE - the staged commitment of MSLP v2,
+ * below.  The raw-trace root is computed because ms_trace_commit is how the trace gets in; it is absorbed first
  * and BINDS NOTHING - no opening of that tree is part of the proof.
  * The handle's configuration supplies field, digest, blowup, the rounds (fri_rounds = 0), fri_queries and the grinding bits (msh_stark_set_grinding).  The linked proof
  * lives in a slot of its own: msh_stark_prove, MSSP and the two MSFP slots are untouched.
@@ -195,6 +195,70 @@ int msh_stark_verify_linked(const msh_stark* h, const ms_air* air, size_t N, siz
                             char* why, size_t why_cap);
 size_t msh_air_encode(const ms_air* air, uint8_t* out, size_t cap);
 int msh_air_rows(const ms_air* air, uint32_t* rows, int cap);
+/* ---- LINKED PROOFS WITH RUNNING COLUMNS: MSLP v2 (build-defined) -----------------------------------------------------------------------------------------------------
+ * A v2 proof carries permutation and lookup arguments: running columns whose challenges are drawn BEHIND the commitment to the main columns, built by
+ * ms_aux_running_staged and committed in a second LDE tree by ms_lde_commit_stage (ministark.h).  THE STATEMENT: there are w polynomials of degree < N, committed under
+ * the stage-0 LDE root, that satisfy `air` (a program over the w trace columns, at least one constraint) and the nargs arguments.
+ *
+ * msh_aux_arg: one argument with SYMBOLIC challenges.  A proof draws nch challenges ch[0 .. nch) in K (nch in 1..8).  The arrays are those of ms_aux with base-field
+ * values (one u64 each) and a selector beside every value: 0 "times 1", k "times ch[k - 1]".  The column's ext is always E.  Instantiating a descriptor with drawn
+ * challenges gives the ms_aux of ms_aux_running_staged.
+ * msh_aux_encode: the canonical bytes, little-endian: u32 'MSAX' (0x5841534D) | u32 version 1 | u32 nargs | u32 nch, then per argument u32 op, nfrac, nterms |
+ * form_begin (2 nfrac + 1 u32) | term_col, term_ch (nterms u32 each) | form_ch (2 nfrac u32) | term_coef (nterms u64) | form_const (2 nfrac u64).  The counts fix every
+ * length.  Returns the size (writes when cap suffices), 0 for a malformed descriptor: a null array, a selector > nch, a value >= p, nch outside 1..8, more than 16 limb
+ * columns (nargs * E), any limit of ms_aux_running (op, nfrac, form_begin, 16 terms per form).  A column >= w is refused by the drivers, which know w.
+ *
+ * msh_air_prog: a growable copy of an ms_air program (msh_air_prog_new: NULL for a malformed one; msh_air_prog_air: the program as it stands, valid until the next
+ * call on the object).  msh_aux_constraints: the C twin of mini_stark_amd.aux_constraints - for an instantiated ms_aux (ext = E) it appends the transition constraint
+ * cleared of denominators, expanded limb by limb (terms in the order of their sorted monomials), with no exemption, and the boundary z(w^0) = identity, as constraints
+ * over the polynomials first_poly .. first_poly + E - 1: msh_air_encode of the result is the bytes of the Python function's.  MS_ERR_ARG when the expansion exceeds
+ * ms_mix_air's limits (8 factors per term, 65536 terms, 4096 constraints); the program is then unchanged.
+ *
+ * msh_deep_link_verify_staged: msh_deep_link_verify with two LDE trees - per row F_j comes from the stage-0 row (c0 elements, under lde_root) for j < c0 and from the
+ * staged row (c1 elements, under stg_root) for c0 <= j < c0 + c1; the chunk columns are j >= c0 + c1.  Both blobs are consumed exactly, paths checked positionally
+ * under their own roots; the additional reason prefix is "staged opening: ..".
+ *
+ * TRANSCRIPT, domain separator domsep + "/linked/v2":
+ *   1. absorb the statement: the u64 words field, digest id, N, w, blowup, R, nq, grinding bits, nargs, nch; then msh_air_encode(air); then msh_aux_encode(args).
+ *   2. absorb the trace root; draw shift with v1's redraw rule.
+ *   3. ms_interpolate, ms_lde_commit(blowup, shift, lpn = w); absorb the stage-0 root.
+ *   4. draw ch[0 .. nch), E limbs each; instantiate every argument and call ms_aux_running_staged once per argument, in order.  A zero denominator (MS_ERR_SHAPE,
+ *      probability about N / |K|) is returned as it is: there is no redraw rule.  A `final` that is not the identity - the argument does not hold - is MS_ERR_SHAPE too.
+ *   5. ms_lde_commit_stage(lpn = c1 = nargs * E); absorb the staged root.
+ *   6. v1's steps 4-10 on the combined program - air plus msh_aux_constraints of every argument, argument k at first_poly = w + k E - with c = w + c1 columns: r,
+ *      ms_mix_air_ext, ms_validity_commit, z, ms_deep_evals, gamma, ms_deep_compose, the FRI commit phase with round 0's root absorbed, grinding, betas, ms_query_linked
+ *      (the staged layout, MSLS).  The points are msh_air_rows of the combined program; every point opens all c columns.
+ * MSLP v2, little-endian:
+ *   u32 'MSLP' | 2 | E | c0 | c1 | m | npts | R | nq | grinding bits | nargs | nch | u64 N | blowup | len(arthur) | len(MSLS)
+ *   arthur (v1's, with the staged root behind the stage-0 root) | the MSLS blob
+ * msh_stark_prove_linked_aux returns the stage's code on failure and leaves the slot empty; msh_linked_proof returns whichever linked proof was made last.
+ * msh_stark_verify_linked_aux trusts no header field: it compares what the statement fixes, replays the transcript (both redraws, the challenge draw), rebuilds the
+ * combined program from its own statement and the challenges it drew, compares what that program fixes (m, npts, len(arthur); the MSLS lengths must fit exactly), then
+ * runs in order the proof of work, the AIR identity at z, msh_fri_index_verify and msh_deep_link_verify_staged.  `why` prefixes: v1's, plus "staged opening: ".  A v1
+ * verifier given v2 bytes answers "header: ..", and so does a v2 verifier given v1 bytes.  The Python mirror writes the same bytes (Stark.prove_air(.., aux=(args, nch))). */
+typedef struct msh_aux_arg {
+  uint32_t op, nfrac;
+  const uint32_t* form_begin;   /* 2 nfrac + 1 */
+  const uint32_t* term_col;     /* nterms: a trace column, < w */
+  const uint64_t* term_coef;    /* nterms base-field values */
+  const uint32_t* term_ch;      /* nterms selectors */
+  const uint64_t* form_const;   /* 2 nfrac base-field values */
+  const uint32_t* form_ch;      /* 2 nfrac selectors */
+} msh_aux_arg;
+typedef struct msh_air_prog msh_air_prog;
+size_t msh_aux_encode(int field, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, uint8_t* out, size_t cap);
+msh_air_prog* msh_air_prog_new(const ms_air* base);
+void msh_air_prog_free(msh_air_prog* prog);
+const ms_air* msh_air_prog_air(msh_air_prog* prog);
+int msh_aux_constraints(msh_air_prog* prog, int field, const ms_aux* aux /* ext = E */, uint32_t first_poly);
+int msh_deep_link_verify_staged(int digest_id, int field, int zero_display_empty, uint64_t N, uint64_t blowup, uint64_t shift, uint32_t c0, uint32_t c1, uint32_t m,
+                                const uint8_t lde_root[32], const uint8_t stg_root[32], const uint8_t val_root[32], const ms_deep* deep, const uint64_t* evals,
+                                const uint64_t* gamma, const uint64_t* betas, size_t nq, const uint8_t* msfi, size_t msfi_len, const uint8_t* lde_open, size_t lde_len,
+                                const uint8_t* stg_open, size_t stg_len, const uint8_t* val_open, size_t val_len, char* why, size_t why_cap);
+int msh_stark_prove_linked_aux(msh_stark* h, const uint64_t* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args,
+                               uint32_t nargs, uint32_t nch, uint32_t fri_rounds /* 0: the configuration's */);
+int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, uint32_t fri_rounds,
+                                const uint8_t* data, size_t len, int zero_display_empty, char* why, size_t why_cap);
 /* the two redraw rules, for a caller that keeps its own transcript: 1 the draw stands, 0 draw again, < 0 an unknown field or a null z */
 int msh_linked_shift_ok(int field, uint64_t L, uint64_t shift);
 int msh_linked_z_ok(int field, const uint64_t* z /* E limbs */);

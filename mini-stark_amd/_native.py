@@ -22,6 +22,7 @@ FLAG_DIGEST_SHA3_256 = 0x40   # D = SHA3-256 (FIPS 202)
 DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3 = 0, 1, 2   # ms_digest_id
 DIGEST_KECCAK256, DIGEST_SHA3_256 = 4, 5   # (3 is unassigned)
 TREE_TRACE, TREE_LDE, TREE_FRI, TREE_VALIDITY = 0, 1, 2, 4   # ms_tree_id (3 is unassigned)
+TREE_LDE_STAGED = 5                                          # the tree of ms_lde_commit_stage
 OK, ERR_SHAPE, ERR_LEAF_NOT_FOUND, ERR_OUT_OF_RANGE, ERR_STATE, ERR_ARG, ERR_HIP, ERR_NOMEM = 0, -1, -2, -3, -4, -5, -6, -7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -235,6 +236,60 @@ def aux_struct(aux):
 
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
+
+# ---- arguments with symbolic challenges (msh_aux_arg, include/ministark_host.h): the statement of a linked proof with running columns
+AUX_ARG_ARRAYS = (("form_begin", np.uint32), ("term_col", np.uint32), ("term_coef", np.uint64), ("term_ch", np.uint32), ("form_const", np.uint64), ("form_ch", np.uint32))
+
+
+def flatten_aux_arg(op, fractions):
+    """The arrays of an msh_aux_arg as a dict from fractions = [(numerator, denominator), ...], a form being ((const, sel), [(col, coef, sel), ...]): base-field
+    values with a selector each - 0: times 1, k: times the proof's challenge ch[k - 1]."""
+    form_begin, term_col, term_coef, term_ch, form_const, form_ch = [0], [], [], [], [], []
+    for frac in fractions:
+        if len(frac) != 2:
+            raise ValueError("flatten_aux_arg: a fraction is a (numerator, denominator) pair of forms")
+        for (const, sel), terms in frac:
+            form_const.append(int(const)); form_ch.append(int(sel))
+            for col, coef, tsel in terms:
+                term_col.append(int(col)); term_coef.append(int(coef)); term_ch.append(int(tsel))
+            form_begin.append(len(term_col))
+    vals = dict(form_begin=form_begin, term_col=term_col, term_coef=term_coef, term_ch=term_ch, form_const=form_const, form_ch=form_ch)
+    out = {"op": int(op), "nfrac": len(fractions)}
+    out.update({k: np.array(vals[k], dtype=t) for k, t in AUX_ARG_ARRAYS})
+    return out
+
+
+def instantiate_aux(field, arg, ch):
+    """The flatten_aux dict (ext = E) of a flatten_aux_arg dict with the challenges ch (E-tuples) in place: value * ch[sel - 1], or the base-field value itself."""
+    p, e = _MODULUS[field], _EXT[field]
+
+    def limbs(value, sel):
+        return [int(value) * int(x) % p for x in ch[int(sel) - 1]] if int(sel) else [int(value)] + [0] * (e - 1)
+    coef = [x for v, sel in zip(arg["term_coef"], arg["term_ch"]) for x in limbs(v, sel)]
+    const = [x for v, sel in zip(arg["form_const"], arg["form_ch"]) for x in limbs(v, sel)]
+    return {"op": int(arg["op"]), "ext": e, "nfrac": int(arg["nfrac"]), "form_begin": np.array(arg["form_begin"], dtype=np.uint32),
+            "term_col": np.array(arg["term_col"], dtype=np.uint32), "term_coef": np.array(coef, dtype=np.uint64), "form_const": np.array(const, dtype=np.uint64)}
+
+
+def aux_fractions(aux):
+    """the fractions of a flatten_aux dict (ext > 1), in the format flatten_aux and aux_constraints take"""
+    e, fb = int(aux["ext"]), [int(x) for x in aux["form_begin"]]
+    k = lambda a, i: tuple(int(x) for x in a[i * e:(i + 1) * e])   # noqa: E731
+    forms = [(k(aux["form_const"], f), [(int(aux["term_col"][m]), k(aux["term_coef"], m)) for m in range(fb[f], fb[f + 1])]) for f in range(2 * int(aux["nfrac"]))]
+    return [(forms[2 * i], forms[2 * i + 1]) for i in range(int(aux["nfrac"]))]
+
+
+def encode_aux(args, nch) -> bytes:
+    """msh_aux_encode in Python: 'MSAX' | version 1 | nargs | nch, then per argument op, nfrac, nterms | form_begin | term_col | term_ch | form_ch | term_coef | form_const"""
+    import struct
+    out = struct.pack("<4I", 0x5841534D, 1, len(args), int(nch))
+    for a in args:
+        arr = {k: np.ascontiguousarray(a[k], dtype=t).astype("<u4" if t is np.uint32 else "<u8") for k, t in AUX_ARG_ARRAYS}
+        out += struct.pack("<3I", int(a["op"]), int(a["nfrac"]), arr["term_col"].size)
+        out += b"".join(arr[k].tobytes() for k in ("form_begin", "term_col", "term_ch", "form_ch", "term_coef", "form_const"))
+    return out
+
+
 _EXT = {GOLDILOCKS: 2, BABYBEAR: 4}
 _NR2 = {GOLDILOCKS: 7, BABYBEAR: 11}       # Fp2 = Fp[u] / (u^2 - NR2)
 _NR4 = (2013265910, 1)                     # Fp4 = Fp2[v] / (v^2 - (2013265910 + u))  (BabyBear)
@@ -506,6 +561,28 @@ class Context:
             return rc, None, None
         return 0, (int(fin[0]) if e == 1 else tuple(int(v) for v in fin)), col
 
+    def aux_running_staged(self, op, fractions, ext=1, read=False):
+        """ms_aux_running_staged: aux_running's column built while the LDE tree of the main columns is live (after lde_commit, before lde_commit_stage and any mix
+        stage); the limbs become the last `ext` polynomials.  Arguments and result as aux_running."""
+        aux = fractions if isinstance(fractions, dict) else flatten_aux(op, fractions, ext)
+        s, _keep = aux_struct(aux)
+        e = int(aux["ext"])
+        fin = np.zeros(max(1, e), dtype=np.uint64)
+        col = np.zeros((self.N, e), dtype=np.uint64) if read else None
+        rc = self.L.ms_aux_running_staged(self.h, C.byref(s), fin.ctypes.data_as(_u64p), col.ctypes.data_as(_u64p) if read else None)
+        if rc != 0:
+            return rc, None, None
+        return 0, (int(fin[0]) if e == 1 else tuple(int(v) for v in fin)), col
+
+    def aux_staged_count(self):
+        return self.L.ms_aux_staged_count(self.h)
+
+    def lde_commit_stage(self, lpn):
+        """ms_lde_commit_stage: the staged columns evaluated behind the LDE's columns and committed in a second tree -> (rc, root)"""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_lde_commit_stage(self.h, C.c_size_t(lpn), root)
+        return rc, bytes(root)
+
     def aux_count(self):
         return self.L.ms_aux_count(self.h)
 
@@ -540,7 +617,7 @@ class Context:
         return self.L.ms_bench_lde(self.h, C.c_size_t(blowup), C.c_uint64(shift))
 
     def lde_read(self):
-        out = np.zeros((self.Lsize, self.polys_count()), dtype=np.uint64)
+        out = np.zeros((self.Lsize, self.polys_count() - self.aux_staged_count()), dtype=np.uint64)   # (staged columns are in the matrix once their stage is committed)
         self.check(self.L.ms_lde_read(self.h, out.ctypes.data_as(_u64p)))
         return out
 

@@ -170,12 +170,15 @@ int ms_trace_commit_device(ms_ctx* ctx, const void* t, size_t N, size_t w, size_
 int ms_trace_upload_async(ms_ctx* ctx, const uint64_t* t, size_t N, size_t w) { MS_ENTRY(ctx, B(ctx)->trace_upload_async(t, N, w)); }
 int ms_aux_running(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out, uint64_t* column_out) { MS_ENTRY(ctx, B(ctx)->aux_running(aux, final_out, column_out)); }
 int ms_aux_count(const ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->aux_count()); }
+int ms_aux_running_staged(ms_ctx* ctx, const ms_aux* aux, uint64_t* final_out, uint64_t* column_out) { MS_ENTRY(ctx, B(ctx)->aux_running_staged(aux, final_out, column_out)); }
+int ms_aux_staged_count(const ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->aux_staged_count()); }
 int ms_interpolate(ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->interpolate()); }
 int ms_polys_lincomb(ms_ctx* ctx, const uint64_t* s, const int* idx, int k) { MS_ENTRY(ctx, B(ctx)->polys_lincomb(s, idx, k)); }
 int ms_polys_append(ms_ctx* ctx, const uint64_t* c, size_t n) { MS_ENTRY(ctx, B(ctx)->polys_append(c, n)); }
 int ms_polys_count(const ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->polys_count()); }
 int ms_poly_read(ms_ctx* ctx, int i, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->poly_read(i, out)); }
 int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit(blowup, shift, lpn, root)); }
+int ms_lde_commit_stage(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit_stage(lpn, root)); }
 int ms_lde_read(ms_ctx* ctx, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->lde_read(out)); }
 int ms_mix(ms_ctx* ctx, uint64_t r) { MS_ENTRY(ctx, B(ctx)->mix(r)); }
 int ms_validity_read(ms_ctx* ctx, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->validity_read(out)); }

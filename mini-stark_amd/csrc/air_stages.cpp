@@ -149,7 +149,8 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
   const size_t c = (size_t)npolys;
   TreeShape ts;
   RQ(tree_shape(L_ * c, lpn, 2, &ts));
-  L = L_; blowup = blowup_; lde_c = c; lde_shift = shift; drop_vtree();
+  L = L_; blowup = blowup_; lde_c = lde_c0 = c; lde_shift = shift; drop_vtree();
+  have_stg = false; stg_pending = 0;   // (staged columns not committed yet are ordinary polynomials of this tree)
   auto stage = res.expect();
   if (lpn == c && shardable(L_)) {  // one LDE row per leaf group: rank k evaluates and hashes the rows k (mod world)
     RQ(lde_compute_sharded(blowup_, shift));
@@ -161,6 +162,40 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
   lde_ts = ts;
   RQ(read_root(d_lde_nodes, ts, root));
   have_lde = true;
+  return MS_OK;
+}
+
+// ms_lde_commit_stage (build-defined, include/ministark.h): the c1 polynomials ms_aux_running_staged appended, evaluated on the coset of the live LDE - lde_compute's
+// own path, scale by shift^k and one size-L transform - into the columns c0 .. c0 + c1 - 1 of d_lde, and a second tree over that L x c1 row-major view.  Column j stays
+// at d_lde + j * L: a buffer too small for c0 + c1 columns is replaced by a larger one with the c0 columns copied (DevBuf::ensure would free them).  Nothing the
+// stage-0 tree covers is written; lde_c, the staged tree and the count change behind the root's arrival only
+template <class F>
+int Ctx<F>::lde_commit_stage(size_t lpn, u8* root) {
+  if (sh_on) return fail(MS_ERR_STATE, "lde_commit_stage: not available on a context with sharding on");
+  if (!root) return fail(MS_ERR_ARG, "lde_commit_stage: null root");
+  if (!have_polys || !have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "lde_commit_stage: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+  if (have_stg) return fail(MS_ERR_STATE, "lde_commit_stage: the stage of this ms_lde_commit is committed already");
+  if (stg_pending < 1) return fail(MS_ERR_STATE, "lde_commit_stage: no staged columns (ms_aux_running_staged)");
+  const size_t c0 = lde_c, c1 = (size_t)stg_pending;
+  if (c0 + c1 != (size_t)npolys) return fail(MS_ERR_STATE, "lde_commit_stage: the staged columns are not the last polynomials");
+  TreeShape ts;
+  RQ(tree_shape(L * c1, lpn, 2, &ts));
+  RQ(res.join_side());
+  if (d_coef.ensure(c1 * N * sizeof(T))) return fail(MS_ERR_NOMEM, "lde_commit_stage buffers");
+  const size_t need = (c0 + c1) * L * sizeof(T);
+  if (need > d_lde.cap) {
+    DevBuf nb;
+    if (nb.ensure(need)) return fail(MS_ERR_NOMEM, "lde_commit_stage buffers");
+    CK(msrt::d2d(nb.p, d_lde.p, c0 * L * sizeof(T), stream)); CK(msrt::sync(stream));
+    d_lde = std::move(nb);
+  }
+  auto stage = res.expect();
+  T* dst = d_lde.as<T>() + c0 * L;
+  RQ(scale_pow(d_polys.as<T>() + c0 * N, N, d_coef.as<T>(), N, N, F::from_u64(lde_shift), c1));
+  RQ(ntt_run(ctz64(L), false, d_coef.as<T>(), N, N, dst, L, c1));
+  RQ((tree_build<1>(dst, L, 1, 0, (u32)c1, ts, d_stg_nodes)));
+  RQ(read_root(d_stg_nodes, ts, root));
+  stg_ts = ts; lde_c = c0 + c1; stg_pending = 0; have_stg = true;
   return MS_OK;
 }
 
@@ -191,6 +226,7 @@ int Ctx<F>::lde_read(u64* out) {
 template <class F>
 int Ctx<F>::mix(u64 r) {
   if (!have_polys) return fail(MS_ERR_STATE, "mix before interpolate");
+  if (stg_pending) return fail(MS_ERR_STATE, "mix: uncommitted staged columns (ms_lde_commit_stage, or ms_lde_commit)");
   if (r >= F::P) return fail(MS_ERR_ARG, "r not canonical");
   RQ(ensure_polys(npolys + 1));
   bool any_lazy = false;
@@ -231,6 +267,7 @@ template <class F>
 int Ctx<F>::mix_gate(const char* who, u64 r) {
   if (!have_lde) return fail(MS_ERR_STATE, std::string(who) + " before lde_commit");
   if (lde_ts.sharded) return fail(MS_ERR_STATE, std::string(who) + ": the LDE of a sharded proof is distributed over the ranks");
+  if (stg_pending) return fail(MS_ERR_STATE, std::string(who) + ": uncommitted staged columns (ms_lde_commit_stage, or ms_lde_commit)");
   if (r >= F::P) return fail(MS_ERR_ARG, std::string(who) + " arguments");
   return 0;
 }
@@ -880,6 +917,7 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
 template <class F>
 int Ctx<F>::validity_commit(size_t lpn, u8* root) {
   if (sh_on) return fail(MS_ERR_STATE, "validity_commit: not available on a context with sharding on");
+  if (stg_pending) return fail(MS_ERR_STATE, "validity_commit: uncommitted staged columns (ms_lde_commit_stage, or ms_lde_commit)");
   if (!have_validity) return fail(MS_ERR_STATE, "validity_commit before a mix stage");
   if (!have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "validity_commit: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
   const size_t ve = (size_t)validity_ext, nch = validity_len / N, m = ve * nch;
@@ -1039,6 +1077,7 @@ int Ctx<F>::deep_compose(const ms_deep* deep, const u64* gamma) {
   template int Ctx<FF>::finish_linear_columns(size_t stride, size_t n); \
   template int Ctx<FF>::lde_compute_sharded(size_t blowup_, u64 shift); \
   template int Ctx<FF>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root); \
+  template int Ctx<FF>::lde_commit_stage(size_t lpn, u8* root); \
   template int Ctx<FF>::bench_lde(size_t blowup_, u64 shift); \
   template int Ctx<FF>::lde_read(u64* out); \
   template int Ctx<FF>::mix(u64 r); \

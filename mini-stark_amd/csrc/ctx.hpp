@@ -1,9 +1,9 @@
 // ctx.hpp — the prover session behind the C ABI (include/ministark.h): one class template per field, Ctx<F>, declared here and DEFINED in
 // the translation units below (r05: one 2547-line unit until then; every kernel experiment paid its 2.5-minute rebuild).  A kernel template is
 // instantiated - and its device code generated - in the unit that launches it, so the units also partition the device code:
-//   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / aux_running / interpolate / polys_*  (transpose, narrow / widen, running-column kernels)
+//   session.cpp      ms_create's init, pools, I/O staging, profile, trace_commit / aux_running[_staged] / interpolate / polys_*  (transpose, narrow / widen, running-column kernels)
 //   io.cpp           the boundary's bulk transfers: trace in, FRI proof out, on SDMA engines or the HIP runtime; their failure handling
-//   air_stages.cpp   constraint columns, LDE commit, mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels,
+//   air_stages.cpp   constraint columns, LDE commit (and its second stage), mix, the build-defined mix stages (mix_cubic, mix_terms, mix_air:     (lincomb, mix, cubic, terms, air, eval kernels,
 //                    one host pipeline, a compose kernel each), the trace-domain check of their program, DEEP-ALI evaluations     the check kernel of air_check.hpp)
 //   ntt_plan.cpp     NTT plans (shape, instances, tables), coset evaluation, ms_ntt / ms_coset_lde                        (every NTT pass instance)
 //   merkle_tree.cpp  MerkleTree::new, replicated and sharded, ms_merkle_commit; ms_grind                            (leaf / inner kernels of every digest, grind kernels)
@@ -120,6 +120,9 @@ struct CtxBase {
   virtual int trace_upload_async(const u64* trace, size_t N, size_t w) = 0;
   virtual int aux_running(const ms_aux* aux, u64* final_out, u64* column_out) = 0;
   virtual int aux_count() const = 0;
+  virtual int aux_running_staged(const ms_aux* aux, u64* final_out, u64* column_out) = 0;
+  virtual int aux_staged_count() const = 0;
+  virtual int lde_commit_stage(size_t lpn, u8* root) = 0;
   virtual int interpolate() = 0;
   virtual int polys_lincomb(const u64* s, const int* idx, int k) = 0;
   virtual int polys_append(const u64* coeffs, size_t n) = 0;
@@ -532,7 +535,24 @@ template <class F> struct Ctx : CtxBase {
   int aux_running(const ms_aux* aux, u64* final_out, u64* column_out) override;
   int aux_count() const override { return naux; }
   template <int EA> int aux_running_t(const ms_aux& a, u64* final_out, u64* column_out);
-  template <int EA, int SEG> int aux_tile_launch(const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag);
+  template <int EA, int SEG> int aux_tile_launch(const T* cols, const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag);
+  // what both entry points ask of a descriptor (`used`: the limb columns there are already), and the launches they share: the program with `term_col` as its column
+  // indices over `cols` (N apart), the column into `out` (limb l at + l * N), final into fin[0..EA) - or MS_ERR_SHAPE for a zero denominator - behind one synchronisation
+  int aux_args_check(const char* who, const ms_aux& a, size_t used);
+  template <int EA> int aux_columns(const char* who, const ms_aux& a, const u32* term_col, const T* cols, size_t ncols, T* out, u64* fin);
+  // ------------------------------------------------------------------ build-defined: the staged LDE commitment (include/ministark.h).  Running columns built AFTER ms_lde_commit
+  // - their challenges may depend on the LDE root - become polynomials behind the c0 = lde_c0 committed ones (ms_aux_running_staged: stg_pending of them, not in any tree yet);
+  // ms_lde_commit_stage evaluates them into the columns c0 .. of d_lde and builds a second tree (d_stg_nodes) over that L x c1 view.  From then on lde_c = c0 + c1: the mix
+  // stages, the DEEP stage and ms_lde_read see all columns, MS_TREE_LDE still opens rows of c0.  The staged tree lives and dies with the LDE tree (stg_live); one stage per
+  // ms_lde_commit.  d_stg: the forward transform of the trace polynomials a descriptor names, and the column before its inverse transform
+  int stg_pending = 0, stg_total = 0;   // limb columns staged and not committed | staged since ms_trace_commit (the limit of 16 counts them with naux)
+  size_t lde_c0 = 0; bool have_stg = false;
+  DevBuf d_stg, d_stg_nodes; TreeShape stg_ts;
+  bool stg_live() const { return have_stg && have_lde; }
+  int aux_running_staged(const ms_aux* aux, u64* final_out, u64* column_out) override;
+  int aux_staged_count() const override { return stg_pending; }
+  template <int EA> int aux_running_staged_t(const ms_aux& a, u64* final_out, u64* column_out);
+  int lde_commit_stage(size_t lpn, u8* root) override;
   // ------------------------------------------------------------------ air.rs:147-160
   int interpolate() override;
   int polys_lincomb(const u64* s, const int* idx, int k) override;

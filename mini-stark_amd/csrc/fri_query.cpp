@@ -338,7 +338,11 @@ int Ctx<F>::open_view(int tree, int round, OpenView* v) {
   } else if (tree == MS_TREE_LDE) {
     if (!have_lde) return fail(MS_ERR_STATE, "tree_open: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
     ts = &lde_ts;
-    o.base = d_lde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)lde_c; o.lin = lde_lin(); o.nodes = d_lde_nodes.template as<u32>();
+    o.base = d_lde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)lde_c0; o.lin = lde_lin(); o.nodes = d_lde_nodes.template as<u32>();   // (lde_c0: the columns ms_lde_commit hashed; a staged tree covers the ones behind them)
+  } else if (tree == MS_TREE_LDE_STAGED) {
+    if (!stg_live()) return fail(MS_ERR_STATE, "tree_open: no staged LDE tree (ms_lde_commit_stage, and nothing that kills the LDE tree since)");
+    ts = &stg_ts;
+    o.base = d_lde.template as<T>() + lde_c0 * L; o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)(lde_c - lde_c0); o.nodes = d_stg_nodes.template as<u32>();
   } else if (tree == MS_TREE_VALIDITY) {
     if (!vtree_live()) return fail(MS_ERR_STATE, "tree_open: no validity tree (ms_validity_commit, and no mix stage, ms_polys_*, ms_lde_commit or ms_trace_commit since)");
     ts = &vtree_ts;
@@ -400,7 +404,7 @@ template <class F>
 int Ctx<F>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) {
   if (!index || !len || (!out && cap)) return fail(MS_ERR_ARG, "tree_open: null argument");
   if (n < 1 || n > 65536) return fail(MS_ERR_ARG, "tree_open: n outside 1..65536");
-  if (tree != MS_TREE_TRACE && tree != MS_TREE_LDE && tree != MS_TREE_FRI && tree != MS_TREE_VALIDITY) return fail(MS_ERR_ARG, "tree_open: unknown tree id");
+  if (tree != MS_TREE_TRACE && tree != MS_TREE_LDE && tree != MS_TREE_FRI && tree != MS_TREE_VALIDITY && tree != MS_TREE_LDE_STAGED) return fail(MS_ERR_ARG, "tree_open: unknown tree id");
   if (sh_on) return fail(MS_ERR_STATE, "tree_open: not available on a context with sharding on");
   OpenView v;
   RQ(open_view(tree, round, &v));
@@ -470,26 +474,32 @@ int Ctx<F>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* 
   if (D0 > L || L % D0) return fail(MS_ERR_STATE, "query_linked: round 0's domain does not divide the LDE domain (ms_fri_begin with the LDE's blowup)");
   if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "query_linked: null argument");
   if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "query_linked: nq outside 1..4096");
-  OpenView lde, val;
+  const bool staged = stg_live();   // the staged layout (MSLS): a section of staged openings between the LDE and the validity openings, its length in the header
+  OpenView lde, stg, val;
   RQ(open_view(MS_TREE_LDE, 0, &lde));
+  if (staged) RQ(open_view(MS_TREE_LDE_STAGED, 0, &stg));
   RQ(open_view(MS_TREE_VALIDITY, 0, &val));
   if (lde.ngroups != L || val.ngroups != L) return fail(MS_ERR_STATE, "query_linked: the LDE tree does not hold one row per leaf group (ms_lde_commit with lpn = the number of polynomials)");
-  u64 hd[4 + 6]; size_t body;
-  RQ(msfi_plan(betas, nq, hd + 4, &body, nullptr));
-  const size_t nrows = 2 * (size_t)nq, len_lde = nrows * lde.path_bytes(), len_val = nrows * val.path_bytes();
-  hd[0] = 0x514C534DULL /* 'MSLQ' */; hd[1] = 6 * 8 + body; hd[2] = len_lde; hd[3] = len_val;
-  *len = sizeof hd + body + len_lde + len_val;
+  if (staged && stg.ngroups != L) return fail(MS_ERR_STATE, "query_linked: the staged LDE tree does not hold one row per leaf group (ms_lde_commit_stage with lpn = the number of staged columns)");
+  const size_t nh = staged ? 5 : 4;
+  u64 hd[5 + 6]; size_t body;
+  RQ(msfi_plan(betas, nq, hd + nh, &body, nullptr));
+  const size_t nrows = 2 * (size_t)nq, len_lde = nrows * lde.path_bytes(), len_stg = staged ? nrows * stg.path_bytes() : 0, len_val = nrows * val.path_bytes();
+  hd[0] = staged ? 0x534C534DULL /* 'MSLS' */ : 0x514C534DULL /* 'MSLQ' */; hd[1] = 6 * 8 + body; hd[2] = len_lde; hd[nh - 2] = staged ? len_stg : len_lde; hd[nh - 1] = len_val;
+  const size_t hbytes = (nh + 6) * 8;
+  *len = hbytes + body + len_lde + len_stg + len_val;
   if (!out) return MS_OK;   // size query
   if (cap < *len) return fail(MS_ERR_ARG, "query_linked: buffer too small (the size needed is in *len)");
   std::vector<msmerkle::OpenJob<F>> jobs;
-  jobs.reserve(((fri_rounds - 1) + 2) * nrows);
-  RQ(msfi_plan(betas, nq, hd + 4, &body, &jobs));
+  jobs.reserve(((fri_rounds - 1) + 3) * nrows);
+  RQ(msfi_plan(betas, nq, hd + nh, &body, &jobs));
   std::vector<u64> rows(nrows);   // round-0 position b is LDE row b * (L / D_0); its partner b + D_0 / 2 is row + L / 2
   for (int j = 0; j < nq; j++) { rows[2 * j] = betas[j] % D0 * (L / D0); rows[2 * j + 1] = (rows[2 * j] + L / 2) % L; }
   open_jobs(lde, rows.data(), nrows, false, body, jobs);
-  open_jobs(val, rows.data(), nrows, false, body + len_lde, jobs);
-  memcpy(out, hd, sizeof hd);
-  return open_launch(jobs, body + len_lde + len_val, rounds[fri_rounds - 1].get(), out + sizeof hd);
+  if (staged) open_jobs(stg, rows.data(), nrows, false, body + len_lde, jobs);
+  open_jobs(val, rows.data(), nrows, false, body + len_lde + len_stg, jobs);
+  memcpy(out, hd, hbytes);
+  return open_launch(jobs, body + len_lde + len_stg + len_val, rounds[fri_rounds - 1].get(), out + hbytes);
 }
 
 // src/merkle.rs:272-288 on a standalone binary tree: leaves de-interleaved to SoA limbs, then the same

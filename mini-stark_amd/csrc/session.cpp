@@ -3,6 +3,8 @@
 #include "ctx.hpp"
 #include "running.hpp"
 
+#include <algorithm>
+
 namespace msctx {
 
 template <class F>
@@ -183,7 +185,7 @@ int Ctx<F>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_,
   RQ(tree_shape(N_ * w_, lpn, 2, &ts));
   // (the canonical range of the trace is checked by the transposing kernel for host and device input alike: a host-side scan of the N x w matrix
   //  cost ~3 ms of the proving thread per 2^20-row proof, with its stream idle - r04, I/O leg)
-  have_trace = have_polys = have_lde = have_validity = false; npolys = 0; naux = 0; nrounds_done = 0; have_deep = false; blob_size = 0;
+  have_trace = have_polys = have_lde = have_validity = have_stg = false; npolys = 0; naux = 0; stg_pending = stg_total = 0; nrounds_done = 0; have_deep = false; blob_size = 0;
   if (N_ != N) { polys_cap = 0; d_polys.release(); }
   N = N_; w = w_;
   const u64* dsrc;
@@ -211,27 +213,26 @@ int Ctx<F>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_,
   return MS_OK;
 }
 
-// ------------------------------------------------------------------ build-defined: ms_aux_running (include/ministark.h; kernels: running.hpp)
+// ------------------------------------------------------------------ build-defined: ms_aux_running, ms_aux_running_staged (include/ministark.h; kernels: running.hpp)
 template <class F>
 template <int EA, int SEG>
-int Ctx<F>::aux_tile_launch(const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag) {
+int Ctx<F>::aux_tile_launch(const T* cols, const void* prog, T* out, T* agg, size_t ntiles, u64* fin, u32* flag) {
   typedef msrun::AuxTileKernel<F, EA, SEG> TK;
-  typename TK::Params tp{d_polys.as<T>(), N, N, reinterpret_cast<const typename TK::Program*>(prog), out, N, agg, ntiles, ntiles == 1 ? fin : nullptr, flag};
+  typename TK::Params tp{cols, N, N, reinterpret_cast<const typename TK::Program*>(prog), out, N, agg, ntiles, ntiles == 1 ? fin : nullptr, flag};
   CK(run_coop<TK>(K_AUX, (unsigned)ntiles, TK::THREADS, TK::lds_bytes(), tp));
   return 0;
 }
 
 template <class F>
 template <int EA>
-int Ctx<F>::aux_running_t(const ms_aux& a, u64* final_out, u64* column_out) {
+int Ctx<F>::aux_columns(const char* who, const ms_aux& a, const u32* term_col, const T* cols, size_t ncols, T* out, u64* fin_out) {
   typedef msrun::AuxProgram<F, EA> Program;
   const u32 nforms = 2 * a.nfrac, nterms = a.form_begin[nforms];
   const size_t tile = N < (size_t)aux_tile ? (N < (size_t)msrun::THREADS ? (size_t)msrun::THREADS : N) : (size_t)aux_tile;   // (a trace shorter than the tile: the smallest instance that holds it)
   const size_t ntiles = (N + tile - 1) / tile;
   // d_aux: [0, 8) the zero-denominator flag | [64, 64 + 8 EA) final as u64 limbs | [256, ..) the tile aggregates [EA][ntiles] | the carries [EA][ntiles]
   const size_t off_fin = 64, off_agg = 256, agg_bytes = ((size_t)EA * ntiles * sizeof(T) + 255) & ~(size_t)255;
-  if (d_aux.ensure(off_agg + 2 * agg_bytes) || d_tabs.ensure(sizeof(Program) + 64)) return fail(MS_ERR_NOMEM, "aux_running buffers");
-  RQ(ensure_polys(w + (size_t)naux + EA + 1));
+  if (d_aux.ensure(off_agg + 2 * agg_bytes) || d_tabs.ensure(sizeof(Program) + 64)) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
   // the program, staged in page-locked memory (tabs_host synchronises the stream first: nothing of an earlier stage still reads the area)
   u8* ht;
   RQ(tabs_host(sizeof(Program) + 64, &ht));
@@ -239,22 +240,21 @@ int Ctx<F>::aux_running_t(const ms_aux& a, u64* final_out, u64* column_out) {
   memset(pg, 0, sizeof(Program));
   pg->op = a.op; pg->nfrac = a.nfrac;
   for (u32 f = 0; f <= nforms; f++) pg->form_begin[f] = a.form_begin[f];
-  for (u32 m = 0; m < nterms; m++) { pg->term_col[m] = a.term_col[m]; for (int l = 0; l < EA; l++) pg->term_coef[m].c[l] = F::from_u64(a.term_coef[(size_t)m * EA + l]); }
+  for (u32 m = 0; m < nterms; m++) { pg->term_col[m] = term_col[m]; for (int l = 0; l < EA; l++) pg->term_coef[m].c[l] = F::from_u64(a.term_coef[(size_t)m * EA + l]); }
   for (u32 f = 0; f < nforms; f++) for (int l = 0; l < EA; l++) pg->form_const[f].c[l] = F::from_u64(a.form_const[(size_t)f * EA + l]);
   CK(msrt::h2d(d_tabs.p, ht, sizeof(Program), stream));
   u32* flag = d_aux.as<u32>();
   u64* fin = reinterpret_cast<u64*>(d_aux.as<u8>() + off_fin);
   T* agg = reinterpret_cast<T*>(d_aux.as<u8>() + off_agg);
   T* carry = reinterpret_cast<T*>(d_aux.as<u8>() + off_agg + agg_bytes);
-  T* out = d_polys.as<T>() + (w + (size_t)naux) * N;
   CK(msrt::memset_dev(flag, 0, 8, stream));
   const double row_bytes = (double)N * sizeof(T);
-  next_bytes = row_bytes * (double)(w + EA);      // (at most: the columns the forms name, and the column out)
+  next_bytes = row_bytes * (double)(ncols + EA);      // (at most: the columns the forms name, and the column out)
   switch (tile / msrun::THREADS) {
-    case 1: RQ((aux_tile_launch<EA, 1>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
-    case 2: RQ((aux_tile_launch<EA, 2>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
-    case 4: RQ((aux_tile_launch<EA, 4>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
-    default: RQ((aux_tile_launch<EA, 8>(d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    case 1: RQ((aux_tile_launch<EA, 1>(cols, d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    case 2: RQ((aux_tile_launch<EA, 2>(cols, d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    case 4: RQ((aux_tile_launch<EA, 4>(cols, d_tabs.p, out, agg, ntiles, fin, flag))); break;
+    default: RQ((aux_tile_launch<EA, 8>(cols, d_tabs.p, out, agg, ntiles, fin, flag))); break;
   }
   if (ntiles > 1) {
     typedef msrun::AuxCarryKernel<F, EA> CKn;
@@ -268,11 +268,43 @@ int Ctx<F>::aux_running_t(const ms_aux& a, u64* final_out, u64* column_out) {
   u64 res[8 + 4];   // [flag | 7 words of padding | final]
   CK(msrt::d2h(res, d_aux.p, off_fin + (size_t)EA * 8, stream));
   CK(msrt::sync(stream));
-  if (res[0] & 0xFFFFFFFFu) return fail(MS_ERR_SHAPE, "aux_running: a denominator is zero on some row (draw another challenge)");
+  if (res[0] & 0xFFFFFFFFu) return fail(MS_ERR_SHAPE, std::string(who) + ": a denominator is zero on some row (draw another challenge)");
+  for (int l = 0; l < EA; l++) fin_out[l] = res[off_fin / 8 + l];
+  return 0;
+}
+
+template <class F>
+template <int EA>
+int Ctx<F>::aux_running_t(const ms_aux& a, u64* final_out, u64* column_out) {
+  RQ(ensure_polys(w + (size_t)naux + EA + 1));
+  T* out = d_polys.as<T>() + (w + (size_t)naux) * N;
+  u64 fin[4];
+  RQ(aux_columns<EA>("aux_running", a, a.term_col, d_polys.as<T>(), w, out, fin));
   if (column_out) RQ(download_widen(out, N, N, (u32)EA, column_out));
-  for (int l = 0; l < EA; l++) final_out[l] = res[off_fin / 8 + l];
+  for (int l = 0; l < EA; l++) final_out[l] = fin[l];
   naux += EA;
   return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::aux_args_check(const char* who, const ms_aux& a, size_t used) {
+  auto bad = [&](const char* what) { return fail(MS_ERR_ARG, std::string(who) + what); };
+  if (a.op > 1) return bad(": op must be MS_AUX_SUM or MS_AUX_PRODUCT");
+  if (a.ext != 1 && a.ext != (u32)E) return bad(": ext must be 1 or the extension degree");
+  if (a.nfrac < 1 || a.nfrac > (u32)msrun::MAX_FRAC) return bad(": nfrac outside 1..4");
+  if (!a.form_begin || !a.form_const) return bad(": null array");
+  const u32 nforms = 2 * a.nfrac;
+  if (a.form_begin[0] != 0) return bad(": form_begin[0] must be 0");
+  for (u32 f = 0; f < nforms; f++) {
+    if (a.form_begin[f + 1] < a.form_begin[f]) return bad(": form_begin decreases");
+    if (a.form_begin[f + 1] - a.form_begin[f] > (u32)msrun::MAX_FORM_TERMS) return bad(": more than 16 terms in a form");
+  }
+  const u32 nterms = a.form_begin[nforms];
+  if (nterms && (!a.term_col || !a.term_coef)) return bad(": null array");
+  for (u32 m = 0; m < nterms; m++) if (a.term_col[m] >= w) return bad(": a term names a column >= w");
+  if (!canonical(a.term_coef, (size_t)nterms * a.ext) || !canonical(a.form_const, (size_t)nforms * a.ext)) return bad(": limb not canonical");
+  if (used + a.ext > (size_t)msrun::MAX_COLUMNS) return bad(": more than 16 limb columns in all");
+  return 0;
 }
 
 template <class F>
@@ -282,22 +314,52 @@ int Ctx<F>::aux_running(const ms_aux* aux, u64* final_out, u64* column_out) {
   if (have_polys) return fail(MS_ERR_STATE, "aux_running after interpolate: the trace columns have been transformed");
   if (sh_on) return fail(MS_ERR_STATE, "aux_running: not available on a context with sharding on");
   const ms_aux& a = *aux;
-  if (a.op > 1) return fail(MS_ERR_ARG, "aux_running: op must be MS_AUX_SUM or MS_AUX_PRODUCT");
-  if (a.ext != 1 && a.ext != (u32)E) return fail(MS_ERR_ARG, "aux_running: ext must be 1 or the extension degree");
-  if (a.nfrac < 1 || a.nfrac > (u32)msrun::MAX_FRAC) return fail(MS_ERR_ARG, "aux_running: nfrac outside 1..4");
-  if (!a.form_begin || !a.form_const) return fail(MS_ERR_ARG, "aux_running: null array");
-  const u32 nforms = 2 * a.nfrac;
-  if (a.form_begin[0] != 0) return fail(MS_ERR_ARG, "aux_running: form_begin[0] must be 0");
-  for (u32 f = 0; f < nforms; f++) {
-    if (a.form_begin[f + 1] < a.form_begin[f]) return fail(MS_ERR_ARG, "aux_running: form_begin decreases");
-    if (a.form_begin[f + 1] - a.form_begin[f] > (u32)msrun::MAX_FORM_TERMS) return fail(MS_ERR_ARG, "aux_running: more than 16 terms in a form");
-  }
-  const u32 nterms = a.form_begin[nforms];
-  if (nterms && (!a.term_col || !a.term_coef)) return fail(MS_ERR_ARG, "aux_running: null array");
-  for (u32 m = 0; m < nterms; m++) if (a.term_col[m] >= w) return fail(MS_ERR_ARG, "aux_running: a term names a column >= w");
-  if (!canonical(a.term_coef, (size_t)nterms * a.ext) || !canonical(a.form_const, (size_t)nforms * a.ext)) return fail(MS_ERR_ARG, "aux_running: limb not canonical");
-  if ((size_t)naux + a.ext > (size_t)msrun::MAX_COLUMNS) return fail(MS_ERR_ARG, "aux_running: more than 16 limb columns in all");
+  RQ(aux_args_check("aux_running", a, (size_t)naux));
   return a.ext == 1 ? aux_running_t<1>(a, final_out, column_out) : aux_running_t<E>(a, final_out, column_out);
+}
+
+// ms_aux_running_staged: the same column, built while the LDE tree of the main columns is live.  The trace columns the forms name exist as polynomials only, so they
+// are evaluated on the trace domain again - one forward size-N transform per maximal run of named columns, out of place into d_stg, term_col remapped to its
+// slots - the launches of ms_aux_running run over that scratch, and one inverse transform puts the EA limb columns behind the polynomials.  Nothing the LDE tree
+// covers is written; the polynomial store may move (ensure_polys), with everything live in it
+template <class F>
+template <int EA>
+int Ctx<F>::aux_running_staged_t(const ms_aux& a, u64* final_out, u64* column_out) {
+  const u32 nterms = a.form_begin[2 * a.nfrac];
+  std::vector<u32> named(a.term_col, a.term_col + nterms), slot(nterms);
+  std::sort(named.begin(), named.end());
+  named.erase(std::unique(named.begin(), named.end()), named.end());
+  for (u32 m = 0; m < nterms; m++) slot[m] = (u32)(std::lower_bound(named.begin(), named.end(), a.term_col[m]) - named.begin());
+  const size_t ns = named.size();
+  poly_lin.reserve((size_t)npolys + EA); poly_mat.reserve((size_t)npolys + EA);   // (what the end of the call appends cannot fail any more)
+  if (d_stg.ensure((ns + EA) * N * sizeof(T))) return fail(MS_ERR_NOMEM, "aux_running_staged buffers");
+  RQ(ensure_polys((size_t)npolys + EA));
+  RQ(res.join_side());
+  T* scr = d_stg.as<T>(); T* out = scr + ns * N;
+  for (size_t i = 0; i < ns;) {   // maximal runs of named columns
+    size_t j = i + 1;
+    while (j < ns && named[j] == named[j - 1] + 1) j++;
+    RQ(ntt_run(ctz64(N), false, d_polys.as<T>() + (size_t)named[i] * N, N, N, scr + i * N, N, j - i));
+    i = j;
+  }
+  u64 fin[4];
+  RQ(aux_columns<EA>("aux_running_staged", a, slot.data(), scr, ns, out, fin));
+  if (column_out) RQ(download_widen(out, N, N, (u32)EA, column_out));
+  RQ(ntt_run(ctz64(N), true, out, N, N, d_polys.as<T>() + (size_t)npolys * N, N, (size_t)EA));
+  for (int l = 0; l < EA; l++) { poly_lin.push_back(Lin()); poly_mat.push_back(1); final_out[l] = fin[l]; }
+  npolys += EA; stg_pending += EA; stg_total += EA;
+  return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::aux_running_staged(const ms_aux* aux, u64* final_out, u64* column_out) {
+  if (!aux || !final_out) return fail(MS_ERR_ARG, "aux_running_staged: null argument");
+  if (sh_on) return fail(MS_ERR_STATE, "aux_running_staged: not available on a context with sharding on");
+  if (!have_polys || !have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "aux_running_staged: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+  if (have_stg) return fail(MS_ERR_STATE, "aux_running_staged after lde_commit_stage: one stage per ms_lde_commit");
+  if (have_validity) return fail(MS_ERR_STATE, "aux_running_staged after a mix stage: the validity polynomial lies behind the polynomials");
+  RQ(aux_args_check("aux_running_staged", *aux, (size_t)naux + (size_t)stg_total));
+  return aux->ext == 1 ? aux_running_staged_t<1>(*aux, final_out, column_out) : aux_running_staged_t<E>(*aux, final_out, column_out);
 }
 
 // ------------------------------------------------------------------ air.rs:147-160
@@ -402,6 +464,7 @@ int Ctx<F>::arith_launch(int op, u64* buf, size_t n) {
   template int Ctx<FF>::transpose_in(const u64* src, Ctx<FF>::T* dst, size_t rows, size_t cols, Ctx<FF>::T rinv, int mont, u32* bad); \
   template int Ctx<FF>::trace_commit(const u64* trace, bool on_device, size_t N_, size_t w_, size_t lpn, u8* root); \
   template int Ctx<FF>::aux_running(const ms_aux* aux, u64* final_out, u64* column_out); \
+  template int Ctx<FF>::aux_running_staged(const ms_aux* aux, u64* final_out, u64* column_out); \
   template int Ctx<FF>::interpolate(); \
   template int Ctx<FF>::polys_lincomb(const u64* s, const int* idx, int k); \
   template int Ctx<FF>::polys_append(const u64* coeffs, size_t n); \

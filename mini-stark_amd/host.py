@@ -40,13 +40,18 @@ def _host():
         L = C.CDLL(path, mode=C.RTLD_GLOBAL)
         L.msh_stark_new.restype = C.c_void_p
         for n in ("msh_proof_arthur", "msh_proof_evals", "msh_proof_fri_roots", "msh_proof_fri_blob", "msh_proof_challenges", "msh_proof_num_polys", "msh_proof_serialize",
-                  "msh_linked_proof", "msh_air_encode",
+                  "msh_linked_proof", "msh_air_encode", "msh_aux_encode",
                   "msh_prev_proof_arthur", "msh_prev_proof_fri_roots", "msh_prev_proof_fri_blob"):
             getattr(L, n).restype = C.c_size_t
         L.msh_proof_blob_checksum.restype = C.c_uint64
         L.msh_proof_blob_sample.restype = C.c_uint64
         L.msh_hash.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_char_p]
         L.msh_hash.restype = C.c_int
+        L.msh_air_prog_new.restype = C.c_void_p
+        L.msh_air_prog_new.argtypes = [C.c_void_p]
+        L.msh_air_prog_air.restype = C.c_void_p
+        L.msh_air_prog_air.argtypes = [C.c_void_p]
+        L.msh_air_prog_free.argtypes = [C.c_void_p]
         _HOST = L
     return _HOST
 
@@ -204,6 +209,62 @@ def air_encode(air) -> bytes:
     buf = (C.c_uint8 * max(1, n))()
     H.msh_air_encode(C.byref(s), buf, C.c_size_t(n))
     return bytes(buf[:n])
+
+
+class MshAuxArg(C.Structure):
+    """msh_aux_arg of include/ministark_host.h"""
+    _fields_ = [("op", C.c_uint32), ("nfrac", C.c_uint32), ("form_begin", C.POINTER(C.c_uint32)), ("term_col", C.POINTER(C.c_uint32)), ("term_coef", C.POINTER(C.c_uint64)),
+                ("term_ch", C.POINTER(C.c_uint32)), ("form_const", C.POINTER(C.c_uint64)), ("form_ch", C.POINTER(C.c_uint32))]
+
+
+def aux_args_struct(args):
+    """(an array of msh_aux_arg, what it points into) from flatten_aux_arg dicts; an entry that is None becomes a NULL pointer"""
+    from ._native import AUX_ARG_ARRAYS
+    arr = (MshAuxArg * max(1, len(args)))()
+    keep = []
+    for k, a in enumerate(args):
+        arr[k].op, arr[k].nfrac = int(a["op"]), int(a["nfrac"])
+        for name, t in AUX_ARG_ARRAYS:
+            if a.get(name) is not None:
+                v = np.ascontiguousarray(a[name], dtype=t)
+                keep.append(v)
+                setattr(arr[k], name, v.ctypes.data_as(C.POINTER(C.c_uint64 if t is np.uint64 else C.c_uint32)))
+    return arr, keep
+
+
+def aux_encode(field, args, nch) -> bytes:
+    """msh_aux_encode: the canonical bytes of the arguments of a linked proof with running columns; b"" for a malformed descriptor."""
+    H = _host()
+    arr, _keep = aux_args_struct(args)
+    n = H.msh_aux_encode(C.c_int(field), arr, C.c_uint32(len(args)), C.c_uint32(nch), None, C.c_size_t(0))
+    buf = (C.c_uint8 * max(1, n))()
+    H.msh_aux_encode(C.c_int(field), arr, C.c_uint32(len(args)), C.c_uint32(nch), buf, C.c_size_t(n))
+    return bytes(buf[:n])
+
+
+def aux_constraints_native(field, air, auxes, first_poly):
+    """msh_aux_constraints: `air` with the constraints of every flatten_aux dict of `auxes` appended, argument k over the polynomials first_poly + k E ..; returns
+    (rc of the first refusal or 0, msh_air_encode of the program as it stands)"""
+    from ._native import aux_struct
+    H = _host()
+    s, _keep = _air(air)
+    g = H.msh_air_prog_new(C.byref(s))
+    if not g:
+        raise MsError(-5, "msh_air_prog_new: malformed program")
+    try:
+        rc = 0
+        for k, aux in enumerate(auxes):
+            a, _k2 = aux_struct(aux)
+            rc = H.msh_aux_constraints(C.c_void_p(g), C.c_int(field), C.byref(a), C.c_uint32(first_poly + k * int(aux["ext"])))
+            if rc:
+                break
+        view = C.c_void_p(H.msh_air_prog_air(C.c_void_p(g)))
+        n = H.msh_air_encode(view, None, C.c_size_t(0))
+        buf = (C.c_uint8 * max(1, n))()
+        H.msh_air_encode(view, buf, C.c_size_t(n))
+        return rc, bytes(buf[:n])
+    finally:
+        H.msh_air_prog_free(C.c_void_p(g))
 
 
 def air_rows_native(air):
@@ -396,6 +457,25 @@ class HostStark:
             N, w = t.shape
             host_ptr = t.ctypes.data_as(C.POINTER(C.c_uint64))
         return self.H.msh_stark_prove_linked(self.h, host_ptr, C.c_void_p(trace_device_ptr), C.c_size_t(N), C.c_size_t(w), C.byref(s), C.c_uint32(fri_rounds))
+
+    def prove_linked_aux(self, trace, air, args, nch, fri_rounds=0) -> int:
+        """msh_stark_prove_linked_aux (MSLP v2): air over the w trace columns, args flatten_aux_arg dicts with selectors into nch challenges"""
+        s, _keep = _air(air)
+        arr, _keep2 = aux_args_struct(args)
+        t = np.ascontiguousarray(trace, dtype=np.uint64)
+        N, w = t.shape
+        return self.H.msh_stark_prove_linked_aux(self.h, t.ctypes.data_as(C.POINTER(C.c_uint64)), None, C.c_size_t(N), C.c_size_t(w), C.byref(s), arr, C.c_uint32(len(args)),
+                                                 C.c_uint32(nch), C.c_uint32(fri_rounds))
+
+    def verify_linked_aux(self, data, air, args, nch, N, w, fri_rounds=0, zero_display_empty=True):
+        """msh_stark_verify_linked_aux: (rc, why) as verify_linked"""
+        s, _keep = _air(air)
+        arr, _keep2 = aux_args_struct(args)
+        why = C.create_string_buffer(512)
+        data = bytes(data)
+        rc = self.H.msh_stark_verify_linked_aux(self.h, C.byref(s), arr, C.c_uint32(len(args)), C.c_uint32(nch), C.c_size_t(N), C.c_size_t(w), C.c_uint32(fri_rounds), data,
+                                                C.c_size_t(len(data)), C.c_int(1 if zero_display_empty else 0), why, C.c_size_t(512))
+        return rc, why.value.decode()
 
     def linked_proof(self) -> bytes:
         """msh_linked_proof: the MSLP bytes of the last linked proof (b"": none)."""

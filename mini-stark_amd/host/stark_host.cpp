@@ -17,7 +17,10 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/ministark.h"
@@ -663,10 +666,12 @@ template <class F, int E> static void validity_from_chunks(u32 ve, u32 nchunks, 
 }
 
 // the link between FRI's round 0 and the two committed trees: 1 accepted, 0 rejected (reason in *why), < 0 malformed arguments
-template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N, u64 blowup, u64 shift, u32 c, u32 m, const u8* lde_root, const u8* val_root, const ms_deep& d,
-                                                      const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msfi, size_t msfi_len,
-                                                      const u8* lde_open, size_t lde_len, const u8* val_open, size_t val_len, std::string* why) {
+// c1 > 0 (msh_deep_link_verify_staged): the columns c0 .. c0 + c1 - 1 come from rows of a second tree under stg_root, opened at the same rows
+template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N, u64 blowup, u64 shift, u32 c0, u32 c1, u32 m, const u8* lde_root, const u8* stg_root, const u8* val_root,
+                                                      const ms_deep& d, const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msfi, size_t msfi_len,
+                                                      const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open, size_t val_len, std::string* why) {
   typedef typename F::T T;
+  const u32 c = c0 + c1;
   typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
   const u64 L = N * blowup;
@@ -708,15 +713,22 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
   for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
   const u8* lp = lde_open; size_t lleft = lde_len;
   const u8* vp = val_open; size_t vleft = val_len;
+  const u8* sp = stg_open; size_t sleft = stg_len;
   for (size_t j = 0; j < nq; j++) {
     const u64 b = betas[j] % D0;
     for (int s = 0; s < 2; s++) {
       const u64 pos = s ? (b + D0 / 2) % D0 : b, row = pos * step;
       size_t used = 0;
       std::string w;
-      if (!check_path_at<F>(digest, 1, c, zae, lde_root, lp, lleft, row * c, &used, &w)) { *why = "LDE opening: " + w; return 0; }
+      if (!check_path_at<F>(digest, 1, c0, zae, lde_root, lp, lleft, row * c0, &used, &w)) { *why = "LDE opening: " + w; return 0; }
       const u64* lrow = (const u64*)(lp + 8);
       lp += used; lleft -= used;
+      const u64* srow = nullptr;
+      if (c1) {
+        if (!check_path_at<F>(digest, 1, c1, zae, stg_root, sp, sleft, row * c1, &used, &w)) { *why = "staged opening: " + w; return 0; }
+        srow = (const u64*)(sp + 8);
+        sp += used; sleft -= used;
+      }
       if (!check_path_at<F>(digest, 1, m, zae, val_root, vp, vleft, row * m, &used, &w)) { *why = "validity opening: " + w; return 0; }
       const u64* vrow = (const u64*)(vp + 8);
       vp += used; vleft -= used;
@@ -727,7 +739,7 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
       X Dx = e_zero<F, E>();
       for (size_t n = 0; n < ne; n++) {
         const u32 fi = d.pt_poly[n];
-        const T fx = F::from_u64(fi < c ? lrow[fi] : vrow[fi - c]);
+        const T fx = F::from_u64(fi < c0 ? lrow[fi] : fi < c ? srow[fi - c0] : vrow[fi - c]);
         Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
       }
       X y;
@@ -749,6 +761,7 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
     }
   }
   if (lleft != 0) { *why = "LDE opening: trailing bytes"; return 0; }
+  if (c1 && sleft != 0) { *why = "staged opening: trailing bytes"; return 0; }
   if (vleft != 0) { *why = "validity opening: trailing bytes"; return 0; }
   return 1;
 }
@@ -963,14 +976,9 @@ struct LinkedShape {
   std::vector<u8> statement;
   size_t arthur_len(int e) const { return 3 * 32 + ne * e * 8 + 32 + (size_t)(R - 1) * (2 * e * 8 + 32) + (gb ? 8 : 0); }
 };
-template <class F> static int linked_shape(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
-  const int e = c.e;
-  AirShape sh;
-  if (!air_shape(air, &sh) || N < 2 || (N & (N - 1)) || w < 1 || w > (1u << 16) || !c.blowup_factor || (c.blowup_factor & (c.blowup_factor - 1))) return MS_ERR_ARG;
-  if (N > ((u64)1 << F::TWO_ADICITY) / c.blowup_factor) return MS_ERR_ARG;
-  o->c = (u32)w; o->N = N; o->blowup = c.blowup_factor; o->L = N * c.blowup_factor; o->gb = c.grinding_bits;
-  o->R = fri_rounds ? fri_rounds : (u32)c.rounds; o->nq = (u32)c.fri_queries;
-  if (o->R < 1 || o->R > 64 || o->nq < 1 || o->nq > 4096) return MS_ERR_ARG;
+// what the program fixes, for c columns: m, the points and what they open (o->c, o->N set by the caller)
+static int linked_program_shape(const ms_air* air, const AirShape& sh, int e, LinkedShape* o) {
+  const u64 N = o->N;
   // m = E * VL / N, VL by ms_mix_air's rule (ministark.h): nq = max(max_t (d_t (N - 1) + e_t - N + 1), N - 1 if nbound > 0, 1), VL = N * next_pow2(ceil(nq / N))
   u64 nqv = sh.nbound ? N - 1 : 1;
   if (nqv < 1) nqv = 1;
@@ -994,6 +1002,21 @@ template <class F> static int linked_shape(const StarkConfig& c, const ms_air* a
   }
   o->ne = o->pt_poly.size();
   if (o->ne > 8192) return MS_ERR_ARG;
+  return MS_OK;
+}
+// what the configuration fixes: field sizes, rounds, queries, grinding bits
+template <class F> static int linked_config_shape(const StarkConfig& c, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
+  if (N < 2 || (N & (N - 1)) || w < 1 || w > (1u << 16) || !c.blowup_factor || (c.blowup_factor & (c.blowup_factor - 1))) return MS_ERR_ARG;
+  if (N > ((u64)1 << F::TWO_ADICITY) / c.blowup_factor) return MS_ERR_ARG;
+  o->c = (u32)w; o->N = N; o->blowup = c.blowup_factor; o->L = N * c.blowup_factor; o->gb = c.grinding_bits;
+  o->R = fri_rounds ? fri_rounds : (u32)c.rounds; o->nq = (u32)c.fri_queries;
+  if (o->R < 1 || o->R > 64 || o->nq < 1 || o->nq > 4096) return MS_ERR_ARG;
+  return MS_OK;
+}
+template <class F> static int linked_shape(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
+  const int e = c.e;
+  AirShape sh;
+  if (!air_shape(air, &sh) || linked_config_shape<F>(c, N, w, fri_rounds, o) || linked_program_shape(air, sh, e, o)) return MS_ERR_ARG;
   const u64 words[8] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)o->R, (u64)o->nq, (u64)o->gb};
   std::vector<u8> enc;
   if (!air_encode(air, &enc)) return MS_ERR_ARG;
@@ -1167,8 +1190,363 @@ template <class F, int E> static int verify_linked(const StarkConfig& c, const m
   // ---- 4. round 0 against the two trees
   const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
   const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, sh.c, sh.m, lroot, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
-                              val_open, l_val, &sub);
+  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, sh.c, 0, sh.m, lroot, nullptr, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
+                              nullptr, 0, val_open, l_val, &sub);
+  if (rc != 1) { *why = sub; return rc; }
+  return 1;
+}
+
+// ---- linked proofs with running columns: MSLP v2 (ministark_host.h) ---------------------------------------------------------------------------------------------
+// msh_aux_arg: what ms_aux_running's limits and the selectors ask of a descriptor; nterms out
+static bool aux_arg_shape(const msh_aux_arg& a, u32 nch, u64 p, u32* nterms_out) {
+  if (a.op > 1 || a.nfrac < 1 || a.nfrac > 4 || !a.form_begin || !a.form_const || !a.form_ch || a.form_begin[0] != 0) return false;
+  const u32 nforms = 2 * a.nfrac;
+  for (u32 f = 0; f < nforms; f++) if (a.form_begin[f + 1] < a.form_begin[f] || a.form_begin[f + 1] - a.form_begin[f] > 16) return false;
+  const u32 nterms = a.form_begin[nforms];
+  if (nterms && (!a.term_col || !a.term_coef || !a.term_ch)) return false;
+  for (u32 m = 0; m < nterms; m++) if (a.term_ch[m] > nch || a.term_coef[m] >= p) return false;
+  for (u32 f = 0; f < nforms; f++) if (a.form_ch[f] > nch || a.form_const[f] >= p) return false;
+  *nterms_out = nterms;
+  return true;
+}
+static const u32 AUX_MAGIC = 0x5841534Du;   // 'MSAX'
+// msh_aux_encode: 'MSAX' | version 1 | nargs | nch, then per argument op, nfrac, nterms | form_begin | term_col | term_ch | form_ch | term_coef | form_const.  w: the
+// columns a term may name (0: not checked)
+static bool aux_encode(const msh_aux_arg* args, u32 nargs, u32 nch, u64 p, int e, u64 w, std::vector<u8>* out) {
+  if (!args || nargs < 1 || nch < 1 || nch > 8 || (u64)nargs * e > 16) return false;
+  out->clear();
+  auto put = [&](const void* src, size_t n) { const u8* b = (const u8*)src; out->insert(out->end(), b, b + n); };
+  const u32 head[4] = {AUX_MAGIC, 1, nargs, nch};
+  put(head, sizeof head);
+  for (u32 k = 0; k < nargs; k++) {
+    const msh_aux_arg& a = args[k];
+    u32 nterms;
+    if (!aux_arg_shape(a, nch, p, &nterms)) return false;
+    if (w) for (u32 m = 0; m < nterms; m++) if (a.term_col[m] >= w) return false;
+    const u32 nforms = 2 * a.nfrac, h3[3] = {a.op, a.nfrac, nterms};
+    put(h3, sizeof h3);
+    put(a.form_begin, 4 * ((size_t)nforms + 1)); put(a.term_col, 4 * (size_t)nterms); put(a.term_ch, 4 * (size_t)nterms); put(a.form_ch, 4 * (size_t)nforms);
+    put(a.term_coef, 8 * (size_t)nterms); put(a.form_const, 8 * (size_t)nforms);
+  }
+  return true;
+}
+// a descriptor with the drawn challenges in place: the ms_aux of ms_aux_running_staged (ext = E).  A selector k > 0 multiplies the base-field value by ch[k - 1]
+struct AuxInstance { std::vector<u64> term_coef, form_const; ms_aux aux; };
+template <class F> static void aux_instantiate(const msh_aux_arg& a, const u64* ch, int e, AuxInstance* o) {
+  const u32 nforms = 2 * a.nfrac, nterms = a.form_begin[nforms];
+  auto value = [&](u64 base, u32 sel, u64* dst) {
+    for (int l = 0; l < e; l++) dst[l] = sel ? F::to_u64(F::mul(F::from_u64(base), F::from_u64(ch[(size_t)(sel - 1) * e + l]))) : (l == 0 ? base : 0);
+  };
+  o->term_coef.assign((size_t)nterms * e, 0); o->form_const.assign((size_t)nforms * e, 0);
+  for (u32 m = 0; m < nterms; m++) value(a.term_coef[m], a.term_ch[m], o->term_coef.data() + (size_t)m * e);
+  for (u32 f = 0; f < nforms; f++) value(a.form_const[f], a.form_ch[f], o->form_const.data() + (size_t)f * e);
+  o->aux = ms_aux{a.op, (u32)e, a.nfrac, a.form_begin, a.term_col, o->term_coef.data(), o->form_const.data()};
+}
+// a growable copy of an ms_air program
+struct AirProg {
+  std::vector<u32> tb{0}, fb{0}, fp, fr, eb{0}, er, pb{0}, bp, br;
+  std::vector<u64> coef, pv, bv;
+  ms_air air{};
+  bool load(const ms_air* a) {
+    AirShape sh;
+    if (!air_shape(a, &sh)) return false;
+    tb.assign(a->term_begin, a->term_begin + sh.ncons + 1); coef.assign(a->coef, a->coef + sh.nterms); fb.assign(a->fac_begin, a->fac_begin + sh.nterms + 1);
+    fp.assign(a->fac_poly, a->fac_poly + sh.nfacs); fr.assign(a->fac_row, a->fac_row + sh.nfacs);
+    eb.assign(a->ex_begin, a->ex_begin + sh.ncons + 1); er.assign(a->ex_row, a->ex_row + sh.nex);
+    if (sh.nperiodic) { pb.assign(a->per_begin, a->per_begin + sh.nperiodic + 1); pv.assign(a->per_val, a->per_val + sh.nperval); }
+    bp.assign(a->bnd_poly, a->bnd_poly + sh.nbound); br.assign(a->bnd_row, a->bnd_row + sh.nbound); bv.assign(a->bnd_val, a->bnd_val + sh.nbound);
+    return true;
+  }
+  const ms_air* view() {
+    air.ncons = (u32)tb.size() - 1; air.term_begin = tb.data(); air.coef = coef.data(); air.fac_begin = fb.data(); air.fac_poly = fp.data(); air.fac_row = fr.data();
+    air.ex_begin = eb.data(); air.ex_row = er.data(); air.nperiodic = (u32)pb.size() - 1; air.per_begin = pb.data(); air.per_val = pv.data();
+    air.nbound = (u32)bp.size(); air.bnd_poly = bp.data(); air.bnd_row = br.data(); air.bnd_val = bv.data();
+    return &air;
+  }
+};
+// msh_aux_constraints: mini_stark_amd.aux_constraints in C++ - the transition constraint cleared of denominators as a polynomial in the (polynomial, row) variables
+// with coefficients in K (monomial: its sorted factors), one base-field constraint per limb, terms in the monomials' order; no exemption; z(w^0) = identity
+template <class F, int E> static int aux_constraints(AirProg& pg, const ms_aux& a, u32 first_poly) {
+  typedef Ext<F, E> X;
+  typedef std::vector<std::pair<u32, u32>> Mono;
+  typedef std::map<Mono, X> Poly;
+  if (a.ext != (u32)E || a.op > 1 || a.nfrac < 1 || a.nfrac > 4) return MS_ERR_ARG;
+  bool over = false;
+  auto padd = [&](Poly& acc, const Poly& b, bool minus) { for (auto& kv : b) { auto it = acc.find(kv.first); const X v = it == acc.end() ? e_zero<F, E>() : it->second; acc[kv.first] = minus ? e_sub<F, E>(v, kv.second) : e_add<F, E>(v, kv.second); } };
+  auto pmul = [&](const Poly& x, const Poly& y) {
+    Poly out;
+    for (auto& ka : x) {
+      for (auto& kb : y) {
+        Mono mo(ka.first); mo.insert(mo.end(), kb.first.begin(), kb.first.end());
+        std::sort(mo.begin(), mo.end());
+        if (mo.size() > 8) { over = true; return out; }
+        const X c = e_mul<F>(ka.second, kb.second);
+        auto it = out.find(mo);
+        if (it == out.end()) out[mo] = c; else it->second = e_add<F, E>(it->second, c);
+      }
+      if (out.size() * E > 65536) { over = true; return out; }
+    }
+    return out;
+  };
+  auto load = [&](const u64* v) { X x; for (int l = 0; l < E; l++) x.c[l] = F::from_u64(v[l]); return x; };
+  auto form = [&](u32 f) {
+    Poly out; out[Mono()] = load(a.form_const + (size_t)f * E);
+    for (u32 m = a.form_begin[f]; m < a.form_begin[f + 1]; m++) { Poly t; t[Mono{{a.term_col[m], 0}}] = load(a.term_coef + (size_t)m * E); padd(out, t, false); }
+    return out;
+  };
+  auto unit = [&](int l) { X x = e_zero<F, E>(); x.c[l] = F::from_u64(1); return x; };
+  Poly z, zn, one; one[Mono()] = unit(0);
+  for (int l = 0; l < E; l++) { z[Mono{{first_poly + l, 0}}] = unit(l); zn[Mono{{first_poly + l, 1}}] = unit(l); }
+  std::vector<Poly> nums, dens;
+  for (u32 k = 0; k < a.nfrac; k++) { nums.push_back(form(2 * k)); dens.push_back(form(2 * k + 1)); }
+  Poly den_all = one, expr;
+  for (auto& d : dens) den_all = pmul(den_all, d);
+  if (a.op == MS_AUX_PRODUCT) {
+    Poly num_all = one;
+    for (auto& n : nums) num_all = pmul(num_all, n);
+    expr = pmul(zn, den_all);
+    padd(expr, pmul(z, num_all), true);
+  } else {
+    Poly dz = zn; padd(dz, z, true);
+    expr = pmul(dz, den_all);
+    for (u32 k = 0; k < a.nfrac; k++) {
+      Poly t = nums[k];
+      for (u32 j = 0; j < a.nfrac; j++) if (j != k) t = pmul(t, dens[j]);
+      padd(expr, t, true);
+    }
+  }
+  if (over) return MS_ERR_ARG;
+  size_t total = pg.coef.size();
+  for (int l = 0; l < E; l++) {
+    bool any_factor = false; size_t n = 0;
+    for (auto& kv : expr) if (kv.second.c[l] != 0) { n++; any_factor = any_factor || !kv.first.empty(); }
+    if (!any_factor) return MS_ERR_ARG;
+    total += n;
+  }
+  if (total > 65536 || pg.tb.size() - 1 + E > 4096 || pg.bp.size() + E > 4096) return MS_ERR_ARG;
+  for (int l = 0; l < E; l++) {
+    for (auto& kv : expr) if (kv.second.c[l] != 0) {
+      pg.coef.push_back(F::to_u64(kv.second.c[l]));
+      for (auto& fc : kv.first) { pg.fp.push_back(fc.first); pg.fr.push_back(fc.second); }
+      pg.fb.push_back((u32)pg.fp.size());
+    }
+    pg.tb.push_back((u32)pg.coef.size());
+    pg.eb.push_back((u32)pg.er.size());
+  }
+  for (int l = 0; l < E; l++) { pg.bp.push_back(first_poly + l); pg.br.push_back(0); pg.bv.push_back((a.op == MS_AUX_PRODUCT && l == 0) ? 1 : 0); }
+  return MS_OK;
+}
+static const size_t MSLP2_HEAD = 12 * 4 + 4 * 8;
+// the statement of a v2 proof and what the configuration fixes; the program's part of the shape follows the challenge draw (linked_combined)
+template <class F> static int linked_shape_aux(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
+  AirShape sh;
+  if (!air_shape(air, &sh) || linked_config_shape<F>(c, N, w, fri_rounds, o)) return MS_ERR_ARG;
+  for (u32 k = 0; k < sh.nfacs; k++) if (!(air->fac_poly[k] & 0x80000000u) && air->fac_poly[k] >= w) return MS_ERR_ARG;   // the main program is over the w trace columns
+  const u64 words[10] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)o->R, (u64)o->nq, (u64)o->gb, (u64)nargs, (u64)nch};
+  std::vector<u8> enc, enx;
+  if (!air_encode(air, &enc) || !aux_encode(args, nargs, nch, c.p, c.e, w, &enx)) return MS_ERR_ARG;
+  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
+  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
+  o->statement.insert(o->statement.end(), enx.begin(), enx.end());
+  o->c = (u32)w + nargs * (u32)c.e;
+  return (int)enc.size();   // (> 0: where the second part of the statement ends)
+}
+static Transcript linked_transcript_aux(const StarkConfig& c, const LinkedShape& sh, size_t air_bytes) {
+  Transcript t(c.domsep + "/linked/v2", c.digest);
+  t.add_bytes(sh.statement.data(), 80);                                                  // field, digest, N, w, blowup, R, nq, grinding bits, nargs, nch
+  t.add_bytes(sh.statement.data() + 80, air_bytes);                                      // msh_air_encode(air)
+  t.add_bytes(sh.statement.data() + 80 + air_bytes, sh.statement.size() - 80 - air_bytes);   // msh_aux_encode(args)
+  t.prover_bytes.clear();
+  return t;
+}
+// the combined program - air plus msh_aux_constraints of every instantiated argument, argument k at first_poly = w + k E - and the shape it fixes
+template <class F, int E> static int linked_combined(const ms_air* air, const msh_aux_arg* args, u32 nargs, const u64* ch, size_t w, AirProg* pg, std::vector<AuxInstance>* inst, LinkedShape* o) {
+  if (!pg->load(air)) return MS_ERR_ARG;
+  inst->resize(nargs);
+  for (u32 k = 0; k < nargs; k++) {
+    aux_instantiate<F>(args[k], ch, E, &(*inst)[k]);
+    const int rc = aux_constraints<F, E>(*pg, (*inst)[k].aux, (u32)w + k * E);
+    if (rc) return rc;
+  }
+  AirShape sh;
+  if (!air_shape(pg->view(), &sh)) return MS_ERR_ARG;
+  return linked_program_shape(pg->view(), sh, E, o);
+}
+static size_t arthur_len_aux(const LinkedShape& sh, int e) { return sh.arthur_len(e) + 32; }   // (the staged root behind the stage-0 root)
+
+template <class F, int E> static int prove_linked_aux(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, u32 fri_rounds) {
+  const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = E; const u64 p = c.p;
+  s.linked.clear();
+  if (!ctx || c.e != E || (!trace_host && !trace_dev)) return MS_ERR_ARG;
+  LinkedShape sh;
+  int rc = linked_shape_aux<F>(c, air, args, nargs, nch, N, w, fri_rounds, &sh);
+  if (rc < 0) return rc;
+  Transcript t = linked_transcript_aux(c, sh, (size_t)rc);
+  u8 root[32];
+  rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
+  if (rc) return rc;
+  t.add_bytes(root, 32);
+  const u64 shift = draw_shift<F>(t, sh.L);
+  if ((rc = ms_interpolate(ctx))) return rc;
+  if ((rc = ms_lde_commit(ctx, sh.blowup, shift, w, root))) return rc;
+  t.add_bytes(root, 32);
+  // the arguments' challenges follow the commitment to the main columns
+  std::vector<u64> ch((size_t)nch * e);
+  t.challenge_scalars(ch.data(), ch.size(), p);
+  AirProg pg; std::vector<AuxInstance> inst;
+  if ((rc = linked_combined<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh))) return rc;
+  for (u32 k = 0; k < nargs; k++) {
+    u64 fin[E];
+    if ((rc = ms_aux_running_staged(ctx, &inst[k].aux, fin, nullptr))) return rc;          // MS_ERR_SHAPE: a zero denominator (probability about N / |K|)
+    for (int l = 0; l < e; l++) if (fin[l] != ((args[k].op == MS_AUX_PRODUCT && l == 0) ? 1u : 0u)) return MS_ERR_SHAPE;   // the argument does not hold
+  }
+  const u32 c1 = nargs * (u32)e;
+  if ((rc = ms_lde_commit_stage(ctx, c1, root))) return rc;
+  t.add_bytes(root, 32);
+  const ms_air* prog = pg.view();
+  std::vector<u64> r(e), z(e), gamma(e);
+  t.challenge_scalars(r.data(), e, p);
+  if ((rc = ms_mix_air_ext(ctx, r.data(), prog))) return rc;
+  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;
+  if ((rc = ms_validity_commit(ctx, sh.m, root))) return rc;
+  t.add_bytes(root, 32);
+  draw_z(t, z.data(), e, p);
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  std::vector<u64> evals(sh.ne * e);
+  if ((rc = ms_deep_evals(ctx, &deep, evals.data()))) return rc;
+  t.add_scalars(evals.data(), evals.size());
+  t.challenge_scalars(gamma.data(), e, p);
+  if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
+  if ((rc = ms_fri_begin(ctx, sh.blowup, sh.R, root))) return rc;
+  t.add_bytes(root, 32);
+  std::vector<u64> zq(e), B(2 * e), alpha(e);
+  for (u32 i = 1; i < sh.R; i++) {
+    t.challenge_scalars(zq.data(), e, p);
+    if ((rc = ms_fri_deep(ctx, zq.data(), B.data()))) return rc;
+    t.add_scalars(B.data(), 2 * e);
+    t.challenge_scalars(alpha.data(), e, p);
+    if ((rc = ms_fri_fold_commit(ctx, alpha.data(), root))) return rc;
+    t.add_bytes(root, 32);
+  }
+  if (sh.gb) {
+    u8 seed[32]; t.challenge_bytes(seed, 32);
+    u64 nonce = 0;
+    if (!ms_grind) return MS_ERR_ARG;
+    if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
+    u8 le[8]; for (int k = 0; k < 8; k++) le[k] = (u8)(nonce >> (8 * k));
+    t.add_bytes(le, 8);
+  }
+  std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
+  std::vector<u64> betas(sh.nq);
+  memcpy(betas.data(), raw.data(), raw.size());
+  size_t lq = 0;
+  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
+  const size_t la = t.prover_bytes.size();
+  if (la != arthur_len_aux(sh, e)) return MS_ERR_STATE;
+  std::vector<u8> out(MSLP2_HEAD + la + lq);
+  const u32 h32[12] = {MSLP_MAGIC, 2, (u32)e, (u32)w, c1, sh.m, sh.npts, sh.R, sh.nq, sh.gb, nargs, nch};
+  const u64 h64[4] = {sh.N, sh.blowup, (u64)la, (u64)lq};
+  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
+  memcpy(out.data() + MSLP2_HEAD, t.prover_bytes.data(), la);
+  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, out.data() + MSLP2_HEAD + la, lq, &lq))) return rc;
+  s.linked.swap(out);
+  return MS_OK;
+}
+
+// the v2 verifier: as verify_linked, with the challenge draw behind the stage-0 root, the combined program rebuilt from it, and two LDE trees in the link
+template <class F, int E> static int verify_linked_aux(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, u32 fri_rounds,
+                                                       const u8* data, size_t len, int zae, std::string* why) {
+  typedef Verifier<F, E> V;
+  const u64 p = c.p;
+  LinkedShape sh;
+  const int air_bytes = c.e != E ? MS_ERR_ARG : linked_shape_aux<F>(c, air, args, nargs, nch, N, w, fri_rounds, &sh);
+  if (air_bytes < 0) { *why = "malformed arguments: the AIR program, the arguments, N, w, the rounds or the configuration"; return MS_ERR_ARG; }
+  const u32 c0 = (u32)w, c1 = nargs * (u32)E;
+  // ---- header, first part: what the statement fixes without the challenges
+  if (len < MSLP2_HEAD) { *why = "header: the proof is shorter than the MSLP v2 header"; return 0; }
+  u32 h32[12]; u64 h64[4];
+  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
+  if (h32[0] != MSLP_MAGIC) { *why = "header: magic is not the verifier's"; return 0; }
+  if (h32[1] != 2) { *why = "header: version is not 2"; return 0; }
+  const u32 want32[12] = {MSLP_MAGIC, 2, (u32)E, c0, c1, 0, 0, sh.R, sh.nq, sh.gb, nargs, nch};
+  static const char* const name32[12] = {"magic", "version", "E", "c0", "c1", "m", "npts", "R", "nq", "grinding bits", "nargs", "nch"};
+  for (int k = 2; k < 12; k++) if (k != 5 && k != 6 && h32[k] != want32[k]) { *why = std::string("header: ") + name32[k] + " is not the verifier's"; return 0; }
+  if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
+  if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
+  if (h64[2] > len - MSLP2_HEAD || h64[3] != (u64)(len - MSLP2_HEAD) - h64[2]) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
+  const size_t la = (size_t)h64[2], lq = len - MSLP2_HEAD - la;
+  if (la < 64) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
+  // ---- transcript up to the challenges of the arguments; then the combined program and the rest of the header
+  Arthur a(c.domsep, c.digest, data + MSLP2_HEAD, la);
+  a.t = linked_transcript_aux(c, sh, (size_t)air_bytes);
+  u8 troot[32], lroot[32], sroot[32], vroot[32];
+  const char* cut = "transcript: arthur ends early";
+  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
+  const u64 shift = draw_shift<F>(a.t, sh.L);
+  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
+  std::vector<u64> ch((size_t)nch * E);
+  a.t.challenge_scalars(ch.data(), ch.size(), p);
+  AirProg pg; std::vector<AuxInstance> inst;
+  if (linked_combined<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh)) { *why = "malformed arguments: the combined program exceeds ms_mix_air's limits"; return MS_ERR_ARG; }
+  const ms_air* prog = pg.view();
+  if (h32[5] != sh.m) { *why = "header: m is not the verifier's"; return 0; }
+  if (h32[6] != sh.npts) { *why = "header: npts is not the verifier's"; return 0; }
+  if (la != arthur_len_aux(sh, E)) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
+  std::vector<u64> q((lq + 7) / 8 + 5, 0);            // the MSLS blob, aligned for the section verifiers
+  memcpy(q.data(), data + MSLP2_HEAD + la, lq);
+  if (lq < 40 || q[0] != 0x534C534DULL) { *why = "header: no MSLS blob behind arthur"; return 0; }
+  const u64 l_msfi = q[1], l_lde = q[2], l_stg = q[3], l_val = q[4];
+  if (l_msfi > lq - 40 || l_lde > lq - 40 - l_msfi || l_stg > lq - 40 - l_msfi - l_lde || l_val != lq - 40 - l_msfi - l_lde - l_stg) { *why = "header: the MSLS section lengths do not fit the blob exactly"; return 0; }
+  if ((l_msfi | l_lde | l_stg | l_val) & 7) { *why = "header: an MSLS section length is no multiple of 8"; return 0; }
+  const u8* msfi = (const u8*)q.data() + 40; const u8* lde_open = msfi + l_msfi; const u8* stg_open = lde_open + l_lde; const u8* val_open = stg_open + l_stg;
+  std::vector<u8> roots((size_t)sh.R * 32);
+  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), zs((size_t)(sh.R - 1) * E), Bs((size_t)(sh.R - 1) * 2 * E), alphas((size_t)(sh.R - 1) * E), betas(sh.nq);
+  if (!a.next_bytes(sroot, 32)) { *why = cut; return 0; }
+  a.t.challenge_scalars(r.data(), E, p);
+  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
+  draw_z(a.t, z.data(), E, p);
+  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
+  if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
+  a.t.challenge_scalars(gamma.data(), E, p);
+  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
+  for (u32 i = 1; i < sh.R; i++) {
+    a.t.challenge_scalars(zs.data() + (size_t)(i - 1) * E, E, p);
+    if (!a.next_scalars(Bs.data() + (size_t)(i - 1) * 2 * E, 2 * E)) { *why = cut; return 0; }
+    a.t.challenge_scalars(alphas.data() + (size_t)(i - 1) * E, E, p);
+    if (!a.next_bytes(roots.data() + (size_t)i * 32, 32)) { *why = cut; return 0; }
+  }
+  if (!V::canon(Bs.data(), Bs.size())) { *why = "transcript: a round's B is not canonical"; return 0; }
+  u8 seed[32] = {0}; u64 nonce = 0;
+  if (sh.gb) {
+    a.t.challenge_bytes(seed, 32);
+    u8 le[8];
+    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
+    for (int k = 0; k < 8; k++) nonce |= (u64)le[k] << (8 * k);
+  }
+  if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
+  { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
+  // ---- 1. the proof of work
+  if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
+  // ---- 2. the AIR identity at z, on the combined program
+  {
+    std::vector<u64> opened((size_t)sh.npts * sh.c * E);
+    for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
+    u64 want[E], got[E];
+    const int rc = air_expected<F, E>(r.data(), *prog, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
+    if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
+    validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
+    if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
+  }
+  // ---- 3. FRI on the MSFI section
+  std::string sub;
+  int rc = fri_index_verify<F, E>(c.digest, zae, sh.blowup, roots.data(), sh.R, zs.data(), Bs.data(), alphas.data(), betas.data(), sh.nq, msfi, l_msfi, &sub);
+  if (rc != 1) { *why = "FRI: " + sub; return rc; }
+  // ---- 4. round 0 against the three trees
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, c0, c1, sh.m, lroot, sroot, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
+                              stg_open, l_stg, val_open, l_val, &sub);
   if (rc != 1) { *why = sub; return rc; }
   return 1;
 }
@@ -1464,8 +1842,8 @@ int msh_deep_link_verify(int digest_id, int field, int zero_display_empty, u64 N
   try {
     std::string w;
     const int rc = field == MS_FIELD_GOLDILOCKS
-      ? deep_link_verify<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, val_open, val_len, &w)
-      : deep_link_verify<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, val_open, val_len, &w);
+      ? deep_link_verify<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, c, 0, m, lde_root, nullptr, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, nullptr, 0, val_open, val_len, &w)
+      : deep_link_verify<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, c, 0, m, lde_root, nullptr, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, nullptr, 0, val_open, val_len, &w);
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }
@@ -1484,6 +1862,66 @@ int msh_stark_verify_linked(const msh_stark* h, const ms_air* air, size_t N, siz
     const StarkConfig& c = h->s.cfg;
     const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked<GL, 2>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg)
                                                   : verify_linked<BB, 4>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg);
+    return set_why(why, why_cap, msg.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+// ---- linked proofs with running columns (MSLP v2)
+struct msh_air_prog { AirProg p; };
+msh_air_prog* msh_air_prog_new(const ms_air* base) {
+  try { std::unique_ptr<msh_air_prog> g(new msh_air_prog()); if (!g->p.load(base)) return nullptr; return g.release(); } catch (...) { return nullptr; }
+}
+void msh_air_prog_free(msh_air_prog* g) { delete g; }
+const ms_air* msh_air_prog_air(msh_air_prog* g) { return g ? g->p.view() : nullptr; }
+int msh_aux_constraints(msh_air_prog* g, int field, const ms_aux* aux, uint32_t first_poly) {
+  if (!g || !aux || !aux->form_begin || !aux->form_const || (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR)) return MS_ERR_ARG;
+  try {
+    AirProg work = g->p;   // (a refused expansion leaves the program as it was)
+    const int rc = field == MS_FIELD_GOLDILOCKS ? aux_constraints<GL, 2>(work, *aux, first_poly) : aux_constraints<BB, 4>(work, *aux, first_poly);
+    if (!rc) g->p = std::move(work);
+    return rc;
+  } catch (...) { return MS_ERR_NOMEM; }
+}
+size_t msh_aux_encode(int field, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, u8* out, size_t cap) {
+  if (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR) return 0;
+  try {
+    std::vector<u8> enc;
+    const bool gl = field == MS_FIELD_GOLDILOCKS;
+    return aux_encode(args, nargs, nch, gl ? (u64)GL::P : (u64)BB::P, gl ? 2 : 4, 0, &enc) ? copy_out(enc.data(), enc.size(), out, cap) : 0;
+  } catch (...) { return 0; }
+}
+int msh_deep_link_verify_staged(int digest_id, int field, int zero_display_empty, u64 N, u64 blowup, u64 shift, uint32_t c0, uint32_t c1, uint32_t m, const u8 lde_root[32],
+                                const u8 stg_root[32], const u8 val_root[32], const ms_deep* deep, const u64* evals, const u64* gamma, const u64* betas, size_t nq,
+                                const u8* msfi, size_t msfi_len, const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open, size_t val_len,
+                                char* why, size_t why_cap) {
+  if (!known_digest(digest_id) || (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR)) return set_why(why, why_cap, "unknown digest or field", MS_ERR_ARG);
+  if (!lde_root || !stg_root || !val_root || !deep || !deep->z || !deep->pt_begin || !deep->pt_poly || !evals || !gamma || !betas || !msfi || !lde_open || !stg_open || !val_open ||
+      nq < 1 || nq > 4096 || !N || (N & (N - 1)) || !blowup || (blowup & (blowup - 1)) || N > ((u64)1 << 32) || blowup > ((u64)1 << 16) || c0 < 1 || c1 < 1 || m < 1 ||
+      c0 > (1u << 24) || c1 > (1u << 24) || m > (1u << 24))
+    return set_why(why, why_cap, "null argument, or N, blowup, c0, c1, m or queries out of range", MS_ERR_ARG);
+  try {
+    std::string w;
+    const int rc = field == MS_FIELD_GOLDILOCKS
+      ? deep_link_verify<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, stg_open, stg_len, val_open, val_len, &w)
+      : deep_link_verify<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msfi, msfi_len, lde_open, lde_len, stg_open, stg_len, val_open, val_len, &w);
+    return set_why(why, why_cap, w.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+int msh_stark_prove_linked_aux(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
+                               uint32_t nch, uint32_t fri_rounds) {
+  if (!h) return MS_ERR_ARG;
+  try {
+    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked_aux<GL, 2>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, fri_rounds)
+                                                 : prove_linked_aux<BB, 4>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, fri_rounds);
+  } catch (...) { h->s.linked.clear(); return MS_ERR_NOMEM; }
+}
+int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, uint32_t fri_rounds,
+                                const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
+  if (!h || !data || !air || !args) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
+  try {
+    std::string msg;
+    const StarkConfig& c = h->s.cfg;
+    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked_aux<GL, 2>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg)
+                                                  : verify_linked_aux<BB, 4>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg);
     return set_why(why, why_cap, msg.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }

@@ -22,6 +22,7 @@ from typing import List
 
 import numpy as np
 
+from ._native import AUX_PRODUCT, aux_constraints, aux_fractions, encode_aux, instantiate_aux
 from ._native import Context, MsError, AIR_ARRAYS, air_rows, flatten_air, GOLDILOCKS, BABYBEAR, ERR_SHAPE, ERR_ARG, DIGEST_SHA256, DIGEST_BLAKE2S256, DIGEST_BLAKE3, DIGEST_KECCAK256, DIGEST_SHA3_256
 
 _MODULUS = {GOLDILOCKS: 2**64 - 2**32 + 1, BABYBEAR: 2013265921}
@@ -219,6 +220,43 @@ class LinkedProof:
         return LinkedProof(e, c, m, npts, rounds, nq, gb, N, blowup, bytes(data[hs:hs + la]), bytes(data[hs + la:]))
 
 
+@dataclass
+class LinkedProofV2:
+    """A linked proof with running columns, MSLP v2 (include/ministark_host.h): the header's counts, the transcript bytes and the MSLS blob of Context.query_linked."""
+    e: int
+    c0: int
+    c1: int
+    m: int
+    npts: int
+    rounds: int
+    nq: int
+    grinding_bits: int
+    nargs: int
+    nch: int
+    N: int
+    blowup: int
+    arthur: bytes
+    msls: bytes
+
+    _HEAD = "<4s11I4Q"
+
+    def to_bytes(self) -> bytes:
+        return struct.pack(self._HEAD, b"MSLP", 2, self.e, self.c0, self.c1, self.m, self.npts, self.rounds, self.nq, self.grinding_bits, self.nargs, self.nch, self.N,
+                           self.blowup, len(self.arthur), len(self.msls)) + self.arthur + self.msls
+
+
+def unflatten_air(air):
+    """(constraints, exempt, periodic, boundary) as lists from a flatten_air dict"""
+    tb, fb, eb = [int(x) for x in air["term_begin"]], [int(x) for x in air["fac_begin"]], [int(x) for x in air["ex_begin"]]
+    cons = [[(int(air["coef"][m]), [(int(air["fac_poly"][f]), int(air["fac_row"][f])) for f in range(fb[m], fb[m + 1])]) for m in range(tb[t], tb[t + 1])]
+            for t in range(int(air["ncons"]))]
+    exempt = [[int(air["ex_row"][k]) for k in range(eb[t], eb[t + 1])] for t in range(int(air["ncons"]))]
+    pb = [int(x) for x in air["per_begin"]] if int(air["nperiodic"]) else [0]
+    periodic = [[int(air["per_val"][k]) for k in range(pb[q], pb[q + 1])] for q in range(int(air["nperiodic"]))]
+    boundary = [(int(air["bnd_poly"][b]), int(air["bnd_row"][b]), int(air["bnd_val"][b])) for b in range(int(air["nbound"]))]
+    return cons, exempt, periodic, boundary
+
+
 class StarkConfig:
     """src/starks.rs:238-333."""
 
@@ -309,10 +347,14 @@ class Stark:
 
 
     # ---- linked proofs (build-defined; MSLP v1, transcript order and redraw rules: include/ministark_host.h) -----------------------
-    def prove_air(self, trace, air, fri_rounds: int = 0) -> LinkedProof:
+    def prove_air(self, trace, air, fri_rounds: int = 0, aux=None, forced_challenges=None):
         """msh_stark_prove_linked driven from Python: the same stages, the same transcript, the same bytes.  trace: the N x w matrix; air: a flatten_air dict or the
         tuple (constraints, exempt, periodic, boundary).  The statement: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air`.
-        Raises MsError(ERR_SHAPE) for a trace that violates the program."""
+        Raises MsError(ERR_SHAPE) for a trace that violates the program.
+        aux = (args, nch): a proof with running columns, MSLP v2 (msh_stark_prove_linked_aux) - args flatten_aux_arg dicts whose selectors name nch challenges;
+        returns a LinkedProofV2.  forced_challenges (tests only): the columns are built from these instead of the transcript's."""
+        if aux is not None:
+            return self._prove_air_aux(trace, air, fri_rounds, aux[0], aux[1], forced_challenges)
         cfg, ctx = self.cfg, self.cfg.ctx
         p, e = _MODULUS[ctx.field], ctx.e
         if not isinstance(air, dict):
@@ -376,13 +418,100 @@ class Stark:
         self.last_challenges = dict(shift=shift, r=r, z=z, gamma=gamma, betas=betas)
         return LinkedProof(e, w, m, len(rows), R, nq, gb, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
 
-    def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True) -> bool:
+    def _prove_air_aux(self, trace, air, fri_rounds, args, nch, forced_challenges=None):
+        cfg, ctx = self.cfg, self.cfg.ctx
+        field, p, e = ctx.field, _MODULUS[ctx.field], ctx.e
+        if not isinstance(air, dict):
+            air = flatten_air(*air)
+        data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
+        N, w = data.shape
+        blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
+        R, nq, gb = fri_rounds or cfg.rounds, cfg.fri_queries, cfg.grinding_bits
+        t = Transcript(cfg.domsep + "/linked/v2", ctx.digest)
+        t.add_bytes(struct.pack("<10Q", field, ctx.digest, N, w, blowup, R, nq, gb, len(args), nch))
+        t.add_bytes(encode_air(air))
+        t.add_bytes(encode_aux(args, nch))
+        t.prover_bytes = bytearray()
+        rc, root = ctx.trace_commit(data, w)
+        ctx.check(rc)
+        t.add_bytes(root)
+        (shift,) = t.challenge_scalars(1, p)
+        while shift == 0 or pow(shift, L, p) == 1:
+            (shift,) = t.challenge_scalars(1, p)
+        ctx.check(ctx.interpolate())
+        rc, root = ctx.lde_commit(blowup, shift, w)
+        ctx.check(rc)
+        t.add_bytes(root)
+        flat = t.challenge_scalars(nch * e, p)                    # the arguments' challenges follow the commitment to the main columns
+        ch = [tuple(int(v) for v in flat[k * e:(k + 1) * e]) for k in range(nch)]
+        used = ch if forced_challenges is None else [tuple(c) for c in forced_challenges]
+        cons, exempt, periodic, boundary = unflatten_air(air)
+        for k, arg in enumerate(args):
+            inst = instantiate_aux(field, arg, used)              # (forced challenges: column AND constraints are the forger's, so the mix stage accepts them)
+            rc, final, _ = ctx.aux_running_staged(inst["op"], inst, e)
+            ctx.check(rc)                                         # ERR_SHAPE: a zero denominator
+            if tuple(final) != ((1 if inst["op"] == AUX_PRODUCT else 0),) + (0,) * (e - 1):
+                raise MsError(ERR_SHAPE, "prove_air: an argument does not hold (final is not the identity)")
+            c2, e2, b2 = aux_constraints(field, inst["op"], aux_fractions(inst), e, w + k * e)
+            cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
+        c1 = len(args) * e
+        c = w + c1
+        rc, root = ctx.lde_commit_stage(c1)
+        ctx.check(rc)
+        t.add_bytes(root)
+        prog = flatten_air(cons, exempt, periodic, boundary)
+        r = t.challenge_scalars(e, p)
+        ctx.check(ctx.mix_air_ext(r, prog))
+        m = e * ctx.validity_len() // N
+        rc, root = ctx.validity_commit(m)
+        ctx.check(rc)
+        t.add_bytes(root)
+        z = t.challenge_scalars(e, p)
+        while not any(z[1:]):
+            z = t.challenge_scalars(e, p)
+        rows = sorted({0} | {int(x) for x in np.asarray(prog["fac_row"]).reshape(-1)})
+        if len(rows) > 8:
+            raise MsError(ERR_ARG, "prove_air: the program touches more than 8 row offsets")
+        omega = ctx.root_of_unity(N)
+        pts = [[v * pow(omega, row, p) % p for v in z] for row in rows]
+        lists = [list(range(c)) + (list(range(c, c + m)) if k == 0 else []) for k in range(len(rows))]
+        rc, ev = ctx.deep_evals(pts, lists)
+        ctx.check(rc)
+        t.add_scalars(ev.reshape(-1))
+        gamma = t.challenge_scalars(e, p)
+        ctx.check(ctx.deep_compose(pts, lists, gamma))
+        rc, root = ctx.fri_begin(blowup, R)
+        ctx.check(rc)
+        t.add_bytes(root)
+        for _ in range(1, R):
+            zq = t.challenge_scalars(e, p)
+            rc, B = ctx.fri_deep(zq)
+            ctx.check(rc)
+            t.add_scalars(B)
+            alpha = t.challenge_scalars(e, p)
+            rc, root = ctx.fri_fold_commit(alpha)
+            ctx.check(rc)
+            t.add_bytes(root)
+        if gb:
+            rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
+            ctx.check(rc)
+            t.add_bytes(struct.pack("<Q", nonce))
+        raw = t.challenge_bytes(8 * nq)
+        betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
+        self.last_challenges = dict(shift=shift, ch=ch, r=r, z=z, gamma=gamma, betas=betas)
+        return LinkedProofV2(e, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
+
+    def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True, aux=None) -> bool:
         """msh_stark_verify_linked on MSLP bytes (or a LinkedProof) under this configuration.  True / False, the reason of a rejection - naming the step - in
         `self.last_verify_error`; raises MsError on malformed arguments."""
         from .host import HostStark   # (host.py imports this module)
         cfg = self.cfg
         hs = HostStark(cfg.ctx, cfg.security_bits, cfg.blowup_factor, cfg.steps, cfg.trace_columns, cfg.grinding_bits)
-        rc, self.last_verify_error = hs.verify_linked(data.to_bytes() if isinstance(data, LinkedProof) else data, air, N, w, fri_rounds, zero_display_empty)
+        data = data if isinstance(data, (bytes, bytearray)) else data.to_bytes()
+        if aux is not None:
+            rc, self.last_verify_error = hs.verify_linked_aux(data, air, aux[0], aux[1], N, w, fri_rounds, zero_display_empty)
+        else:
+            rc, self.last_verify_error = hs.verify_linked(data, air, N, w, fri_rounds, zero_display_empty)
         if rc < 0:
             raise MsError(rc, self.last_verify_error)
         return rc == 1

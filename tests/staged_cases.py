@@ -1,0 +1,570 @@
+"""Cases of the staged LDE commitment (ms_aux_running_staged, ms_lde_commit_stage, MS_TREE_LDE_STAGED and the MSLS layout of ms_query_linked; include/ministark.h -
+build-defined, no reference counterpart), shared by the emulation suite (tests/test_staged_emu.py) and the GPU suite (tests/test_staged_gpu.py).  The oracle of the
+columns is ms_aux_running itself: context A builds the running columns EARLY (ms_aux_running before ms_interpolate, one ms_lde_commit over all columns), context B
+builds them STAGED (ms_lde_commit over the trace columns, ms_aux_running_staged, ms_lde_commit_stage), and everything both can be asked for must be equal.  The oracle
+of the openings is the definition (tests/pyref_staged.py restates the MSLS layout).  Every comparison is exact.
+`make(field, flags, env=None)` returns a fresh mini_stark_amd.Context created with `flags` while the variables of `env` are set; `d` is the ms_digest_id."""
+import ctypes as C
+
+import numpy as np
+
+import mini_stark_amd as ms
+import aux_cases as ac
+import deep_cases as dc
+import linked_cases as lc
+import open_cases as oc
+import pyref_staged as rs
+from common import MODULUS, EXT, SplitMix64
+
+SHA, KECCAK = dc.SHA, dc.ro.KECCAK256
+ctx_of = oc.ctx_of
+SUM, PRODUCT = ms.AUX_SUM, ms.AUX_PRODUCT
+MIX_REFUSAL = "uncommitted staged columns"
+
+
+# ---------------------------------------------------------------- traces and arguments.  Columns 0 and 1 are Fibonacci columns (deep_cases.fib_spec: the main program)
+def fib_columns(field, N, seed):
+    trace, cons, exempt, _periodic, boundary = dc.fib_spec(field, N, seed=seed)
+    return [[int(v) for v in row] for row in trace], (cons, exempt, boundary)
+
+
+def k_of(field, b):
+    return (b,) + (0,) * (EXT[field] - 1)
+
+
+def permutation_case(field, N, seed, spoil=False):
+    """columns 2, 3 and 4, 5: the rows of (4, 5) are a permutation of the rows of (2, 3); PRODUCT of (ch0 + T2 + ch1 T3) / (ch0 + T4 + ch1 T5), ch in K"""
+    p, rng = MODULUS[field], SplitMix64(seed)
+    fib, main = fib_columns(field, N, seed)
+    pairs = [(rng.field(p), rng.field(p)) for _ in range(N)]
+    perm = list(pairs)
+    for i in range(N - 1, 0, -1):
+        j = rng.next() % (i + 1)
+        perm[i], perm[j] = perm[j], perm[i]
+    if spoil:
+        perm[N // 2] = ((perm[N // 2][0] + 1) % p, perm[N // 2][1])
+    rows = [f + list(a) + list(b) for f, a, b in zip(fib, pairs, perm)]
+    ch0, ch1, one = dc.full_ext(rng, field), dc.full_ext(rng, field), k_of(field, 1)
+    return rows, main, PRODUCT, [((ch0, [(2, one), (3, ch1)]), (ch0, [(4, one), (5, ch1)]))]
+
+
+def logup_case(field, N, seed):
+    """columns f = 2 (looked up), t = 3 (the table, distinct values), m = 4 (multiplicities): SUM of 1 / (ch0 + f) and (p - 1) m / (ch0 + t)"""
+    p, rng = MODULUS[field], SplitMix64(seed)
+    fib, main = fib_columns(field, N, seed)
+    t = []
+    while len(t) < N:
+        v = rng.field(p)
+        if v not in t:
+            t.append(v)
+    f = [t[rng.next() % min(N, 8)] if i % 3 else t[rng.next() % N] for i in range(N)]
+    m = [f.count(v) for v in t]
+    rows = [fb + [x, y, z] for fb, x, y, z in zip(fib, f, t, m)]
+    ch0, one = dc.full_ext(rng, field), k_of(field, 1)
+    return rows, main, SUM, [((one, []), (ch0, [(2, one)])), ((k_of(field, 0), [(4, k_of(field, p - 1))]), (ch0, [(3, one)]))]
+
+
+def last_column_form(field, w, seed):
+    """a form that names only column w - 1: a single-column run is transformed, and its slot is 0, not w - 1"""
+    rng = SplitMix64(seed)
+    return SUM, [((k_of(field, 1), []), (dc.full_ext(rng, field), [(w - 1, dc.full_ext(rng, field))]))]
+
+
+CASES = {"permutation": permutation_case, "logup": logup_case}
+
+
+def commit_trace(ctx, rows):
+    return ac.commit_trace(ctx, rows)
+
+
+def early(ctx, rows, args, blowup, shift):
+    """context A: ms_aux_running for every argument, ms_interpolate, ONE ms_lde_commit over all columns -> ([(final, column)], root)"""
+    commit_trace(ctx, rows)
+    out = []
+    for op, fr in args:
+        rc, final, col = ctx.aux_running(op, fr, ctx.e, read=True)
+        assert rc == 0, ctx.last_error()
+        out.append((final, col.tolist()))
+    assert ctx.interpolate() == 0
+    c = ctx.polys_count()
+    rc, root = ctx.lde_commit(blowup, shift, c)
+    assert rc == 0, ctx.last_error()
+    return out, root
+
+
+def main_commit(ctx, rows, blowup, shift):
+    """ms_trace_commit, ms_interpolate, ms_lde_commit over the w trace columns -> the stage-0 root"""
+    t = commit_trace(ctx, rows)
+    assert ctx.interpolate() == 0
+    rc, root = ctx.lde_commit(blowup, shift, t.shape[1])
+    assert rc == 0, ctx.last_error()
+    return root
+
+
+def staged(ctx, rows, args, blowup, shift, commit=True):
+    """context B -> ([(final, column)], stage-0 root, staged root)"""
+    root0 = main_commit(ctx, rows, blowup, shift)
+    out, n = [], 0
+    for op, fr in args:
+        assert ctx.aux_staged_count() == n
+        rc, final, col = ctx.aux_running_staged(op, fr, ctx.e, read=True)
+        assert rc == 0, ctx.last_error()
+        out.append((final, col.tolist()))
+        n += ctx.e
+    assert ctx.aux_staged_count() == n and ctx.polys_count() == len(rows[0]) + n
+    if not commit:
+        return out, root0, None
+    rc, root1 = ctx.lde_commit_stage(n)
+    assert rc == 0, ctx.last_error()
+    assert ctx.aux_staged_count() == 0 and ctx.polys_count() == len(rows[0]) + n
+    return out, root0, root1
+
+
+def combined_air(field, N, w, main, args, finals):
+    """the main program plus aux_constraints of every argument, argument k over the polynomials w + k E ..; row N - 1 exempt where `final` is not the identity"""
+    e = EXT[field]
+    cons, exempt, boundary = [list(x) for x in main]
+    for k, ((op, fr), final) in enumerate(zip(args, finals)):
+        ident = tuple(k_of(field, 1 if op == PRODUCT else 0))
+        c2, e2, b2 = ms.aux_constraints(field, op, fr, e, w + k * e, exempt_last=tuple(final) != ident, N=N)
+        cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
+    return cons, exempt, (), boundary
+
+
+def linked_state(ctx, field, N, blowup, c, air, R, seed):
+    """ms_mix_air_ext .. the FRI commit phase on a context whose LDE holds c columns -> a dict with what was read on the way"""
+    e = EXT[field]
+    rng = SplitMix64(seed)
+    cons, exempt, periodic, boundary = air
+    P = dict(r=dc.full_ext(rng, field))
+    assert ctx.mix_air_ext(P["r"], cons, exempt, periodic, boundary) == 0, ctx.last_error()
+    P["validity"] = ctx.validity_read().tolist()
+    P["m"] = m = e * dc.vl_of(ctx) // N
+    rc, P["vroot"] = ctx.validity_commit(m)
+    assert rc == 0, ctx.last_error()
+    rows = ms.air_rows(cons, boundary)
+    zs = dc.shifted_points(field, dc.full_ext(rng, field), ctx.root_of_unity(N), rows)
+    lists = [list(range(c)) + (list(range(c, c + m)) if k == 0 else []) for k in range(len(rows))]
+    assert ctx.deep_compose(zs, lists, dc.full_ext(rng, field)) == 0, ctx.last_error()
+    P["S"] = oc.commit_phase(ctx, field, blowup, R, seed=seed + 1)
+    P["D0"] = P["S"]["D0"]
+    return P
+
+
+# ---------------------------------------------------------------- 1. the column is ms_aux_running's
+def case_columns(make, d, field, which, N, blowup=4, env=None, two=False, last_only=False, R=2):
+    p, e = MODULUS[field], EXT[field]
+    rows, main, op, fr = CASES[which](field, N, 700 + N + field)
+    w = len(rows[0])
+    args = [(op, fr)]
+    if two:
+        args.append(last_column_form(field, w, 900 + field))
+    if last_only:
+        args = [last_column_form(field, w, 900 + field)]
+    shift = SplitMix64(800 + N).nonzero(p)
+    A, B, plain = ctx_of(make, d, field, env=env), ctx_of(make, d, field, env=env), ctx_of(make, d, field, env=env)
+    got_a, root_a = early(A, rows, args, blowup, shift)
+    got_b, root0, root1 = staged(B, rows, args, blowup, shift)
+    assert got_a == got_b                                                            # final_out and column_out
+    c1 = e * len(args)
+    c = w + c1
+    assert A.polys_count() == B.polys_count() == c
+    for j in range(c):
+        assert A.poly_read(j).tolist() == B.poly_read(j).tolist(), j
+    lde_a, lde_b = A.lde_read(), B.lde_read()
+    assert lde_a.shape == lde_b.shape == (N * blowup, c) and np.array_equal(lde_a, lde_b)
+    assert root0 == main_commit(plain, rows, blowup, shift)                          # the stage-0 root is the root of a context that never staged anything
+    nodes = dc.ro.tree_nodes(d, np.ascontiguousarray(lde_b[:, w:]).reshape(-1, 1), 1, c1)
+    assert bytes(nodes[-1]) == root1 and root1 != root0 != root_a
+    air = combined_air(field, N, w, main, args, [g[0] for g in got_a])
+    Pa, Pb = linked_state(A, field, N, blowup, c, air, R, 40 + N), linked_state(B, field, N, blowup, c, air, R, 40 + N)
+    assert Pa["validity"] == Pb["validity"] and any(any(v) if isinstance(v, list) else v for v in Pa["validity"])
+    assert Pa["vroot"] == Pb["vroot"] and Pa["S"]["roots"] == Pb["S"]["roots"]       # round 0's root, and the rounds behind it
+    if which in CASES and not last_only:                                             # the argument closes: final is the identity
+        assert tuple(got_a[0][0]) == tuple(k_of(field, 1 if op == PRODUCT else 0))
+    return B, Pb, dict(rows=rows, w=w, c1=c1, lde=lde_b, root0=root0, root1=root1, nodes=nodes, L=N * blowup)
+
+
+# ---------------------------------------------------------------- 2. openings
+def by_definition(ctx, betas, D0, L):
+    rows = lc.rl.link_rows(betas, D0, L)
+    return rs.msls(ctx.fri_query_index(betas), ctx.tree_open(ms.TREE_LDE, rows), ctx.tree_open(ms.TREE_LDE_STAGED, rows), ctx.tree_open(ms.TREE_VALIDITY, rows))
+
+
+def case_openings(make, d, field, which, R, N=8, blowup=4):
+    p = MODULUS[field]
+    rows, main, op, fr = CASES[which](field, N, 1200 + field)
+    w = len(rows[0])
+    shift = SplitMix64(1300).nonzero(p)
+    plain = ctx_of(make, d, field)
+    main_commit(plain, rows, blowup, shift)
+    L = N * blowup
+    lists = oc.index_lists(L)
+    before = [plain.tree_open(ms.TREE_LDE, ix) for ix in lists]
+    B = ctx_of(make, d, field)
+    got, root0, root1 = staged(B, rows, [(op, fr)], blowup, shift, commit=False)
+    assert [B.tree_open(ms.TREE_LDE, ix) for ix in lists] == before                  # columns pending: the LDE tree opens what it opened
+    assert oc.raw_open(B, ms.TREE_LDE_STAGED, 0, [0], 1, None, 0)[0] == ms.ERR_STATE  # no staged tree yet
+    c1 = B.e
+    rc, root1 = B.lde_commit_stage(c1)
+    assert rc == 0, B.last_error()
+    assert [B.tree_open(ms.TREE_LDE, ix) for ix in lists] == before                  # ... and behind the stage's commitment: rows of c0 elements, the stage-0 root
+    lde = B.lde_read()
+    values = np.ascontiguousarray(lde[:, w:]).reshape(-1, 1)
+    nodes = dc.ro.tree_nodes(d, values, 1, c1)
+    for ix in lists:
+        oc.check_paths(B, d, field, B.tree_open(ms.TREE_LDE_STAGED, ix), values, 1, c1, nodes, root1, ix)
+    nodes0 = dc.ro.tree_nodes(d, np.ascontiguousarray(lde[:, :w]).reshape(-1, 1), 1, w)
+    oc.check_paths(B, d, field, B.tree_open(ms.TREE_LDE, lists[-1]), np.ascontiguousarray(lde[:, :w]).reshape(-1, 1), 1, w, nodes0, root0, lists[-1])
+    assert oc.raw_open(B, 3, 0, [0], 1, None, 0)[0] == ms.ERR_ARG                     # id 3 stays refused
+    assert oc.raw_open(B, ms.TREE_LDE_STAGED, 0, [L], 1, (C.c_uint8 * 4096)(), 4096)[0] == ms.ERR_OUT_OF_RANGE
+    air = combined_air(field, N, w, main, [(op, fr)], [got[0][0]])
+    P = linked_state(B, field, N, blowup, w + c1, air, R, 60 + R)
+    D0 = P["D0"]
+    for betas in lc.beta_sets(D0):
+        want = by_definition(B, betas, D0, L)
+        blob = B.query_linked(betas)
+        assert blob == want
+        sec = rs.split_msls(blob)
+        assert sec is not None and len(sec[2]) == 2 * len(betas) * dc.ro.path_size(1, c1, L) and len(sec[1]) == 2 * len(betas) * dc.ro.path_size(1, w, L)
+        assert lc.rl.split_mslq(blob) is None                                        # not an MSLQ blob
+    betas = lc.beta_sets(D0)[1]
+    blob, prof = oc.profile(B, lambda: B.query_linked(betas))
+    launches = {k: v["launches"] for k, v in prof.items() if isinstance(v, dict) and v.get("launches")}
+    assert launches == {"merkle_path": 1}, launches
+    assert blob == by_definition(B, betas, D0, L)
+    # the size query and the cap rule, as without a staged tree
+    size = len(blob)
+    assert lc.raw_linked(B, betas, len(betas), None, 0) == (0, size)
+    buf = (C.c_uint8 * size)()
+    assert lc.raw_linked(B, betas, len(betas), buf, size - 1) == (ms.ERR_ARG, size)
+    assert lc.raw_linked(B, betas, len(betas), buf, size) == (0, size) and bytes(buf) == blob
+    # a staged tree that does not hold one row per leaf group
+    Cx = ctx_of(make, d, field)
+    staged(Cx, rows, [(op, fr)], blowup, shift, commit=False)
+    assert Cx.lde_commit_stage(2 * c1)[0] == 0
+    linked_state(Cx, field, N, blowup, w + c1, air, R, 60 + R)
+    assert lc.raw_linked(Cx, betas, len(betas), None, 0)[0] == ms.ERR_STATE and "staged" in Cx.last_error()
+
+
+# ---------------------------------------------------------------- 3. states and refusals
+def raw_staged(ctx, aux, final="buf", column=None):
+    """ms_aux_running_staged through the raw ABI (as aux_cases.raw_aux)"""
+    u64p = C.POINTER(C.c_uint64)
+    fin = np.zeros(4, dtype=np.uint64)
+    fp = None if final is None else fin.ctypes.data_as(u64p)
+    if aux is None:
+        return ctx.L.ms_aux_running_staged(ctx.h, None, fp, column)
+    s, _keep = ms.aux_struct(aux)
+    return ctx.L.ms_aux_running_staged(ctx.h, C.byref(s), fp, column)
+
+
+def snapshot(ctx, c, L, rows=(0, 3)):
+    """what the entry points that stay valid return: every polynomial, the LDE matrix, rows of the LDE tree, the counts"""
+    rows = [r % L for r in rows] + [L - 1]
+    return ([ctx.poly_read(j).tolist() for j in range(c)], ctx.lde_read().tolist(), ctx.tree_open(ms.TREE_LDE, rows), ctx.polys_count(), ctx.aux_staged_count(), ctx.aux_count())
+
+
+def mix_calls(ctx, field, air):
+    """(status, error text) of every mix stage and of ms_validity_commit"""
+    p = MODULUS[field]
+    cons, exempt, periodic, boundary = air
+    r = 5
+    calls = [lambda: ctx.mix(r), lambda: ctx.mix_cubic(r, [[0, 0, 0, 0, 0]], [1]), lambda: ctx.mix_terms(r, cons, 1), lambda: ctx.mix_air(r, cons, exempt, periodic, boundary),
+             lambda: ctx.mix_air_ext(k_of(field, r), cons, exempt, periodic, boundary), lambda: ctx.validity_commit(1)[0]]
+    return [(call(), ctx.last_error()) for call in calls]
+
+
+def case_refusals(make, d, field, N=8, blowup=4):
+    p, E = MODULUS[field], EXT[field]
+    rows, main, op, fr = permutation_case(field, N, 1500 + field)
+    w, L = len(rows[0]), N * blowup
+    aux = ms.flatten_aux(op, fr, E)
+    shift = SplitMix64(1501).nonzero(p)
+    root = (C.c_uint8 * 32)()
+    fib_air = (main[0], main[1], (), main[2])
+    # no LDE: nothing committed, a trace, polynomials
+    ctx = ctx_of(make, d, field)
+    for step in (lambda: None, lambda: commit_trace(ctx, rows), ctx.interpolate):
+        step()
+        assert raw_staged(ctx, aux) == ms.ERR_STATE and ctx.lde_commit_stage(E)[0] == ms.ERR_STATE and ctx.aux_staged_count() == 0
+    assert ctx.L.ms_aux_running_staged(None, None, None, None) == ms.ERR_ARG and ctx.L.ms_lde_commit_stage(None, C.c_size_t(1), root) == ms.ERR_ARG
+    assert ctx.L.ms_aux_staged_count(None) == ms.ERR_ARG
+    # arguments, on a valid state; after each the context gives what one that never made the call gives
+    ctx, fresh = ctx_of(make, d, field), ctx_of(make, d, field)
+    main_commit(ctx, rows, blowup, shift)
+    main_commit(fresh, rows, blowup, shift)
+    want = snapshot(fresh, w, L)
+    u32 = lambda v: np.array(v, dtype=np.uint32)   # noqa: E731
+
+    def arr(name, at, value):
+        b = aux[name].copy()
+        b[at] = value
+        return {name: b}
+
+    def refused(rc, code):
+        assert rc == code, (rc, ctx.last_error())
+        assert snapshot(ctx, w, L) == want
+    refused(ctx.lde_commit_stage(E)[0], ms.ERR_STATE)                                # nothing staged
+    refused(raw_staged(ctx, None), ms.ERR_ARG)
+    refused(raw_staged(ctx, aux, final=None), ms.ERR_ARG)
+    for name, _t in ms._native.AUX_ARRAYS:
+        refused(raw_staged(ctx, dict(aux, **{name: None})), ms.ERR_ARG)
+    for over in (dict(op=2), dict(ext=3), dict(ext=0), dict(nfrac=0), arr("form_begin", 0, 1), arr("term_col", 0, w), arr("term_coef", 1, p), arr("form_const", 0, p),
+                 dict(form_begin=u32([0, 17, 17]), term_col=u32([0] * 17), term_coef=np.ones(17 * E, dtype=np.uint64))):
+        refused(raw_staged(ctx, dict(aux, **over)), ms.ERR_ARG)
+    gamma = (-rows[3][2]) % p                                                        # a zero denominator on row 3: decided on the device
+    bad = [((k_of(field, 1), []), (k_of(field, gamma), [(2, k_of(field, 1))]))]
+    refused(ctx.aux_running_staged(SUM, bad, E)[0], ms.ERR_SHAPE)
+    assert oc.raw_open(ctx, ms.TREE_LDE_STAGED, 0, [0], 1, None, 0)[0] == ms.ERR_STATE
+    # columns pending: the mix stages and ms_validity_commit refuse, the rest works
+    rc, final, col = ctx.aux_running_staged(op, fr, E, read=True)
+    assert rc == 0 and ctx.aux_staged_count() == E
+    A = ctx_of(make, d, field)
+    got_a, root_a = early(A, rows, [(op, fr)], blowup, shift)
+    assert (final, col.tolist()) == got_a[0]
+    pending = snapshot(ctx, w + E, L)
+    assert pending[:3] == ([A.poly_read(j).tolist() for j in range(w + E)], want[1], want[2])
+    for rc, why in mix_calls(ctx, field, fib_air):
+        assert rc == ms.ERR_STATE and MIX_REFUSAL in why, (rc, why)
+    assert ctx.L.ms_lde_commit_stage(ctx.h, C.c_size_t(E), None) == ms.ERR_ARG         # a null root
+    assert ctx.lde_commit_stage(3 * E + 1)[0] == A.lde_commit(blowup, shift, 3 * (w + E) + 1)[0] != 0   # lpn: refused as ms_lde_commit refuses it
+    assert snapshot(ctx, w + E, L) == pending
+    rc, report = ctx.air_check(*fib_air)
+    assert rc == 0 and report["ok"]
+    # a full ms_lde_commit with columns pending: all c0 + c1 columns in one tree, as the early order gives, and the stage is cleared
+    rc, root_all = ctx.lde_commit(blowup, shift, w + E)
+    assert rc == 0 and root_all == root_a and ctx.aux_staged_count() == 0
+    assert np.array_equal(ctx.lde_read(), A.lde_read()) and ctx.lde_commit_stage(E)[0] == ms.ERR_STATE
+    # ms_polys_lincomb with columns pending kills the LDE, as always
+    ctx = ctx_of(make, d, field)
+    staged(ctx, rows, [(op, fr)], blowup, shift, commit=False)
+    assert ctx.polys_lincomb([1, p - 1], [0, 1]) == 0
+    assert oc.raw_open(ctx, ms.TREE_LDE, 0, [0], 1, None, 0)[0] == ms.ERR_STATE and ctx.lde_commit_stage(E)[0] == ms.ERR_STATE
+    assert raw_staged(ctx, aux) == ms.ERR_STATE
+    # a second stage commit; a staged call behind the commit; a staged call behind a mix stage
+    ctx = ctx_of(make, d, field)
+    staged(ctx, rows, [(op, fr)], blowup, shift)
+    done = snapshot(ctx, w + E, L)
+    assert ctx.lde_commit_stage(E)[0] == ms.ERR_STATE and raw_staged(ctx, aux) == ms.ERR_STATE and snapshot(ctx, w + E, L) == done
+    assert ctx.polys_append([1, 2, 3]) == 0                                          # what kills the LDE tree kills the staged tree with it
+    assert oc.raw_open(ctx, ms.TREE_LDE_STAGED, 0, [0], 1, None, 0)[0] == ms.ERR_STATE
+    rc, _ = ctx.lde_commit(blowup, shift, w + E + 1)
+    assert rc == 0 and oc.raw_open(ctx, ms.TREE_LDE_STAGED, 0, [0], 1, None, 0)[0] == ms.ERR_STATE
+    ctx = ctx_of(make, d, field)
+    main_commit(ctx, rows, blowup, shift)
+    assert ctx.mix_air_ext(k_of(field, 5), *fib_air) == 0, ctx.last_error()
+    validity = ctx.validity_read().tolist()
+    assert raw_staged(ctx, aux) == ms.ERR_STATE and "mix" in ctx.last_error() and ctx.validity_read().tolist() == validity
+    # the 17th limb column, early and staged ones counted together
+    ctx = ctx_of(make, d, field)
+    commit_trace(ctx, rows)
+    assert ctx.aux_running(op, fr, E)[0] == 0
+    assert ctx.interpolate() == 0 and ctx.lde_commit(blowup, shift, w + E)[0] == 0
+    n = E
+    while n + E <= 16:
+        assert raw_staged(ctx, aux) == 0
+        n += E
+    assert raw_staged(ctx, aux) == ms.ERR_ARG and ctx.aux_staged_count() == n - E and ctx.polys_count() == w + n
+    assert ctx.lde_commit_stage(n - E)[0] == 0, ctx.last_error()
+
+
+def case_sharded(ctx, field=0):
+    """a context with sharding on (a one-rank world, MS_SHARD_WORLD1=1 set by the caller) refuses the three entry points, as ms_tree_open does"""
+    from mini_stark_amd.dist import LocalShard
+    sh = LocalShard(ctx, 4 << 20)
+    rows, main, op, fr = permutation_case(field, 64, 1600)
+    t = commit_trace(ctx, rows)
+    assert ctx.interpolate() == 0 and ctx.lde_commit(4, 3, t.shape[1])[0] == 0
+    assert ctx.aux_running_staged(op, fr, ctx.e)[0] == ms.ERR_STATE and "sharding" in ctx.last_error()
+    assert ctx.lde_commit_stage(ctx.e)[0] == ms.ERR_STATE and "sharding" in ctx.last_error()
+    assert ctx.aux_staged_count() == 0
+    assert oc.raw_open(ctx, ms.TREE_LDE_STAGED, 0, [0], 1, None, 0)[0] == ms.ERR_STATE
+    sh.close()
+
+
+def case_v1_unchanged(make, d, field):
+    """a context that has run a whole staged flow proves, by msh_stark_prove_linked, the bytes a context that never called the new entry points proves; and its MSLQ blob
+    on a state without a staged tree is the three-section one"""
+    used = ctx_of(make, d, field)
+    case_openings_state(used, field)
+    trace, cons, exempt, periodic, boundary = lc.spec_of("fib", field, 8, 101)
+    air = (cons, exempt, periodic, boundary)
+    hs, _cfg = lc.handle(used, 8, 2)
+    assert hs.prove_linked(trace, air, 3) == 0, used.last_error()
+    P = lc.prove(make, d, field, "fib", N=8, R=3)
+    assert hs.linked_proof() == P["data"] and lc.verdicts(P, hs.linked_proof()) == (1, "", "")
+    Q = lc.build_state(used, d, field, "fib", N=64, R=3)
+    betas = [7, Q["D0"] + 3]
+    blob = used.query_linked(betas)
+    assert blob == lc.by_definition(used, betas, Q["D0"], Q["L"]) and rs.split_msls(blob) is None
+
+
+def case_openings_state(ctx, field, N=8, blowup=4, R=2):
+    """a whole staged flow up to ms_query_linked on `ctx`"""
+    rows, main, op, fr = logup_case(field, N, 1700 + field)
+    got, _r0, _r1 = staged(ctx, rows, [(op, fr)], blowup, SplitMix64(1701).nonzero(MODULUS[field]))
+    w = len(rows[0])
+    air = combined_air(field, N, w, main, [(op, fr)], [got[0][0]])
+    P = linked_state(ctx, field, N, blowup, w + ctx.e, air, R, 77)
+    assert rs.split_msls(ctx.query_linked([3, P["D0"]])) is not None
+
+
+# ================================================================ linked proofs with running columns: MSLP v2 and the drivers (include/ministark_host.h)
+import struct   # noqa: E402
+
+from mini_stark_amd import host as mh   # noqa: E402
+from mini_stark_amd.stark import Stark   # noqa: E402
+
+HEAD2 = struct.calcsize(rs.MSLP2_HEAD)
+BLOWUP = lc.BLOWUP
+
+
+def symbolic(field, which):
+    """(the arguments as flatten_aux_arg dicts, nch): the permutation argument (ch0 + T2 + ch1 T3) / (ch0 + T4 + ch1 T5) with two challenges, the LogUp argument
+    1 / (ch0 + f) + (p - 1) m / (ch0 + t) with one"""
+    p = MODULUS[field]
+    if which == "permutation":
+        return [ms.flatten_aux_arg(PRODUCT, [(((1, 1), [(2, 1, 0), (3, 1, 2)]), ((1, 1), [(4, 1, 0), (5, 1, 2)]))])], 2
+    return [ms.flatten_aux_arg(SUM, [(((1, 0), []), ((1, 1), [(2, 1, 0)])), (((0, 0), [(4, p - 1, 0)]), ((1, 1), [(3, 1, 0)]))])], 1
+
+
+def statement(field, which, N, seed, spoil=False):
+    rows, main, _op, _fr = permutation_case(field, N, seed, spoil=spoil) if which == "permutation" else logup_case(field, N, seed)
+    args, nch = symbolic(field, which)
+    return np.array(rows, dtype=np.uint64), (main[0], main[1], (), main[2]), args, nch
+
+
+def prove2(make, d, field, which, N=8, R=3, gb=0, seed=1):
+    """one v2 proof by the C++ driver: a dict with everything the verifying sides are given"""
+    ctx = ctx_of(make, d, field)
+    trace, air, args, nch = statement(field, which, N, 3000 + seed)
+    w = trace.shape[1]
+    hs, cfg = lc.handle(ctx, N, w, gb)
+    rc = hs.prove_linked_aux(trace, air, args, nch, R)
+    assert rc == 0, (rc, ctx.last_error())
+    return dict(ctx=ctx, hs=hs, cfg=cfg, d=d, field=field, N=N, w=w, R=R, gb=gb, nq=hs.fri_queries, air=air, args=args, nch=nch, trace=trace, data=hs.linked_proof())
+
+
+def verdicts2(P, data=None, air=None, args=None):
+    """(the host library's rc and why, pyref_staged's step): the same verdict, and `why` beginning as the step's prefix"""
+    data = P["data"] if data is None else data
+    air, args = air or P["air"], args or P["args"]
+    rc, why = P["hs"].verify_linked_aux(data, air, args, P["nch"], P["N"], P["w"], P["R"])
+    ok, step = rs.verify(P["field"], P["d"], True, P["N"], P["w"], BLOWUP, P["R"], P["nq"], P["gb"], air, args, P["nch"], data)
+    assert rc in (0, 1) and (rc == 1) == ok, (rc, why, step)
+    assert (why == "" and step == "") if ok else why.startswith(rs.PREFIX[step]), (why, step)
+    return rc, why, step
+
+
+def rejected2(P, data=None, steps=None, **over):
+    rc, why, step = verdicts2(P, data, **over)
+    assert rc == 0 and (steps is None or step in steps), (why, step, steps)
+    return step
+
+
+# ---------------------------------------------------------------- 5. end to end
+def case_end_to_end(make, d, field, which, N=8, R=3, gb=0):
+    p, e = MODULUS[field], EXT[field]
+    P = prove2(make, d, field, which, N=N, R=R, gb=gb)
+    data, w, args, nch = P["data"], P["w"], P["args"], P["nch"]
+    assert verdicts2(P) == (1, "", "")
+    st = Stark(P["cfg"])
+    lp = st.prove_air(P["trace"], P["air"], R, aux=(args, nch))                     # the Python driver writes the same bytes
+    assert lp.to_bytes() == data
+    h = rs.parse_mslp2(data)
+    assert h is not None and (h["version"], h["c0"], h["c1"], h["nargs"], h["nch"], h["R"], h["nq"], h["gb"], h["N"]) == (2, w, e * len(args), len(args), nch, R, P["nq"], gb, N)
+    assert rs.split_msls(h["msls"]) is not None and P["hs"].linked_proof() == data
+    assert st.verify_air(data, P["air"], N, w, R, aux=(args, nch)) is True
+    assert st.verify_air(data[:-1], P["air"], N, w, R, aux=(args, nch)) is False and st.last_verify_error.startswith("header: ")
+    # msh_aux_encode against both restatements; msh_aux_constraints against aux_constraints and the restatement, with the proof's challenges
+    assert mh.aux_encode(field, args, nch) == rs.encode_aux(args, nch) == ms.encode_aux(args, nch) != b""
+    ch = st.last_challenges["ch"]
+    inst = [ms.instantiate_aux(field, a, ch) for a in args]
+    cons, exempt, periodic, boundary = P["air"]
+    for k, a in enumerate(inst):
+        c2, e2, b2 = ms.aux_constraints(field, a["op"], ms.aux_fractions(a), e, w + k * e)
+        cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
+    rc, enc = mh.aux_constraints_native(field, P["air"], inst, w)
+    assert rc == 0 and enc == mh.air_encode((cons, exempt, periodic, boundary)) == lc.rl.encode_air(*rs.combined_program(field, w, P["air"], args, ch))
+    # a malformed descriptor: a selector above nch, a non-canonical value, nch outside 1..8
+    bad = dict(args[0]); bad["form_ch"] = args[0]["form_ch"].copy(); bad["form_ch"][1] = nch + 1
+    assert mh.aux_encode(field, [bad], nch) == b""
+    bad = dict(args[0]); bad["form_const"] = args[0]["form_const"].copy(); bad["form_const"][1] = p
+    assert mh.aux_encode(field, [bad], nch) == b"" and mh.aux_encode(field, args, 0) == b"" and mh.aux_encode(field, args, 9) == b""
+    # a v1 proof on the same handle replaces the slot, and is what it is on a context that never staged anything
+    trace, fc, fe, fp, fb = lc.spec_of("fib", field, 8, 101)
+    assert P["hs"].prove_linked(trace, (fc, fe, fp, fb), 3) == 0
+    if N == 8 and gb == 0:
+        assert P["hs"].linked_proof() == lc.prove(make, d, field, "fib", N=8, R=3)["data"]
+
+
+# ---------------------------------------------------------------- 6. rejections
+def case_rejections(make, d, field, gb=0):
+    p, e = MODULUS[field], EXT[field]
+    P = prove2(make, d, field, "permutation", N=8, R=3, gb=gb)
+    data, w, N, R, args, nch = P["data"], P["w"], P["N"], P["R"], P["args"], P["nch"]
+    assert verdicts2(P) == (1, "", "")
+    flip, put_u64 = lc.flip, lc.put_u64
+    la, lq = struct.unpack_from("<2Q", data, HEAD2 - 16)
+    a0, q0 = HEAD2, HEAD2 + la
+    l_msfi, l_lde, l_stg, l_val = struct.unpack_from("<4Q", data, q0 + 8)
+    s_lde = q0 + 40 + l_msfi
+    s_stg, s_val = s_lde + l_lde, s_lde + l_lde + l_stg
+    assert s_val + l_val == len(data)
+    rejected2(P, flip(data, a0 + 64 + 5))                                            # the staged root
+    rejected2(P, flip(data, a0 + 32 + 5))                                            # the stage-0 root
+    rejected2(P, flip(data, s_stg + 8), steps=("staged",))                           # a value of a staged opening
+    rejected2(P, flip(data, s_stg + l_stg - 1), steps=("staged",))                   # ... and its last digest
+    rejected2(P, put_u64(data, s_stg + 8, p), steps=("staged",))                     # a non-canonical opened value
+    rejected2(P, flip(data, s_lde + 8), steps=("lde",))
+    rejected2(P, flip(data, s_val + 8), steps=("validity",))
+    for k in range(5):                                                               # the MSLS magic and every length word
+        rejected2(P, flip(data, q0 + 8 * k), steps=("header",))
+    rejected2(P, put_u64(put_u64(data, q0 + 16, l_lde + 8), q0 + 24, l_stg - 8), steps=("lde", "staged"))   # the sum fits: the sections are cut elsewhere
+    for k in range(12):                                                              # every header field, the new ones among them
+        rejected2(P, flip(data, 4 * k), steps=("header",))
+    for k in range(4):
+        rejected2(P, flip(data, 48 + 8 * k), steps=("header",))
+    rejected2(P, data[:-1], steps=("header",))
+    rejected2(P, data + bytes(8), steps=("header",))
+    rejected2(P, data[:HEAD2 - 1], steps=("header",))
+    rejected2(P, data[:HEAD2 + 40], steps=("header",))
+    rejected2(P, b"", steps=("header",))
+    # the staged section of a second proof of the same shape
+    B = prove2(make, d, field, "permutation", N=8, R=3, gb=gb, seed=2)
+    assert len(B["data"]) == len(data) and B["data"] != data and verdicts2(B) == (1, "", "")
+    rejected2(P, data[:s_stg] + B["data"][s_stg:s_val] + data[s_val:], steps=("staged",))
+    # the statement with one selector, one term_coef changed
+    for name, at, v in (("term_ch", 1, 1), ("form_ch", 0, 2), ("term_coef", 0, 2)):
+        other = dict(args[0]); other[name] = args[0][name].copy(); other[name][at] = v
+        rejected2(P, args=[other], steps=("pow", "air"))
+    # the two versions and the two verifiers
+    fib = lc.prove(make, d, field, "fib", N=8, R=3, gb=gb)
+    rc, why = P["hs"].verify_linked_aux(fib["data"], P["air"], args, nch, N, w, R)
+    assert rc == 0 and why.startswith("header: ")
+    assert rs.verify(field, d, True, N, w, BLOWUP, R, P["nq"], gb, P["air"], args, nch, fib["data"]) == (False, "header")
+    rc, why = P["hs"].verify_linked(data, P["air"], N, w, R)
+    assert rc == 0 and why.startswith("header: ")
+    assert lc.rl.verify(field, d, True, N, w, BLOWUP, R, P["nq"], gb, P["air"], data) == (False, "header")
+    # a running column built from challenges other than the transcript's
+    st = Stark(P["cfg"])
+    forged = st.prove_air(P["trace"], P["air"], R, aux=(args, nch), forced_challenges=[k_of(field, 3), k_of(field, 5)]).to_bytes()
+    assert len(forged) == len(data)
+    rejected2(P, forged, steps=("air",))
+    assert st.prove_air(P["trace"], P["air"], R, aux=(args, nch)).to_bytes() == data   # (and the driver's own bytes behind it)
+
+
+def case_false_argument(make, d, field):
+    """columns (4, 5) are not a permutation of (2, 3): MS_ERR_SHAPE from the prover, an empty slot"""
+    ctx = ctx_of(make, d, field)
+    trace, air, args, nch = statement(field, "permutation", 8, 3001)
+    bad = statement(field, "permutation", 8, 3001, spoil=True)[0]
+    hs, cfg = lc.handle(ctx, 8, trace.shape[1])
+    assert hs.prove_linked_aux(bad, air, args, nch, 3) == ms.ERR_SHAPE and hs.linked_proof() == b""
+    assert hs.prove_linked_aux(trace, air, args, nch, 3) == 0 and hs.linked_proof() != b""
+    assert hs.prove_linked_aux(bad, air, args, nch, 3) == ms.ERR_SHAPE and hs.linked_proof() == b""
+    wrong = dict(args[0]); wrong["term_col"] = args[0]["term_col"].copy(); wrong["term_col"][0] = trace.shape[1]
+    assert hs.prove_linked_aux(trace, air, [wrong], nch, 3) == ms.ERR_ARG                # a column >= w
+    with np.testing.assert_raises(ms.MsError):
+        Stark(cfg).prove_air(bad, air, 3, aux=(args, nch))
