@@ -443,7 +443,7 @@ def prove2(make, d, field, which, N=8, R=3, gb=0, seed=1):
     hs, cfg = lc.handle(ctx, N, w, gb)
     rc = hs.prove_linked_aux(trace, air, args, nch, R)
     assert rc == 0, (rc, ctx.last_error())
-    return dict(ctx=ctx, hs=hs, cfg=cfg, d=d, field=field, N=N, w=w, R=R, gb=gb, nq=hs.fri_queries, air=air, args=args, nch=nch, trace=trace, data=hs.linked_proof())
+    return dict(ctx=ctx, hs=hs, cfg=cfg, d=d, field=field, N=N, w=w, R=R, Rr=R or hs.rounds, gb=gb, nq=hs.fri_queries, air=air, args=args, nch=nch, trace=trace, data=hs.linked_proof())
 
 
 def verdicts2(P, data=None, air=None, args=None):
@@ -451,7 +451,7 @@ def verdicts2(P, data=None, air=None, args=None):
     data = P["data"] if data is None else data
     air, args = air or P["air"], args or P["args"]
     rc, why = P["hs"].verify_linked_aux(data, air, args, P["nch"], P["N"], P["w"], P["R"])
-    ok, step = rs.verify(P["field"], P["d"], True, P["N"], P["w"], BLOWUP, P["R"], P["nq"], P["gb"], air, args, P["nch"], data)
+    ok, step = rs.verify(P["field"], P["d"], True, P["N"], P["w"], BLOWUP, P["R"] or P["hs"].rounds, P["nq"], P["gb"], air, args, P["nch"], data)   # (R = 0: the configuration's own rounds)
     assert rc in (0, 1) and (rc == 1) == ok, (rc, why, step)
     assert (why == "" and step == "") if ok else why.startswith(rs.PREFIX[step]), (why, step)
     return rc, why, step
@@ -473,7 +473,7 @@ def case_end_to_end(make, d, field, which, N=8, R=3, gb=0):
     lp = st.prove_air(P["trace"], P["air"], R, aux=(args, nch))                     # the Python driver writes the same bytes
     assert lp.to_bytes() == data
     h = rs.parse_mslp2(data)
-    assert h is not None and (h["version"], h["c0"], h["c1"], h["nargs"], h["nch"], h["R"], h["nq"], h["gb"], h["N"]) == (2, w, e * len(args), len(args), nch, R, P["nq"], gb, N)
+    assert h is not None and (h["version"], h["c0"], h["c1"], h["nargs"], h["nch"], h["R"], h["nq"], h["gb"], h["N"]) == (2, w, e * len(args), len(args), nch, P["Rr"], P["nq"], gb, N)
     assert rs.split_msls(h["msls"]) is not None and P["hs"].linked_proof() == data
     assert st.verify_air(data, P["air"], N, w, R, aux=(args, nch)) is True
     assert st.verify_air(data[:-1], P["air"], N, w, R, aux=(args, nch)) is False and st.last_verify_error.startswith("header: ")

@@ -101,6 +101,11 @@ def test_end_to_end_sponge_digest(make):
 
 
 @pytest.mark.parametrize("field", [0, 1])
+def test_end_to_end_rounds_of_the_configuration(make, field):
+    sc.case_end_to_end(make, SHA, field, "permutation", N=64, R=0, gb=0)
+
+
+@pytest.mark.parametrize("field", [0, 1])
 def test_rejections(make, field):
     sc.case_rejections(make, SHA, field)
 
