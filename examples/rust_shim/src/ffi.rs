@@ -77,6 +77,7 @@ extern "C" {
     pub fn ms_digest(ctx: *const ms_ctx) -> c_int;
     pub fn ms_set_stream(ctx: *mut ms_ctx, hip_stream: *mut c_void) -> c_int;
     pub fn ms_synchronize(ctx: *mut ms_ctx) -> c_int;
+    pub fn ms_stream(ctx: *const ms_ctx) -> *mut c_void;
     pub fn ms_pinned_alloc(bytes: usize) -> *mut c_void;
     pub fn ms_pinned_free(p: *mut c_void);
     // ---- one proof over the GPUs of a node

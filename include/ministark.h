@@ -85,8 +85,32 @@ void ms_destroy(ms_ctx* ctx);
 const char* ms_last_error(const ms_ctx* ctx);
 int ms_ext_degree(const ms_ctx* ctx);             /* 2 (Goldilocks) / 4 (BabyBear): StarkField::Extension */
 int ms_digest(const ms_ctx* ctx);                 /* ms_digest_id: what the context commits with */
-int ms_set_stream(ms_ctx* ctx, void* hip_stream); /* run on a caller-owned hipStream_t (NULL: back to the ctx's own) */
+/* Streams.  A context enqueues all its work on ONE stream: its own (created by ms_create, hipStreamNonBlocking) or a caller-owned hipStream_t.
+ *   ms_set_stream(ctx, s)   from now on the context works on `s`; NULL (0) selects the context's OWN stream.  HIP's null stream - PyTorch's default stream, whose
+ *                           handle is 0 - can therefore not be named: a caller on it creates a stream and orders the two with an event.
+ *   ordering at the switch  ms_set_stream is a hand-over point: everything the context enqueued before the call happens before everything it enqueues after it.  The
+ *                           stream being left is drained inside the call (the calling thread waits for it, for the side stream of MS_FLAG_LATENCY and for a sharded
+ *                           context's communication stream), so it must still exist then: if draining fails, the call returns MS_ERR_HIP and the context is on the
+ *                           new stream all the same.  A caller's own work on the NEW stream is ordered by that stream as usual.  Naming the stream the context is
+ *                           on already costs nothing.
+ *   unsynchronised returns  EXACTLY these return with launches still in flight: ms_interpolate, ms_mix, ms_polys_lincomb (with MS_LAZY_LINCOMB=0; by default it
+ *                           launches nothing) and ms_bench_lde.  Every other entry point returns with the context's stream idle: it has waited for what it hands to
+ *                           the host, and the ones whose last launch comes behind that wait - ms_mix_cubic, ms_mix_terms, ms_mix_air, ms_mix_air_ext,
+ *                           ms_aux_running_staged, ms_polys_append - synchronise once more behind it.  (Under MS_FLAG_LATENCY a stage's results are home when its
+ *                           last kernel has stored them, a moment before the kernel retires.)  ms_fri_proof_read_async is asynchronous by design, on a copy stream of
+ *                           the context's own, until ms_fri_proof_wait.  The effects of the four are ordered before every later call on the context, across
+ *                           ms_set_stream too; a caller that needs them FINISHED - to time them - calls ms_synchronize, or records an event on ms_stream(ctx).
+ *                           Before destroying a stream it lent, a caller ALWAYS moves the context off it (ms_set_stream drains it) or calls ms_synchronize.
+ *                           ms_trace_upload_async queues a copy-engine transfer and touches no stream.
+ *   caller's buffers        are only read or written during the call that takes them (device pointers too: ms_trace_commit_device reads `trace` on the context's
+ *                           stream, behind whatever the caller enqueued there, and has finished reading when it returns).
+ *   ms_synchronize(ctx)     waits for the stream the context is on NOW (after ms_set_stream: the new one; the one left was drained by the switch).
+ *   ms_stream(ctx)          the hipStream_t the context is on now: the caller's, or the context's own (valid until ms_destroy).  For events and for work the caller
+ *                           orders behind an unsynchronised return; NULL for a null ctx.
+ * ms_destroy with work in flight on a caller's stream: call ms_synchronize first. */
+int ms_set_stream(ms_ctx* ctx, void* hip_stream);
 int ms_synchronize(ms_ctx* ctx);
+void* ms_stream(const ms_ctx* ctx);
 /* page-locked host memory for the boundary's bulk transfers (the trace going in, the FRI proof coming out): copies to and from
  * it are DMA transfers that overlap with kernels of other contexts.  NULL on failure. */
 void* ms_pinned_alloc(size_t bytes);

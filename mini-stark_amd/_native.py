@@ -67,6 +67,9 @@ def load_library(path=None):
     L.ms_root_of_unity.restype = C.c_uint64
     L.ms_ceil_log2_k.restype = C.c_uint64
     L.ms_logarithm_of_two_k.restype = C.c_long
+    if hasattr(L, "ms_stream"):   # (a library built before the symbol existed: MS_LIB_PATH naming an older build)
+        L.ms_stream.restype = C.c_void_p
+        L.ms_stream.argtypes = [C.c_void_p]
     _LIBS[path] = L
     return L
 
@@ -472,9 +475,20 @@ class Context:
         return out
 
     def set_stream(self, hip_stream_ptr):
-        self.check(self.L.ms_set_stream(self.h, C.c_void_p(hip_stream_ptr)))
+        """ms_set_stream: from now on the context enqueues its work on the caller's hipStream_t (`torch.cuda.Stream.cuda_stream`); 0 / None selects the context's OWN
+        stream - so HIP's null stream, torch's default stream (handle 0), cannot be named: create a stream and order it with an event.  A hand-over point: whatever the
+        context enqueued before the call happens before whatever it enqueues after it; the stream being left is drained inside the call, so it must still exist (if
+        draining fails, MsError is raised and the context is on the new stream all the same).  Exactly interpolate, mix, polys_lincomb (MS_LAZY_LINCOMB=0) and bench_lde
+        return with launches in flight; every other entry point returns with the stream idle.  The four are ordered before every later call, across a switch too;
+        synchronize() waits for them - call it, or move the context away, before destroying a stream that was lent."""
+        self.check(self.L.ms_set_stream(self.h, C.c_void_p(hip_stream_ptr or None)))
+
+    def stream(self):
+        """ms_stream: the handle of the stream the context is on now - the caller's, or its own (`torch.cuda.ExternalStream(ctx.stream())` records events on it)."""
+        return int(self.L.ms_stream(self.h) or 0)
 
     def synchronize(self):
+        """ms_synchronize: waits for the stream the context is on now."""
         self.check(self.L.ms_synchronize(self.h))
 
     def set_shard(self, rank, world, send_ptr, recv_ptr, cap_bytes, callback):

@@ -122,6 +122,7 @@ int ms_shard_proof_is_elsewhere(const ms_ctx* ctx) { return ctx ? B(ctx)->shard_
 int ms_shard_proof_on_root(ms_ctx* ctx, int on) { if (!ctx) return MS_ERR_ARG; return B(ctx)->shard_proof_on_root(on); }
 int ms_shard_slice_layout(ms_ctx* ctx, size_t* offset, size_t* stride) { MS_ENTRY(ctx, B(ctx)->shard_slice_layout(offset, stride)); }
 int ms_synchronize(ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->synchronize()); }
+void* ms_stream(const ms_ctx* ctx) { return ctx ? B(ctx)->current_stream() : nullptr; }
 
 int ms_is_power_of_two(uint64_t n) { return is_pow2(n) ? 1 : 0; }
 long ms_logarithm_of_two_k(uint64_t n, uint64_t base) { return log_two_k(n, base); }

@@ -333,6 +333,7 @@ int Ctx<F>::finish_mix(const char* refusal, size_t VL, int ne) {
   { auto scan = res.expect(dres, false, false); RQ(res.collect(nullptr, nullptr, &ncoef)); }
   if (ncoef > VL) return fail(MS_ERR_SHAPE, refusal);
   RQ(scale_pow(cf, L, d_polys.as<T>() + (size_t)npolys * N, VL, VL, f_inv<F>(F::from_u64(lde_shift)), (size_t)ne));
+  CK(msrt::sync(stream));   // (include/ministark.h, Streams: these mix stages return with nothing in flight - the un-shift above is launched behind the exactness check's wait)
   validity_ncoef = (size_t)ncoef; validity_len_at = VLEN_HOST;   // (scaling by shift^-k keeps the trimmed length)
   have_validity = true; validity_len = VL; validity_ext = ne; nrounds_done = 0; drop_vtree();
   return MS_OK;

@@ -107,6 +107,7 @@ struct CtxBase {
   virtual int ext_degree() const = 0;
   virtual void bind_device() const = 0;  // HIP's current device is per host thread: every entry point binds the context's device
   virtual int set_stream(void* s) = 0;
+  virtual void* current_stream() const = 0;
   virtual int synchronize() = 0;
   virtual int set_shard(int rank, int world, void* d_send, void* d_recv, size_t cap, ms_exchange_fn fn, void* user) = 0;
   virtual int set_shard_rccl(int rank, int world, const u8* unique_id, size_t cap) = 0;
@@ -512,7 +513,24 @@ template <class F> struct Ctx : CtxBase {
   }
   int ext_degree() const override { return E; }
   void bind_device() const override { msrt::set_device(device); }
-  int set_stream(void* s) override { stream = s ? reinterpret_cast<msrt::Stream*>(s) : own_stream.get(); zero_used = zero_cap; return 0; }
+  // A HAND-OVER POINT: everything enqueued before the switch happens before everything enqueued after it.  ms_interpolate, ms_mix, ms_polys_lincomb (MS_LAZY_LINCOMB=0)
+  // and ms_bench_lde return with launches in flight that write d_polys, d_lde or the validity-length word, which the next stage reads on whatever stream it finds: the
+  // stream being left is drained here, and with it the side stream (every stage joins it back before it returns; an error exit may not have) and a sharded context's
+  // communication stream.  No handle is needed, and naming the stream the context is on already costs nothing.  The switch happens even when the drain fails (the
+  // caller destroyed the stream it had lent): the error is reported, and the context is not left on a dead stream.
+  int set_stream(void* s) override {
+    msrt::Stream* next = s ? reinterpret_cast<msrt::Stream*>(s) : own_stream.get();
+    int e = 0;
+    if (next != stream) {
+      e = msrt::sync(stream);
+      if (side_stream) { const int e2 = msrt::sync(side_stream.get()); if (!e) e = e2; }
+      if (comm_stream) { const int e2 = msrt::sync(comm_stream.get()); if (!e) e = e2; }
+    }
+    stream = next; zero_used = zero_cap;
+    if (e) return fail_rt(e, "ms_set_stream: draining the stream being left (the context is on the new stream)");
+    return 0;
+  }
+  void* current_stream() const override { return stream; }
   int synchronize() override { CK(msrt::sync(stream)); return 0; }
 
   static unsigned grid1(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }

@@ -346,6 +346,7 @@ int Ctx<F>::aux_running_staged_t(const ms_aux& a, u64* final_out, u64* column_ou
   RQ(aux_columns<EA>("aux_running_staged", a, slot.data(), scr, ns, out, fin));
   if (column_out) RQ(download_widen(out, N, N, (u32)EA, column_out));
   RQ(ntt_run(ctz64(N), true, out, N, N, d_polys.as<T>() + (size_t)npolys * N, N, (size_t)EA));
+  CK(msrt::sync(stream));   // (include/ministark.h, Streams: the stage returns with nothing in flight - the interpolation above is launched behind aux_columns' wait)
   for (int l = 0; l < EA; l++) { poly_lin.push_back(Lin()); poly_mat.push_back(1); final_out[l] = fin[l]; }
   npolys += EA; stg_pending += EA; stg_total += EA;
   return MS_OK;
@@ -395,7 +396,8 @@ int Ctx<F>::polys_append(const u64* coeffs, size_t n) {
   RQ(ensure_polys(npolys + 2));
   T* dst = d_polys.as<T>() + (size_t)npolys * N;
   CK(msrt::memset_dev(dst, 0, N * sizeof(T), stream));
-  if (n) { RQ(upload_narrow(coeffs, n, dst)); CK(msrt::sync(stream)); }   // the caller's buffer is only read during the call (include/ministark.h)
+  if (n) RQ(upload_narrow(coeffs, n, dst));
+  CK(msrt::sync(stream));   // the caller's buffer is only read during the call, and the call returns with nothing in flight, n = 0 included (include/ministark.h)
   poly_mat.push_back(1);
   poly_lin.push_back(Lin());
   npolys++; have_lde = have_validity = false;
