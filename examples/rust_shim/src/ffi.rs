@@ -146,6 +146,11 @@ extern "C" {
     // ---- the compact query phase (build-defined): the MSFI blob - openings by position, the last round's polynomial in the clear
     pub fn ms_fri_query_index(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     pub fn ms_query_linked(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    // ---- folded FRI (build-defined): arity 2^log_arity, one coset per leaf group; R committed rounds, the final fold's polynomial in the clear, the MSFF blob
+    pub fn ms_fri_begin_folded(ctx: *mut ms_ctx, blowup: usize, log_arity: c_int, root0: *mut u8) -> c_int;
+    pub fn ms_fri_fold_folded(ctx: *mut ms_ctx, alpha: *const u64, root: *mut u8) -> c_int;
+    pub fn ms_fri_fold_final(ctx: *mut ms_ctx, alpha: *const u64, coeffs: *mut u64, cap: usize, n: *mut usize) -> c_int;
+    pub fn ms_fri_query_folded(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- the composition commitment and the DEEP stage (build-defined): the tree over the validity polynomial's chunk columns on the LDE coset; the claimed evaluations;
     // D' = sum_t (A_t - A_t(z_t)) / (x - z_t) on the coset's own variable, which ms_fri_begin then starts from
     pub fn ms_validity_commit(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;

@@ -552,6 +552,53 @@ int ms_deep_len(const ms_ctx* ctx);   /* 0, or N once a DEEP polynomial is insta
  *   MSFI blob | ms_tree_open(MS_TREE_LDE, 0, rows) | ms_tree_open(MS_TREE_LDE_STAGED, 0, rows) | ms_tree_open(MS_TREE_VALIDITY, 0, rows)       the same rows */
 int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
 
+/* ---- folded FRI: arity 2, 4 or 8, one coset per leaf, one path per round (BUILD-DEFINED; the reference folds by 2, with a DEEP quotient in every round) ------------
+ * Arity a = 2^k, k = log_arity in {1, 2, 3}, fixed for one FRI; K the context's extension of E limbs.  Round i has the codeword c_i on the subgroup <g_i> of size D_i
+ * in natural order, c_i[b] at g_i^b, g_i = ms_root_of_unity(field, D_i); D_(i+1) = D_i / a, g_(i+1) = g_i^a.  The domain is unshifted, as ms_fri_begin's is.
+ *   Round 0   is ms_fri_begin's: the polynomial is D' while a DEEP polynomial is installed, otherwise the validity polynomial (all E limbs live after ms_mix_air_ext,
+ *             else limb 0), trimmed by the usual degree scan; D_0 = next_pow2(ncoef * blowup); c_0 its transform at size D_0.
+ *   Fold      for b < D_(i+1), x = g_i^b, w = g_i^(D_i / a): P the polynomial of degree < a over K with P(x w^t) = c_i[b + t D_(i+1)], t < a; c_(i+1)[b] = P(alpha_i),
+ *             for any alpha_i in K.  (The split f(X) = sum_s X^s f_s(X^a) folded as sum_s alpha^s f_s.)
+ *   Trees     round i's tree has D_i / a leaf groups; group j holds c_i[j + t D_(i+1)], t = 0 .. a - 1, in that order, E limbs each, hashed as every FRI leaf is
+ *             (ic = 2, the context's digest and zero_as_empty).  The two, four or eight points of a fold share ONE leaf.
+ *   Schedule  with R >= 1 folds the rounds 0 .. R - 1 are committed; c_R is not: its inverse transform, the final polynomial, is shipped in the clear with exactly
+ *             nfinal = D_R / blowup coefficients.  Hence a^R <= D_0 / blowup.  Transcript order (the caller's): root 0, alpha_0, root 1, .., root R - 1, alpha_(R-1),
+ *             final polynomial, (grind,) betas - one host round trip per round.
+ *   Positions b_(0,j) = betas[j] mod D_0, b_(i+1,j) = b_(i,j) mod D_(i+1).  In round i query j opens the single leaf group b_(i+1,j): the coset that holds position
+ *             b_(i,j), in its slot b_(i,j) / D_(i+1).
+ * ms_fri_begin_folded is valid exactly where ms_fri_begin is and puts the FRI state into FOLDED MODE.  MS_ERR_ARG: log_arity outside 1..3, a null root, a blowup that
+ * is zero or no power of two.  MS_ERR_SHAPE: D_0 above the field's two-adicity, or D_0 < a * blowup (no fold possible).  MS_ERR_STATE: no validity polynomial, or a
+ * context with sharding on (as ms_tree_open).
+ * ms_fri_fold_folded(alpha, root) folds the last committed round at alpha (E canonical limbs) and commits the result as the next round: one launch of the fold kernel
+ * and the tree over the coset view - no coefficient side, no scan, no side stream.  It needs D_(i+1) >= a * blowup, so that a final fold stays possible: else
+ * MS_ERR_SHAPE.
+ * ms_fri_fold_final(alpha, coeffs, cap, n) folds once more, into a codeword that is not committed, inverse-transforms it and writes the nfinal * E limbs of the final
+ * polynomial (coefficient-major) to coeffs; *n = nfinal.  cap counts u64 words.  Size query: coeffs = NULL with cap = 0 sets *n and computes nothing; cap below
+ * nfinal * E: MS_ERR_ARG with *n set.  A coefficient at or above nfinal that is not zero: MS_ERR_SHAPE - round 0 was not of the degree its domain assumes; the call
+ * may be repeated.  The polynomial stays on the device for the query phase.  After it, ms_fri_fold_folded and a second ms_fri_fold_final return MS_ERR_STATE.
+ * ms_fri_query_folded is valid after ms_fri_fold_final, any number of times, and leaves the context unchanged: ONE launch, R * nq openings and the final polynomial.
+ * nq outside 1..4096: MS_ERR_ARG.  Size query and cap rule as ms_fri_query_index.  MSFF layout, u64 little-endian words:
+ *   'MSFF' (0x4646534D) | E | k | R | nq | D_0 | nfinal
+ *   nfinal * E limbs                                                  the final polynomial
+ *   for round i = 0 .. R - 1, for query j in order:                   MerklePath of leaf group b_(i+1,j) of round i
+ * Each path is, by definition, the bytes ms_tree_open(MS_TREE_FRI, i, [b_(i+1,j)]) returns.  Verifying side: msh_fri_folded_verify (ministark_host.h).  Round 0's
+ * values are bound to nothing here, as in MSFI.
+ * Mode rules.  In folded mode ms_fri_deep, ms_fri_fold_commit, ms_fri_query[_into], ms_fri_proof_read[_async], ms_fri_proof_wait, ms_fri_query_index, ms_query_linked
+ * and ms_fri_round_poly_read return MS_ERR_STATE (ms_fri_proof_size is 0); outside it the three fold and query calls above do.  Either ms_fri_begin* starts afresh,
+ * and whatever clears the FRI state (a mix stage, ms_trace_commit, ms_set_shard) clears the mode with it.  In folded mode ms_fri_round_info(i) reports D_i and, as
+ * ncoef, the bound D_i / blowup; ms_fri_round_codeword_read(i) reads the committed rounds; ms_tree_open(MS_TREE_FRI, i, index) opens leaf group `index`: lpn = a,
+ * leaf_index = index * a, the a * E limbs of the coset as leaf_neighbours.  ms_grind is independent of all this.  Every refusal is decided before anything is launched
+ * on the FRI state: after one the context is as if the call had not been made.  Without these calls every other entry point, blob and proof is byte for byte what it
+ * was.
+ * Measured (tools/fri_folded_bench.py, profiles/fri_folded.json; one paired run on one MI355X, Goldilocks, 2^20 rows, blowup 8, D_0 = 2^23, one context, phases
+ * alternated): ms_fri_begin .. ms_fri_fold_commit (23 rounds, 45 host round trips) 4.54 ms per commit phase, 4.23 ms of kernel time; folded at arity 2 / 4 / 8
+ * (R = 20 / 10 / 6; 21 / 11 / 7 round trips) 3.30 / 1.66 / 1.27 ms, 3.40 / 1.72 / 1.29 ms of kernel time.  Blob for 2 queries: MSFI 69 040 bytes, MSFF 33 992 /
+ * 17 032 / 11 448; for 32 queries 1 103 920 against 542 792 / 271 432 / 181 368.  ms_fri_query_folded: one launch, 0.03-0.08 ms per call. */
+int ms_fri_begin_folded(ms_ctx* ctx, size_t blowup, int log_arity, uint8_t root0[32]);
+int ms_fri_fold_folded(ms_ctx* ctx, const uint64_t* alpha /* E limbs */, uint8_t root[32]);              /* commits round i + 1 */
+int ms_fri_fold_final(ms_ctx* ctx, const uint64_t* alpha, uint64_t* coeffs, size_t cap /* u64 words */, size_t* n /* nfinal */);
+int ms_fri_query_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
+
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
  * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI
  * queries (ms_num_queries_grind).  The transcript stays with the caller: the library is given a seed and returns the nonce.

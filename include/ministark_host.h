@@ -102,6 +102,19 @@ int msh_merkle_path_check_index(int digest_id, int field, int ext, size_t lpn, i
  * < 0 malformed arguments. */
 int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, uint64_t blowup, const uint8_t* roots, size_t rounds, const uint64_t* z, const uint64_t* B,
                          const uint64_t* alpha, const uint64_t* betas, size_t nq, const uint8_t* blob, size_t len, char* why, size_t why_cap);
+/* The MSFF blob of ms_fri_query_folded (ministark.h: folded FRI, build-defined) against its commit phase: roots rounds * 32 bytes (the R committed rounds, round 0
+ * first), alpha rounds * E limbs (alpha_0 .. alpha_(R-1): what ms_fri_fold_folded and ms_fri_fold_final took), the nq betas, a = 2^log_arity.  It trusts no header
+ * field: E, k, R and nq must be the verifier's, D_0 a power of two within the field's two-adicity with a^R * blowup <= D_0, nfinal = D_R / blowup exactly, and the
+ * blob exactly as long as that header fixes (truncated, or trailing bytes: rejected); a non-canonical limb and a path of another height than its round's are rejected.
+ * With b_(0,j) = betas[j] mod D_0, b_(i+1,j) = b_(i,j) mod D_(i+1), per round i and query j it checks the path by msh_merkle_path_check_index's rule (lpn = a,
+ * ext = E, leaf group b_(i+1,j)) under round i's root; then for i >= 1 that slot b_(i,j) / D_(i+1) of the opened coset is the fold of round i - 1's coset at
+ * alpha_(i-1) - the value at alpha_(i-1) of the polynomial of degree < a through the coset's a values, the coset being x w^t with x = g_(i-1)^(b_(i,j)),
+ * w = g_(i-1)^(D_(i-1) / a) -; then that the fold of round R - 1's coset at alpha_(R-1) is the final polynomial at g_R^(b_(R,j)).
+ * ROUND 0'S VALUES ARE BOUND TO NOTHING HERE, as in MSFI: what ties them to a trace is a DEEP link over the a LDE rows under a round-0 coset (not built yet).
+ * 1 accepted, 0 rejected (`why` names the step: "header: ..", "round i opening: ..", "round i fold: ..", "final polynomial: .."), < 0 malformed arguments (a null
+ * pointer, an unknown digest id or field, rounds outside 1..64, nq outside 1..4096, a blowup that is zero or no power of two, log_arity outside 1..3, an alpha limb that is not canonical). */
+int msh_fri_folded_verify(int digest_id, int field, int zero_display_empty, uint64_t blowup, int log_arity, const uint8_t* roots, size_t rounds, const uint64_t* alpha,
+                          const uint64_t* betas, size_t nq, const uint8_t* blob, size_t len, char* why, size_t why_cap);
 /* The verifying side of the DEEP stage (ministark.h: ms_validity_commit, ms_deep_evals, ms_deep_compose; build-defined, no reference counterpart): the link between
  * FRI's round 0 and the two committed trees.  N rows, L = blowup * N (the FRI blowup is the LDE's), c LDE columns, m chunk columns, `deep` / evals / gamma what the
  * prover's ms_deep_evals / ms_deep_compose took and returned, msfi the blob of ms_fri_query_index for `betas`.  With D_0 from the MSFI header (required: a power of two

@@ -70,6 +70,11 @@ def load_library(path=None):
     if hasattr(L, "ms_stream"):   # (a library built before the symbol existed: MS_LIB_PATH naming an older build)
         L.ms_stream.restype = C.c_void_p
         L.ms_stream.argtypes = [C.c_void_p]
+    if hasattr(L, "ms_fri_begin_folded"):   # folded FRI (likewise absent from an older build)
+        L.ms_fri_begin_folded.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint8 * 32)]
+        L.ms_fri_fold_folded.argtypes = [C.c_void_p, _u64p, C.POINTER(C.c_uint8 * 32)]
+        L.ms_fri_fold_final.argtypes = [C.c_void_p, _u64p, _u64p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ms_fri_query_folded.argtypes = [C.c_void_p, _u64p, C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     _LIBS[path] = L
     return L
 
@@ -786,6 +791,36 @@ class Context:
         """ms_fri_query_index: the compact query phase, the MSFI blob (openings by position, the last round's polynomial in the clear)."""
         b, bp = _u64(betas)
         return self._sized_bytes(lambda out, cap, n: self.L.ms_fri_query_index(self.h, bp, C.c_int(b.size), out, cap, n))
+
+    # ---- folded FRI: arity 2, 4 or 8, one coset per leaf group (BUILD-DEFINED; include/ministark.h) -----------------------
+    def fri_begin_folded(self, blowup, log_arity):
+        """ms_fri_begin_folded: (rc, root of round 0's coset-leaf tree); the FRI state is in folded mode from here on."""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_fri_begin_folded(self.h, C.c_size_t(blowup), C.c_int(log_arity), root)
+        return rc, bytes(root)
+
+    def fri_fold_folded(self, alpha):
+        """ms_fri_fold_folded: folds the last committed round at alpha (E limbs) and commits the result: (rc, root)."""
+        a, ap = _u64(alpha)
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_fri_fold_folded(self.h, ap, root)
+        return rc, bytes(root)
+
+    def fri_fold_final(self, alpha):
+        """ms_fri_fold_final: the last fold, not committed: (rc, its polynomial as (nfinal, E) limbs - None unless rc == 0)."""
+        a, ap = _u64(alpha)
+        n = C.c_size_t(0)
+        rc = self.L.ms_fri_fold_final(self.h, ap, None, C.c_size_t(0), C.byref(n))
+        if rc != 0:
+            return rc, None
+        out = np.zeros((n.value, self.e), dtype=np.uint64)
+        rc = self.L.ms_fri_fold_final(self.h, ap, out.ctypes.data_as(_u64p), C.c_size_t(out.size), C.byref(n))
+        return rc, (out if rc == 0 else None)
+
+    def fri_query_folded(self, betas) -> bytes:
+        """ms_fri_query_folded: the MSFF blob - the final polynomial and one opened coset per round and query."""
+        b, bp = _u64(betas)
+        return self._sized_bytes(lambda out, cap, n: self.L.ms_fri_query_folded(self.h, bp, C.c_int(b.size), out, cap, n))
 
     # ---- the composition commitment and the DEEP stage (BUILD-DEFINED; include/ministark.h) -----------------------
     def validity_commit(self, lpn):

@@ -205,9 +205,10 @@ int ms_fri_query_into(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, 
   MS_ENTRY(ctx, B(ctx)->fri_query(betas, nq, out ? out : &probe, out ? cap : 0, len));
 }
 size_t ms_fri_proof_size(const ms_ctx* ctx) { return ctx ? B(ctx)->fri_proof_size() : 0; }
-int ms_fri_proof_read(ms_ctx* ctx, uint8_t* out) { MS_ENTRY(ctx, B(ctx)->fri_proof_read(out)); }
-int ms_fri_proof_read_async(ms_ctx* ctx, uint8_t* out) { MS_ENTRY(ctx, B(ctx)->fri_proof_read_async(out)); }
-int ms_fri_proof_wait(ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->fri_proof_wait()); }
+// (a folded FRI has no MSFP blob: the three are refused while the FRI state is in folded mode)
+int ms_fri_proof_read(ms_ctx* ctx, uint8_t* out) { MS_ENTRY(ctx, B(ctx)->fri_folded_refusal("fri_proof_read") ? MS_ERR_STATE : B(ctx)->fri_proof_read(out)); }
+int ms_fri_proof_read_async(ms_ctx* ctx, uint8_t* out) { MS_ENTRY(ctx, B(ctx)->fri_folded_refusal("fri_proof_read_async") ? MS_ERR_STATE : B(ctx)->fri_proof_read_async(out)); }
+int ms_fri_proof_wait(ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->fri_folded_refusal("fri_proof_wait") ? MS_ERR_STATE : B(ctx)->fri_proof_wait()); }
 int ms_io_engine(const ms_ctx* ctx) { return ctx ? B(ctx)->io_engine() : MS_ERR_ARG; }
 const char* ms_io_runtime_path(void) { return msrt::Sdma::get().runtime_path(); }
 int ms_merkle_commit(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext, size_t lpn, size_t ic, uint8_t* nodes_out, size_t cap, size_t* nn, uint8_t root[32]) {
@@ -219,6 +220,10 @@ int ms_merkle_prove(ms_ctx* ctx, const uint64_t* leafs, size_t leaf_num, int ext
 int ms_tree_open(ms_ctx* ctx, int tree, int round, const uint64_t* index, size_t n, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->tree_open(tree, round, index, n, out, cap, len)); }
 int ms_fri_query_index(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_index(betas, nq, out, cap, len)); }
 int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->query_linked(betas, nq, out, cap, len)); }
+int ms_fri_begin_folded(ms_ctx* ctx, size_t blowup, int log_arity, uint8_t root0[32]) { MS_ENTRY(ctx, B(ctx)->fri_begin_folded(blowup, log_arity, root0)); }
+int ms_fri_fold_folded(ms_ctx* ctx, const uint64_t* alpha, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->fri_fold_folded(alpha, root)); }
+int ms_fri_fold_final(ms_ctx* ctx, const uint64_t* alpha, uint64_t* coeffs, size_t cap, size_t* n) { MS_ENTRY(ctx, B(ctx)->fri_fold_final(alpha, coeffs, cap, n)); }
+int ms_fri_query_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_folded(betas, nq, out, cap, len)); }
 int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->validity_commit(lpn, root)); }
 int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals) { MS_ENTRY(ctx, B(ctx)->deep_evals(deep, evals)); }
 int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma) { MS_ENTRY(ctx, B(ctx)->deep_compose(deep, gamma)); }

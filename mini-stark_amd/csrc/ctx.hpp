@@ -158,6 +158,11 @@ struct CtxBase {
   virtual int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) = 0;
   virtual int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
   virtual int query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
+  virtual int fri_begin_folded(size_t blowup, int log_arity, u8* root0) = 0;
+  virtual int fri_fold_folded(const u64* alpha, u8* root) = 0;
+  virtual int fri_fold_final(const u64* alpha, u64* coeffs, size_t cap, size_t* n) = 0;
+  virtual int fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
+  virtual int fri_folded_refusal(const char* who) = 0;
   virtual int validity_commit(size_t lpn, u8* root) = 0;
   virtual int deep_evals(const ms_deep* deep, u64* evals) = 0;
   virtual int deep_compose(const ms_deep* deep, const u64* gamma) = 0;
@@ -754,6 +759,19 @@ template <class F> struct Ctx : CtxBase {
   int fri_round_info(int r, u64* ncoef, u64* D) override;
   int fri_round_poly_read(int r, u64* out) override;
   int fri_round_codeword_read(int r, u64* out) override;
+  // ------------------------------------------------------------------ build-defined: folded FRI (include/ministark.h; kernel: mspoly::FriFoldArityKernel, host side: fri_commit.cpp,
+  // the query phase: fri_query.cpp).  fri_k = log2 of the arity while the FRI state is in folded mode: rounds[i] then holds codeword and tree of round i only (no
+  // polynomial), its tree over the coset view (width = lpn = a, col_stride = D_i / a), ncoef the bound D_i / blowup.  The mode lives as long as the rounds do: whatever
+  // zeroes nrounds_done ends it.  fold_fin: the final polynomial (cap = its limb stride D_R, ncoef = nfinal) once ms_fri_fold_final has run
+  int fri_k = 0; bool fold_final_done = false; Round fold_fin; DevBuf d_fold_cw;
+  bool folded() const { return fri_k != 0 && nrounds_done != 0; }
+  int fri_folded_refusal(const char* who) override { return folded() ? fail(MS_ERR_STATE, std::string(who) + ": the FRI state is in folded mode (ms_fri_begin_folded)") : 0; }
+  int fold_arity_launch(const Round* pr, const XE& a, T* dst);   // ONE launch: pr's codeword folded by 2^fri_k at `a` into dst (limbs pr->D >> fri_k apart)
+  int coset_tree(Round* r);                                      // the tree over r's codeword, one coset of the next fold per leaf group
+  int fri_begin_folded(size_t blowup_, int log_arity, u8* root0) override;
+  int fri_fold_folded(const u64* alpha, u8* root) override;
+  int fri_fold_final(const u64* alpha, u64* coeffs, size_t cap, size_t* n) override;
+  int fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
 
   // ------------------------------------------------------------------ fri.rs:115-189
   // The whole query phase is a fixed handful of batched launches, whatever the number of

@@ -131,7 +131,7 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
   if (!have_validity) return fail(MS_ERR_STATE, "fri_begin before mix");
   if (!root0 || nrounds < 1 || !blowup_) return fail(MS_ERR_ARG, "fri_begin");
   nrounds_done = 0; have_deep = false; blob_size = 0;
-  fri_rounds = nrounds; fri_blowup = blowup_;
+  fri_rounds = nrounds; fri_blowup = blowup_; fri_k = 0; fold_final_done = false;   // (either ms_fri_begin* starts afresh)
   // the self-clearing length word (and completion counter) of ms_fri_fold_commit: zeroed HERE, behind this stage's stream synchronisation - zeroing it
   // lazily in the first ms_fri_fold_commit raced with the side stream's length scan (r05: first proof of a context, eight lanes in flight) - and zero again even if
   // an earlier proof was abandoned mid-round
@@ -174,6 +174,7 @@ int Ctx<F>::fri_begin(size_t blowup_, size_t nrounds, u8* root0) {
 // fri.rs:89-94
 template <class F>
 int Ctx<F>::fri_deep(const u64* z, u64* B) {
+  RQ(fri_folded_refusal("fri_deep"));
   if (nrounds_done == 0 || nrounds_done >= fri_rounds) return fail(MS_ERR_STATE, "fri_deep out of order");
   if (!z || !B) return fail(MS_ERR_ARG, "fri_deep");
   if (!load_ext(z, &cur_z)) return fail(MS_ERR_ARG, "z not canonical");
@@ -405,6 +406,7 @@ int Ctx<F>::fri_tail_round_t(Round* pr, Round* nr, const XE& a, bool* done) {
 // fri.rs:96-109
 template <class F>
 int Ctx<F>::fri_fold_commit(const u64* alpha, u8* root) {
+  RQ(fri_folded_refusal("fri_fold_commit"));
   if (!have_deep) return fail(MS_ERR_STATE, "fri_fold_commit before fri_deep");
   XE a;
   if (!alpha || !root || !load_ext(alpha, &a)) return fail(MS_ERR_ARG, "alpha");
@@ -470,6 +472,7 @@ int Ctx<F>::fri_round_info(int r, u64* ncoef, u64* D) {
 
 template <class F>
 int Ctx<F>::fri_round_poly_read(int r, u64* out) {
+  RQ(fri_folded_refusal("fri_round_poly_read"));
   if (r < 0 || (size_t)r >= nrounds_done || !out) return fail(MS_ERR_ARG, "round index");
   if (rounds[r]->local_store) return fail(MS_ERR_STATE, "round_poly_read: the polynomial of a sharded round is distributed over the ranks");
   return download_widen(rounds[r]->poly.template as<T>(), rounds[r]->ncoef, rounds[r]->cap, E, out);
@@ -480,6 +483,134 @@ int Ctx<F>::fri_round_codeword_read(int r, u64* out) {
   if (r < 0 || (size_t)r >= nrounds_done || !out) return fail(MS_ERR_ARG, "round index");
   if (rounds[r]->ts.sharded) return fail(MS_ERR_STATE, "codeword_read: the codeword of a sharded round is distributed over the ranks");
   return download_widen(rounds[r]->cw.template as<T>(), rounds[r]->D, rounds[r]->D, E, out);
+}
+
+// ------------------------------------------------------------------ build-defined: folded FRI (include/ministark.h)
+// Round i's codeword c_i on <g_i> in natural order; a fold takes the a = 2^fri_k values of a coset {x w^t} to P(alpha), P their interpolant (FriFoldArityKernel).
+// No round polynomial, no DEEP quotient, no scan, no side stream: a round is one fold launch and the tree over the coset view.
+template <class F>
+int Ctx<F>::fold_arity_launch(const Round* pr, const XE& a, T* dst) {
+  const size_t A = (size_t)1 << fri_k, m_out = pr->D / A;
+  Plan* pl;
+  RQ(get_plan(ctz64(pr->D), 0, false, &pl));   // w_D^e tables of the domain being folded
+  const T w_inv = f_pow<F>(pl->root, (u64)(pr->D - m_out));   // (w_D^(D/a))^-1
+  auto launch = [&](auto* kernel) {
+    typedef typename std::remove_pointer<decltype(kernel)>::type FK;
+    typename FK::Params fp;
+    fp.src = pr->cw.template as<T>(); fp.src_limb_stride = pr->D; fp.dst = dst; fp.dst_limb_stride = m_out; fp.m_out = m_out;
+    fp.tw_lo = pl->tw_lo.template as<T>(); fp.tw_hi = pl->tw_hi.template as<T>(); fp.lo_bits = (u32)pl->lo_bits; fp.log_D = (u32)ctz64(pr->D);
+    fp.alpha = a;
+    T wj = F::from_u64(1);
+    for (int j = 0; j < 4; j++) { fp.wt[j] = F::to_tw(wj); wj = F::mul(wj, w_inv); }
+    fp.inv_a = F::to_tw(f_inv<F>(F::from_u64((u64)A)));
+    next_bytes = (double)m_out * (A + 1) * E * sizeof(T);   // a E words read, E written per output
+    return run<FK>(K_FOLD, grid1(m_out, FK::THREADS), 1, FK::THREADS, 0, fp);
+  };
+  if (fri_k == 1) CK(launch((mspoly::FriFoldArityKernel<F, E, 1>*)nullptr));
+  else if (fri_k == 2) CK(launch((mspoly::FriFoldArityKernel<F, E, 2>*)nullptr));
+  else CK(launch((mspoly::FriFoldArityKernel<F, E, 3>*)nullptr));
+  return 0;
+}
+
+// leaf group j = the a elements c[j + t D / a], t < a: the view width = lpn = a, col_stride = D / a (r->ts: tree_shape(D, a, 2))
+template <class F>
+int Ctx<F>::coset_tree(Round* r) {
+  const size_t A = (size_t)1 << fri_k;
+  return tree_build<E>(r->cw.template as<T>(), r->D / A, 1, r->D, (u32)A, r->ts, r->nodes);
+}
+
+template <class F>
+int Ctx<F>::fri_begin_folded(size_t blowup_, int log_arity, u8* root0) {
+  if (!have_validity) return fail(MS_ERR_STATE, "fri_begin_folded before mix");
+  if (!root0 || !blowup_ || (blowup_ & (blowup_ - 1)) || log_arity < 1 || log_arity > 3) return fail(MS_ERR_ARG, "fri_begin_folded: null root, log_arity outside 1..3, or a blowup that is zero or no power of two");
+  if (sh_on) return fail(MS_ERR_STATE, "fri_begin_folded: not available on a context with sharding on");
+  const size_t A = (size_t)1 << log_arity;
+  if (blowup_ > ((size_t)1 << F::TWO_ADICITY) / A) return fail(MS_ERR_SHAPE, "fri_begin_folded: arity * blowup is above the field's two-adicity, no domain can hold a fold");   // (D_0 >= blowup whatever the degree: refused without the scan)
+  // round 0's polynomial where it lies (ms_fri_begin's rule): D' while a DEEP polynomial is installed (N coefficients, E limbs N apart), otherwise the validity polynomial
+  const bool dp = dpoly_live();
+  const size_t VL = dp ? N : validity_len;
+  const bool vx = dp || validity_ext > 1;
+  const T* src = dp ? d_deep.template as<T>() : d_polys.template as<T>() + (size_t)npolys * N;
+  unsigned long long nc = validity_ncoef;
+  if (dp || validity_len_at != VLEN_HOST) {   // the trimmed length, scanned in place (a base-field polynomial: every limb of the scan reads the one plane)
+    unsigned long long* dres;
+    RQ(degree_launch(src, vx ? VL : 0, VL, &dres));
+    auto scan = res.expect(dres, false, false);
+    RQ(res.collect(nullptr, nullptr, &nc));
+  }
+  size_t D = 1; while (D < (nc ? nc : 1) * blowup_) D <<= 1;   // next_pow2(ncoef * blowup), as ms_fri_begin
+  if (ctz64(D) > F::TWO_ADICITY) return fail(MS_ERR_SHAPE, "FRI domain larger than the field's two-adicity");
+  if (D / A < blowup_) return fail(MS_ERR_SHAPE, "fri_begin_folded: D_0 < arity * blowup, no fold is possible");
+  TreeShape ts;
+  RQ(tree_shape(D, A, 2, &ts));
+  if (copy_pending) RQ(fri_proof_wait());   // (a read-back of an earlier MSFP blob in flight: ms_fri_proof_wait is refused from here on)
+  // ---- decided: from here on the FRI state is this call's
+  nrounds_done = 0; have_deep = false; blob_size = 0;
+  fri_rounds = 0; fri_blowup = blowup_; fri_k = log_arity; fold_final_done = false;
+  Round* r = round_slot(0);
+  r->D = D; r->cap = 0; r->ncoef = D / blowup_; r->ts = ts; r->m = 0; r->dist = false; r->local_store = false; r->S = 0;
+  const int live = vx ? E : 1;
+  r->base_cw = live == 1;
+  auto stage = res.expect();
+  RQ(res.join_side());
+  if (r->cw.ensure(D * E * sizeof(T))) return fail(MS_ERR_NOMEM, "codeword");
+  RQ(ntt_run(ctz64(D), false, src, VL, (size_t)nc, r->cw.template as<T>(), D, (size_t)live));
+  if (live < E) CK(msrt::memset_dev(r->cw.template as<T>() + (size_t)live * D, 0, (size_t)(E - live) * D * sizeof(T), stream));
+  RQ(coset_tree(r));
+  RQ(read_root(r->nodes, r->ts, root0));
+  nrounds_done = 1;
+  return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::fri_fold_folded(const u64* alpha, u8* root) {
+  if (!folded()) return fail(MS_ERR_STATE, "fri_fold_folded outside folded mode (ms_fri_begin_folded)");
+  if (fold_final_done) return fail(MS_ERR_STATE, "fri_fold_folded after fri_fold_final");
+  XE a;
+  if (!alpha || !root || !load_ext(alpha, &a)) return fail(MS_ERR_ARG, "alpha");
+  const size_t A = (size_t)1 << fri_k;
+  const Round* pr = rounds[nrounds_done - 1].get();
+  const size_t Dn = pr->D / A;
+  if (Dn / A < fri_blowup) return fail(MS_ERR_SHAPE, "fri_fold_folded: D_(i+1) < arity * blowup, only the final fold is left");
+  TreeShape ts;
+  RQ(tree_shape(Dn, A, 2, &ts));
+  Round* nr = round_slot(nrounds_done);
+  pr = rounds[nrounds_done - 1].get();
+  if (nr->cw.ensure(Dn * E * sizeof(T))) return fail(MS_ERR_NOMEM, "codeword");
+  nr->D = Dn; nr->cap = 0; nr->ncoef = Dn / fri_blowup; nr->ts = ts; nr->m = 0; nr->dist = false; nr->local_store = false; nr->S = 0; nr->base_cw = false;
+  auto stage = res.expect();
+  RQ(fold_arity_launch(pr, a, nr->cw.template as<T>()));
+  RQ(coset_tree(nr));
+  RQ(read_root(nr->nodes, nr->ts, root));
+  nrounds_done++;
+  return MS_OK;
+}
+
+template <class F>
+int Ctx<F>::fri_fold_final(const u64* alpha, u64* coeffs, size_t cap, size_t* n) {
+  if (!folded()) return fail(MS_ERR_STATE, "fri_fold_final outside folded mode (ms_fri_begin_folded)");
+  if (fold_final_done) return fail(MS_ERR_STATE, "fri_fold_final: the final fold has been made");
+  XE a;
+  if (!alpha || !n || (!coeffs && cap) || !load_ext(alpha, &a)) return fail(MS_ERR_ARG, "fri_fold_final: null argument, or alpha not canonical");
+  const Round* pr = rounds[nrounds_done - 1].get();
+  const size_t DR = pr->D >> fri_k, nfinal = DR / fri_blowup;   // (D_(R-1) >= arity * blowup: nfinal >= 1)
+  *n = nfinal;
+  if (!coeffs) return MS_OK;   // size query
+  if (cap < nfinal * E) return fail(MS_ERR_ARG, "fri_fold_final: buffer too small (the coefficients needed are in *n)");
+  if (d_fold_cw.ensure(DR * E * sizeof(T)) || fold_fin.poly.ensure(DR * E * sizeof(T))) return fail(MS_ERR_NOMEM, "final polynomial");
+  RQ(fold_arity_launch(pr, a, d_fold_cw.template as<T>()));
+  RQ(ntt_run(ctz64(DR), true, d_fold_cw.template as<T>(), DR, DR, fold_fin.poly.template as<T>(), DR, (size_t)E));
+  if (DR > nfinal) {   // nothing at or above nfinal: the codeword was of the degree the domain rule assumes
+    unsigned long long* dres; unsigned long long top = 0;
+    RQ(degree_launch(fold_fin.poly.template as<T>() + nfinal, DR, DR - nfinal, &dres));
+    auto scan = res.expect(dres, false, false);
+    RQ(res.collect(nullptr, nullptr, &top));
+    if (top) return fail(MS_ERR_SHAPE, "fri_fold_final: the folded codeword is of higher degree than D_R / blowup (round 0 was not of the degree its domain assumes)");
+  }
+  RQ(download_widen(fold_fin.poly.template as<T>(), nfinal, DR, E, coeffs));
+  fold_fin.cap = DR; fold_fin.ncoef = nfinal; fold_fin.D = DR;
+  fold_final_done = true;
+  return MS_OK;
 }
 
 // the members this unit defines, for both fields (the other units see declarations only)
@@ -499,7 +630,12 @@ int Ctx<F>::fri_round_codeword_read(int r, u64* out) {
   template int Ctx<FF>::fri_fold_commit(const u64* alpha, u8* root); \
   template int Ctx<FF>::fri_round_info(int r, u64* ncoef, u64* D); \
   template int Ctx<FF>::fri_round_poly_read(int r, u64* out); \
-  template int Ctx<FF>::fri_round_codeword_read(int r, u64* out);
+  template int Ctx<FF>::fri_round_codeword_read(int r, u64* out); \
+  template int Ctx<FF>::fold_arity_launch(const Ctx<FF>::Round* pr, const Ctx<FF>::XE& a, Ctx<FF>::T* dst); \
+  template int Ctx<FF>::coset_tree(Ctx<FF>::Round* r); \
+  template int Ctx<FF>::fri_begin_folded(size_t blowup_, int log_arity, u8* root0); \
+  template int Ctx<FF>::fri_fold_folded(const u64* alpha, u8* root); \
+  template int Ctx<FF>::fri_fold_final(const u64* alpha, u64* coeffs, size_t cap, size_t* n);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

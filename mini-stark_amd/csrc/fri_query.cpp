@@ -292,6 +292,7 @@ int Ctx<F>::query_openings(QueryPlan& q) {
 // memory (ms_pinned_alloc; hipHostMalloc memory is mapped into the device's address space) or device memory - instead of d_blob
 template <class F>
 int Ctx<F>::fri_query(const u64* betas, int nq, u8* ext_out, size_t ext_cap, size_t* ext_len) {
+  RQ(fri_folded_refusal("fri_query"));
   if (nrounds_done != fri_rounds || fri_rounds == 0) return fail(MS_ERR_STATE, "fri_query before the commit phase finished");
   if (!betas || nq < 1) return fail(MS_ERR_ARG, "fri_query");
   QueryPlan q;
@@ -353,6 +354,7 @@ int Ctx<F>::open_view(int tree, int round, OpenView* v) {
     const Round* r = rounds[round].get();
     ts = &r->ts;
     o.base = r->cw.template as<T>(); o.col_stride = 0; o.row_stride = 1; o.limb_stride = r->D; o.width = 1; o.nodes = r->nodes.template as<u32>(); o.el = E;
+    if (folded()) { o.col_stride = r->D >> fri_k; o.width = 1u << fri_k; }   // folded FRI: leaf group j = the coset {j + t D / a}
   } else return fail(MS_ERR_ARG, "tree_open: unknown tree id");
   if (ts->sharded || ts->ic != 2) return fail(MS_ERR_STATE, "tree_open: the tree is distributed over the ranks");
   o.lpn = (u32)ts->lpn; o.ngroups = ts->leaf_num / ts->lpn; o.nlevels = (u32)(ts->levels - 1);
@@ -447,6 +449,7 @@ int Ctx<F>::msfi_plan(const u64* betas, int nq, u64 hd[6], size_t* body, std::ve
 // The compact query phase (MSFI, include/ministark.h): the positions ms_fri_query opens by value, opened by index, and the last round's polynomial
 template <class F>
 int Ctx<F>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  RQ(fri_folded_refusal("fri_query_index"));
   if (nrounds_done != fri_rounds || fri_rounds == 0) return fail(MS_ERR_STATE, "fri_query_index before the commit phase finished");
   if (sh_on) return fail(MS_ERR_STATE, "fri_query_index: not available on a context with sharding on");
   if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "fri_query_index: null argument");
@@ -467,6 +470,7 @@ int Ctx<F>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_
 // every opening and the last round's polynomial in ONE launch.  The device image is the blob behind both headers: final polynomial | FRI paths | LDE paths | validity paths
 template <class F>
 int Ctx<F>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  RQ(fri_folded_refusal("query_linked"));
   if (sh_on) return fail(MS_ERR_STATE, "query_linked: not available on a context with sharding on");
   if (nrounds_done != fri_rounds || fri_rounds == 0) return fail(MS_ERR_STATE, "query_linked before the commit phase finished");
   if (!dpoly_live()) return fail(MS_ERR_STATE, "query_linked: no DEEP polynomial installed (ms_validity_commit, ms_deep_compose, and nothing that kills the validity tree since)");
@@ -500,6 +504,37 @@ int Ctx<F>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* 
   open_jobs(val, rows.data(), nrows, false, body + len_lde + len_stg, jobs);
   memcpy(out, hd, hbytes);
   return open_launch(jobs, body + len_lde + len_stg + len_val, rounds[fri_rounds - 1].get(), out + hbytes);
+}
+
+// The query phase of a folded FRI (MSFF, include/ministark.h): per round and query ONE opening, the leaf group b_(i+1,j) = the coset holding position b_(i,j), and the
+// final polynomial, in one launch.  Each path is what ms_tree_open(MS_TREE_FRI, i, [b_(i+1,j)]) returns
+template <class F>
+int Ctx<F>::fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  if (!folded()) return fail(MS_ERR_STATE, "fri_query_folded outside folded mode (ms_fri_begin_folded)");
+  if (!fold_final_done) return fail(MS_ERR_STATE, "fri_query_folded before fri_fold_final");
+  if (sh_on) return fail(MS_ERR_STATE, "fri_query_folded: not available on a context with sharding on");
+  if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "fri_query_folded: null argument");
+  if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "fri_query_folded: nq outside 1..4096");
+  const size_t R = nrounds_done, nfinal = fold_fin.ncoef;
+  std::vector<OpenView> views(R);
+  size_t body = nfinal * (size_t)E * 8;
+  for (size_t i = 0; i < R; i++) { RQ(open_view(MS_TREE_FRI, (int)i, &views[i])); body += views[i].path_bytes() * (size_t)nq; }
+  const u64 hd[7] = {0x4646534DULL /* 'MSFF' */, (u64)E, (u64)fri_k, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)nfinal};
+  *len = sizeof hd + body;
+  if (!out) return MS_OK;   // size query
+  if (cap < *len) return fail(MS_ERR_ARG, "fri_query_folded: buffer too small (the size needed is in *len)");
+  std::vector<msmerkle::OpenJob<F>> jobs;
+  jobs.reserve(R * (size_t)nq);
+  std::vector<u64> b(betas, betas + nq);
+  size_t pos = nfinal * (size_t)E * 8;
+  for (int j = 0; j < nq; j++) b[j] %= rounds[0]->D;                       // b_(0,j)
+  for (size_t i = 0; i < R; i++) {
+    for (int j = 0; j < nq; j++) b[j] %= rounds[i]->D >> fri_k;            // b_(i+1,j): the leaf group of round i
+    open_jobs(views[i], b.data(), (size_t)nq, false, pos, jobs);
+    pos += views[i].path_bytes() * (size_t)nq;
+  }
+  memcpy(out, hd, sizeof hd);
+  return open_launch(jobs, body, &fold_fin, out + sizeof hd);
 }
 
 // src/merkle.rs:272-288 on a standalone binary tree: leaves de-interleaved to SoA limbs, then the same
@@ -561,7 +596,8 @@ int Ctx<F>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn,
   template int Ctx<FF>::open_view(int tree, int round, Ctx<FF>::OpenView* v); \
   template int Ctx<FF>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len); \
   template int Ctx<FF>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
-  template int Ctx<FF>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
+  template int Ctx<FF>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
+  template int Ctx<FF>::fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -588,6 +588,78 @@ template <class F, int E, int ITEMS_ = 8> struct FriFoldEvalKernel {
   }
 };
 
+// ---------------------------------------------------------------- folded FRI (build-defined; include/ministark.h): the fold by a = 2^K_ in the evaluation domain
+// Output b < m_out = D / a of the next codeword from the a values of the coset {x w^t}, x = w_D^b, w = w_D^(D/a), which lie m_out apart in the source:
+// with P the interpolant of degree < a of those values, P(X) = sum_s p_s X^s, the unnormalised inverse DFT gives u_s = sum_t v_t w^(-ts) = a p_s x^s, and
+//   P(alpha) = (1/a) sum_s u_s (alpha / x)^s
+// is a Horner scan in alpha x^-1 over the DFT outputs.  x^-1 = w_D^(D - b) comes from the plan's tables (as FriFoldEvalKernel::w_tab), the powers of w^-1 and 1/a
+// from the host in table form: no inversion here.  The DFT is decimation in frequency, its outputs left in bit-reversed order and read in that order by the scan;
+// every array index is a compile-time constant (a * E limbs in registers: 32 u32 for BabyBear at a = 8, 16 u64 for Goldilocks).
+// One thread owns one output; lanes hold consecutive b, so each of the a * E loads of a wave is one contiguous run.  a E words read, E written per output.
+template <class F, int E, int K_> struct FriFoldArityKernel {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  static_assert(K_ >= 1 && K_ <= 3, "arity 2, 4 or 8");
+  static constexpr int THREADS = mspoly::THREADS, A = 1 << K_;
+  struct Params {
+    const T* src; size_t src_limb_stride; T* dst; size_t dst_limb_stride;
+    size_t m_out;                                          // D / a outputs
+    const T* tw_lo; const T* tw_hi; u32 lo_bits, log_D;   // F::to_tw(w_D^e) = tw_lo[e & mask] * tw_hi[e >> lo_bits] (the size-D forward plan)
+    X alpha;
+    T wt[4];                                               // table form of w^-j, j < a / 2 (wt[0] is not read)
+    T inv_a;                                               // table form of 1 / a
+  };
+  static MS_HD int nphases(const Params&) { return 1; }
+  static constexpr int bitrev(int s) { int r = 0; for (int k = 0; k < K_; k++) r |= ((s >> k) & 1) << (K_ - 1 - k); return r; }
+  // one decimation-in-frequency stage over blocks of 2 LEN: (x, y) -> (x + y, (x - y) w^(-j a / (2 LEN)))
+  template <int LEN> static MS_DEV void stage(X (&v)[A], const Params& p) {
+#pragma unroll
+    for (int i = 0; i < A; i += 2 * LEN) {
+#pragma unroll
+      for (int j = 0; j < LEN; j++) {
+        const X x = v[i + j], y = v[i + j + LEN];
+        v[i + j] = e_add<F, E>(x, y);
+        X d = e_sub<F, E>(x, y);
+        constexpr int STEP = A / (2 * LEN);
+        if (j * STEP != 0) {
+#pragma unroll
+          for (int l = 0; l < E; l++) d.c[l] = F::mul_tw(d.c[l], p.wt[(j * STEP) & 3]);
+        }
+        v[i + j + LEN] = d;
+      }
+    }
+  }
+  static MS_DEV void phase(int, const Params& p, int bx, int, int tid, int nthreads, unsigned char*) {
+    const size_t b = (size_t)bx * nthreads + tid;
+    if (b >= p.m_out) return;
+    X v[A];
+#pragma unroll
+    for (int t = 0; t < A; t++) {
+#pragma unroll
+      for (int l = 0; l < E; l++) v[t].c[l] = p.src[(size_t)l * p.src_limb_stride + (size_t)t * p.m_out + b];
+    }
+    if constexpr (K_ >= 3) stage<4>(v, p);
+    if constexpr (K_ >= 2) stage<2>(v, p);
+    stage<1>(v, p);
+    const size_t Dm = ((size_t)1 << p.log_D) - 1;
+    const T xinv = w_tab(p, (Dm + 1 - b) & Dm);                        // table form of x^-1 = w_D^(D - b)
+    X y;                                                                // alpha / x
+#pragma unroll
+    for (int l = 0; l < E; l++) y.c[l] = F::mul_tw(p.alpha.c[l], xinv);
+    X r = v[bitrev(A - 1)];
+#pragma unroll
+    for (int s = A - 2; s >= 0; s--) r = e_add<F, E>(e_mul<F>(r, y), v[bitrev(s)]);
+#pragma unroll
+    for (int l = 0; l < E; l++) p.dst[(size_t)l * p.dst_limb_stride + b] = F::mul_tw(r.c[l], p.inv_a);
+  }
+  static MS_DEV T w_tab(const Params& p, size_t e) {
+    T tw = p.tw_lo[e & (((size_t)1 << p.lo_bits) - 1)];
+    const size_t eh = e >> p.lo_bits;
+    if (eh) tw = F::mul_tw(tw, p.tw_hi[eh]);
+    return tw;
+  }
+};
+
 // The THROUGHPUT form of the fold (launches above MS_FOLD_SMALL_MAX outputs): eight outputs per thread like FriFoldEvalKernel<F, E, 8> before it, same values, fewer
 // multiplications per output (Goldilocks: ~28 -> ~19 general-product equivalents, ~16 in the first fold):
 //  * ONE field inversion per workgroup instead of one per thread (a wave executes the 73-product chain whether one lane needs it or all): every thread leaves the

@@ -101,6 +101,22 @@ def fri_index_verify(digest_id, field, zero_display_empty, blowup, roots, z, B, 
     return rc, why.value.decode()
 
 
+def fri_folded_verify(digest_id, field, zero_display_empty, blowup, log_arity, roots, alpha, betas, blob):
+    """msh_fri_folded_verify: the MSFF blob of Context.fri_query_folded against the commit phase.  roots: the R committed rounds' roots (32 bytes each); alpha: the R
+    fold challenges of E limbs (the last one ms_fri_fold_final's); betas: the query values.  Returns (rc, why): rc 1 accepted, 0 rejected, < 0 malformed arguments."""
+    H = _host()
+    u64p = C.POINTER(C.c_uint64)
+    H.msh_fri_folded_verify.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_char_p, C.c_size_t, u64p, u64p, C.c_size_t, C.c_char_p, C.c_size_t,
+                                        C.c_char_p, C.c_size_t]
+    arr = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))   # noqa: E731
+    aa, be = arr(alpha), arr(betas)
+    ptr = lambda a: a.ctypes.data_as(u64p) if a.size else None   # noqa: E731
+    why = C.create_string_buffer(512)
+    rc = H.msh_fri_folded_verify(int(digest_id), int(field), 1 if zero_display_empty else 0, int(blowup), int(log_arity), b"".join(bytes(r) for r in roots), len(roots),
+                                 ptr(aa), ptr(be), be.size, bytes(blob), len(blob), why, 512)
+    return rc, why.value.decode()
+
+
 def deep_link_verify(digest_id, field, zero_display_empty, N, blowup, shift, c, m, lde_root, val_root, z, lists, evals, gamma, betas, msfi, lde_open, val_open):
     """msh_deep_link_verify: FRI's round 0 (the MSFI blob) against the LDE tree and the validity tree.  z / lists as for Context.deep_evals, evals its output, gamma the
     challenge of Context.deep_compose; lde_open / val_open: Context.tree_open of TREE_LDE / TREE_VALIDITY at the rows of window 0's positions (ministark_host.h).

@@ -650,6 +650,87 @@ template <class F, int E> static int fri_index_verify(int digest, int zae, u64 b
   return 1;
 }
 
+// ---- the verifying side of the folded FRI (ministark.h: ms_fri_begin_folded .. ms_fri_query_folded; build-defined) ------------------------------------------------
+// The MSFF blob against the rounds' roots and the fold challenges: 1 accepted, 0 rejected (*why names the step).  Order: header, the length the header fixes, the
+// final polynomial's limbs, every opening round by round, every fold, the final polynomial.  Round 0's values are bound to nothing here
+template <class F, int E> static int fri_folded_verify(int digest, int zae, u64 blowup, int k, const u8* roots, size_t R, const u64* alpha, const u64* betas, size_t nq,
+                                                       const u8* blob, size_t len, std::string* why) {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  const size_t a = (size_t)1 << k;
+  if (len < 56) { *why = "header: MSFF blob shorter than its header"; return 0; }
+  u64 hd[7]; memcpy(hd, blob, 56);
+  if (hd[0] != 0x4646534DULL) { *why = "header: not an MSFF blob (magic)"; return 0; }
+  if (hd[1] != (u64)E || hd[2] != (u64)k || hd[3] != (u64)R || hd[4] != (u64)nq) { *why = "header: E, log_arity, rounds or queries are not the verifier's"; return 0; }
+  const u64 D0 = hd[5], nfinal = hd[6];
+  const unsigned sh = (unsigned)k * (unsigned)R;   // (R <= 64: no overflow; above the two-adicity no domain is that large)
+  if (sh > (unsigned)F::TWO_ADICITY || D0 < 1 || (D0 & (D0 - 1)) || D0 > ((u64)1 << F::TWO_ADICITY) || (D0 >> sh) < blowup) { *why = "header: D_0 is no domain size with arity^R * blowup <= D_0"; return 0; }
+  const u64 DR = D0 >> sh;
+  if (nfinal != DR / blowup) { *why = "header: nfinal is not D_R / blowup"; return 0; }
+  std::vector<u64> height(R), psize(R);
+  size_t want = 56 + (size_t)nfinal * E * 8;
+  for (size_t i = 0; i < R; i++) {
+    u64 groups = D0 >> ((unsigned)k * (unsigned)(i + 1)), h = 0;
+    while (((u64)1 << h) < groups) h++;
+    height[i] = h; psize[i] = 16 + a * E * 8 + 64 * h;
+    want += nq * (size_t)psize[i];
+  }
+  if (len != want) { *why = "header: the blob's length is not the one its header fixes (truncated, or trailing bytes)"; return 0; }
+  const u64* fin = (const u64*)(blob + 56);
+  if (!V::canon(fin, (size_t)nfinal * E)) { *why = "final polynomial: coefficient not canonical"; return 0; }
+  const u8* bp = blob + 56 + (size_t)nfinal * E * 8;
+  // positions b[i * nq + j], i = 0 .. R
+  std::vector<u64> b((R + 1) * nq);
+  for (size_t j = 0; j < nq; j++) b[j] = betas[j] % D0;
+  for (size_t i = 0; i < R; i++) for (size_t j = 0; j < nq; j++) b[(i + 1) * nq + j] = b[i * nq + j] % (D0 >> ((unsigned)k * (unsigned)(i + 1)));
+  std::vector<X> cos(R * nq * a);
+  for (size_t i = 0; i < R; i++)
+    for (size_t j = 0; j < nq; j++) {
+      const std::string at = "round " + std::to_string(i) + " opening: ";
+      const u64 grp = b[(i + 1) * nq + j];
+      u64 nlev; memcpy(&nlev, bp + 8 + a * E * 8, 8);
+      if (nlev != height[i]) { *why = at + "a path's height is not its round's"; return 0; }
+      size_t used = 0; std::string w;
+      if (!check_path_at<F>(digest, E, a, zae, roots + i * 32, bp, (size_t)psize[i], grp * a, &used, &w) || used != psize[i]) { *why = at + w; return 0; }
+      for (size_t t = 0; t < a; t++) cos[(i * nq + j) * a + t] = V::load((const u64*)(bp + 8) + t * E);
+      bp += used;
+    }
+  // the fold of round i's opened coset at alpha_i, by Lagrange interpolation on the coset of x = g_i^(b_(i+1,j)): the value at position b_(i+1,j) of round i + 1
+  auto folded = [&](size_t i, size_t j) {
+    const u64 D = D0 >> ((unsigned)k * (unsigned)i), m = D / a;
+    int lg = 0; while (((u64)1 << lg) < D) lg++;
+    const T g = f_root_of_unity<F>(lg), w = f_pow<F>(g, m);
+    const X al = V::load(alpha + i * E);
+    T xs[8];
+    xs[0] = f_pow<F>(g, b[(i + 1) * nq + j]);
+    for (size_t t = 1; t < a; t++) xs[t] = F::mul(xs[t - 1], w);
+    X acc = e_zero<F, E>();
+    for (size_t t = 0; t < a; t++) {
+      X num = e_one<F, E>(); T den = F::from_u64(1);
+      for (size_t u = 0; u < a; u++) if (u != t) { num = e_mul<F>(num, e_sub<F, E>(al, e_from_base<F, E>(xs[u]))); den = F::mul(den, F::sub(xs[t], xs[u])); }
+      acc = e_add<F, E>(acc, e_mul_base<F, E>(e_mul<F>(cos[(i * nq + j) * a + t], num), f_inv<F>(den)));
+    }
+    return acc;
+  };
+  for (size_t i = 1; i < R; i++) {
+    const u64 Dn = D0 >> ((unsigned)k * (unsigned)(i + 1));
+    for (size_t j = 0; j < nq; j++)
+      if (!e_eq<F, E>(cos[(i * nq + j) * a + b[i * nq + j] / Dn], folded(i - 1, j))) {
+        *why = "round " + std::to_string(i) + " fold: the opened value is not the fold of the previous round's coset"; return 0;
+      }
+  }
+  int lgR = 0; while (((u64)1 << lgR) < DR) lgR++;
+  const T gR = f_root_of_unity<F>(lgR);
+  for (size_t j = 0; j < nq; j++) {
+    const X x = e_from_base<F, E>(f_pow<F>(gR, b[R * nq + j]));
+    X y = e_zero<F, E>();
+    for (size_t n = nfinal; n-- > 0;) y = e_add<F, E>(e_mul<F>(y, x), V::load(fin + n * E));
+    if (!e_eq<F, E>(y, folded(R - 1, j))) { *why = "final polynomial: its value is not the fold of the last round's coset"; return 0; }
+  }
+  return 1;
+}
+
 // ---- the verifying side of the DEEP stage (ministark.h: ms_validity_commit, ms_deep_compose; build-defined) -------------------------------------------------------
 // V(z) = sum_k z^(kN) sum_l u_l V_(k,l)(z) from the m = ve * nchunks chunk evaluations (chunk column k * ve + l, E limbs each); u_l = the l-th basis element of K
 template <class F, int E> static void validity_from_chunks(u32 ve, u32 nchunks, u64 N, const u64* z, const u64* ev, u64* out) {
@@ -1819,6 +1900,20 @@ int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, u64 b
     std::string w;
     const int rc = field == MS_FIELD_GOLDILOCKS ? fri_index_verify<GL, 2>(digest_id, zero_display_empty, blowup, roots, rounds, z, B, alpha, betas, nq, blob, len, &w)
                                                 : fri_index_verify<BB, 4>(digest_id, zero_display_empty, blowup, roots, rounds, z, B, alpha, betas, nq, blob, len, &w);
+    return set_why(why, why_cap, w.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+int msh_fri_folded_verify(int digest_id, int field, int zero_display_empty, u64 blowup, int log_arity, const u8* roots, size_t rounds, const u64* alpha, const u64* betas,
+                          size_t nq, const u8* blob, size_t len, char* why, size_t why_cap) {
+  if (!known_digest(digest_id) || (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR)) return set_why(why, why_cap, "unknown digest or field", MS_ERR_ARG);
+  if (!roots || !alpha || !betas || !blob || rounds < 1 || rounds > 64 || nq < 1 || nq > 4096 || !blowup || (blowup & (blowup - 1)) || log_arity < 1 || log_arity > 3)
+    return set_why(why, why_cap, "null argument, or rounds, queries, blowup or log_arity out of range", MS_ERR_ARG);
+  if (!(field == MS_FIELD_GOLDILOCKS ? Verifier<GL, 2>::canon(alpha, rounds * 2) : Verifier<BB, 4>::canon(alpha, rounds * 4)))
+    return set_why(why, why_cap, "fold challenge not canonical", MS_ERR_ARG);
+  try {
+    std::string w;
+    const int rc = field == MS_FIELD_GOLDILOCKS ? fri_folded_verify<GL, 2>(digest_id, zero_display_empty, blowup, log_arity, roots, rounds, alpha, betas, nq, blob, len, &w)
+                                                : fri_folded_verify<BB, 4>(digest_id, zero_display_empty, blowup, log_arity, roots, rounds, alpha, betas, nq, blob, len, &w);
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }

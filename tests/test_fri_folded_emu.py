@@ -1,0 +1,108 @@
+"""Folded FRI (ms_fri_begin_folded, ms_fri_fold_folded, ms_fri_fold_final, ms_fri_query_folded; include/ministark.h - build-defined) and its verifying side
+(msh_fri_folded_verify) on the emulation build of the kernel code (tests/emu, -DMS_EMU), against tests/pyref_fri_folded.py.  The same cases run on the HIP build in
+tests/test_fri_folded_gpu.py (-m gpu), which adds the 2^16-point shape and the launch counts."""
+import os
+import subprocess
+
+import pytest
+
+import mini_stark_amd as ms
+import fri_folded_cases as fc
+from mini_stark_amd.host import build_host_library
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+EMU = os.path.join(HERE, "emu", "libministark_emu.so")
+SHA = fc.SHA
+
+
+@pytest.fixture(scope="module")
+def make():
+    subprocess.check_call(["make", "-C", os.path.join(HERE, "emu")], stdout=subprocess.DEVNULL)
+    build_host_library()
+
+    def mk(field, flags, env=None):
+        old = {k: os.environ.get(k) for k in (env or {})}
+        os.environ.update(env or {})
+        try:
+            return ms.Context(field, flags=flags, lib_path=EMU)   # the MS_* variables are read by ms_create
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+    return mk
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("shape", fc.SHAPES, ids=lambda s: "%dx%d" % s)
+def test_fold_both_restatements(make, shape, k, field):
+    fc.case_fold(make, SHA, field, shape[0], shape[1], k, "mix")
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("kind", fc.SOURCES[1:])
+def test_fold_other_round0_sources(make, kind, k, field):
+    fc.case_fold(make, SHA, field, 64, 8, k, kind)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_edge_challenges(make, k, field):
+    fc.case_edge_alphas(make, SHA, field, k)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+@pytest.mark.parametrize("d", fc.DIGESTS)
+def test_trees_and_blob(make, d, k, field):
+    fc.case_trees_and_blob(make, d, field, 64, 8, k)
+
+
+@pytest.mark.parametrize("d", [fc.ro.BLAKE2S, fc.ro.SHA3_256])
+def test_trees_and_blob_other_digests(make, d):
+    fc.case_trees_and_blob(make, d, 0, 64, 8, 2)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("shape", [fc.SHAPES[0], fc.SHAPES[2]], ids=lambda s: "%dx%d" % s)
+def test_trees_and_blob_other_shapes(make, shape, field):
+    fc.case_trees_and_blob(make, SHA, field, shape[0], shape[1], 2 if shape[0] > 8 else 3)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_verifier_and_tampering(make, k, field):
+    fc.case_verifier(make, SHA, field, k)
+
+
+@pytest.mark.parametrize("d", fc.DIGESTS[1:])
+def test_verifier_other_digests(make, d):
+    fc.case_verifier(make, d, 0, 2)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_state_and_refusals(make, k, field):
+    fc.case_refusals(make, SHA, field, k)
+
+
+def test_sharded_context_refuses(make, monkeypatch):
+    monkeypatch.setenv("MS_SHARD_WORLD1", "1")
+    monkeypatch.setenv("MS_SHARD_MIN_LEAVES", "16")
+    fc.case_sharded(fc.ctx_of(make, SHA))
+
+
+@pytest.mark.parametrize("field", [0, 1])
+def test_switching_between_legacy_and_folded(make, field):
+    fc.case_switching(make, SHA, field)
+
+
+@pytest.mark.parametrize("field", [0, 1])
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_latency_context(make, k, field):
+    fc.case_fold(make, SHA, field, 64, 8, k, "mix", extra=fc.LATENCY)
+    fc.case_fold(make, SHA, field, 64, 8, k, "deep", extra=fc.LATENCY)
+    fc.case_trees_and_blob(make, SHA, field, 64, 8, k, extra=fc.LATENCY)
