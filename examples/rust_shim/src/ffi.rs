@@ -113,6 +113,9 @@ extern "C" {
     pub fn ms_poly_read(ctx: *mut ms_ctx, i: c_int, out: *mut u64) -> c_int;
     pub fn ms_lde_commit(ctx: *mut ms_ctx, blowup: usize, shift: u64, lpn: usize, root: *mut u8) -> c_int;
     pub fn ms_lde_commit_stage(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;
+    // coset-grouped row trees (build-defined): one leaf group per coset of the folded FRI's round 0
+    pub fn ms_lde_commit_coset(ctx: *mut ms_ctx, blowup: usize, shift: u64, log_arity: c_int, root: *mut u8) -> c_int;
+    pub fn ms_lde_commit_stage_coset(ctx: *mut ms_ctx, log_arity: c_int, root: *mut u8) -> c_int;
     pub fn ms_lde_read(ctx: *mut ms_ctx, out_rowmajor: *mut u64) -> c_int;
     pub fn ms_mix(ctx: *mut ms_ctx, r: u64) -> c_int;
     pub fn ms_validity_read(ctx: *mut ms_ctx, out: *mut u64) -> c_int;
@@ -151,9 +154,11 @@ extern "C" {
     pub fn ms_fri_fold_folded(ctx: *mut ms_ctx, alpha: *const u64, root: *mut u8) -> c_int;
     pub fn ms_fri_fold_final(ctx: *mut ms_ctx, alpha: *const u64, coeffs: *mut u64, cap: usize, n: *mut usize) -> c_int;
     pub fn ms_fri_query_folded(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
+    pub fn ms_query_linked_folded(ctx: *mut ms_ctx, betas: *const u64, nq: c_int, out: *mut u8, cap: usize, len: *mut usize) -> c_int;
     // ---- the composition commitment and the DEEP stage (build-defined): the tree over the validity polynomial's chunk columns on the LDE coset; the claimed evaluations;
     // D' = sum_t (A_t - A_t(z_t)) / (x - z_t) on the coset's own variable, which ms_fri_begin then starts from
     pub fn ms_validity_commit(ctx: *mut ms_ctx, lpn: usize, root: *mut u8) -> c_int;
+    pub fn ms_validity_commit_coset(ctx: *mut ms_ctx, log_arity: c_int, root: *mut u8) -> c_int;
     pub fn ms_deep_evals(ctx: *mut ms_ctx, deep: *const MsDeep, evals: *mut u64) -> c_int;
     pub fn ms_deep_compose(ctx: *mut ms_ctx, deep: *const MsDeep, gamma: *const u64) -> c_int;
     pub fn ms_deep_len(ctx: *const ms_ctx) -> c_int;

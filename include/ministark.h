@@ -268,6 +268,23 @@ int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_
  * After a refusal or failure the context is as if the call had not been made (the LDE matrix may have moved to a larger buffer, with its columns). */
 int ms_lde_commit_stage(ms_ctx* ctx, size_t lpn, uint8_t root[32]);
 int ms_lde_read(ms_ctx* ctx, uint64_t* out_rowmajor /* L*c; c = c0 + c1 once a stage is committed */);
+/* ---- coset-grouped row trees (BUILD-DEFINED) ---------------------------------------------------------------------------------------------------------------
+ * ms_lde_commit_coset, ms_lde_commit_stage_coset and ms_validity_commit_coset are ms_lde_commit, ms_lde_commit_stage and ms_validity_commit in every respect but the
+ * tree: the transforms, the matrix in device memory, ms_lde_read, the state they set and the state they kill are the plain calls'.  With k = log_arity in 1..3 and
+ * a = 2^k the tree has L / a leaf groups; group j holds, for col = 0 .. c - 1 and then t = 0 .. a - 1, column col of row j + t L / a - element col * a + t of the group
+ * - where c is the number of columns of that tree (c0, c1, or the m chunk columns).  These are the LDE rows under one coset of the folded FRI's round 0
+ * (ms_fri_begin_folded with the same k), so a query of a linked proof opens ONE path per tree.  Leaves are hashed as every row leaf is: one limb per element, ic = 2,
+ * the context's digest and zero_as_empty; lpn = a * c.  The context remembers k per tree: ms_tree_open on such a tree opens leaf group index < L / a, with
+ * leaf_index = index * a * c and the a * c values in hashed order; a later plain commit makes the tree plain again.  ms_query_linked answers MS_ERR_STATE on coset trees
+ * (they do not hold one row per leaf group); ms_query_linked_folded is their query phase.
+ * Refusals, all decided before anything is launched, after which the context is as if the call had not been made: MS_ERR_ARG log_arity outside 1..3; MS_ERR_SHAPE
+ * L < 2a; MS_ERR_STATE a context with sharding on; MS_ERR_STATE (ms_lde_commit_coset) an LDE that would have virtual linear columns - the view has a * c "columns", the
+ * specification table c, and linked proofs never have such columns; MS_ERR_STATE (ms_lde_commit_stage_coset) a live LDE tree that is not a coset tree of the same k.
+ * BLAKE3: a leaf message above 1024 bytes runs the multi-chunk leaf kernels, one that may exceed 16 KiB is MS_ERR_ARG, as for every leaf group.
+ * Not supported: sharded contexts, virtual columns under coset leaves.  Measured inside whole proofs only: MSLP v3 in ministark_host.h. */
+int ms_lde_commit_coset(ms_ctx* ctx, size_t blowup, uint64_t shift, int log_arity, uint8_t root[32]);
+int ms_lde_commit_stage_coset(ms_ctx* ctx, int log_arity, uint8_t root[32]);
+int ms_validity_commit_coset(ms_ctx* ctx, int log_arity, uint8_t root[32]);
 /* 1.3  validity = sum_i r^i f_i (remainder of divide_by_vanishing_poly; quirk Q1).  starks.rs:108-119. */
 int ms_mix(ms_ctx* ctx, uint64_t r);
 int ms_validity_read(ms_ctx* ctx, uint64_t* out /* ms_validity_len(ctx): N, 2N after ms_mix_cubic, VL after ms_mix_terms / ms_mix_air; times ms_validity_ext(ctx) limbs after ms_mix_air_ext */);
@@ -582,7 +599,7 @@ int ms_query_linked(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, si
  *   nfinal * E limbs                                                  the final polynomial
  *   for round i = 0 .. R - 1, for query j in order:                   MerklePath of leaf group b_(i+1,j) of round i
  * Each path is, by definition, the bytes ms_tree_open(MS_TREE_FRI, i, [b_(i+1,j)]) returns.  Verifying side: msh_fri_folded_verify (ministark_host.h).  Round 0's
- * values are bound to nothing here, as in MSFI.
+ * values are bound to nothing by the MSFF alone, as in MSFI: ms_query_linked_folded and msh_deep_link_verify_folded bind them to the coset row trees.
  * Mode rules.  In folded mode ms_fri_deep, ms_fri_fold_commit, ms_fri_query[_into], ms_fri_proof_read[_async], ms_fri_proof_wait, ms_fri_query_index, ms_query_linked
  * and ms_fri_round_poly_read return MS_ERR_STATE (ms_fri_proof_size is 0); outside it the three fold and query calls above do.  Either ms_fri_begin* starts afresh,
  * and whatever clears the FRI state (a mix stage, ms_trace_commit, ms_set_shard) clears the mode with it.  In folded mode ms_fri_round_info(i) reports D_i and, as
@@ -598,6 +615,20 @@ int ms_fri_begin_folded(ms_ctx* ctx, size_t blowup, int log_arity, uint8_t root0
 int ms_fri_fold_folded(ms_ctx* ctx, const uint64_t* alpha /* E limbs */, uint8_t root[32]);              /* commits round i + 1 */
 int ms_fri_fold_final(ms_ctx* ctx, const uint64_t* alpha, uint64_t* coeffs, size_t cap /* u64 words */, size_t* n /* nfinal */);
 int ms_fri_query_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
+
+/* The WHOLE query phase of a linked proof over a folded FRI (MSLP v3, ministark_host.h) in one call and ONE launch: one job table, one launch of R * nq + (2 or 3) * nq
+ * openings plus the final polynomial's workgroups, one read-back, one stream synchronisation.  Valid when the context is in folded mode with ms_fri_fold_final behind
+ * it, a DEEP polynomial is installed, D_0 <= L and D_0 | L, and the LDE tree, the validity tree and a live staged tree are coset trees whose k is the FRI's; otherwise
+ * MS_ERR_STATE (also on a context with sharding on).  Argument rules, size query and cap rule as ms_fri_query_folded; the context is unchanged.
+ * With s = L / D_0 and q_j = (betas[j] mod D_0) mod D_1, query j opens leaf group q_j * s of every row tree: round 0's coset {q_j + t D_1} lies over the LDE rows
+ * q_j s + t L / a.  MSLF layout, u64 little-endian words:
+ *   'MSLF' (0x464C534D) | len_msff | len_lde | len_stg (0 without a staged tree) | len_val
+ *   MSFF blob            exactly the bytes ms_fri_query_folded(betas) returns
+ *   LDE openings         exactly the bytes ms_tree_open(MS_TREE_LDE, 0, groups) returns
+ *   staged openings      exactly the bytes ms_tree_open(MS_TREE_LDE_STAGED, 0, groups) returns, or nothing
+ *   validity openings    exactly the bytes ms_tree_open(MS_TREE_VALIDITY, 0, groups) returns
+ * The equality with the separate calls is the definition.  Verifying side: msh_deep_link_verify_folded binds all a slots of round 0's openings to the row trees. */
+int ms_query_linked_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len);
 
 /* ---- proof-of-work grinding (BUILD-DEFINED; the reference has no counterpart) ---------------------------------------------------------------------------------
  * Between the last ms_fri_fold_commit and ms_fri_query a prover may spend `bits` bits of work on a nonce, and draw that many bits of security fewer from the FRI

@@ -110,7 +110,8 @@ int msh_fri_index_verify(int digest_id, int field, int zero_display_empty, uint6
  * ext = E, leaf group b_(i+1,j)) under round i's root; then for i >= 1 that slot b_(i,j) / D_(i+1) of the opened coset is the fold of round i - 1's coset at
  * alpha_(i-1) - the value at alpha_(i-1) of the polynomial of degree < a through the coset's a values, the coset being x w^t with x = g_(i-1)^(b_(i,j)),
  * w = g_(i-1)^(D_(i-1) / a) -; then that the fold of round R - 1's coset at alpha_(R-1) is the final polynomial at g_R^(b_(R,j)).
- * ROUND 0'S VALUES ARE BOUND TO NOTHING HERE, as in MSFI: what ties them to a trace is a DEEP link over the a LDE rows under a round-0 coset (not built yet).
+ * Round 0's values are bound to nothing by this check alone, as in MSFI: what ties them to a trace is msh_deep_link_verify_folded, over the a LDE rows under each
+ * round-0 coset.
  * 1 accepted, 0 rejected (`why` names the step: "header: ..", "round i opening: ..", "round i fold: ..", "final polynomial: .."), < 0 malformed arguments (a null
  * pointer, an unknown digest id or field, rounds outside 1..64, nq outside 1..4096, a blowup that is zero or no power of two, log_arity outside 1..3, an alpha limb that is not canonical). */
 int msh_fri_folded_verify(int digest_id, int field, int zero_display_empty, uint64_t blowup, int log_arity, const uint8_t* roots, size_t rounds, const uint64_t* alpha,
@@ -272,6 +273,45 @@ int msh_stark_prove_linked_aux(msh_stark* h, const uint64_t* trace_host, const v
                                uint32_t nargs, uint32_t nch, uint32_t fri_rounds /* 0: the configuration's */);
 int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, uint32_t fri_rounds,
                                 const uint8_t* data, size_t len, int zero_display_empty, char* why, size_t why_cap);
+/* ---- THE LINK OF A FOLDED FRI TO COSET-GROUPED ROW TREES (build-defined) ------------------------------------------------------------------------------------------------
+ * msh_deep_link_verify_folded: what msh_deep_link_verify[_staged] is to an MSFI, for the MSFF of a folded FRI at arity a = 2^log_arity over row trees committed by
+ * ms_lde_commit_coset, ms_lde_commit_stage_coset and ms_validity_commit_coset at the same log_arity (ministark.h).  c0 LDE columns, c1 staged columns (stg_root NULL iff
+ * c1 = 0; stg_open is then not read), m chunk columns; deep / evals / gamma as for msh_deep_link_verify; msff the blob of ms_fri_query_folded for `betas`; the three
+ * opening sections those of ms_query_linked_folded.  D_0 comes from the MSFF header: a power of two that divides L = blowup * N, a <= D_0 <= L.  With s = L / D_0,
+ * D_1 = D_0 / a and q_j = (betas[j] mod D_0) mod D_1 every row path is checked positionally under its root (msh_merkle_path_check_index with lpn = a * c, leaf group
+ * q_j s) and each section must be consumed exactly.  For EVERY t < a, at x = shift g_L^(q_j s + t L / a), it recomputes
+ *   sum_n gamma^n (F_(pt_poly[n])(x) - evals[n]) / (x - z_t(n)),   F_n from slot col * a + t of the proper tree's leaf group,
+ * and requires it to equal slot t (E limbs) of round 0's path for query j in the MSFF: all a slots feed the fold, so all a slots are bound.  It does NOT repeat
+ * msh_fri_folded_verify (run it on the same MSFF) nor the AIR identity at z.  1 accepted, 0 rejected (`why` names the step: "LDE opening: ..", "staged opening: ..",
+ * "validity opening: ..", "DEEP link: ..", "MSFF .."), < 0 malformed arguments. */
+int msh_deep_link_verify_folded(int digest_id, int field, int zero_display_empty, uint64_t N, uint64_t blowup, uint64_t shift, int log_arity, uint32_t c0, uint32_t c1,
+                                uint32_t m, const uint8_t lde_root[32], const uint8_t stg_root[32] /* NULL iff c1 = 0 */, const uint8_t val_root[32], const ms_deep* deep,
+                                const uint64_t* evals, const uint64_t* gamma, const uint64_t* betas, size_t nq, const uint8_t* msff, size_t msff_len, const uint8_t* lde_open,
+                                size_t lde_len, const uint8_t* stg_open, size_t stg_len, const uint8_t* val_open, size_t val_len, char* why, size_t why_cap);
+/* ---- LINKED PROOFS OVER A FOLDED FRI: MSLP v3 (build-defined) --------------------------------------------------------------------------------------------------------
+ * A v3 proof is a v2 proof (v1 when nargs = 0: args NULL, nch 0) whose three row commitments are the `_coset` ones at k = log_arity and whose FRI is the folded one at
+ * arity a = 2^k, R = fri_folds folds (0: floor(log2 N / k)).  THE STATEMENT is v2's.
+ * TRANSCRIPT, domain separator domsep + "/linked/v3" - v2's steps with these changes:
+ *   1. the statement words are field, digest id, N, w, blowup, k, R, nq, grinding bits, nargs, nch; msh_air_encode(air) follows, then msh_aux_encode(args) when nargs > 0.
+ *   2. ms_lde_commit_coset, (nargs > 0: the challenge draw, ms_aux_running_staged per argument,) ms_lde_commit_stage_coset, ms_validity_commit_coset, all at k.
+ *   3. ms_fri_begin_folded(blowup, k): absorb root 0; for i < R - 1 draw alpha_i, ms_fri_fold_folded, absorb root i + 1; draw alpha_(R-1), ms_fri_fold_final, absorb the
+ *      nfinal * E limbs of the final polynomial as u64 little-endian.
+ *   4. grind as v1; draw nq = fri_queries betas; ms_query_linked_folded.
+ * A stage's MS_ERR_SHAPE is returned as it is - a trace that violates the AIR, an argument that does not hold, a DEEP polynomial so short that R folds do not fit - and
+ * the slot is then left empty.
+ * MSLP v3, little-endian:
+ *   u32 'MSLP' | 3 | E | k | c0 | c1 | m | npts | R | nq | grinding bits | nargs | nch | u64 N | blowup | D_0 | len(arthur) | len(MSLF)
+ *   arthur: trace root, LDE root, staged root (nargs > 0), validity root, evaluations, the R round roots, the final polynomial, nonce | the MSLF blob (ministark.h)
+ * msh_stark_verify_linked_folded trusts no header field: it compares everything the statement and its own rebuilt program fix; D_0 must be the MSFF's own, a power of two
+ * that divides L, and >= a^R * blowup; lengths must fit exactly, with no trailing bytes, and every limb must be canonical; it replays the transcript with both redraw
+ * rules and requires the final polynomial in arthur to equal the one in the MSFF ("transcript: .."); then it runs, in order, the proof of work, the AIR identity at z,
+ * msh_fri_folded_verify and msh_deep_link_verify_folded.  `why` prefixes: v2's.  A v1 or v2 verifier given v3 bytes answers "header: ..", and so does a v3 verifier
+ * given v1 or v2 bytes.  The proof goes into the linked slot (msh_linked_proof).  The Python mirror writes the same bytes (Stark.prove_air(.., log_arity=k)).
+ * Measured (tools/linked_folded_bench.py, profiles/linked_folded.json; one paired run on one MI355X, Goldilocks, 2^20 rows, six trace columns, blowup 8, 2 queries, one context, legs alternated x 5): a v1 linked proof 11.30 ms (9.39 ms of kernel time, 221 launches); v3 at arity 2 / 4 / 8 (R = 20 / 10 / 6) 9.36 / 7.02 / 6.31 ms (7.77 / 5.66 / 5.05 ms, 186 / 121 / 96 launches): 0.83 / 0.62 / 0.56 of v1.  Inner hashing 2.87 ms in v1 against 2.70 / 1.42 / 0.97 ms, leaf hashing 2.51 against 2.76 / 1.98 / 1.85 ms.  Proof bytes 83 060 against 41 052 / 23 772 / 18 364; with 32 queries 1 300 340 against 639 132 / 367 452 / 281 404.  Only the paired ratios of this run mean anything. */
+int msh_stark_prove_linked_folded(msh_stark* h, const uint64_t* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args /* NULL iff nargs = 0 */,
+                                  uint32_t nargs, uint32_t nch, int log_arity, uint32_t fri_folds /* 0: floor(log2 N / log_arity) */);
+int msh_stark_verify_linked_folded(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, int log_arity,
+                                   uint32_t fri_folds, const uint8_t* data, size_t len, int zero_display_empty, char* why, size_t why_cap);
 /* the two redraw rules, for a caller that keeps its own transcript: 1 the draw stands, 0 draw again, < 0 an unknown field or a null z */
 int msh_linked_shift_ok(int field, uint64_t L, uint64_t shift);
 int msh_linked_z_ok(int field, const uint64_t* z /* E limbs */);

@@ -75,6 +75,11 @@ def load_library(path=None):
         L.ms_fri_fold_folded.argtypes = [C.c_void_p, _u64p, C.POINTER(C.c_uint8 * 32)]
         L.ms_fri_fold_final.argtypes = [C.c_void_p, _u64p, _u64p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ms_fri_query_folded.argtypes = [C.c_void_p, _u64p, C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "ms_query_linked_folded"):   # coset-grouped row trees and the v3 query phase (likewise)
+        L.ms_lde_commit_coset.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_int, C.POINTER(C.c_uint8 * 32)]
+        L.ms_lde_commit_stage_coset.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8 * 32)]
+        L.ms_validity_commit_coset.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8 * 32)]
+        L.ms_query_linked_folded.argtypes = [C.c_void_p, _u64p, C.c_int, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     _LIBS[path] = L
     return L
 
@@ -602,6 +607,12 @@ class Context:
         rc = self.L.ms_lde_commit_stage(self.h, C.c_size_t(lpn), root)
         return rc, bytes(root)
 
+    def lde_commit_stage_coset(self, log_arity):
+        """ms_lde_commit_stage_coset: ms_lde_commit_stage with the second tree over coset leaf groups (the live LDE tree's own log_arity) -> (rc, root)"""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_lde_commit_stage_coset(self.h, C.c_int(log_arity), root)
+        return rc, bytes(root)
+
     def aux_count(self):
         return self.L.ms_aux_count(self.h)
 
@@ -628,6 +639,14 @@ class Context:
     def lde_commit(self, blowup, shift, lpn):
         root = (C.c_uint8 * 32)()
         rc = self.L.ms_lde_commit(self.h, C.c_size_t(blowup), C.c_uint64(shift), C.c_size_t(lpn), root)
+        if rc == 0:
+            self.Lsize = self.N * blowup
+        return rc, bytes(root)
+
+    def lde_commit_coset(self, blowup, shift, log_arity):
+        """ms_lde_commit_coset: ms_lde_commit with the tree over L / 2^log_arity coset leaf groups (group j: the rows j + t L / a, column-major) -> (rc, root)"""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_lde_commit_coset(self.h, C.c_size_t(blowup), C.c_uint64(shift), C.c_int(log_arity), root)
         if rc == 0:
             self.Lsize = self.N * blowup
         return rc, bytes(root)
@@ -829,6 +848,12 @@ class Context:
         rc = self.L.ms_validity_commit(self.h, C.c_size_t(lpn), root)
         return rc, bytes(root)
 
+    def validity_commit_coset(self, log_arity):
+        """ms_validity_commit_coset: ms_validity_commit with the tree over coset leaf groups -> (rc, root)"""
+        root = (C.c_uint8 * 32)()
+        rc = self.L.ms_validity_commit_coset(self.h, C.c_int(log_arity), root)
+        return rc, bytes(root)
+
     def deep_evals(self, z, lists):
         """ms_deep_evals: (rc, evals) with evals[n] = F_{pt_poly[n]}(z_t), E limbs each, in entry order (deep_struct describes z and lists)."""
         s, keep = deep_struct(z, lists)
@@ -855,6 +880,12 @@ class Context:
         """ms_query_linked: the whole query phase of a linked proof in one launch, the MSLQ blob (MSFI, then the LDE and validity rows under round 0's positions)."""
         b, bp = _u64(betas)
         return self._sized_bytes(lambda out, cap, n: self.L.ms_query_linked(self.h, bp, C.c_int(b.size), out, cap, n))
+
+    def query_linked_folded(self, betas) -> bytes:
+        """ms_query_linked_folded: the whole query phase of a linked proof over a folded FRI in one launch, the MSLF blob (MSFF, then one coset leaf group per query
+        of the LDE, staged and validity trees)."""
+        b, bp = _u64(betas)
+        return self._sized_bytes(lambda out, cap, n: self.L.ms_query_linked_folded(self.h, bp, C.c_int(b.size), out, cap, n))
 
     # ---- standalone ----------------------------------------------------------------
     def merkle_commit(self, leafs, ext=1, lpn=2, ic=2):

@@ -180,6 +180,8 @@ int ms_polys_count(const ms_ctx* ctx) { MS_ENTRY(ctx, B(ctx)->polys_count()); }
 int ms_poly_read(ms_ctx* ctx, int i, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->poly_read(i, out)); }
 int ms_lde_commit(ms_ctx* ctx, size_t blowup, uint64_t shift, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit(blowup, shift, lpn, root)); }
 int ms_lde_commit_stage(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit_stage(lpn, root)); }
+int ms_lde_commit_coset(ms_ctx* ctx, size_t blowup, uint64_t shift, int log_arity, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit_coset(blowup, shift, log_arity, root)); }
+int ms_lde_commit_stage_coset(ms_ctx* ctx, int log_arity, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->lde_commit_stage_coset(log_arity, root)); }
 int ms_lde_read(ms_ctx* ctx, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->lde_read(out)); }
 int ms_mix(ms_ctx* ctx, uint64_t r) { MS_ENTRY(ctx, B(ctx)->mix(r)); }
 int ms_validity_read(ms_ctx* ctx, uint64_t* out) { MS_ENTRY(ctx, B(ctx)->validity_read(out)); }
@@ -224,7 +226,9 @@ int ms_fri_begin_folded(ms_ctx* ctx, size_t blowup, int log_arity, uint8_t root0
 int ms_fri_fold_folded(ms_ctx* ctx, const uint64_t* alpha, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->fri_fold_folded(alpha, root)); }
 int ms_fri_fold_final(ms_ctx* ctx, const uint64_t* alpha, uint64_t* coeffs, size_t cap, size_t* n) { MS_ENTRY(ctx, B(ctx)->fri_fold_final(alpha, coeffs, cap, n)); }
 int ms_fri_query_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->fri_query_folded(betas, nq, out, cap, len)); }
+int ms_query_linked_folded(ms_ctx* ctx, const uint64_t* betas, int nq, uint8_t* out, size_t cap, size_t* len) { MS_ENTRY(ctx, B(ctx)->query_linked_folded(betas, nq, out, cap, len)); }
 int ms_validity_commit(ms_ctx* ctx, size_t lpn, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->validity_commit(lpn, root)); }
+int ms_validity_commit_coset(ms_ctx* ctx, int log_arity, uint8_t root[32]) { MS_ENTRY(ctx, B(ctx)->validity_commit_coset(log_arity, root)); }
 int ms_deep_evals(ms_ctx* ctx, const ms_deep* deep, uint64_t* evals) { MS_ENTRY(ctx, B(ctx)->deep_evals(deep, evals)); }
 int ms_deep_compose(ms_ctx* ctx, const ms_deep* deep, const uint64_t* gamma) { MS_ENTRY(ctx, B(ctx)->deep_compose(deep, gamma)); }
 int ms_deep_len(const ms_ctx* ctx) { return ctx ? B(ctx)->deep_len_() : 0; }

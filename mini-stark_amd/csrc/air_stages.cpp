@@ -140,8 +140,56 @@ int Ctx<F>::lde_compute_sharded(size_t blowup_, u64 shift) {
   return 0;
 }
 
+// what the three `_coset` commits ask of k and the domain, before anything else is decided
 template <class F>
-int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
+int Ctx<F>::coset_arity_check(const char* who, int k, size_t L_) {
+  if (k < 1 || k > 3) return fail(MS_ERR_ARG, std::string(who) + ": log_arity outside 1..3");
+  if (sh_on) return fail(MS_ERR_STATE, std::string(who) + ": not available on a context with sharding on");
+  if (L_ < ((size_t)2 << k)) return fail(MS_ERR_SHAPE, std::string(who) + ": fewer than two leaf groups (L < 2 * arity)");
+  return 0;
+}
+
+// leaf_hash's BLAKE3 rule for a leaf group of lpn one-limb elements, asked before a coset commit changes anything: the message may not exceed 16 KiB
+template <class F>
+int Ctx<F>::coset_leaf_check(const char* who, size_t lpn) {
+  if (digest == MS_DIGEST_BLAKE3 && (lpn > 16384 || lpn * (size_t)F::MAX_DIGITS > 16384))
+    return fail(MS_ERR_ARG, std::string(who) + ": BLAKE3: a leaf group's message may exceed 16384 bytes (arity x columns x longest decimal)");
+  return 0;
+}
+
+// finish_linear_columns' decision for the polynomials as they stand: would ms_lde_commit leave the linear columns to the leaf kernel?
+template <class F>
+bool Ctx<F>::linear_columns_would_be_virtual() const {
+  const size_t c = (size_t)npolys;
+  if (!lde_linear) return false;
+  bool any = false, simple = lde_virtual < 0 ? c >= 16 : lde_virtual != 0;
+  for (size_t i = 0; i < c; i++) {
+    const Lin& li = poly_lin[i];
+    if (li.idx.empty()) continue;
+    any = true;
+    if (li.idx.size() > (size_t)msmerkle::LIN_MAXT) simple = false;
+    for (int ix : li.idx) if (ix < 0 || (size_t)ix >= c || !poly_lin[ix].idx.empty()) simple = false;
+  }
+  return any && simple && c * sizeof(msmerkle::LinColSpec) <= pinned_cap - 8192;
+}
+
+template <class F>
+int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) { return lde_commit_k(blowup_, shift, lpn, 0, root); }
+
+// ms_lde_commit_coset: ms_lde_commit in every respect but the tree (ctx.hpp)
+template <class F>
+int Ctx<F>::lde_commit_coset(size_t blowup_, u64 shift, int log_arity, u8* root) {
+  if (!have_polys) return fail(MS_ERR_STATE, "lde_commit_coset before interpolate");
+  if (!root || !blowup_ || !is_pow2(blowup_) || shift == 0 || shift >= F::P) return fail(MS_ERR_ARG, "lde_commit_coset: bad blowup/shift");
+  RQ(coset_arity_check("lde_commit_coset", log_arity, N * blowup_));
+  RQ(coset_leaf_check("lde_commit_coset", (size_t)npolys << log_arity));
+  if (linear_columns_would_be_virtual()) return fail(MS_ERR_STATE, "lde_commit_coset: the LDE would have virtual linear columns, which a coset leaf cannot name (MS_LDE_VIRTUAL=0, or ms_lde_commit)");
+  return lde_commit_k(blowup_, shift, (size_t)npolys << log_arity, log_arity, root);
+}
+
+// k = 0: the plain tree, leaf groups of lpn consecutive elements of the row-major matrix.  k > 0 (lpn = c << k): the coset tree
+template <class F>
+int Ctx<F>::lde_commit_k(size_t blowup_, u64 shift, size_t lpn, int k, u8* root) {
   if (!have_polys) return fail(MS_ERR_STATE, "lde_commit before interpolate");
   if (!root || !blowup_ || !is_pow2(blowup_) || shift == 0 || shift >= F::P) return fail(MS_ERR_ARG, "bad blowup/shift");
   const size_t L_ = N * blowup_;
@@ -152,14 +200,17 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
   L = L_; blowup = blowup_; lde_c = lde_c0 = c; lde_shift = shift; drop_vtree();
   have_stg = false; stg_pending = 0;   // (staged columns not committed yet are ordinary polynomials of this tree)
   auto stage = res.expect();
-  if (lpn == c && shardable(L_)) {  // one LDE row per leaf group: rank k evaluates and hashes the rows k (mod world)
+  if (k) {   // group j = the rows j + t L / a: element col * a + t of the group is column col of row j + t L / a
+    RQ(lde_compute(blowup_, shift));   // (no virtual column: ms_lde_commit_coset has refused an LDE that would have one)
+    RQ((tree_build<1>(d_lde.as<T>(), L >> k, 1, 0, (u32)(c << k), ts, d_lde_nodes)));
+  } else if (lpn == c && shardable(L_)) {  // one LDE row per leaf group: rank k evaluates and hashes the rows k (mod world)
     RQ(lde_compute_sharded(blowup_, shift));
     RQ((tree_build_sharded<1>(d_lde.as<T>(), L / (size_t)sh_world, 1, 0, (u32)c, ts, d_lde_nodes, lde_lin())));
   } else {
     RQ(lde_compute(blowup_, shift));
     RQ((tree_build<1>(d_lde.as<T>(), L, 1, 0, (u32)c, ts, d_lde_nodes, lde_lin())));
   }
-  lde_ts = ts;
+  lde_ts = ts; lde_ck = k;   // (the tree's shape and its grouping change together: a launch refused above leaves the earlier tree's view)
   RQ(read_root(d_lde_nodes, ts, root));
   have_lde = true;
   return MS_OK;
@@ -170,22 +221,36 @@ int Ctx<F>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root) {
 // at d_lde + j * L: a buffer too small for c0 + c1 columns is replaced by a larger one with the c0 columns copied (DevBuf::ensure would free them).  Nothing the
 // stage-0 tree covers is written; lde_c, the staged tree and the count change behind the root's arrival only
 template <class F>
-int Ctx<F>::lde_commit_stage(size_t lpn, u8* root) {
-  if (sh_on) return fail(MS_ERR_STATE, "lde_commit_stage: not available on a context with sharding on");
-  if (!root) return fail(MS_ERR_ARG, "lde_commit_stage: null root");
-  if (!have_polys || !have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "lde_commit_stage: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
-  if (have_stg) return fail(MS_ERR_STATE, "lde_commit_stage: the stage of this ms_lde_commit is committed already");
-  if (stg_pending < 1) return fail(MS_ERR_STATE, "lde_commit_stage: no staged columns (ms_aux_running_staged)");
+int Ctx<F>::lde_commit_stage(size_t lpn, u8* root) { return lde_commit_stage_k(lpn, 0, root); }
+
+// ms_lde_commit_stage_coset: the staged columns under a coset tree of the live LDE tree's own k
+template <class F>
+int Ctx<F>::lde_commit_stage_coset(int log_arity, u8* root) {
+  if (!root) return fail(MS_ERR_ARG, "lde_commit_stage_coset: null root");
+  RQ(coset_arity_check("lde_commit_stage_coset", log_arity, have_lde ? L : ~(size_t)0));
+  if (have_polys && have_lde && !lde_ts.sharded && lde_ck != log_arity) return fail(MS_ERR_STATE, "lde_commit_stage_coset: the live LDE tree is not a coset tree of this log_arity (ms_lde_commit_coset)");
+  RQ(coset_leaf_check("lde_commit_stage_coset", (size_t)stg_pending << log_arity));
+  return lde_commit_stage_k((size_t)stg_pending << log_arity, log_arity, root);
+}
+
+template <class F>
+int Ctx<F>::lde_commit_stage_k(size_t lpn, int k, u8* root) {
+  const char* const who = k ? "lde_commit_stage_coset" : "lde_commit_stage";   // (the entry point, for the messages)
+  if (sh_on) return fail(MS_ERR_STATE, std::string(who) + ": not available on a context with sharding on");
+  if (!root) return fail(MS_ERR_ARG, std::string(who) + ": null root");
+  if (!have_polys || !have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, std::string(who) + ": no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+  if (have_stg) return fail(MS_ERR_STATE, std::string(who) + ": the stage of this ms_lde_commit is committed already");
+  if (stg_pending < 1) return fail(MS_ERR_STATE, std::string(who) + ": no staged columns (ms_aux_running_staged)");
   const size_t c0 = lde_c, c1 = (size_t)stg_pending;
-  if (c0 + c1 != (size_t)npolys) return fail(MS_ERR_STATE, "lde_commit_stage: the staged columns are not the last polynomials");
+  if (c0 + c1 != (size_t)npolys) return fail(MS_ERR_STATE, std::string(who) + ": the staged columns are not the last polynomials");
   TreeShape ts;
   RQ(tree_shape(L * c1, lpn, 2, &ts));
   RQ(res.join_side());
-  if (d_coef.ensure(c1 * N * sizeof(T))) return fail(MS_ERR_NOMEM, "lde_commit_stage buffers");
+  if (d_coef.ensure(c1 * N * sizeof(T))) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
   const size_t need = (c0 + c1) * L * sizeof(T);
   if (need > d_lde.cap) {
     DevBuf nb;
-    if (nb.ensure(need)) return fail(MS_ERR_NOMEM, "lde_commit_stage buffers");
+    if (nb.ensure(need)) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
     CK(msrt::d2d(nb.p, d_lde.p, c0 * L * sizeof(T), stream)); CK(msrt::sync(stream));
     d_lde = std::move(nb);
   }
@@ -193,9 +258,9 @@ int Ctx<F>::lde_commit_stage(size_t lpn, u8* root) {
   T* dst = d_lde.as<T>() + c0 * L;
   RQ(scale_pow(d_polys.as<T>() + c0 * N, N, d_coef.as<T>(), N, N, F::from_u64(lde_shift), c1));
   RQ(ntt_run(ctz64(L), false, d_coef.as<T>(), N, N, dst, L, c1));
-  RQ((tree_build<1>(dst, L, 1, 0, (u32)c1, ts, d_stg_nodes)));
+  RQ((tree_build<1>(dst, L >> k, 1, 0, (u32)(c1 << k), ts, d_stg_nodes)));   // (k = 0: the plain view, col_stride = L, width = c1)
   RQ(read_root(d_stg_nodes, ts, root));
-  stg_ts = ts; lde_c = c0 + c1; stg_pending = 0; have_stg = true;
+  stg_ts = ts; stg_ck = k; lde_c = c0 + c1; stg_pending = 0; have_stg = true;
   return MS_OK;
 }
 
@@ -916,26 +981,40 @@ int Ctx<F>::eval_ext(const u64* z, int q, u64* out) {
 // transform, a limb plane's VL / N chunks per batch - and the tree over the L x m row-major matrix.  Reads the validity polynomial, writes d_coef (scratch), d_vlde
 // and d_vlde_nodes only: the polynomial, its trimmed length and a following ms_fri_begin are what they were.
 template <class F>
-int Ctx<F>::validity_commit(size_t lpn, u8* root) {
-  if (sh_on) return fail(MS_ERR_STATE, "validity_commit: not available on a context with sharding on");
-  if (stg_pending) return fail(MS_ERR_STATE, "validity_commit: uncommitted staged columns (ms_lde_commit_stage, or ms_lde_commit)");
-  if (!have_validity) return fail(MS_ERR_STATE, "validity_commit before a mix stage");
-  if (!have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, "validity_commit: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
+int Ctx<F>::validity_commit(size_t lpn, u8* root) { return validity_commit_k(lpn, 0, root); }
+
+// ms_validity_commit_coset: the chunk columns under a coset tree
+template <class F>
+int Ctx<F>::validity_commit_coset(int log_arity, u8* root) {
+  if (!root) return fail(MS_ERR_ARG, "validity_commit_coset: null root");
+  RQ(coset_arity_check("validity_commit_coset", log_arity, have_lde ? L : ~(size_t)0));
+  const size_t m = have_validity ? (size_t)validity_ext * (validity_len / N) : 0;
+  RQ(coset_leaf_check("validity_commit_coset", m << log_arity));
+  return validity_commit_k(m << log_arity, log_arity, root);
+}
+
+template <class F>
+int Ctx<F>::validity_commit_k(size_t lpn, int k, u8* root) {
+  const char* const who = k ? "validity_commit_coset" : "validity_commit";
+  if (sh_on) return fail(MS_ERR_STATE, std::string(who) + ": not available on a context with sharding on");
+  if (stg_pending) return fail(MS_ERR_STATE, std::string(who) + ": uncommitted staged columns (ms_lde_commit_stage, or ms_lde_commit)");
+  if (!have_validity) return fail(MS_ERR_STATE, std::string(who) + " before a mix stage");
+  if (!have_lde || lde_ts.sharded) return fail(MS_ERR_STATE, std::string(who) + ": no committed LDE (ms_lde_commit, and no ms_polys_* since)");
   const size_t ve = (size_t)validity_ext, nch = validity_len / N, m = ve * nch;
-  if (!root || lpn != m) return fail(MS_ERR_ARG, "validity_commit: null root, or lpn is not the number of chunk columns (ms_validity_ext * ms_validity_len / N)");
+  if (!root || lpn != m << k) return fail(MS_ERR_ARG, std::string(who) + ": null root, or lpn is not the number of chunk columns (ms_validity_ext * ms_validity_len / N)");
   TreeShape ts;
   RQ(tree_shape(L * m, lpn, 2, &ts));
   drop_vtree();   // (the buffers are rewritten from here on)
-  if (d_coef.ensure(nch * N * sizeof(T)) || d_vlde.ensure(m * L * sizeof(T))) return fail(MS_ERR_NOMEM, "validity_commit buffers");
+  if (d_coef.ensure(nch * N * sizeof(T)) || d_vlde.ensure(m * L * sizeof(T))) return fail(MS_ERR_NOMEM, std::string(who) + " buffers");
   auto stage = res.expect();
   const T* v = d_polys.as<T>() + (size_t)npolys * N;
   for (size_t l = 0; l < ve; l++) {   // chunk column k * ve + l = coefficients [kN, (k+1)N) of plane l
     RQ(scale_pow(v + l * validity_len, N, d_coef.as<T>(), N, N, F::from_u64(lde_shift), nch));
     RQ(ntt_run(ctz64(L), false, d_coef.as<T>(), N, N, d_vlde.as<T>() + l * L, ve * L, nch));
   }
-  RQ((tree_build<1>(d_vlde.as<T>(), L, 1, 0, (u32)m, ts, d_vlde_nodes)));
+  RQ((tree_build<1>(d_vlde.as<T>(), L >> k, 1, 0, (u32)(m << k), ts, d_vlde_nodes)));   // (k = 0: the plain view)
   RQ(read_root(d_vlde_nodes, ts, root));
-  vtree_ts = ts; vtree_m = m; have_vtree = true;
+  vtree_ts = ts; vtree_m = m; val_ck = k; have_vtree = true;
   return MS_OK;
 }
 
@@ -1079,6 +1158,15 @@ int Ctx<F>::deep_compose(const ms_deep* deep, const u64* gamma) {
   template int Ctx<FF>::lde_compute_sharded(size_t blowup_, u64 shift); \
   template int Ctx<FF>::lde_commit(size_t blowup_, u64 shift, size_t lpn, u8* root); \
   template int Ctx<FF>::lde_commit_stage(size_t lpn, u8* root); \
+  template int Ctx<FF>::coset_arity_check(const char* who, int k, size_t L_); \
+  template int Ctx<FF>::coset_leaf_check(const char* who, size_t lpn); \
+  template bool Ctx<FF>::linear_columns_would_be_virtual() const; \
+  template int Ctx<FF>::lde_commit_k(size_t blowup_, u64 shift, size_t lpn, int k, u8* root); \
+  template int Ctx<FF>::lde_commit_coset(size_t blowup_, u64 shift, int log_arity, u8* root); \
+  template int Ctx<FF>::lde_commit_stage_k(size_t lpn, int k, u8* root); \
+  template int Ctx<FF>::lde_commit_stage_coset(int log_arity, u8* root); \
+  template int Ctx<FF>::validity_commit_k(size_t lpn, int k, u8* root); \
+  template int Ctx<FF>::validity_commit_coset(int log_arity, u8* root); \
   template int Ctx<FF>::bench_lde(size_t blowup_, u64 shift); \
   template int Ctx<FF>::lde_read(u64* out); \
   template int Ctx<FF>::mix(u64 r); \

@@ -124,6 +124,10 @@ struct CtxBase {
   virtual int aux_running_staged(const ms_aux* aux, u64* final_out, u64* column_out) = 0;
   virtual int aux_staged_count() const = 0;
   virtual int lde_commit_stage(size_t lpn, u8* root) = 0;
+  virtual int lde_commit_coset(size_t blowup, u64 shift, int log_arity, u8* root) = 0;
+  virtual int lde_commit_stage_coset(int log_arity, u8* root) = 0;
+  virtual int validity_commit_coset(int log_arity, u8* root) = 0;
+  virtual int query_linked_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) = 0;
   virtual int interpolate() = 0;
   virtual int polys_lincomb(const u64* s, const int* idx, int k) = 0;
   virtual int polys_append(const u64* coeffs, size_t n) = 0;
@@ -576,6 +580,19 @@ template <class F> struct Ctx : CtxBase {
   int aux_staged_count() const override { return stg_pending; }
   template <int EA> int aux_running_staged_t(const ms_aux& a, u64* final_out, u64* column_out);
   int lde_commit_stage(size_t lpn, u8* root) override;
+  // ------------------------------------------------------------------ build-defined: coset-grouped row trees (include/ministark.h).  The `_coset` twins of ms_lde_commit,
+  // ms_lde_commit_stage and ms_validity_commit differ in the tree alone: L / a leaf groups, a = 2^k, group j = the a rows j + t L / a of the folded FRI's round-0 coset,
+  // column-major (element col * a + t) - the leaf kernels' own view with width = lpn = a * c and col_stride = L / a.  *_ck: the k of the live tree, 0 for a plain one
+  int lde_ck = 0, stg_ck = 0, val_ck = 0;
+  int lde_commit_k(size_t blowup_, u64 shift, size_t lpn, int k, u8* root);
+  int lde_commit_stage_k(size_t lpn, int k, u8* root);
+  int validity_commit_k(size_t lpn, int k, u8* root);
+  int coset_arity_check(const char* who, int k, size_t L_);   // MS_ERR_ARG: k outside 1..3; MS_ERR_STATE: sharding on; MS_ERR_SHAPE: L < 2a
+  int coset_leaf_check(const char* who, size_t lpn);          // MS_ERR_ARG: BLAKE3 and a leaf message that may exceed 16 KiB (leaf_hash's rule, asked before anything changes)
+  bool linear_columns_would_be_virtual() const;               // finish_linear_columns' decision, without its effects
+  int lde_commit_coset(size_t blowup_, u64 shift, int log_arity, u8* root) override;
+  int lde_commit_stage_coset(int log_arity, u8* root) override;
+  int validity_commit_coset(int log_arity, u8* root) override;
   // ------------------------------------------------------------------ air.rs:147-160
   int interpolate() override;
   int polys_lincomb(const u64* s, const int* idx, int k) override;
@@ -844,6 +861,10 @@ template <class F> struct Ctx : CtxBase {
   int tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len) override;
   int fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
   int query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
+  // the FRI part of both folded query phases: the MSFF header into hd, the size of the blob behind it into *body (the final polynomial, then the rounds' paths), and
+  // (jobs != nullptr) the openings, their offsets counted from the final polynomial's first byte
+  int msff_plan(const u64* betas, int nq, u64 hd[7], size_t* body, std::vector<msmerkle::OpenJob<F>>* jobs);
+  int query_linked_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) override;
   // ------------------------------------------------------------------ build-defined: the composition commitment and the DEEP stage (include/ministark.h; kernels:
   // mspoly::DeepCombineKernel, mspoly::DeepSumScaleKernel; host side: air_stages.cpp).  The validity polynomial's ve limb planes of VL coefficients are m = ve * VL / N
   // chunk columns of N coefficients, column k * ve + l = coefficients [kN, (k+1)N) of plane l: views of the polynomial where it lies, behind the constraint polynomials.

@@ -1,5 +1,5 @@
 // fri_query.cpp — the FRI query phase (fri.rs:115-189, merkle.rs:216-288) as a handful of batched launches over device job tables, the standalone ms_merkle_prove,
-// and the build-defined openings by index (ms_tree_open, ms_fri_query_index, ms_query_linked).  (The proof's way to the host: io.cpp.)
+// and the build-defined openings by index (ms_tree_open, ms_fri_query_index, ms_query_linked, ms_query_linked_folded).  (The proof's way to the host: io.cpp.)
 #include "ctx.hpp"
 
 namespace msctx {
@@ -340,14 +340,17 @@ int Ctx<F>::open_view(int tree, int round, OpenView* v) {
     if (!have_lde) return fail(MS_ERR_STATE, "tree_open: no committed LDE (ms_lde_commit, and no ms_polys_* since)");
     ts = &lde_ts;
     o.base = d_lde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)lde_c0; o.lin = lde_lin(); o.nodes = d_lde_nodes.template as<u32>();   // (lde_c0: the columns ms_lde_commit hashed; a staged tree covers the ones behind them)
+    if (lde_ck) { o.col_stride = L >> lde_ck; o.width = (u32)(lde_c0 << lde_ck); o.lin = nullptr; }   // coset tree: leaf group j = the rows j + t L / a, element col * a + t
   } else if (tree == MS_TREE_LDE_STAGED) {
     if (!stg_live()) return fail(MS_ERR_STATE, "tree_open: no staged LDE tree (ms_lde_commit_stage, and nothing that kills the LDE tree since)");
     ts = &stg_ts;
     o.base = d_lde.template as<T>() + lde_c0 * L; o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)(lde_c - lde_c0); o.nodes = d_stg_nodes.template as<u32>();
+    if (stg_ck) { o.col_stride = L >> stg_ck; o.width = (u32)((lde_c - lde_c0) << stg_ck); }
   } else if (tree == MS_TREE_VALIDITY) {
     if (!vtree_live()) return fail(MS_ERR_STATE, "tree_open: no validity tree (ms_validity_commit, and no mix stage, ms_polys_*, ms_lde_commit or ms_trace_commit since)");
     ts = &vtree_ts;
     o.base = d_vlde.template as<T>(); o.col_stride = L; o.row_stride = 1; o.limb_stride = 0; o.width = (u32)vtree_m; o.nodes = d_vlde_nodes.template as<u32>();
+    if (val_ck) { o.col_stride = L >> val_ck; o.width = (u32)(vtree_m << val_ck); }
   } else if (tree == MS_TREE_FRI) {
     if (nrounds_done == 0) return fail(MS_ERR_STATE, "tree_open: no FRI round committed (ms_fri_begin)");
     if (round < 0 || (size_t)round >= nrounds_done) return fail(MS_ERR_ARG, "tree_open: round index");
@@ -515,26 +518,74 @@ int Ctx<F>::fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size
   if (sh_on) return fail(MS_ERR_STATE, "fri_query_folded: not available on a context with sharding on");
   if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "fri_query_folded: null argument");
   if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "fri_query_folded: nq outside 1..4096");
-  const size_t R = nrounds_done, nfinal = fold_fin.ncoef;
-  std::vector<OpenView> views(R);
-  size_t body = nfinal * (size_t)E * 8;
-  for (size_t i = 0; i < R; i++) { RQ(open_view(MS_TREE_FRI, (int)i, &views[i])); body += views[i].path_bytes() * (size_t)nq; }
-  const u64 hd[7] = {0x4646534DULL /* 'MSFF' */, (u64)E, (u64)fri_k, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)nfinal};
+  u64 hd[7]; size_t body;
+  RQ(msff_plan(betas, nq, hd, &body, nullptr));
   *len = sizeof hd + body;
   if (!out) return MS_OK;   // size query
   if (cap < *len) return fail(MS_ERR_ARG, "fri_query_folded: buffer too small (the size needed is in *len)");
   std::vector<msmerkle::OpenJob<F>> jobs;
-  jobs.reserve(R * (size_t)nq);
+  jobs.reserve(nrounds_done * (size_t)nq);
+  RQ(msff_plan(betas, nq, hd, &body, &jobs));
+  memcpy(out, hd, sizeof hd);
+  return open_launch(jobs, body, &fold_fin, out + sizeof hd);
+}
+
+template <class F>
+int Ctx<F>::msff_plan(const u64* betas, int nq, u64 hd[7], size_t* body, std::vector<msmerkle::OpenJob<F>>* jobs) {
+  const size_t R = nrounds_done, nfinal = fold_fin.ncoef;
+  std::vector<OpenView> views(R);
+  for (size_t i = 0; i < R; i++) RQ(open_view(MS_TREE_FRI, (int)i, &views[i]));
   std::vector<u64> b(betas, betas + nq);
   size_t pos = nfinal * (size_t)E * 8;
   for (int j = 0; j < nq; j++) b[j] %= rounds[0]->D;                       // b_(0,j)
   for (size_t i = 0; i < R; i++) {
     for (int j = 0; j < nq; j++) b[j] %= rounds[i]->D >> fri_k;            // b_(i+1,j): the leaf group of round i
-    open_jobs(views[i], b.data(), (size_t)nq, false, pos, jobs);
+    if (jobs) open_jobs(views[i], b.data(), (size_t)nq, false, pos, *jobs);
     pos += views[i].path_bytes() * (size_t)nq;
   }
+  const u64 h[7] = {0x4646534DULL /* 'MSFF' */, (u64)E, (u64)fri_k, (u64)R, (u64)nq, (u64)rounds[0]->D, (u64)nfinal};
+  memcpy(hd, h, sizeof h);
+  *body = pos;
+  return 0;
+}
+
+// The whole query phase of a linked proof over a folded FRI (MSLF, include/ministark.h): MSFF, then ONE leaf group per query of every coset row tree - the group that holds the LDE rows
+// under round 0's coset - every opening and the final polynomial in ONE launch.  The device image is the blob behind both headers: final polynomial | FRI paths | LDE
+// paths | staged paths | validity paths
+template <class F>
+int Ctx<F>::query_linked_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len) {
+  if (!folded()) return fail(MS_ERR_STATE, "query_linked_folded outside folded mode (ms_fri_begin_folded)");
+  if (!fold_final_done) return fail(MS_ERR_STATE, "query_linked_folded before fri_fold_final");
+  if (sh_on) return fail(MS_ERR_STATE, "query_linked_folded: not available on a context with sharding on");
+  if (!dpoly_live()) return fail(MS_ERR_STATE, "query_linked_folded: no DEEP polynomial installed (ms_validity_commit_coset, ms_deep_compose, and nothing that kills the validity tree since)");
+  const u64 D0 = rounds[0]->D;
+  if (D0 > L || L % D0) return fail(MS_ERR_STATE, "query_linked_folded: round 0's domain does not divide the LDE domain (ms_fri_begin_folded with the LDE's blowup)");
+  const bool staged = stg_live();
+  if (lde_ck != fri_k || val_ck != fri_k || (staged && stg_ck != fri_k))
+    return fail(MS_ERR_STATE, "query_linked_folded: a row tree is not a coset tree of the FRI's log_arity (ms_lde_commit_coset, ms_lde_commit_stage_coset, ms_validity_commit_coset)");
+  if (!betas || !len || (!out && cap)) return fail(MS_ERR_ARG, "query_linked_folded: null argument");
+  if (nq < 1 || nq > 4096) return fail(MS_ERR_ARG, "query_linked_folded: nq outside 1..4096");
+  OpenView lde, stg, val;
+  RQ(open_view(MS_TREE_LDE, 0, &lde));
+  if (staged) RQ(open_view(MS_TREE_LDE_STAGED, 0, &stg));
+  RQ(open_view(MS_TREE_VALIDITY, 0, &val));
+  u64 hd[5 + 7]; size_t body;
+  RQ(msff_plan(betas, nq, hd + 5, &body, nullptr));
+  const size_t n = (size_t)nq, len_lde = n * lde.path_bytes(), len_stg = staged ? n * stg.path_bytes() : 0, len_val = n * val.path_bytes();
+  hd[0] = 0x464C534DULL /* 'MSLF' */; hd[1] = 7 * 8 + body; hd[2] = len_lde; hd[3] = len_stg; hd[4] = len_val;
+  *len = sizeof hd + body + len_lde + len_stg + len_val;
+  if (!out) return MS_OK;   // size query
+  if (cap < *len) return fail(MS_ERR_ARG, "query_linked_folded: buffer too small (the size needed is in *len)");
+  std::vector<msmerkle::OpenJob<F>> jobs;
+  jobs.reserve((nrounds_done + 3) * n);
+  RQ(msff_plan(betas, nq, hd + 5, &body, &jobs));
+  std::vector<u64> groups(n);   // round 0's coset {q + t D_1} lies over the LDE rows q s + t L / a, s = L / D_0: leaf group q s
+  for (int j = 0; j < nq; j++) groups[j] = betas[j] % D0 % (D0 >> fri_k) * (L / D0);
+  open_jobs(lde, groups.data(), n, false, body, jobs);
+  if (staged) open_jobs(stg, groups.data(), n, false, body + len_lde, jobs);
+  open_jobs(val, groups.data(), n, false, body + len_lde + len_stg, jobs);
   memcpy(out, hd, sizeof hd);
-  return open_launch(jobs, body, &fold_fin, out + sizeof hd);
+  return open_launch(jobs, body + len_lde + len_stg + len_val, &fold_fin, out + sizeof hd);
 }
 
 // src/merkle.rs:272-288 on a standalone binary tree: leaves de-interleaved to SoA limbs, then the same
@@ -597,7 +648,9 @@ int Ctx<F>::merkle_prove(const u64* leafs, size_t leaf_num, int ext, size_t lpn,
   template int Ctx<FF>::tree_open(int tree, int round, const u64* index, size_t n, u8* out, size_t cap, size_t* len); \
   template int Ctx<FF>::fri_query_index(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
   template int Ctx<FF>::query_linked(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
-  template int Ctx<FF>::fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
+  template int Ctx<FF>::fri_query_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len); \
+  template int Ctx<FF>::msff_plan(const u64* betas, int nq, u64 hd[7], size_t* body, std::vector<msmerkle::OpenJob<FF>>* jobs); \
+  template int Ctx<FF>::query_linked_folded(const u64* betas, int nq, u8* out, size_t cap, size_t* len);
 MS_INSTANTIATE(GL)
 MS_INSTANTIATE(BB)
 #undef MS_INSTANTIATE

@@ -136,6 +136,28 @@ def deep_link_verify(digest_id, field, zero_display_empty, N, blowup, shift, c, 
     return rc, why.value.decode()
 
 
+def deep_link_verify_folded(digest_id, field, zero_display_empty, N, blowup, shift, log_arity, c0, c1, m, lde_root, stg_root, val_root, z, lists, evals, gamma, betas,
+                            msff, lde_open, stg_open, val_open):
+    """msh_deep_link_verify_folded: round 0 of a folded FRI (the MSFF blob) against the coset-grouped LDE, staged and validity trees - every slot of every opened coset.
+    stg_root is None and stg_open empty iff c1 = 0; the three opening sections are those of Context.query_linked_folded (ministark_host.h).
+    Returns (rc, why): rc 1 accepted, 0 rejected, < 0 malformed arguments."""
+    from ._native import deep_struct
+    H = _host()
+    u64p = C.POINTER(C.c_uint64)
+    H.msh_deep_link_verify_folded.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p,
+                                              C.c_char_p, C.c_void_p, u64p, u64p, u64p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t,
+                                              C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+    arr = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.uint64).reshape(-1))   # noqa: E731
+    s, _keep = deep_struct(z, lists)
+    ev, gg, be = arr(evals), arr(gamma), arr(betas)
+    why = C.create_string_buffer(512)
+    rc = H.msh_deep_link_verify_folded(int(digest_id), int(field), 1 if zero_display_empty else 0, int(N), int(blowup), int(shift), int(log_arity), int(c0), int(c1), int(m),
+                                       bytes(lde_root), None if stg_root is None else bytes(stg_root), bytes(val_root), C.addressof(s), ev.ctypes.data_as(u64p),
+                                       gg.ctypes.data_as(u64p), be.ctypes.data_as(u64p), be.size, bytes(msff), len(msff), bytes(lde_open), len(lde_open),
+                                       bytes(stg_open), len(stg_open), bytes(val_open), len(val_open), why, 512)
+    return rc, why.value.decode()
+
+
 def validity_from_chunks(field, ve, N, z, chunk_evals):
     """msh_validity_from_chunks: V(z) from the evaluations of the m = ve * nchunks chunk columns ([m][E] limbs, chunk column k * ve + l at index k * ve + l).
     Returns (status, E limbs)."""
@@ -491,6 +513,26 @@ class HostStark:
         data = bytes(data)
         rc = self.H.msh_stark_verify_linked_aux(self.h, C.byref(s), arr, C.c_uint32(len(args)), C.c_uint32(nch), C.c_size_t(N), C.c_size_t(w), C.c_uint32(fri_rounds), data,
                                                 C.c_size_t(len(data)), C.c_int(1 if zero_display_empty else 0), why, C.c_size_t(512))
+        return rc, why.value.decode()
+
+    def prove_linked_folded(self, trace, air, log_arity, args=(), nch=0, fri_folds=0) -> int:
+        """msh_stark_prove_linked_folded (MSLP v3): the folded FRI at arity 2^log_arity over coset-grouped row trees; args: flatten_aux_arg dicts ([]: no running columns)"""
+        s, _keep = _air(air)
+        arr, _keep2 = aux_args_struct(args)
+        t = np.ascontiguousarray(trace, dtype=np.uint64)
+        N, w = t.shape
+        return self.H.msh_stark_prove_linked_folded(self.h, t.ctypes.data_as(C.POINTER(C.c_uint64)), None, C.c_size_t(N), C.c_size_t(w), C.byref(s), arr if len(args) else None,
+                                                    C.c_uint32(len(args)), C.c_uint32(nch), C.c_int(log_arity), C.c_uint32(fri_folds))
+
+    def verify_linked_folded(self, data, air, N, w, log_arity, args=(), nch=0, fri_folds=0, zero_display_empty=True):
+        """msh_stark_verify_linked_folded: (rc, why) as verify_linked"""
+        s, _keep = _air(air)
+        arr, _keep2 = aux_args_struct(args)
+        why = C.create_string_buffer(512)
+        data = bytes(data)
+        rc = self.H.msh_stark_verify_linked_folded(self.h, C.byref(s), arr if len(args) else None, C.c_uint32(len(args)), C.c_uint32(nch), C.c_size_t(N), C.c_size_t(w),
+                                                   C.c_int(log_arity), C.c_uint32(fri_folds), data, C.c_size_t(len(data)), C.c_int(1 if zero_display_empty else 0), why,
+                                                   C.c_size_t(512))
         return rc, why.value.decode()
 
     def linked_proof(self) -> bytes:

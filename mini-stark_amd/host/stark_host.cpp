@@ -847,6 +847,94 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
   return 1;
 }
 
+// the link between a FOLDED FRI's round 0 and the coset-grouped row trees (ministark.h: ms_lde_commit_coset .., ms_query_linked_folded): 1 accepted, 0 rejected (the
+// reason in *why, beginning with the step's name), < 0 malformed arguments.  Query j opens ONE leaf group of every tree, group q_j s with q_j = (beta mod D_0) mod D_1
+// and s = L / D_0: slot col * a + t of it is column col of the LDE row q_j s + t L / a, which lies under position q_j + t D_1 of round 0 - slot t of round 0's opened
+// coset.  ALL a slots are recomputed and compared: all of them feed the fold.  The MSFF itself is msh_fri_folded_verify's to check
+template <class F, int E> static int deep_link_verify_folded(int digest, int zae, u64 N, u64 blowup, u64 shift, int k, u32 c0, u32 c1, u32 m, const u8* lde_root, const u8* stg_root,
+                                                             const u8* val_root, const ms_deep& d, const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msff,
+                                                             size_t msff_len, const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open, size_t val_len,
+                                                             std::string* why) {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  const u32 c = c0 + c1;
+  const u64 L = N * blowup, a = (u64)1 << k;
+  if (shift == 0 || shift >= F::P || L > ((u64)1 << F::TWO_ADICITY) || L < 2 * a) { *why = "shift or domain size out of range"; return MS_ERR_ARG; }
+  if (d.npts < 1 || d.npts > 8 || d.pt_begin[0] != 0) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+  for (u32 t = 0; t < d.npts; t++) if (d.pt_begin[t + 1] <= d.pt_begin[t] || d.pt_begin[t + 1] > 8192) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+  const size_t ne = d.pt_begin[d.npts];
+  for (size_t n = 0; n < ne; n++) if (d.pt_poly[n] >= c + m) { *why = "malformed ms_deep: an index at or above c + m"; return MS_ERR_ARG; }
+  if (!V::canon(d.z, (size_t)d.npts * E) || !V::canon(gamma, E)) { *why = "a point or gamma is not canonical"; return MS_ERR_ARG; }
+  if (!V::canon(evals, ne * E)) { *why = "DEEP link: claimed evaluation not canonical"; return 0; }
+  int lgL = 0; while (((u64)1 << lgL) < L) lgL++;
+  const T sh = F::from_u64(shift), gL = f_root_of_unity<F>(lgL), shL = f_pow<F>(sh, L);
+  std::vector<X> z(d.npts);
+  for (u32 t = 0; t < d.npts; t++) {
+    z[t] = V::load(d.z + (size_t)t * E);
+    if (e_eq<F, E>(e_pow<F, E>(z[t], L), e_from_base<F, E>(shL))) { *why = "DEEP link: a point lies in the LDE coset: the quotient by (x - z) is undefined at one of its rows"; return 0; }
+  }
+  // the MSFF header and round 0's paths: D_0 is the blob's own
+  if (msff_len < 56) { *why = "MSFF blob shorter than its header"; return 0; }
+  u64 hd[7]; memcpy(hd, msff, 56);
+  if (hd[0] != 0x4646534DULL) { *why = "MSFF: not an MSFF blob (magic)"; return 0; }
+  if (hd[1] != (u64)E || hd[2] != (u64)k || hd[4] != (u64)nq || hd[3] < 1 || hd[3] > 64) { *why = "MSFF header: E, log_arity, rounds or queries are not the verifier's"; return 0; }
+  const u64 D0 = hd[5], nfinal = hd[6];
+  if (D0 < a || (D0 & (D0 - 1)) || D0 > L || L % D0) { *why = "MSFF header: D_0 is no power of two that divides the LDE domain and holds a coset"; return 0; }
+  const u64 s = L / D0, D1 = D0 >> k;
+  u64 h0 = 0; while (((u64)1 << h0) < D1) h0++;
+  const size_t psize = 16 + (size_t)a * E * 8 + 64 * (size_t)h0;
+  if (nfinal > D0 || (msff_len - 56) / 8 < nfinal * E) { *why = "MSFF blob truncated in the final polynomial"; return 0; }
+  const u8* r0 = msff + 56 + (size_t)nfinal * E * 8;
+  if ((msff_len - 56 - (size_t)nfinal * E * 8) / psize < nq) { *why = "MSFF blob truncated in round 0's openings"; return 0; }
+  X gp = e_one<F, E>();
+  const X g = V::load(gamma);
+  std::vector<X> gpow(ne), ev(ne), inv(d.npts);
+  std::vector<u32> pt_of(ne);
+  for (u32 t = 0; t < d.npts; t++) for (u32 n = d.pt_begin[t]; n < d.pt_begin[t + 1]; n++) pt_of[n] = t;
+  for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
+  const u8* lp = lde_open; size_t lleft = lde_len;
+  const u8* vp = val_open; size_t vleft = val_len;
+  const u8* sp = stg_open; size_t sleft = stg_len;
+  const T wa = f_pow<F>(gL, L / a);   // the step between the coset's rows
+  for (size_t j = 0; j < nq; j++) {
+    const u64 q = betas[j] % D0 % D1, grp = q * s;
+    size_t used = 0;
+    std::string w;
+    if (!check_path_at<F>(digest, 1, (size_t)a * c0, zae, lde_root, lp, lleft, grp * a * c0, &used, &w)) { *why = "LDE opening: " + w; return 0; }
+    const u64* lrow = (const u64*)(lp + 8);
+    lp += used; lleft -= used;
+    const u64* srow = nullptr;
+    if (c1) {
+      if (!check_path_at<F>(digest, 1, (size_t)a * c1, zae, stg_root, sp, sleft, grp * a * c1, &used, &w)) { *why = "staged opening: " + w; return 0; }
+      srow = (const u64*)(sp + 8);
+      sp += used; sleft -= used;
+    }
+    if (!check_path_at<F>(digest, 1, (size_t)a * m, zae, val_root, vp, vleft, grp * a * m, &used, &w)) { *why = "validity opening: " + w; return 0; }
+    const u64* vrow = (const u64*)(vp + 8);
+    vp += used; vleft -= used;
+    const u64* slots = (const u64*)(r0 + j * psize + 8);
+    u64 li; memcpy(&li, r0 + j * psize, 8);
+    if (li != q * a) { *why = "MSFF: a round-0 path is not at the query's leaf group"; return 0; }
+    if (!V::canon(slots, (size_t)a * E)) { *why = "MSFF: opened value not canonical"; return 0; }
+    T x = F::mul(sh, f_pow<F>(gL, grp));
+    for (u64 t = 0; t < a; t++, x = F::mul(x, wa)) {   // x = shift * g_L^(q s + t L / a)
+      for (u32 p = 0; p < d.npts; p++) inv[p] = e_inv<F>(e_sub<F, E>(e_from_base<F, E>(x), z[p]));
+      X Dx = e_zero<F, E>();
+      for (size_t n = 0; n < ne; n++) {
+        const u32 fi = d.pt_poly[n];
+        const T fx = F::from_u64(fi < c0 ? lrow[(u64)fi * a + t] : fi < c ? srow[(u64)(fi - c0) * a + t] : vrow[(u64)(fi - c) * a + t]);
+        Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
+      }
+      if (!e_eq<F, E>(Dx, V::load(slots + t * E))) { *why = "DEEP link: the composition recomputed from the opened leaf groups and the claimed evaluations is not the value in slot " + std::to_string(t) + " of round 0's coset"; return 0; }
+    }
+  }
+  if (lleft != 0) { *why = "LDE opening: trailing bytes"; return 0; }
+  if (c1 && sleft != 0) { *why = "staged opening: trailing bytes"; return 0; }
+  if (vleft != 0) { *why = "validity opening: trailing bytes"; return 0; }
+  return 1;
+}
+
 }  // namespace ministark
 
 // ---- C entry points for the Python test / bench harness ---------------------------------------
@@ -1631,6 +1719,235 @@ template <class F, int E> static int verify_linked_aux(const StarkConfig& c, con
   if (rc != 1) { *why = sub; return rc; }
   return 1;
 }
+
+// ---- linked proofs over a folded FRI and coset-grouped row trees: MSLP v3 (ministark_host.h) -----------------------------------------------------------------------
+static const size_t MSLP3_HEAD = 13 * 4 + 5 * 8;
+// the statement of a v3 proof and what the configuration fixes.  R = fri_folds, or floor(log2 N / k).  Returns the bytes of msh_air_encode(air) (> 0), or < 0
+template <class F> static int linked_shape_folded(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, int k, u32 fri_folds, LinkedShape* o) {
+  AirShape sh;
+  if (k < 1 || k > 3 || !air_shape(air, &sh) || linked_config_shape<F>(c, N, w, 1, o)) return MS_ERR_ARG;
+  if ((nargs == 0) != (args == nullptr) || (nargs == 0 && nch != 0)) return MS_ERR_ARG;
+  int lgN = 0; while (((u64)1 << lgN) < N) lgN++;
+  o->R = fri_folds ? fri_folds : (u32)(lgN / k);
+  if (o->R < 1 || o->R > 64 || o->L < ((u64)2 << k)) return MS_ERR_ARG;
+  for (u32 j = 0; j < sh.nfacs; j++) if (!(air->fac_poly[j] & 0x80000000u) && air->fac_poly[j] >= w) return MS_ERR_ARG;   // the main program is over the w trace columns
+  const u64 words[11] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)k, (u64)o->R, (u64)o->nq, (u64)o->gb, (u64)nargs, (u64)nch};
+  std::vector<u8> enc, enx;
+  if (!air_encode(air, &enc) || (nargs && !aux_encode(args, nargs, nch, c.p, c.e, w, &enx))) return MS_ERR_ARG;
+  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
+  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
+  o->statement.insert(o->statement.end(), enx.begin(), enx.end());
+  o->c = (u32)w + nargs * (u32)c.e;
+  return (int)enc.size();
+}
+static Transcript linked_transcript_folded(const StarkConfig& c, const LinkedShape& sh, size_t air_bytes) {
+  Transcript t(c.domsep + "/linked/v3", c.digest);
+  t.add_bytes(sh.statement.data(), 88);                                                  // field, digest, N, w, blowup, k, R, nq, grinding bits, nargs, nch
+  t.add_bytes(sh.statement.data() + 88, air_bytes);                                      // msh_air_encode(air)
+  if (sh.statement.size() > 88 + air_bytes) t.add_bytes(sh.statement.data() + 88 + air_bytes, sh.statement.size() - 88 - air_bytes);   // msh_aux_encode(args), when nargs > 0
+  t.prover_bytes.clear();
+  return t;
+}
+// the program a v3 proof is about: air alone (nargs = 0), or combined with the arguments' constraints; the shape it fixes
+template <class F, int E> static int linked_program_folded(const ms_air* air, const msh_aux_arg* args, u32 nargs, const u64* ch, size_t w, AirProg* pg, std::vector<AuxInstance>* inst, LinkedShape* o) {
+  if (nargs) return linked_combined<F, E>(air, args, nargs, ch, w, pg, inst, o);
+  AirShape sh;
+  if (!pg->load(air) || !air_shape(pg->view(), &sh)) return MS_ERR_ARG;
+  return linked_program_shape(pg->view(), sh, E, o);
+}
+// trace root, LDE root, (staged root,) validity root, evaluations, R round roots, final polynomial, nonce
+static size_t arthur_len_folded(const LinkedShape& sh, int e, u32 nargs, u64 nfinal) {
+  return (size_t)(3 + (nargs ? 1 : 0)) * 32 + sh.ne * e * 8 + (size_t)sh.R * 32 + (size_t)nfinal * e * 8 + (sh.gb ? 8 : 0);
+}
+
+template <class F, int E> static int prove_linked_folded(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch,
+                                                         int k, u32 fri_folds) {
+  const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = E; const u64 p = c.p;
+  s.linked.clear();
+  if (!ctx || c.e != E || (!trace_host && !trace_dev)) return MS_ERR_ARG;
+  LinkedShape sh;
+  int rc = linked_shape_folded<F>(c, air, args, nargs, nch, N, w, k, fri_folds, &sh);
+  if (rc < 0) return rc;
+  Transcript t = linked_transcript_folded(c, sh, (size_t)rc);
+  u8 root[32];
+  rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
+  if (rc) return rc;
+  t.add_bytes(root, 32);
+  const u64 shift = draw_shift<F>(t, sh.L);
+  if ((rc = ms_interpolate(ctx))) return rc;
+  if ((rc = ms_lde_commit_coset(ctx, sh.blowup, shift, k, root))) return rc;
+  t.add_bytes(root, 32);
+  std::vector<u64> ch((size_t)nch * e);
+  if (nargs) t.challenge_scalars(ch.data(), ch.size(), p);                   // the arguments' challenges follow the commitment to the main columns
+  AirProg pg; std::vector<AuxInstance> inst;
+  if ((rc = linked_program_folded<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh))) return rc;
+  for (u32 j = 0; j < nargs; j++) {
+    u64 fin[E];
+    if ((rc = ms_aux_running_staged(ctx, &inst[j].aux, fin, nullptr))) return rc;
+    for (int l = 0; l < e; l++) if (fin[l] != ((args[j].op == MS_AUX_PRODUCT && l == 0) ? 1u : 0u)) return MS_ERR_SHAPE;   // the argument does not hold
+  }
+  const u32 c1 = nargs * (u32)e;
+  if (nargs) {
+    if ((rc = ms_lde_commit_stage_coset(ctx, k, root))) return rc;
+    t.add_bytes(root, 32);
+  }
+  const ms_air* prog = pg.view();
+  std::vector<u64> r(e), z(e), gamma(e), alpha(e);
+  t.challenge_scalars(r.data(), e, p);
+  if ((rc = ms_mix_air_ext(ctx, r.data(), prog))) return rc;                 // MS_ERR_SHAPE: the trace violates the AIR
+  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;
+  if ((rc = ms_validity_commit_coset(ctx, k, root))) return rc;
+  t.add_bytes(root, 32);
+  draw_z(t, z.data(), e, p);
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  std::vector<u64> evals(sh.ne * e);
+  if ((rc = ms_deep_evals(ctx, &deep, evals.data()))) return rc;
+  t.add_scalars(evals.data(), evals.size());
+  t.challenge_scalars(gamma.data(), e, p);
+  if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
+  if ((rc = ms_fri_begin_folded(ctx, sh.blowup, k, root))) return rc;
+  t.add_bytes(root, 32);
+  u64 nc = 0, D0 = 0;
+  if ((rc = ms_fri_round_info(ctx, 0, &nc, &D0))) return rc;
+  for (u32 i = 0; i + 1 < sh.R; i++) {
+    t.challenge_scalars(alpha.data(), e, p);
+    if ((rc = ms_fri_fold_folded(ctx, alpha.data(), root))) return rc;       // MS_ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
+    t.add_bytes(root, 32);
+  }
+  t.challenge_scalars(alpha.data(), e, p);
+  size_t nfinal = 0;
+  if ((rc = ms_fri_fold_final(ctx, alpha.data(), nullptr, 0, &nfinal))) return rc;
+  std::vector<u64> fin(nfinal * e + 1);
+  if ((rc = ms_fri_fold_final(ctx, alpha.data(), fin.data(), nfinal * e, &nfinal))) return rc;
+  t.add_scalars(fin.data(), nfinal * e);
+  if (sh.gb) {
+    u8 seed[32]; t.challenge_bytes(seed, 32);
+    u64 nonce = 0;
+    if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
+    u8 le[8]; for (int b = 0; b < 8; b++) le[b] = (u8)(nonce >> (8 * b));
+    t.add_bytes(le, 8);
+  }
+  std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
+  std::vector<u64> betas(sh.nq);
+  memcpy(betas.data(), raw.data(), raw.size());
+  size_t lq = 0;
+  if ((rc = ms_query_linked_folded(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
+  const size_t la = t.prover_bytes.size();
+  if (la != arthur_len_folded(sh, e, nargs, nfinal)) return MS_ERR_STATE;
+  std::vector<u8> out(MSLP3_HEAD + la + lq);
+  const u32 h32[13] = {MSLP_MAGIC, 3, (u32)e, (u32)k, (u32)w, c1, sh.m, sh.npts, sh.R, sh.nq, sh.gb, nargs, nch};
+  const u64 h64[5] = {sh.N, sh.blowup, D0, (u64)la, (u64)lq};
+  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
+  memcpy(out.data() + MSLP3_HEAD, t.prover_bytes.data(), la);
+  if ((rc = ms_query_linked_folded(ctx, betas.data(), (int)sh.nq, out.data() + MSLP3_HEAD + la, lq, &lq))) return rc;
+  s.linked.swap(out);
+  return MS_OK;
+}
+
+// the v3 verifier: nothing of the proof is trusted.  Order: header, transcript replay (both redraw rules, the challenge draw), proof of work, AIR identity, the folded
+// FRI on the MSFF, round 0's cosets against the coset-grouped trees
+template <class F, int E> static int verify_linked_folded(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, int k, u32 fri_folds,
+                                                          const u8* data, size_t len, int zae, std::string* why) {
+  typedef Verifier<F, E> V;
+  const u64 p = c.p;
+  LinkedShape sh;
+  const int air_bytes = c.e != E ? MS_ERR_ARG : linked_shape_folded<F>(c, air, args, nargs, nch, N, w, k, fri_folds, &sh);
+  if (air_bytes < 0) { *why = "malformed arguments: the AIR program, the arguments, N, w, log_arity, the folds or the configuration"; return MS_ERR_ARG; }
+  const u32 c0 = (u32)w, c1 = nargs * (u32)E;
+  if (len < MSLP3_HEAD) { *why = "header: the proof is shorter than the MSLP v3 header"; return 0; }
+  u32 h32[13]; u64 h64[5];
+  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
+  if (h32[0] != MSLP_MAGIC) { *why = "header: magic is not the verifier's"; return 0; }
+  if (h32[1] != 3) { *why = "header: version is not 3"; return 0; }
+  const u32 want32[13] = {MSLP_MAGIC, 3, (u32)E, (u32)k, c0, c1, 0, 0, sh.R, sh.nq, sh.gb, nargs, nch};
+  static const char* const name32[13] = {"magic", "version", "E", "log_arity", "c0", "c1", "m", "npts", "R", "nq", "grinding bits", "nargs", "nch"};
+  for (int j = 2; j < 13; j++) if (j != 6 && j != 7 && h32[j] != want32[j]) { *why = std::string("header: ") + name32[j] + " is not the verifier's"; return 0; }
+  if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
+  if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
+  const u64 D0 = h64[2];
+  const unsigned kr = (unsigned)k * sh.R;
+  if (D0 < 1 || (D0 & (D0 - 1)) || D0 > sh.L || sh.L % D0 || kr >= 64 || (D0 >> kr) < sh.blowup) { *why = "header: D_0 is no power of two that divides L with arity^R * blowup <= D_0"; return 0; }
+  const u64 nfinal = (D0 >> kr) / sh.blowup;
+  if (h64[3] > len - MSLP3_HEAD || h64[4] != (u64)(len - MSLP3_HEAD) - h64[3]) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
+  const size_t la = (size_t)h64[3], lq = len - MSLP3_HEAD - la;
+  if (la < 64) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
+  // ---- transcript up to the challenges of the arguments; then the program and the rest of the header
+  Arthur a(c.domsep, c.digest, data + MSLP3_HEAD, la);
+  a.t = linked_transcript_folded(c, sh, (size_t)air_bytes);
+  u8 troot[32], lroot[32], sroot[32], vroot[32];
+  const char* cut = "transcript: arthur ends early";
+  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
+  const u64 shift = draw_shift<F>(a.t, sh.L);
+  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
+  std::vector<u64> ch((size_t)nch * E);
+  if (nargs) a.t.challenge_scalars(ch.data(), ch.size(), p);
+  AirProg pg; std::vector<AuxInstance> inst;
+  if (linked_program_folded<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh)) { *why = "malformed arguments: the program exceeds ms_mix_air's limits"; return MS_ERR_ARG; }
+  const ms_air* prog = pg.view();
+  if (h32[6] != sh.m) { *why = "header: m is not the verifier's"; return 0; }
+  if (h32[7] != sh.npts) { *why = "header: npts is not the verifier's"; return 0; }
+  if (la != arthur_len_folded(sh, E, nargs, nfinal)) { *why = "header: len(arthur) is not what the statement and D_0 fix"; return 0; }
+  std::vector<u64> q((lq + 7) / 8 + 5, 0);            // the MSLF blob, aligned for the section verifiers
+  memcpy(q.data(), data + MSLP3_HEAD + la, lq);
+  if (lq < 40 || q[0] != 0x464C534DULL) { *why = "header: no MSLF blob behind arthur"; return 0; }
+  const u64 l_msff = q[1], l_lde = q[2], l_stg = q[3], l_val = q[4];
+  if (l_msff > lq - 40 || l_lde > lq - 40 - l_msff || l_stg > lq - 40 - l_msff - l_lde || l_val != lq - 40 - l_msff - l_lde - l_stg) { *why = "header: the MSLF section lengths do not fit the blob exactly"; return 0; }
+  if ((l_msff | l_lde | l_stg | l_val) & 7) { *why = "header: an MSLF section length is no multiple of 8"; return 0; }
+  if (!c1 && l_stg) { *why = "header: a staged section in a proof without running columns"; return 0; }
+  const u8* msff = (const u8*)q.data() + 40; const u8* lde_open = msff + l_msff; const u8* stg_open = lde_open + l_lde; const u8* val_open = stg_open + l_stg;
+  if (l_msff < 56 + nfinal * E * 8 || q[5 + 5] != D0) { *why = "header: D_0 is not the MSFF's own"; return 0; }
+  std::vector<u8> roots((size_t)sh.R * 32);
+  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), alphas((size_t)sh.R * E), fin((size_t)nfinal * E + 1), betas(sh.nq);
+  if (nargs && !a.next_bytes(sroot, 32)) { *why = cut; return 0; }
+  a.t.challenge_scalars(r.data(), E, p);
+  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
+  draw_z(a.t, z.data(), E, p);
+  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
+  if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
+  a.t.challenge_scalars(gamma.data(), E, p);
+  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
+  for (u32 i = 0; i + 1 < sh.R; i++) {
+    a.t.challenge_scalars(alphas.data() + (size_t)i * E, E, p);
+    if (!a.next_bytes(roots.data() + (size_t)(i + 1) * 32, 32)) { *why = cut; return 0; }
+  }
+  a.t.challenge_scalars(alphas.data() + (size_t)(sh.R - 1) * E, E, p);
+  if (!a.next_scalars(fin.data(), (size_t)nfinal * E)) { *why = cut; return 0; }
+  if (!V::canon(fin.data(), (size_t)nfinal * E)) { *why = "transcript: a coefficient of the final polynomial is not canonical"; return 0; }
+  if (memcmp(fin.data(), msff + 56, (size_t)nfinal * E * 8)) { *why = "transcript: the final polynomial in arthur is not the MSFF's"; return 0; }
+  u8 seed[32] = {0}; u64 nonce = 0;
+  if (sh.gb) {
+    a.t.challenge_bytes(seed, 32);
+    u8 le[8];
+    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
+    for (int b = 0; b < 8; b++) nonce |= (u64)le[b] << (8 * b);
+  }
+  if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
+  { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
+  // ---- 1. the proof of work
+  if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
+  // ---- 2. the AIR identity at z
+  {
+    std::vector<u64> opened((size_t)sh.npts * sh.c * E);
+    for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
+    u64 want[E], got[E];
+    const int rc = air_expected<F, E>(r.data(), *prog, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
+    if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
+    validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
+    if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
+  }
+  // ---- 3. the folded FRI on the MSFF section, with the roots and challenges of the replay
+  std::string sub;
+  int rc = fri_folded_verify<F, E>(c.digest, zae, sh.blowup, k, roots.data(), sh.R, alphas.data(), betas.data(), sh.nq, msff, l_msff, &sub);
+  if (rc != 1) { *why = "FRI: " + sub; return rc; }
+  // ---- 4. every slot of round 0's cosets against the coset-grouped trees
+  const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
+  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
+  rc = deep_link_verify_folded<F, E>(c.digest, zae, N, sh.blowup, shift, k, c0, c1, sh.m, lroot, c1 ? sroot : nullptr, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msff, l_msff,
+                                     lde_open, l_lde, stg_open, l_stg, val_open, l_val, &sub);
+  if (rc != 1) { *why = sub; return rc; }
+  return 1;
+}
 static size_t copy_out(const void* src, size_t n, void* dst, size_t cap) { if (dst && cap >= n && n) memcpy(dst, src, n); return n; }
 
 extern "C" {
@@ -2001,6 +2318,23 @@ int msh_deep_link_verify_staged(int digest_id, int field, int zero_display_empty
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }
+int msh_deep_link_verify_folded(int digest_id, int field, int zero_display_empty, u64 N, u64 blowup, u64 shift, int log_arity, uint32_t c0, uint32_t c1, uint32_t m,
+                                const u8 lde_root[32], const u8 stg_root[32], const u8 val_root[32], const ms_deep* deep, const u64* evals, const u64* gamma, const u64* betas,
+                                size_t nq, const u8* msff, size_t msff_len, const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open,
+                                size_t val_len, char* why, size_t why_cap) {
+  if (!known_digest(digest_id) || (field != MS_FIELD_GOLDILOCKS && field != MS_FIELD_BABYBEAR)) return set_why(why, why_cap, "unknown digest or field", MS_ERR_ARG);
+  if (!lde_root || !val_root || (c1 == 0) != (stg_root == nullptr) || (c1 != 0 && !stg_open) || !deep || !deep->z || !deep->pt_begin || !deep->pt_poly || !evals || !gamma || !betas ||
+      !msff || !lde_open || !val_open || nq < 1 || nq > 4096 || !N || (N & (N - 1)) || !blowup || (blowup & (blowup - 1)) || N > ((u64)1 << 32) || blowup > ((u64)1 << 16) ||
+      log_arity < 1 || log_arity > 3 || c0 < 1 || m < 1 || c0 > (1u << 21) || c1 > (1u << 21) || m > (1u << 21))
+    return set_why(why, why_cap, "null argument (stg_root is NULL iff c1 = 0), or N, blowup, log_arity, c0, c1, m or queries out of range", MS_ERR_ARG);
+  try {
+    std::string w;
+    const int rc = field == MS_FIELD_GOLDILOCKS
+      ? deep_link_verify_folded<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, log_arity, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msff, msff_len, lde_open, lde_len, stg_open, c1 ? stg_len : 0, val_open, val_len, &w)
+      : deep_link_verify_folded<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, log_arity, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msff, msff_len, lde_open, lde_len, stg_open, c1 ? stg_len : 0, val_open, val_len, &w);
+    return set_why(why, why_cap, w.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
 int msh_stark_prove_linked_aux(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
                                uint32_t nch, uint32_t fri_rounds) {
   if (!h) return MS_ERR_ARG;
@@ -2017,6 +2351,26 @@ int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh
     const StarkConfig& c = h->s.cfg;
     const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked_aux<GL, 2>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg)
                                                   : verify_linked_aux<BB, 4>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg);
+    return set_why(why, why_cap, msg.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+// ---- linked proofs over a folded FRI (MSLP v3)
+int msh_stark_prove_linked_folded(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
+                                  uint32_t nch, int log_arity, uint32_t fri_folds) {
+  if (!h) return MS_ERR_ARG;
+  try {
+    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked_folded<GL, 2>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, log_arity, fri_folds)
+                                                 : prove_linked_folded<BB, 4>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, log_arity, fri_folds);
+  } catch (...) { h->s.linked.clear(); return MS_ERR_NOMEM; }
+}
+int msh_stark_verify_linked_folded(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, int log_arity, uint32_t fri_folds,
+                                   const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
+  if (!h || !data || !air) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
+  try {
+    std::string msg;
+    const StarkConfig& c = h->s.cfg;
+    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked_folded<GL, 2>(c, air, args, nargs, nch, N, w, log_arity, fri_folds, data, len, zero_display_empty, &msg)
+                                                  : verify_linked_folded<BB, 4>(c, air, args, nargs, nch, N, w, log_arity, fri_folds, data, len, zero_display_empty, &msg);
     return set_why(why, why_cap, msg.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }

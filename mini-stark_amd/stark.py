@@ -245,6 +245,34 @@ class LinkedProofV2:
                            self.blowup, len(self.arthur), len(self.msls)) + self.arthur + self.msls
 
 
+@dataclass
+class LinkedProofV3:
+    """A linked proof over a folded FRI and coset-grouped row trees, MSLP v3 (include/ministark_host.h): the header's counts, the transcript bytes and the MSLF blob
+    of Context.query_linked_folded."""
+    e: int
+    log_arity: int
+    c0: int
+    c1: int
+    m: int
+    npts: int
+    folds: int
+    nq: int
+    grinding_bits: int
+    nargs: int
+    nch: int
+    N: int
+    blowup: int
+    D0: int
+    arthur: bytes
+    mslf: bytes
+
+    _HEAD = "<4s12I5Q"
+
+    def to_bytes(self) -> bytes:
+        return struct.pack(self._HEAD, b"MSLP", 3, self.e, self.log_arity, self.c0, self.c1, self.m, self.npts, self.folds, self.nq, self.grinding_bits, self.nargs, self.nch,
+                           self.N, self.blowup, self.D0, len(self.arthur), len(self.mslf)) + self.arthur + self.mslf
+
+
 def unflatten_air(air):
     """(constraints, exempt, periodic, boundary) as lists from a flatten_air dict"""
     tb, fb, eb = [int(x) for x in air["term_begin"]], [int(x) for x in air["fac_begin"]], [int(x) for x in air["ex_begin"]]
@@ -347,12 +375,16 @@ class Stark:
 
 
     # ---- linked proofs (build-defined; MSLP v1, transcript order and redraw rules: include/ministark_host.h) -----------------------
-    def prove_air(self, trace, air, fri_rounds: int = 0, aux=None, forced_challenges=None):
+    def prove_air(self, trace, air, fri_rounds: int = 0, aux=None, forced_challenges=None, log_arity: int = 0, fri_folds: int = 0):
         """msh_stark_prove_linked driven from Python: the same stages, the same transcript, the same bytes.  trace: the N x w matrix; air: a flatten_air dict or the
         tuple (constraints, exempt, periodic, boundary).  The statement: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air`.
         Raises MsError(ERR_SHAPE) for a trace that violates the program.
         aux = (args, nch): a proof with running columns, MSLP v2 (msh_stark_prove_linked_aux) - args flatten_aux_arg dicts whose selectors name nch challenges;
-        returns a LinkedProofV2.  forced_challenges (tests only): the columns are built from these instead of the transcript's."""
+        returns a LinkedProofV2.  forced_challenges (tests only): the columns are built from these instead of the transcript's.
+        log_arity = k in 1..3: MSLP v3 (msh_stark_prove_linked_folded) - the folded FRI at arity 2^k over coset-grouped row trees, with or without aux; fri_folds = 0
+        means floor(log2 N / k) folds; returns a LinkedProofV3."""
+        if log_arity:
+            return self._prove_air_folded(trace, air, log_arity, fri_folds, aux[0] if aux else [], aux[1] if aux else 0)
         if aux is not None:
             return self._prove_air_aux(trace, air, fri_rounds, aux[0], aux[1], forced_challenges)
         cfg, ctx = self.cfg, self.cfg.ctx
@@ -501,14 +533,102 @@ class Stark:
         self.last_challenges = dict(shift=shift, ch=ch, r=r, z=z, gamma=gamma, betas=betas)
         return LinkedProofV2(e, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
 
-    def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True, aux=None) -> bool:
+    def _prove_air_folded(self, trace, air, k, fri_folds, args, nch):
+        cfg, ctx = self.cfg, self.cfg.ctx
+        field, p, e = ctx.field, _MODULUS[ctx.field], ctx.e
+        if not isinstance(air, dict):
+            air = flatten_air(*air)
+        data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
+        N, w = data.shape
+        blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
+        if k not in (1, 2, 3) or (not args and nch):
+            raise MsError(ERR_ARG, "prove_air: log_arity outside 1..3, or challenges without arguments")
+        R, nq, gb = fri_folds or (N.bit_length() - 1) // k, cfg.fri_queries, cfg.grinding_bits
+        t = Transcript(cfg.domsep + "/linked/v3", ctx.digest)
+        t.add_bytes(struct.pack("<11Q", field, ctx.digest, N, w, blowup, k, R, nq, gb, len(args), nch))
+        t.add_bytes(encode_air(air))
+        if args:
+            t.add_bytes(encode_aux(args, nch))
+        t.prover_bytes = bytearray()
+        rc, root = ctx.trace_commit(data, w)
+        ctx.check(rc)
+        t.add_bytes(root)
+        (shift,) = t.challenge_scalars(1, p)
+        while shift == 0 or pow(shift, L, p) == 1:
+            (shift,) = t.challenge_scalars(1, p)
+        ctx.check(ctx.interpolate())
+        rc, root = ctx.lde_commit_coset(blowup, shift, k)
+        ctx.check(rc)
+        t.add_bytes(root)
+        cons, exempt, periodic, boundary = unflatten_air(air)
+        ch = []
+        if args:
+            flat = t.challenge_scalars(nch * e, p)                # the arguments' challenges follow the commitment to the main columns
+            ch = [tuple(int(v) for v in flat[j * e:(j + 1) * e]) for j in range(nch)]
+            for j, arg in enumerate(args):
+                inst = instantiate_aux(field, arg, ch)
+                rc, final, _ = ctx.aux_running_staged(inst["op"], inst, e)
+                ctx.check(rc)
+                if tuple(final) != ((1 if inst["op"] == AUX_PRODUCT else 0),) + (0,) * (e - 1):
+                    raise MsError(ERR_SHAPE, "prove_air: an argument does not hold (final is not the identity)")
+                c2, e2, b2 = aux_constraints(field, inst["op"], aux_fractions(inst), e, w + j * e)
+                cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
+            rc, root = ctx.lde_commit_stage_coset(k)
+            ctx.check(rc)
+            t.add_bytes(root)
+        c1 = len(args) * e
+        c = w + c1
+        prog = flatten_air(cons, exempt, periodic, boundary) if args else air
+        r = t.challenge_scalars(e, p)
+        ctx.check(ctx.mix_air_ext(r, prog))
+        m = e * ctx.validity_len() // N
+        rc, root = ctx.validity_commit_coset(k)
+        ctx.check(rc)
+        t.add_bytes(root)
+        z = t.challenge_scalars(e, p)
+        while not any(z[1:]):
+            z = t.challenge_scalars(e, p)
+        rows = sorted({0} | {int(x) for x in np.asarray(prog["fac_row"]).reshape(-1)})
+        if len(rows) > 8:
+            raise MsError(ERR_ARG, "prove_air: the program touches more than 8 row offsets")
+        omega = ctx.root_of_unity(N)
+        pts = [[v * pow(omega, row, p) % p for v in z] for row in rows]
+        lists = [list(range(c)) + (list(range(c, c + m)) if j == 0 else []) for j in range(len(rows))]
+        rc, ev = ctx.deep_evals(pts, lists)
+        ctx.check(rc)
+        t.add_scalars(ev.reshape(-1))
+        gamma = t.challenge_scalars(e, p)
+        ctx.check(ctx.deep_compose(pts, lists, gamma))
+        rc, root = ctx.fri_begin_folded(blowup, k)
+        ctx.check(rc)
+        t.add_bytes(root)
+        D0 = ctx.fri_round_info(0)[1]
+        for _ in range(R - 1):
+            rc, root = ctx.fri_fold_folded(t.challenge_scalars(e, p))
+            ctx.check(rc)                                         # ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
+            t.add_bytes(root)
+        rc, fin = ctx.fri_fold_final(t.challenge_scalars(e, p))
+        ctx.check(rc)
+        t.add_scalars(np.asarray(fin, dtype=np.uint64).reshape(-1))
+        if gb:
+            rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
+            ctx.check(rc)
+            t.add_bytes(struct.pack("<Q", nonce))
+        raw = t.challenge_bytes(8 * nq)
+        betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
+        self.last_challenges = dict(shift=shift, ch=ch, r=r, z=z, gamma=gamma, betas=betas)
+        return LinkedProofV3(e, k, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, D0, bytes(t.prover_bytes), ctx.query_linked_folded(betas))
+
+    def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True, aux=None, log_arity: int = 0, fri_folds: int = 0) -> bool:
         """msh_stark_verify_linked on MSLP bytes (or a LinkedProof) under this configuration.  True / False, the reason of a rejection - naming the step - in
         `self.last_verify_error`; raises MsError on malformed arguments."""
         from .host import HostStark   # (host.py imports this module)
         cfg = self.cfg
         hs = HostStark(cfg.ctx, cfg.security_bits, cfg.blowup_factor, cfg.steps, cfg.trace_columns, cfg.grinding_bits)
         data = data if isinstance(data, (bytes, bytearray)) else data.to_bytes()
-        if aux is not None:
+        if log_arity:
+            rc, self.last_verify_error = hs.verify_linked_folded(data, air, N, w, log_arity, aux[0] if aux else [], aux[1] if aux else 0, fri_folds, zero_display_empty)
+        elif aux is not None:
             rc, self.last_verify_error = hs.verify_linked_aux(data, air, aux[0], aux[1], N, w, fri_rounds, zero_display_empty)
         else:
             rc, self.last_verify_error = hs.verify_linked(data, air, N, w, fri_rounds, zero_display_empty)
