@@ -746,30 +746,78 @@ template <class F, int E> static void validity_from_chunks(u32 ve, u32 nchunks, 
   for (int l = 0; l < E; l++) out[l] = F::to_u64(acc.c[l]);
 }
 
+// ---- what the two link verifiers share: the validation of their arguments, the tables over the claimed evaluations, D(x) from opened leaf groups
+template <class F, int E> struct LinkTables {
+  typedef typename F::T T;
+  typedef Ext<F, E> X;
+  typedef Verifier<F, E> V;
+  const ms_deep& d; u32 c0, c; size_t ne = 0; u64 L = 0; T sh, gL;
+  std::vector<X> z, gpow, ev, inv; std::vector<u32> pt_of;
+  LinkTables(const ms_deep& d_, u32 c0_, u32 c1) : d(d_), c0(c0_), c(c0_ + c1) {}
+  // 1: go on; otherwise the verdict (0 rejected, < 0 malformed arguments) with the reason in *why.  min_L: the smallest LDE domain the caller's leaf groups need;
+  // `step` stands in front of the two rejections (the folded verifier names the step there, the plain one does not)
+  int init(u64 N, u64 blowup, u64 shift, u64 min_L, u32 m, const u64* evals, const u64* gamma, const std::string& step, std::string* why) {
+    L = N * blowup;
+    if (shift == 0 || shift >= F::P || L > ((u64)1 << F::TWO_ADICITY) || L < min_L) { *why = "shift or domain size out of range"; return MS_ERR_ARG; }
+    if (d.npts < 1 || d.npts > 8 || d.pt_begin[0] != 0) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+    for (u32 t = 0; t < d.npts; t++) if (d.pt_begin[t + 1] <= d.pt_begin[t] || d.pt_begin[t + 1] > 8192) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
+    ne = d.pt_begin[d.npts];
+    for (size_t n = 0; n < ne; n++) if (d.pt_poly[n] >= c + m) { *why = "malformed ms_deep: an index at or above c + m"; return MS_ERR_ARG; }
+    if (!V::canon(d.z, (size_t)d.npts * E) || !V::canon(gamma, E)) { *why = "a point or gamma is not canonical"; return MS_ERR_ARG; }
+    if (!V::canon(evals, ne * E)) { *why = step + "claimed evaluation not canonical"; return 0; }
+    int lgL = 0; while (((u64)1 << lgL) < L) lgL++;
+    sh = F::from_u64(shift); gL = f_root_of_unity<F>(lgL);
+    const T shL = f_pow<F>(sh, L);
+    z.resize(d.npts); inv.resize(d.npts);
+    for (u32 t = 0; t < d.npts; t++) {
+      z[t] = V::load(d.z + (size_t)t * E);
+      if (e_eq<F, E>(e_pow<F, E>(z[t], L), e_from_base<F, E>(shL))) { *why = step + "a point lies in the LDE coset: the quotient by (x - z) is undefined at one of its rows"; return 0; }
+    }
+    X gp = e_one<F, E>();
+    const X g = V::load(gamma);
+    gpow.resize(ne); ev.resize(ne); pt_of.resize(ne);
+    for (u32 t = 0; t < d.npts; t++) for (u32 n = d.pt_begin[t]; n < d.pt_begin[t + 1]; n++) pt_of[n] = t;
+    for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
+    return 1;
+  }
+  // D(x) = sum_n gamma^n (f_n(x) - ev_n) / (x - z_t) from the opened leaf groups and the claimed evaluations: word col * a + t of a group is column col at
+  // slot t (a plain row: a = 1, t = 0)
+  X compose_at(T x, const u64* lrow, const u64* srow, const u64* vrow, u64 a, u64 t) {
+    for (u32 p = 0; p < d.npts; p++) inv[p] = e_inv<F>(e_sub<F, E>(e_from_base<F, E>(x), z[p]));
+    X Dx = e_zero<F, E>();
+    for (size_t n = 0; n < ne; n++) {
+      const u32 fi = d.pt_poly[n];
+      const T fx = F::from_u64(fi < c0 ? lrow[(u64)fi * a + t] : fi < c ? srow[(u64)(fi - c0) * a + t] : vrow[(u64)(fi - c) * a + t]);
+      Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
+    }
+    return Dx;
+  }
+};
+// a cursor over one tree's opening section: open() checks the next path at its element index under the root and yields the leaf group's lpn words
+template <class F> struct OpenCursor {
+  const char* name; int digest, zae; const u8* root; size_t lpn; const u8* p; size_t left;
+  const u64* open(u64 index, std::string* why) {
+    size_t used = 0; std::string w;
+    if (!check_path_at<F>(digest, 1, lpn, zae, root, p, left, index, &used, &w)) { *why = std::string(name) + " opening: " + w; return nullptr; }
+    const u64* words = (const u64*)(p + 8);
+    p += used; left -= used;
+    return words;
+  }
+  bool done(std::string* why) const { if (left) *why = std::string(name) + " opening: trailing bytes"; return left == 0; }
+};
+
 // the link between FRI's round 0 and the two committed trees: 1 accepted, 0 rejected (reason in *why), < 0 malformed arguments
 // c1 > 0 (msh_deep_link_verify_staged): the columns c0 .. c0 + c1 - 1 come from rows of a second tree under stg_root, opened at the same rows
 template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N, u64 blowup, u64 shift, u32 c0, u32 c1, u32 m, const u8* lde_root, const u8* stg_root, const u8* val_root,
                                                       const ms_deep& d, const u64* evals, const u64* gamma, const u64* betas, size_t nq, const u8* msfi, size_t msfi_len,
                                                       const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open, size_t val_len, std::string* why) {
   typedef typename F::T T;
-  const u32 c = c0 + c1;
   typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
-  const u64 L = N * blowup;
-  if (shift == 0 || shift >= F::P || L > ((u64)1 << F::TWO_ADICITY)) { *why = "shift or domain size out of range"; return MS_ERR_ARG; }
-  if (d.npts < 1 || d.npts > 8 || d.pt_begin[0] != 0) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
-  for (u32 t = 0; t < d.npts; t++) if (d.pt_begin[t + 1] <= d.pt_begin[t] || d.pt_begin[t + 1] > 8192) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
-  const size_t ne = d.pt_begin[d.npts];
-  for (size_t n = 0; n < ne; n++) if (d.pt_poly[n] >= c + m) { *why = "malformed ms_deep: an index at or above c + m"; return MS_ERR_ARG; }
-  if (!V::canon(d.z, (size_t)d.npts * E) || !V::canon(gamma, E)) { *why = "a point or gamma is not canonical"; return MS_ERR_ARG; }
-  if (!V::canon(evals, ne * E)) { *why = "claimed evaluation not canonical"; return 0; }
-  int lgL = 0; while (((u64)1 << lgL) < L) lgL++;
-  const T sh = F::from_u64(shift), gL = f_root_of_unity<F>(lgL), shL = f_pow<F>(sh, L);
-  std::vector<X> z(d.npts);
-  for (u32 t = 0; t < d.npts; t++) {
-    z[t] = V::load(d.z + (size_t)t * E);
-    if (e_eq<F, E>(e_pow<F, E>(z[t], L), e_from_base<F, E>(shL))) { *why = "a point lies in the LDE coset: the quotient by (x - z) is undefined at one of its rows"; return 0; }
-  }
+  LinkTables<F, E> lt(d, c0, c1);
+  const int ok = lt.init(N, blowup, shift, 0, m, evals, gamma, "", why);
+  if (ok != 1) return ok;
+  const u64 L = lt.L;
   // the MSFI header, the final polynomial, and window 0's openings (the whole blob is msh_fri_index_verify's to check)
   if (msfi_len < 48) { *why = "MSFI blob shorter than its header"; return 0; }
   u64 hd[6]; memcpy(hd, msfi, 48);
@@ -786,43 +834,19 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
   const u64 step = L / D0;
   int lg0 = 0; while (((u64)1 << lg0) < D0) lg0++;
   const T g0 = f_root_of_unity<F>(lg0);
-  X gp = e_one<F, E>();
-  const X g = V::load(gamma);
-  std::vector<X> gpow(ne), ev(ne);
-  std::vector<u32> pt_of(ne);
-  for (u32 t = 0; t < d.npts; t++) for (u32 n = d.pt_begin[t]; n < d.pt_begin[t + 1]; n++) pt_of[n] = t;
-  for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
-  const u8* lp = lde_open; size_t lleft = lde_len;
-  const u8* vp = val_open; size_t vleft = val_len;
-  const u8* sp = stg_open; size_t sleft = stg_len;
+  OpenCursor<F> lde{"LDE", digest, zae, lde_root, c0, lde_open, lde_len}, stg{"staged", digest, zae, stg_root, c1, stg_open, stg_len},
+      val{"validity", digest, zae, val_root, m, val_open, val_len};
   for (size_t j = 0; j < nq; j++) {
     const u64 b = betas[j] % D0;
     for (int s = 0; s < 2; s++) {
       const u64 pos = s ? (b + D0 / 2) % D0 : b, row = pos * step;
-      size_t used = 0;
-      std::string w;
-      if (!check_path_at<F>(digest, 1, c0, zae, lde_root, lp, lleft, row * c0, &used, &w)) { *why = "LDE opening: " + w; return 0; }
-      const u64* lrow = (const u64*)(lp + 8);
-      lp += used; lleft -= used;
-      const u64* srow = nullptr;
-      if (c1) {
-        if (!check_path_at<F>(digest, 1, c1, zae, stg_root, sp, sleft, row * c1, &used, &w)) { *why = "staged opening: " + w; return 0; }
-        srow = (const u64*)(sp + 8);
-        sp += used; sleft -= used;
-      }
-      if (!check_path_at<F>(digest, 1, m, zae, val_root, vp, vleft, row * m, &used, &w)) { *why = "validity opening: " + w; return 0; }
-      const u64* vrow = (const u64*)(vp + 8);
-      vp += used; vleft -= used;
+      const u64* lrow = lde.open(row * c0, why);
+      const u64* srow = lrow && c1 ? stg.open(row * c1, why) : nullptr;
+      if (!lrow || (c1 && !srow)) return 0;
+      const u64* vrow = val.open(row * m, why);
+      if (!vrow) return 0;
       // D(x) at x = shift * g_L^row from the opened rows and the claimed evaluations
-      const T x = F::mul(sh, f_pow<F>(gL, row));
-      std::vector<X> inv(d.npts);
-      for (u32 t = 0; t < d.npts; t++) inv[t] = e_inv<F>(e_sub<F, E>(e_from_base<F, E>(x), z[t]));
-      X Dx = e_zero<F, E>();
-      for (size_t n = 0; n < ne; n++) {
-        const u32 fi = d.pt_poly[n];
-        const T fx = F::from_u64(fi < c0 ? lrow[fi] : fi < c ? srow[fi - c0] : vrow[fi - c]);
-        Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
-      }
+      const X Dx = lt.compose_at(F::mul(lt.sh, f_pow<F>(lt.gL, row)), lrow, srow, vrow, 1, 0);
       X y;
       if (R > 1) {   // what window 0 opened at this position
         const size_t head = 8 + 2 * (size_t)E * 8 + 8;
@@ -841,9 +865,7 @@ template <class F, int E> static int deep_link_verify(int digest, int zae, u64 N
       if (!e_eq<F, E>(Dx, y)) { *why = R > 1 ? "DEEP link: the composition recomputed from the opened rows and the claimed evaluations is not the value round 0 opened" : "DEEP link: the composition recomputed from the opened rows and the claimed evaluations is not the final polynomial's value"; return 0; }
     }
   }
-  if (lleft != 0) { *why = "LDE opening: trailing bytes"; return 0; }
-  if (c1 && sleft != 0) { *why = "staged opening: trailing bytes"; return 0; }
-  if (vleft != 0) { *why = "validity opening: trailing bytes"; return 0; }
+  if (!lde.done(why) || (c1 && !stg.done(why)) || !val.done(why)) return 0;
   return 1;
 }
 
@@ -856,24 +878,12 @@ template <class F, int E> static int deep_link_verify_folded(int digest, int zae
                                                              size_t msff_len, const u8* lde_open, size_t lde_len, const u8* stg_open, size_t stg_len, const u8* val_open, size_t val_len,
                                                              std::string* why) {
   typedef typename F::T T;
-  typedef Ext<F, E> X;
   typedef Verifier<F, E> V;
-  const u32 c = c0 + c1;
-  const u64 L = N * blowup, a = (u64)1 << k;
-  if (shift == 0 || shift >= F::P || L > ((u64)1 << F::TWO_ADICITY) || L < 2 * a) { *why = "shift or domain size out of range"; return MS_ERR_ARG; }
-  if (d.npts < 1 || d.npts > 8 || d.pt_begin[0] != 0) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
-  for (u32 t = 0; t < d.npts; t++) if (d.pt_begin[t + 1] <= d.pt_begin[t] || d.pt_begin[t + 1] > 8192) { *why = "malformed ms_deep"; return MS_ERR_ARG; }
-  const size_t ne = d.pt_begin[d.npts];
-  for (size_t n = 0; n < ne; n++) if (d.pt_poly[n] >= c + m) { *why = "malformed ms_deep: an index at or above c + m"; return MS_ERR_ARG; }
-  if (!V::canon(d.z, (size_t)d.npts * E) || !V::canon(gamma, E)) { *why = "a point or gamma is not canonical"; return MS_ERR_ARG; }
-  if (!V::canon(evals, ne * E)) { *why = "DEEP link: claimed evaluation not canonical"; return 0; }
-  int lgL = 0; while (((u64)1 << lgL) < L) lgL++;
-  const T sh = F::from_u64(shift), gL = f_root_of_unity<F>(lgL), shL = f_pow<F>(sh, L);
-  std::vector<X> z(d.npts);
-  for (u32 t = 0; t < d.npts; t++) {
-    z[t] = V::load(d.z + (size_t)t * E);
-    if (e_eq<F, E>(e_pow<F, E>(z[t], L), e_from_base<F, E>(shL))) { *why = "DEEP link: a point lies in the LDE coset: the quotient by (x - z) is undefined at one of its rows"; return 0; }
-  }
+  const u64 a = (u64)1 << k;
+  LinkTables<F, E> lt(d, c0, c1);
+  const int ok = lt.init(N, blowup, shift, 2 * a, m, evals, gamma, "DEEP link: ", why);
+  if (ok != 1) return ok;
+  const u64 L = lt.L;
   // the MSFF header and round 0's paths: D_0 is the blob's own
   if (msff_len < 56) { *why = "MSFF blob shorter than its header"; return 0; }
   u64 hd[7]; memcpy(hd, msff, 56);
@@ -887,51 +897,26 @@ template <class F, int E> static int deep_link_verify_folded(int digest, int zae
   if (nfinal > D0 || (msff_len - 56) / 8 < nfinal * E) { *why = "MSFF blob truncated in the final polynomial"; return 0; }
   const u8* r0 = msff + 56 + (size_t)nfinal * E * 8;
   if ((msff_len - 56 - (size_t)nfinal * E * 8) / psize < nq) { *why = "MSFF blob truncated in round 0's openings"; return 0; }
-  X gp = e_one<F, E>();
-  const X g = V::load(gamma);
-  std::vector<X> gpow(ne), ev(ne), inv(d.npts);
-  std::vector<u32> pt_of(ne);
-  for (u32 t = 0; t < d.npts; t++) for (u32 n = d.pt_begin[t]; n < d.pt_begin[t + 1]; n++) pt_of[n] = t;
-  for (size_t n = 0; n < ne; n++, gp = e_mul<F>(gp, g)) { gpow[n] = gp; ev[n] = V::load(evals + n * E); }
-  const u8* lp = lde_open; size_t lleft = lde_len;
-  const u8* vp = val_open; size_t vleft = val_len;
-  const u8* sp = stg_open; size_t sleft = stg_len;
-  const T wa = f_pow<F>(gL, L / a);   // the step between the coset's rows
+  OpenCursor<F> lde{"LDE", digest, zae, lde_root, (size_t)a * c0, lde_open, lde_len}, stg{"staged", digest, zae, stg_root, (size_t)a * c1, stg_open, stg_len},
+      val{"validity", digest, zae, val_root, (size_t)a * m, val_open, val_len};
+  const T wa = f_pow<F>(lt.gL, L / a);   // the step between the coset's rows
   for (size_t j = 0; j < nq; j++) {
     const u64 q = betas[j] % D0 % D1, grp = q * s;
-    size_t used = 0;
-    std::string w;
-    if (!check_path_at<F>(digest, 1, (size_t)a * c0, zae, lde_root, lp, lleft, grp * a * c0, &used, &w)) { *why = "LDE opening: " + w; return 0; }
-    const u64* lrow = (const u64*)(lp + 8);
-    lp += used; lleft -= used;
-    const u64* srow = nullptr;
-    if (c1) {
-      if (!check_path_at<F>(digest, 1, (size_t)a * c1, zae, stg_root, sp, sleft, grp * a * c1, &used, &w)) { *why = "staged opening: " + w; return 0; }
-      srow = (const u64*)(sp + 8);
-      sp += used; sleft -= used;
-    }
-    if (!check_path_at<F>(digest, 1, (size_t)a * m, zae, val_root, vp, vleft, grp * a * m, &used, &w)) { *why = "validity opening: " + w; return 0; }
-    const u64* vrow = (const u64*)(vp + 8);
-    vp += used; vleft -= used;
+    const u64* lrow = lde.open(grp * a * c0, why);
+    const u64* srow = lrow && c1 ? stg.open(grp * a * c1, why) : nullptr;
+    if (!lrow || (c1 && !srow)) return 0;
+    const u64* vrow = val.open(grp * a * m, why);
+    if (!vrow) return 0;
     const u64* slots = (const u64*)(r0 + j * psize + 8);
     u64 li; memcpy(&li, r0 + j * psize, 8);
     if (li != q * a) { *why = "MSFF: a round-0 path is not at the query's leaf group"; return 0; }
     if (!V::canon(slots, (size_t)a * E)) { *why = "MSFF: opened value not canonical"; return 0; }
-    T x = F::mul(sh, f_pow<F>(gL, grp));
+    T x = F::mul(lt.sh, f_pow<F>(lt.gL, grp));
     for (u64 t = 0; t < a; t++, x = F::mul(x, wa)) {   // x = shift * g_L^(q s + t L / a)
-      for (u32 p = 0; p < d.npts; p++) inv[p] = e_inv<F>(e_sub<F, E>(e_from_base<F, E>(x), z[p]));
-      X Dx = e_zero<F, E>();
-      for (size_t n = 0; n < ne; n++) {
-        const u32 fi = d.pt_poly[n];
-        const T fx = F::from_u64(fi < c0 ? lrow[(u64)fi * a + t] : fi < c ? srow[(u64)(fi - c0) * a + t] : vrow[(u64)(fi - c) * a + t]);
-        Dx = e_add<F, E>(Dx, e_mul<F>(gpow[n], e_mul<F>(e_sub<F, E>(e_from_base<F, E>(fx), ev[n]), inv[pt_of[n]])));
-      }
-      if (!e_eq<F, E>(Dx, V::load(slots + t * E))) { *why = "DEEP link: the composition recomputed from the opened leaf groups and the claimed evaluations is not the value in slot " + std::to_string(t) + " of round 0's coset"; return 0; }
+      if (!e_eq<F, E>(lt.compose_at(x, lrow, srow, vrow, a, t), V::load(slots + t * E))) { *why = "DEEP link: the composition recomputed from the opened leaf groups and the claimed evaluations is not the value in slot " + std::to_string(t) + " of round 0's coset"; return 0; }
     }
   }
-  if (lleft != 0) { *why = "LDE opening: trailing bytes"; return 0; }
-  if (c1 && sleft != 0) { *why = "staged opening: trailing bytes"; return 0; }
-  if (vleft != 0) { *why = "validity opening: trailing bytes"; return 0; }
+  if (!lde.done(why) || (c1 && !stg.done(why)) || !val.done(why)) return 0;
   return 1;
 }
 
@@ -1078,7 +1063,7 @@ template <class F, int E> static int air_expected(const u64* r, const ms_air& a,
   return MS_OK;
 }
 
-// ---- linked proofs: MSLP v1 (ministark_host.h) -----------------------------------------------------------------------------------------------------------------
+// ---- linked proofs, MSLP v1, v2 and v3 (ministark_host.h): the program's encoding, the redraw rules, the shape a statement fixes ------------------------------------
 // The shape of an ms_air: every array that is needed is there, the CSR offsets start at 0 and do not decrease, the stages' own limits hold.  The counts the encoding carries
 struct AirShape { u32 ncons, nterms, nfacs, nex, nperiodic, nperval, nbound; };
 static bool air_shape(const ms_air* a, AirShape* s) {
@@ -1137,13 +1122,12 @@ static bool linked_z_ok(const u64* z, int e) { for (int l = 1; l < e; l++) if (z
 template <class F> static u64 draw_shift(Transcript& t, u64 L) { u64 s; do t.challenge_scalars(&s, 1, F::P); while (!linked_shift_ok<F>(s, L)); return s; }
 static void draw_z(Transcript& t, u64* z, int e, u64 p) { do t.challenge_scalars(z, e, p); while (!linked_z_ok(z, e)); }
 
-// What prover and verifier derive from the configuration, the AIR, N, w and fri_rounds alone: the statement they absorb and every count of the MSLP header
+// What prover and verifier derive from the configuration, the AIR, the arguments, N, w and the rounds alone: the statement they absorb and every count of the MSLP header
 struct LinkedShape {
   u32 c = 0, m = 0, npts = 0, R = 0, nq = 0, gb = 0; u64 N = 0, blowup = 0, L = 0;
   std::vector<u32> rows;          // the points are z * w^rows[t]; row 0 first
   std::vector<u32> pt_begin, pt_poly; size_t ne = 0;   // every point opens the c columns, the point of row 0 the m chunk columns too
-  std::vector<u8> statement;
-  size_t arthur_len(int e) const { return 3 * 32 + ne * e * 8 + 32 + (size_t)(R - 1) * (2 * e * 8 + 32) + (gb ? 8 : 0); }
+  std::vector<u8> statement; size_t words_bytes = 0, air_bytes = 0;   // the statement's words | msh_air_encode(air) | msh_aux_encode(args), when there are arguments
 };
 // what the program fixes, for c columns: m, the points and what they open (o->c, o->N set by the caller)
 static int linked_program_shape(const ms_air* air, const AirShape& sh, int e, LinkedShape* o) {
@@ -1173,25 +1157,12 @@ static int linked_program_shape(const ms_air* air, const AirShape& sh, int e, Li
   if (o->ne > 8192) return MS_ERR_ARG;
   return MS_OK;
 }
-// what the configuration fixes: field sizes, rounds, queries, grinding bits
-template <class F> static int linked_config_shape(const StarkConfig& c, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
+// what the configuration fixes: field sizes, queries, grinding bits
+template <class F> static int linked_config_shape(const StarkConfig& c, size_t N, size_t w, LinkedShape* o) {
   if (N < 2 || (N & (N - 1)) || w < 1 || w > (1u << 16) || !c.blowup_factor || (c.blowup_factor & (c.blowup_factor - 1))) return MS_ERR_ARG;
   if (N > ((u64)1 << F::TWO_ADICITY) / c.blowup_factor) return MS_ERR_ARG;
-  o->c = (u32)w; o->N = N; o->blowup = c.blowup_factor; o->L = N * c.blowup_factor; o->gb = c.grinding_bits;
-  o->R = fri_rounds ? fri_rounds : (u32)c.rounds; o->nq = (u32)c.fri_queries;
-  if (o->R < 1 || o->R > 64 || o->nq < 1 || o->nq > 4096) return MS_ERR_ARG;
-  return MS_OK;
-}
-template <class F> static int linked_shape(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
-  const int e = c.e;
-  AirShape sh;
-  if (!air_shape(air, &sh) || linked_config_shape<F>(c, N, w, fri_rounds, o) || linked_program_shape(air, sh, e, o)) return MS_ERR_ARG;
-  const u64 words[8] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)o->R, (u64)o->nq, (u64)o->gb};
-  std::vector<u8> enc;
-  if (!air_encode(air, &enc)) return MS_ERR_ARG;
-  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
-  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
-  return MS_OK;
+  o->N = N; o->blowup = c.blowup_factor; o->L = N * c.blowup_factor; o->gb = c.grinding_bits; o->nq = (u32)c.fri_queries;
+  return o->nq < 1 || o->nq > 4096 ? MS_ERR_ARG : MS_OK;
 }
 // z * w^row for every point, E limbs each (an element of K times a base-field scalar: limb by limb)
 template <class F> static std::vector<u64> linked_points(const LinkedShape& sh, const u64* z, int e) {
@@ -1203,169 +1174,7 @@ template <class F> static std::vector<u64> linked_points(const LinkedShape& sh, 
   }
   return pts;
 }
-static Transcript linked_transcript(const StarkConfig& c, const LinkedShape& sh) {
-  Transcript t(c.domsep + "/linked/v1", c.digest);
-  t.add_bytes(sh.statement.data(), 64);                                      // field, digest, N, w, blowup, R, nq, grinding bits
-  t.add_bytes(sh.statement.data() + 64, sh.statement.size() - 64);           // msh_air_encode(air)
-  t.prover_bytes.clear();                                                    // the statement is the verifier's own: it does not travel
-  return t;
-}
-static const size_t MSLP_HEAD = 9 * 4 + 4 * 8;
-static const u32 MSLP_MAGIC = 0x504C534Du;   // 'MSLP'
-
-// the prover's driver: transcript order and redraw rules of ministark_host.h
-template <class F> static int prove_linked(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, u32 fri_rounds) {
-  const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = c.e; const u64 p = c.p;
-  s.linked.clear();
-  if (!ctx || (!trace_host && !trace_dev)) return MS_ERR_ARG;
-  LinkedShape sh;
-  int rc = linked_shape<F>(c, air, N, w, fri_rounds, &sh);
-  if (rc) return rc;
-  Transcript t = linked_transcript(c, sh);
-  u8 root[32];
-  // the raw-trace root: ms_trace_commit is how the trace gets in.  It is absorbed first and binds nothing
-  rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
-  if (rc) return rc;
-  t.add_bytes(root, 32);
-  const u64 shift = draw_shift<F>(t, sh.L);
-  if ((rc = ms_interpolate(ctx))) return rc;
-  if ((rc = ms_lde_commit(ctx, sh.blowup, shift, w, root))) return rc;
-  t.add_bytes(root, 32);
-  std::vector<u64> r(e), z(e), gamma(e);
-  t.challenge_scalars(r.data(), e, p);
-  if ((rc = ms_mix_air_ext(ctx, r.data(), air))) return rc;                  // MS_ERR_SHAPE: the trace violates the AIR
-  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;        // (the stage's VL is the header's rule)
-  if ((rc = ms_validity_commit(ctx, sh.m, root))) return rc;
-  t.add_bytes(root, 32);
-  draw_z(t, z.data(), e, p);
-  const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
-  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  std::vector<u64> evals(sh.ne * e);
-  if ((rc = ms_deep_evals(ctx, &deep, evals.data()))) return rc;
-  t.add_scalars(evals.data(), evals.size());
-  t.challenge_scalars(gamma.data(), e, p);
-  if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
-  if ((rc = ms_fri_begin(ctx, sh.blowup, sh.R, root))) return rc;
-  t.add_bytes(root, 32);                                                     // round 0's root is in the transcript
-  std::vector<u64> zq(e), B(2 * e), alpha(e);
-  for (u32 i = 1; i < sh.R; i++) {
-    t.challenge_scalars(zq.data(), e, p);
-    if ((rc = ms_fri_deep(ctx, zq.data(), B.data()))) return rc;
-    t.add_scalars(B.data(), 2 * e);
-    t.challenge_scalars(alpha.data(), e, p);
-    if ((rc = ms_fri_fold_commit(ctx, alpha.data(), root))) return rc;
-    t.add_bytes(root, 32);
-  }
-  if (sh.gb) {                                                               // the proof of work, exactly as Stark::prove
-    u8 seed[32]; t.challenge_bytes(seed, 32);
-    u64 nonce = 0;
-    if (!ms_grind) return MS_ERR_ARG;
-    if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
-    u8 le[8]; for (int k = 0; k < 8; k++) le[k] = (u8)(nonce >> (8 * k));
-    t.add_bytes(le, 8);
-  }
-  std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
-  std::vector<u64> betas(sh.nq);
-  memcpy(betas.data(), raw.data(), raw.size());
-  size_t lq = 0;
-  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
-  const size_t la = t.prover_bytes.size();
-  if (la != sh.arthur_len(e)) return MS_ERR_STATE;
-  std::vector<u8> out(MSLP_HEAD + la + lq);
-  const u32 h32[9] = {MSLP_MAGIC, 1, (u32)e, sh.c, sh.m, sh.npts, sh.R, sh.nq, sh.gb};
-  const u64 h64[4] = {sh.N, sh.blowup, (u64)la, (u64)lq};
-  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
-  memcpy(out.data() + MSLP_HEAD, t.prover_bytes.data(), la);
-  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, out.data() + MSLP_HEAD + la, lq, &lq))) return rc;
-  s.linked.swap(out);
-  return MS_OK;
-}
-
-// the verifier: 1 accepted, 0 rejected (*why names the step), < 0 malformed arguments.  Nothing of the proof is trusted: every header field is the verifier's own
-template <class F, int E> static int verify_linked(const StarkConfig& c, const ms_air* air, size_t N, size_t w, u32 fri_rounds, const u8* data, size_t len, int zae, std::string* why) {
-  typedef Verifier<F, E> V;
-  const u64 p = c.p;
-  LinkedShape sh;
-  if (c.e != E || linked_shape<F>(c, air, N, w, fri_rounds, &sh)) { *why = "malformed arguments: the AIR program, N, w, the rounds or the configuration"; return MS_ERR_ARG; }
-  // ---- header: MSLP's and MSLQ's, lengths exact
-  if (len < MSLP_HEAD) { *why = "header: the proof is shorter than the MSLP header"; return 0; }
-  u32 h32[9]; u64 h64[4];
-  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
-  const u32 want32[9] = {MSLP_MAGIC, 1, (u32)E, sh.c, sh.m, sh.npts, sh.R, sh.nq, sh.gb};
-  static const char* const name32[9] = {"magic", "version", "E", "c", "m", "npts", "R", "nq", "grinding bits"};
-  for (int k = 0; k < 9; k++) if (h32[k] != want32[k]) { *why = std::string("header: ") + name32[k] + " is not the verifier's"; return 0; }
-  if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
-  if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
-  const size_t la = sh.arthur_len(E);
-  if (h64[2] != (u64)la) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
-  if (len - MSLP_HEAD < la || h64[3] != (u64)(len - MSLP_HEAD - la)) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
-  const size_t lq = len - MSLP_HEAD - la;
-  std::vector<u64> q((lq + 7) / 8 + 4, 0);            // the MSLQ blob, aligned for the section verifiers
-  memcpy(q.data(), data + MSLP_HEAD + la, lq);
-  if (lq < 32 || q[0] != 0x514C534DULL) { *why = "header: no MSLQ blob behind arthur"; return 0; }
-  const u64 l_msfi = q[1], l_lde = q[2], l_val = q[3];
-  if (l_msfi > lq - 32 || l_lde > lq - 32 - l_msfi || l_val != lq - 32 - l_msfi - l_lde) { *why = "header: the MSLQ section lengths do not fit the blob exactly"; return 0; }
-  if ((l_msfi | l_lde | l_val) & 7) { *why = "header: an MSLQ section length is no multiple of 8"; return 0; }
-  const u8* msfi = (const u8*)q.data() + 32; const u8* lde_open = msfi + l_msfi; const u8* val_open = lde_open + l_lde;
-  // ---- transcript: replayed from arthur, both redraw rules included
-  Arthur a(c.domsep, c.digest, data + MSLP_HEAD, la);
-  a.t = linked_transcript(c, sh);
-  u8 troot[32], lroot[32], vroot[32];
-  std::vector<u8> roots((size_t)sh.R * 32);
-  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), zs((size_t)(sh.R - 1) * E), Bs((size_t)(sh.R - 1) * 2 * E), alphas((size_t)(sh.R - 1) * E), betas(sh.nq);
-  const char* cut = "transcript: arthur ends early";
-  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
-  const u64 shift = draw_shift<F>(a.t, sh.L);
-  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
-  a.t.challenge_scalars(r.data(), E, p);
-  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
-  draw_z(a.t, z.data(), E, p);
-  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
-  if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
-  a.t.challenge_scalars(gamma.data(), E, p);
-  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
-  for (u32 i = 1; i < sh.R; i++) {
-    a.t.challenge_scalars(zs.data() + (size_t)(i - 1) * E, E, p);
-    if (!a.next_scalars(Bs.data() + (size_t)(i - 1) * 2 * E, 2 * E)) { *why = cut; return 0; }
-    a.t.challenge_scalars(alphas.data() + (size_t)(i - 1) * E, E, p);
-    if (!a.next_bytes(roots.data() + (size_t)i * 32, 32)) { *why = cut; return 0; }
-  }
-  if (!V::canon(Bs.data(), Bs.size())) { *why = "transcript: a round's B is not canonical"; return 0; }
-  u8 seed[32] = {0}; u64 nonce = 0;
-  if (sh.gb) {
-    a.t.challenge_bytes(seed, 32);
-    u8 le[8];
-    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
-    for (int k = 0; k < 8; k++) nonce |= (u64)le[k] << (8 * k);
-  }
-  if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
-  { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
-  // ---- 1. the proof of work
-  if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
-  // ---- 2. the AIR identity at z: the program on the opened evaluations against V(z) from the chunk evaluations
-  {
-    std::vector<u64> opened((size_t)sh.npts * sh.c * E);
-    for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
-    u64 want[E], got[E];
-    const int rc = air_expected<F, E>(r.data(), *air, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
-    if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
-    validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
-    if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
-  }
-  // ---- 3. FRI on the MSFI section, with the roots and challenges of the replay
-  std::string sub;
-  int rc = fri_index_verify<F, E>(c.digest, zae, sh.blowup, roots.data(), sh.R, zs.data(), Bs.data(), alphas.data(), betas.data(), sh.nq, msfi, l_msfi, &sub);
-  if (rc != 1) { *why = "FRI: " + sub; return rc; }
-  // ---- 4. round 0 against the two trees
-  const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
-  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, sh.c, 0, sh.m, lroot, nullptr, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
-                              nullptr, 0, val_open, l_val, &sub);
-  if (rc != 1) { *why = sub; return rc; }
-  return 1;
-}
-
-// ---- linked proofs with running columns: MSLP v2 (ministark_host.h) ---------------------------------------------------------------------------------------------
+// ---- the running columns of linked proofs (MSLP v2, v3; ministark_host.h): the arguments' encoding, their instances, the combined program ---------------------------
 // msh_aux_arg: what ms_aux_running's limits and the selectors ask of a descriptor; nterms out
 static bool aux_arg_shape(const msh_aux_arg& a, u32 nch, u64 p, u32* nterms_out) {
   if (a.op > 1 || a.nfrac < 1 || a.nfrac > 4 || !a.form_begin || !a.form_const || !a.form_ch || a.form_begin[0] != 0) return false;
@@ -1505,29 +1314,6 @@ template <class F, int E> static int aux_constraints(AirProg& pg, const ms_aux& 
   for (int l = 0; l < E; l++) { pg.bp.push_back(first_poly + l); pg.br.push_back(0); pg.bv.push_back((a.op == MS_AUX_PRODUCT && l == 0) ? 1 : 0); }
   return MS_OK;
 }
-static const size_t MSLP2_HEAD = 12 * 4 + 4 * 8;
-// the statement of a v2 proof and what the configuration fixes; the program's part of the shape follows the challenge draw (linked_combined)
-template <class F> static int linked_shape_aux(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, u32 fri_rounds, LinkedShape* o) {
-  AirShape sh;
-  if (!air_shape(air, &sh) || linked_config_shape<F>(c, N, w, fri_rounds, o)) return MS_ERR_ARG;
-  for (u32 k = 0; k < sh.nfacs; k++) if (!(air->fac_poly[k] & 0x80000000u) && air->fac_poly[k] >= w) return MS_ERR_ARG;   // the main program is over the w trace columns
-  const u64 words[10] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)o->R, (u64)o->nq, (u64)o->gb, (u64)nargs, (u64)nch};
-  std::vector<u8> enc, enx;
-  if (!air_encode(air, &enc) || !aux_encode(args, nargs, nch, c.p, c.e, w, &enx)) return MS_ERR_ARG;
-  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
-  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
-  o->statement.insert(o->statement.end(), enx.begin(), enx.end());
-  o->c = (u32)w + nargs * (u32)c.e;
-  return (int)enc.size();   // (> 0: where the second part of the statement ends)
-}
-static Transcript linked_transcript_aux(const StarkConfig& c, const LinkedShape& sh, size_t air_bytes) {
-  Transcript t(c.domsep + "/linked/v2", c.digest);
-  t.add_bytes(sh.statement.data(), 80);                                                  // field, digest, N, w, blowup, R, nq, grinding bits, nargs, nch
-  t.add_bytes(sh.statement.data() + 80, air_bytes);                                      // msh_air_encode(air)
-  t.add_bytes(sh.statement.data() + 80 + air_bytes, sh.statement.size() - 80 - air_bytes);   // msh_aux_encode(args)
-  t.prover_bytes.clear();
-  return t;
-}
 // the combined program - air plus msh_aux_constraints of every instantiated argument, argument k at first_poly = w + k E - and the shape it fixes
 template <class F, int E> static int linked_combined(const ms_air* air, const msh_aux_arg* args, u32 nargs, const u64* ch, size_t w, AirProg* pg, std::vector<AuxInstance>* inst, LinkedShape* o) {
   if (!pg->load(air)) return MS_ERR_ARG;
@@ -1541,44 +1327,142 @@ template <class F, int E> static int linked_combined(const ms_air* air, const ms
   if (!air_shape(pg->view(), &sh)) return MS_ERR_ARG;
   return linked_program_shape(pg->view(), sh, E, o);
 }
-static size_t arthur_len_aux(const LinkedShape& sh, int e) { return sh.arthur_len(e) + 32; }   // (the staged root behind the stage-0 root)
 
-template <class F, int E> static int prove_linked_aux(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, u32 fri_rounds) {
+// ---- the one prover driver and the one verifier of linked proofs: MSLP v1, v2 and v3 (ministark_host.h) ------------------------------------------------------------
+// The kind of a linked proof.  Everything in which the versions differ follows from these fields, at the places this table names; the rest is shared:
+//   point                          v1                          v2                              v3
+//   domain separator suffix        /linked/v1                  /linked/v2                      /linked/v3
+//   statement words                8                           10 (+ nargs, nch)               11 (+ k in front of R)
+//   aux encoding absorbed          no                          always                          when nargs > 0
+//   program shape fixed            before any device call      after the challenge draw        after the LDE root (challenges drawn when nargs > 0)
+//   LDE / staged / validity root   plain                       plain, staged root always       the _coset calls, staged root when nargs > 0
+//   FRI commit phase               ms_fri_begin, R - 1 x (z, B, alpha, root)       (as v1)     ms_fri_begin_folded, R - 1 x (alpha, root), alpha, final polynomial
+//   query call / blob              ms_query_linked, MSLQ (3)   ms_query_linked, MSLS (4)       ms_query_linked_folded, MSLF (4 sections)
+//   header                         9 x u32 + 4 x u64           12 x u32 + 4 x u64              13 x u32 + 5 x u64 (D_0)
+//   arthur length                  plain FRI, three roots      + 32 (the staged root)          folded FRI, + 32 when nargs > 0
+// (v2 has at least one argument - msh_aux_encode refuses none -, so "when nargs > 0" is v2's "always" and v1's "never")
+struct LinkedKind {
+  u32 version;                              // 1, 2 or 3
+  int k;                                    // log_arity of the folded FRI (v3); 0: the plain FRI
+  const msh_aux_arg* args; u32 nargs, nch;  // the arguments of the running columns and the challenges their selectors name
+  u32 rounds;                               // fri_rounds (plain) or fri_folds (folded); 0: the configuration's rounds, or floor(log2 N / k)
+};
+// what the verifier words per version: the header's and the query blob's name, its magic and sections, the two refusals of malformed arguments
+struct LinkedText { const char* head; const char* blob; u64 magic; int nsec; const char* bad_args; const char* bad_program; };
+static const LinkedText LINKED_TEXT[3] = {
+    {"MSLP", "MSLQ", 0x514C534DULL, 3, "malformed arguments: the AIR program, N, w, the rounds or the configuration", ""},
+    {"MSLP v2", "MSLS", 0x534C534DULL, 4, "malformed arguments: the AIR program, the arguments, N, w, the rounds or the configuration",
+     "malformed arguments: the combined program exceeds ms_mix_air's limits"},
+    {"MSLP v3", "MSLF", 0x464C534DULL, 4, "malformed arguments: the AIR program, the arguments, N, w, log_arity, the folds or the configuration",
+     "malformed arguments: the program exceeds ms_mix_air's limits"}};
+
+// the statement and what the configuration fixes; the program's part of the shape is linked_combined's (v1: at once; v2, v3: once the challenges are drawn)
+template <class F> static int linked_shape(const StarkConfig& c, const ms_air* air, size_t N, size_t w, const LinkedKind& kd, LinkedShape* o) {
+  AirShape sh;
+  if ((kd.version == 3 && (kd.k < 1 || kd.k > 3)) || !air_shape(air, &sh) || linked_config_shape<F>(c, N, w, o)) return MS_ERR_ARG;
+  if ((kd.nargs == 0) != (kd.args == nullptr) || (kd.nargs == 0 && kd.nch != 0)) return MS_ERR_ARG;
+  int lgN = 0; while (((u64)1 << lgN) < N) lgN++;
+  o->R = kd.rounds ? kd.rounds : kd.k ? (u32)(lgN / kd.k) : (u32)c.rounds;
+  if (o->R < 1 || o->R > 64 || (kd.k && o->L < ((u64)2 << kd.k))) return MS_ERR_ARG;
+  if (kd.version > 1)   // the main program is over the w trace columns (v1 leaves a column at or above w to the mix stage and to the evaluation at z)
+    for (u32 j = 0; j < sh.nfacs; j++) if (!(air->fac_poly[j] & 0x80000000u) && air->fac_poly[j] >= w) return MS_ERR_ARG;
+  std::vector<u64> words = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor};
+  if (kd.k) words.push_back((u64)kd.k);
+  words.insert(words.end(), {(u64)o->R, (u64)o->nq, (u64)o->gb});
+  if (kd.version > 1) words.insert(words.end(), {(u64)kd.nargs, (u64)kd.nch});
+  std::vector<u8> enc, enx;
+  if (!air_encode(air, &enc) || ((kd.version == 2 || kd.nargs) && !aux_encode(kd.args, kd.nargs, kd.nch, c.p, c.e, w, &enx))) return MS_ERR_ARG;
+  o->words_bytes = 8 * words.size(); o->air_bytes = enc.size();
+  o->statement.assign((const u8*)words.data(), (const u8*)words.data() + o->words_bytes);
+  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
+  o->statement.insert(o->statement.end(), enx.begin(), enx.end());
+  o->c = (u32)w + kd.nargs * (u32)c.e;
+  return MS_OK;
+}
+static Transcript linked_transcript(const StarkConfig& c, const LinkedShape& sh, const LinkedKind& kd) {
+  Transcript t(c.domsep + "/linked/v" + std::to_string(kd.version), c.digest);
+  const u8* s = sh.statement.data(); const size_t aux_at = sh.words_bytes + sh.air_bytes;
+  t.add_bytes(s, sh.words_bytes);                                            // field, digest, N, w, blowup, (k,) R, nq, grinding bits (, nargs, nch)
+  t.add_bytes(s + sh.words_bytes, sh.air_bytes);                             // msh_air_encode(air)
+  if (sh.statement.size() > aux_at) t.add_bytes(s + aux_at, sh.statement.size() - aux_at);   // msh_aux_encode(args), where it is part of the statement
+  t.prover_bytes.clear();                                                    // the statement is the verifier's own: it does not travel
+  return t;
+}
+// plain: trace, LDE, (staged,) validity root, evaluations, round 0's root, R - 1 x (B, root), nonce; folded: .. evaluations, R round roots, final polynomial, nonce
+static size_t linked_arthur_len(const LinkedShape& sh, const LinkedKind& kd, int e, u64 nfinal) {
+  const size_t fri = kd.k ? (size_t)sh.R * 32 + (size_t)nfinal * e * 8 : 32 + (size_t)(sh.R - 1) * (2 * e * 8 + 32);
+  return (size_t)(3 + (kd.nargs ? 1 : 0)) * 32 + sh.ne * e * 8 + fri + (sh.gb ? 8 : 0);
+}
+// The u32 words of a version's MSLP header, by name; behind them N, blowup, (D_0,) len(arthur), len(blob) as u64.  The prover writes the header from this table, the
+// verifier compares against it.  late: fixed by the program, which v2 and v3 know only once the challenges are drawn
+static const u32 MSLP_MAGIC = 0x504C534Du;   // 'MSLP'
+struct HeadWord { const char* name; u32 v; bool late; };
+template <int E> static std::vector<HeadWord> linked_header(const LinkedShape& sh, const LinkedKind& kd, size_t w) {
+  const bool late = kd.version > 1;
+  std::vector<HeadWord> h = {{"magic", MSLP_MAGIC, false}, {"version", kd.version, false}, {"E", (u32)E, false}};
+  if (kd.k) h.push_back({"log_arity", (u32)kd.k, false});
+  if (kd.version == 1) h.push_back({"c", sh.c, false});
+  else h.insert(h.end(), {{"c0", (u32)w, false}, {"c1", kd.nargs * (u32)E, false}});
+  h.insert(h.end(), {{"m", sh.m, late}, {"npts", sh.npts, late}, {"R", sh.R, false}, {"nq", sh.nq, false}, {"grinding bits", sh.gb, false}});
+  if (kd.version > 1) h.insert(h.end(), {{"nargs", kd.nargs, false}, {"nch", kd.nch, false}});
+  return h;
+}
+static size_t linked_head_bytes(const std::vector<HeadWord>& h, const LinkedKind& kd) { return 4 * h.size() + 8 * (size_t)(kd.k ? 5 : 4); }
+// the proof's u32 words against the verifier's own: the rows the statement fixes (late = false), or those the program fixes
+static bool linked_header_ok(const std::vector<HeadWord>& h, const u8* data, bool late, std::string* why) {
+  for (size_t j = 0; j < h.size(); j++) {
+    u32 got; memcpy(&got, data + 4 * j, 4);
+    if (h[j].late != late || got == h[j].v) continue;
+    if (j == 1 && h[1].v > 1) *why = "header: version is not " + std::to_string(h[1].v);   // (v1 words it like the other rows; both texts are pinned by callers)
+    else *why = std::string("header: ") + h[j].name + " is not the verifier's";
+    return false;
+  }
+  return true;
+}
+
+// the prover's driver: transcript order and redraw rules of ministark_host.h; it branches at the rows of the table above and nowhere else
+template <class F, int E> static int prove_linked(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const LinkedKind& kd) {
   const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = E; const u64 p = c.p;
   s.linked.clear();
   if (!ctx || c.e != E || (!trace_host && !trace_dev)) return MS_ERR_ARG;
+  // the statement
   LinkedShape sh;
-  int rc = linked_shape_aux<F>(c, air, args, nargs, nch, N, w, fri_rounds, &sh);
-  if (rc < 0) return rc;
-  Transcript t = linked_transcript_aux(c, sh, (size_t)rc);
+  int rc = linked_shape<F>(c, air, N, w, kd, &sh);
+  if (rc) return rc;
+  AirProg pg; std::vector<AuxInstance> inst;
+  std::vector<u64> ch((size_t)kd.nch * e);
+  if (kd.version == 1 && (rc = linked_combined<F, E>(air, nullptr, 0, nullptr, w, &pg, &inst, &sh))) return rc;   // v1 refuses a bad program before it touches the context
+  Transcript t = linked_transcript(c, sh, kd);
   u8 root[32];
+  // the raw-trace root: ms_trace_commit is how the trace gets in.  It is absorbed first and binds nothing
   rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
   if (rc) return rc;
   t.add_bytes(root, 32);
+  // the shift (redrawn while the coset would meet the trace domain), the LDE root
   const u64 shift = draw_shift<F>(t, sh.L);
   if ((rc = ms_interpolate(ctx))) return rc;
-  if ((rc = ms_lde_commit(ctx, sh.blowup, shift, w, root))) return rc;
+  if ((rc = kd.k ? ms_lde_commit_coset(ctx, sh.blowup, shift, kd.k, root) : ms_lde_commit(ctx, sh.blowup, shift, w, root))) return rc;
   t.add_bytes(root, 32);
-  // the arguments' challenges follow the commitment to the main columns
-  std::vector<u64> ch((size_t)nch * e);
-  t.challenge_scalars(ch.data(), ch.size(), p);
-  AirProg pg; std::vector<AuxInstance> inst;
-  if ((rc = linked_combined<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh))) return rc;
-  for (u32 k = 0; k < nargs; k++) {
+  // the arguments' challenges follow the commitment to the main columns; the program they fix; the running columns and the staged root
+  if (kd.nargs) t.challenge_scalars(ch.data(), ch.size(), p);
+  if (kd.version > 1 && (rc = linked_combined<F, E>(air, kd.args, kd.nargs, ch.data(), w, &pg, &inst, &sh))) return rc;
+  for (u32 j = 0; j < kd.nargs; j++) {
     u64 fin[E];
-    if ((rc = ms_aux_running_staged(ctx, &inst[k].aux, fin, nullptr))) return rc;          // MS_ERR_SHAPE: a zero denominator (probability about N / |K|)
-    for (int l = 0; l < e; l++) if (fin[l] != ((args[k].op == MS_AUX_PRODUCT && l == 0) ? 1u : 0u)) return MS_ERR_SHAPE;   // the argument does not hold
+    if ((rc = ms_aux_running_staged(ctx, &inst[j].aux, fin, nullptr))) return rc;          // MS_ERR_SHAPE: a zero denominator (probability about N / |K|)
+    for (int l = 0; l < e; l++) if (fin[l] != ((kd.args[j].op == MS_AUX_PRODUCT && l == 0) ? 1u : 0u)) return MS_ERR_SHAPE;   // the argument does not hold
   }
-  const u32 c1 = nargs * (u32)e;
-  if ((rc = ms_lde_commit_stage(ctx, c1, root))) return rc;
-  t.add_bytes(root, 32);
-  const ms_air* prog = pg.view();
+  if (kd.nargs) {
+    if ((rc = kd.k ? ms_lde_commit_stage_coset(ctx, kd.k, root) : ms_lde_commit_stage(ctx, kd.nargs * (u32)e, root))) return rc;
+    t.add_bytes(root, 32);
+  }
+  // r, the mix stage, the validity root
   std::vector<u64> r(e), z(e), gamma(e);
   t.challenge_scalars(r.data(), e, p);
-  if ((rc = ms_mix_air_ext(ctx, r.data(), prog))) return rc;
-  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;
-  if ((rc = ms_validity_commit(ctx, sh.m, root))) return rc;
+  if ((rc = ms_mix_air_ext(ctx, r.data(), pg.view()))) return rc;            // MS_ERR_SHAPE: the trace violates the AIR
+  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;        // (the stage's VL is the header's rule)
+  if ((rc = kd.k ? ms_validity_commit_coset(ctx, kd.k, root) : ms_validity_commit(ctx, sh.m, root))) return rc;
   t.add_bytes(root, 32);
+  // z (redrawn while it lies in the base field), the DEEP evaluations, gamma, the composition
   draw_z(t, z.data(), e, p);
   const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
   const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
@@ -1587,364 +1471,195 @@ template <class F, int E> static int prove_linked_aux(Stark& s, const u64* trace
   t.add_scalars(evals.data(), evals.size());
   t.challenge_scalars(gamma.data(), e, p);
   if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
-  if ((rc = ms_fri_begin(ctx, sh.blowup, sh.R, root))) return rc;
-  t.add_bytes(root, 32);
+  // the FRI commit phase; round 0's root is in the transcript
   std::vector<u64> zq(e), B(2 * e), alpha(e);
-  for (u32 i = 1; i < sh.R; i++) {
-    t.challenge_scalars(zq.data(), e, p);
-    if ((rc = ms_fri_deep(ctx, zq.data(), B.data()))) return rc;
-    t.add_scalars(B.data(), 2 * e);
+  u64 nc = 0, D0 = 0; size_t nfinal = 0;
+  if ((rc = kd.k ? ms_fri_begin_folded(ctx, sh.blowup, kd.k, root) : ms_fri_begin(ctx, sh.blowup, sh.R, root))) return rc;
+  t.add_bytes(root, 32);
+  if (!kd.k) {
+    for (u32 i = 1; i < sh.R; i++) {
+      t.challenge_scalars(zq.data(), e, p);
+      if ((rc = ms_fri_deep(ctx, zq.data(), B.data()))) return rc;
+      t.add_scalars(B.data(), 2 * e);
+      t.challenge_scalars(alpha.data(), e, p);
+      if ((rc = ms_fri_fold_commit(ctx, alpha.data(), root))) return rc;
+      t.add_bytes(root, 32);
+    }
+  } else {
+    if ((rc = ms_fri_round_info(ctx, 0, &nc, &D0))) return rc;
+    for (u32 i = 0; i + 1 < sh.R; i++) {
+      t.challenge_scalars(alpha.data(), e, p);
+      if ((rc = ms_fri_fold_folded(ctx, alpha.data(), root))) return rc;     // MS_ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
+      t.add_bytes(root, 32);
+    }
     t.challenge_scalars(alpha.data(), e, p);
-    if ((rc = ms_fri_fold_commit(ctx, alpha.data(), root))) return rc;
-    t.add_bytes(root, 32);
+    if ((rc = ms_fri_fold_final(ctx, alpha.data(), nullptr, 0, &nfinal))) return rc;
+    std::vector<u64> fin(nfinal * e + 1);
+    if ((rc = ms_fri_fold_final(ctx, alpha.data(), fin.data(), nfinal * e, &nfinal))) return rc;
+    t.add_scalars(fin.data(), nfinal * e);
   }
+  // the proof of work, exactly as Stark::prove
   if (sh.gb) {
     u8 seed[32]; t.challenge_bytes(seed, 32);
     u64 nonce = 0;
     if (!ms_grind) return MS_ERR_ARG;
     if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
-    u8 le[8]; for (int k = 0; k < 8; k++) le[k] = (u8)(nonce >> (8 * k));
-    t.add_bytes(le, 8);
-  }
-  std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
-  std::vector<u64> betas(sh.nq);
-  memcpy(betas.data(), raw.data(), raw.size());
-  size_t lq = 0;
-  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
-  const size_t la = t.prover_bytes.size();
-  if (la != arthur_len_aux(sh, e)) return MS_ERR_STATE;
-  std::vector<u8> out(MSLP2_HEAD + la + lq);
-  const u32 h32[12] = {MSLP_MAGIC, 2, (u32)e, (u32)w, c1, sh.m, sh.npts, sh.R, sh.nq, sh.gb, nargs, nch};
-  const u64 h64[4] = {sh.N, sh.blowup, (u64)la, (u64)lq};
-  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
-  memcpy(out.data() + MSLP2_HEAD, t.prover_bytes.data(), la);
-  if ((rc = ms_query_linked(ctx, betas.data(), (int)sh.nq, out.data() + MSLP2_HEAD + la, lq, &lq))) return rc;
-  s.linked.swap(out);
-  return MS_OK;
-}
-
-// the v2 verifier: as verify_linked, with the challenge draw behind the stage-0 root, the combined program rebuilt from it, and two LDE trees in the link
-template <class F, int E> static int verify_linked_aux(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, u32 fri_rounds,
-                                                       const u8* data, size_t len, int zae, std::string* why) {
-  typedef Verifier<F, E> V;
-  const u64 p = c.p;
-  LinkedShape sh;
-  const int air_bytes = c.e != E ? MS_ERR_ARG : linked_shape_aux<F>(c, air, args, nargs, nch, N, w, fri_rounds, &sh);
-  if (air_bytes < 0) { *why = "malformed arguments: the AIR program, the arguments, N, w, the rounds or the configuration"; return MS_ERR_ARG; }
-  const u32 c0 = (u32)w, c1 = nargs * (u32)E;
-  // ---- header, first part: what the statement fixes without the challenges
-  if (len < MSLP2_HEAD) { *why = "header: the proof is shorter than the MSLP v2 header"; return 0; }
-  u32 h32[12]; u64 h64[4];
-  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
-  if (h32[0] != MSLP_MAGIC) { *why = "header: magic is not the verifier's"; return 0; }
-  if (h32[1] != 2) { *why = "header: version is not 2"; return 0; }
-  const u32 want32[12] = {MSLP_MAGIC, 2, (u32)E, c0, c1, 0, 0, sh.R, sh.nq, sh.gb, nargs, nch};
-  static const char* const name32[12] = {"magic", "version", "E", "c0", "c1", "m", "npts", "R", "nq", "grinding bits", "nargs", "nch"};
-  for (int k = 2; k < 12; k++) if (k != 5 && k != 6 && h32[k] != want32[k]) { *why = std::string("header: ") + name32[k] + " is not the verifier's"; return 0; }
-  if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
-  if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
-  if (h64[2] > len - MSLP2_HEAD || h64[3] != (u64)(len - MSLP2_HEAD) - h64[2]) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
-  const size_t la = (size_t)h64[2], lq = len - MSLP2_HEAD - la;
-  if (la < 64) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
-  // ---- transcript up to the challenges of the arguments; then the combined program and the rest of the header
-  Arthur a(c.domsep, c.digest, data + MSLP2_HEAD, la);
-  a.t = linked_transcript_aux(c, sh, (size_t)air_bytes);
-  u8 troot[32], lroot[32], sroot[32], vroot[32];
-  const char* cut = "transcript: arthur ends early";
-  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
-  const u64 shift = draw_shift<F>(a.t, sh.L);
-  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
-  std::vector<u64> ch((size_t)nch * E);
-  a.t.challenge_scalars(ch.data(), ch.size(), p);
-  AirProg pg; std::vector<AuxInstance> inst;
-  if (linked_combined<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh)) { *why = "malformed arguments: the combined program exceeds ms_mix_air's limits"; return MS_ERR_ARG; }
-  const ms_air* prog = pg.view();
-  if (h32[5] != sh.m) { *why = "header: m is not the verifier's"; return 0; }
-  if (h32[6] != sh.npts) { *why = "header: npts is not the verifier's"; return 0; }
-  if (la != arthur_len_aux(sh, E)) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
-  std::vector<u64> q((lq + 7) / 8 + 5, 0);            // the MSLS blob, aligned for the section verifiers
-  memcpy(q.data(), data + MSLP2_HEAD + la, lq);
-  if (lq < 40 || q[0] != 0x534C534DULL) { *why = "header: no MSLS blob behind arthur"; return 0; }
-  const u64 l_msfi = q[1], l_lde = q[2], l_stg = q[3], l_val = q[4];
-  if (l_msfi > lq - 40 || l_lde > lq - 40 - l_msfi || l_stg > lq - 40 - l_msfi - l_lde || l_val != lq - 40 - l_msfi - l_lde - l_stg) { *why = "header: the MSLS section lengths do not fit the blob exactly"; return 0; }
-  if ((l_msfi | l_lde | l_stg | l_val) & 7) { *why = "header: an MSLS section length is no multiple of 8"; return 0; }
-  const u8* msfi = (const u8*)q.data() + 40; const u8* lde_open = msfi + l_msfi; const u8* stg_open = lde_open + l_lde; const u8* val_open = stg_open + l_stg;
-  std::vector<u8> roots((size_t)sh.R * 32);
-  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), zs((size_t)(sh.R - 1) * E), Bs((size_t)(sh.R - 1) * 2 * E), alphas((size_t)(sh.R - 1) * E), betas(sh.nq);
-  if (!a.next_bytes(sroot, 32)) { *why = cut; return 0; }
-  a.t.challenge_scalars(r.data(), E, p);
-  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
-  draw_z(a.t, z.data(), E, p);
-  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
-  if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
-  a.t.challenge_scalars(gamma.data(), E, p);
-  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
-  for (u32 i = 1; i < sh.R; i++) {
-    a.t.challenge_scalars(zs.data() + (size_t)(i - 1) * E, E, p);
-    if (!a.next_scalars(Bs.data() + (size_t)(i - 1) * 2 * E, 2 * E)) { *why = cut; return 0; }
-    a.t.challenge_scalars(alphas.data() + (size_t)(i - 1) * E, E, p);
-    if (!a.next_bytes(roots.data() + (size_t)i * 32, 32)) { *why = cut; return 0; }
-  }
-  if (!V::canon(Bs.data(), Bs.size())) { *why = "transcript: a round's B is not canonical"; return 0; }
-  u8 seed[32] = {0}; u64 nonce = 0;
-  if (sh.gb) {
-    a.t.challenge_bytes(seed, 32);
-    u8 le[8];
-    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
-    for (int k = 0; k < 8; k++) nonce |= (u64)le[k] << (8 * k);
-  }
-  if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
-  { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
-  // ---- 1. the proof of work
-  if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
-  // ---- 2. the AIR identity at z, on the combined program
-  {
-    std::vector<u64> opened((size_t)sh.npts * sh.c * E);
-    for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
-    u64 want[E], got[E];
-    const int rc = air_expected<F, E>(r.data(), *prog, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
-    if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
-    validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
-    if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
-  }
-  // ---- 3. FRI on the MSFI section
-  std::string sub;
-  int rc = fri_index_verify<F, E>(c.digest, zae, sh.blowup, roots.data(), sh.R, zs.data(), Bs.data(), alphas.data(), betas.data(), sh.nq, msfi, l_msfi, &sub);
-  if (rc != 1) { *why = "FRI: " + sub; return rc; }
-  // ---- 4. round 0 against the three trees
-  const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
-  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  rc = deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, c0, c1, sh.m, lroot, sroot, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msfi, l_msfi, lde_open, l_lde,
-                              stg_open, l_stg, val_open, l_val, &sub);
-  if (rc != 1) { *why = sub; return rc; }
-  return 1;
-}
-
-// ---- linked proofs over a folded FRI and coset-grouped row trees: MSLP v3 (ministark_host.h) -----------------------------------------------------------------------
-static const size_t MSLP3_HEAD = 13 * 4 + 5 * 8;
-// the statement of a v3 proof and what the configuration fixes.  R = fri_folds, or floor(log2 N / k).  Returns the bytes of msh_air_encode(air) (> 0), or < 0
-template <class F> static int linked_shape_folded(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, int k, u32 fri_folds, LinkedShape* o) {
-  AirShape sh;
-  if (k < 1 || k > 3 || !air_shape(air, &sh) || linked_config_shape<F>(c, N, w, 1, o)) return MS_ERR_ARG;
-  if ((nargs == 0) != (args == nullptr) || (nargs == 0 && nch != 0)) return MS_ERR_ARG;
-  int lgN = 0; while (((u64)1 << lgN) < N) lgN++;
-  o->R = fri_folds ? fri_folds : (u32)(lgN / k);
-  if (o->R < 1 || o->R > 64 || o->L < ((u64)2 << k)) return MS_ERR_ARG;
-  for (u32 j = 0; j < sh.nfacs; j++) if (!(air->fac_poly[j] & 0x80000000u) && air->fac_poly[j] >= w) return MS_ERR_ARG;   // the main program is over the w trace columns
-  const u64 words[11] = {(u64)c.field, (u64)c.digest, (u64)N, (u64)w, c.blowup_factor, (u64)k, (u64)o->R, (u64)o->nq, (u64)o->gb, (u64)nargs, (u64)nch};
-  std::vector<u8> enc, enx;
-  if (!air_encode(air, &enc) || (nargs && !aux_encode(args, nargs, nch, c.p, c.e, w, &enx))) return MS_ERR_ARG;
-  o->statement.assign((const u8*)words, (const u8*)words + sizeof words);
-  o->statement.insert(o->statement.end(), enc.begin(), enc.end());
-  o->statement.insert(o->statement.end(), enx.begin(), enx.end());
-  o->c = (u32)w + nargs * (u32)c.e;
-  return (int)enc.size();
-}
-static Transcript linked_transcript_folded(const StarkConfig& c, const LinkedShape& sh, size_t air_bytes) {
-  Transcript t(c.domsep + "/linked/v3", c.digest);
-  t.add_bytes(sh.statement.data(), 88);                                                  // field, digest, N, w, blowup, k, R, nq, grinding bits, nargs, nch
-  t.add_bytes(sh.statement.data() + 88, air_bytes);                                      // msh_air_encode(air)
-  if (sh.statement.size() > 88 + air_bytes) t.add_bytes(sh.statement.data() + 88 + air_bytes, sh.statement.size() - 88 - air_bytes);   // msh_aux_encode(args), when nargs > 0
-  t.prover_bytes.clear();
-  return t;
-}
-// the program a v3 proof is about: air alone (nargs = 0), or combined with the arguments' constraints; the shape it fixes
-template <class F, int E> static int linked_program_folded(const ms_air* air, const msh_aux_arg* args, u32 nargs, const u64* ch, size_t w, AirProg* pg, std::vector<AuxInstance>* inst, LinkedShape* o) {
-  if (nargs) return linked_combined<F, E>(air, args, nargs, ch, w, pg, inst, o);
-  AirShape sh;
-  if (!pg->load(air) || !air_shape(pg->view(), &sh)) return MS_ERR_ARG;
-  return linked_program_shape(pg->view(), sh, E, o);
-}
-// trace root, LDE root, (staged root,) validity root, evaluations, R round roots, final polynomial, nonce
-static size_t arthur_len_folded(const LinkedShape& sh, int e, u32 nargs, u64 nfinal) {
-  return (size_t)(3 + (nargs ? 1 : 0)) * 32 + sh.ne * e * 8 + (size_t)sh.R * 32 + (size_t)nfinal * e * 8 + (sh.gb ? 8 : 0);
-}
-
-template <class F, int E> static int prove_linked_folded(Stark& s, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch,
-                                                         int k, u32 fri_folds) {
-  const StarkConfig& c = s.cfg; ms_ctx* ctx = c.ctx; const int e = E; const u64 p = c.p;
-  s.linked.clear();
-  if (!ctx || c.e != E || (!trace_host && !trace_dev)) return MS_ERR_ARG;
-  LinkedShape sh;
-  int rc = linked_shape_folded<F>(c, air, args, nargs, nch, N, w, k, fri_folds, &sh);
-  if (rc < 0) return rc;
-  Transcript t = linked_transcript_folded(c, sh, (size_t)rc);
-  u8 root[32];
-  rc = trace_dev ? ms_trace_commit_device(ctx, trace_dev, N, w, w, root) : ms_trace_commit(ctx, trace_host, N, w, w, root);
-  if (rc) return rc;
-  t.add_bytes(root, 32);
-  const u64 shift = draw_shift<F>(t, sh.L);
-  if ((rc = ms_interpolate(ctx))) return rc;
-  if ((rc = ms_lde_commit_coset(ctx, sh.blowup, shift, k, root))) return rc;
-  t.add_bytes(root, 32);
-  std::vector<u64> ch((size_t)nch * e);
-  if (nargs) t.challenge_scalars(ch.data(), ch.size(), p);                   // the arguments' challenges follow the commitment to the main columns
-  AirProg pg; std::vector<AuxInstance> inst;
-  if ((rc = linked_program_folded<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh))) return rc;
-  for (u32 j = 0; j < nargs; j++) {
-    u64 fin[E];
-    if ((rc = ms_aux_running_staged(ctx, &inst[j].aux, fin, nullptr))) return rc;
-    for (int l = 0; l < e; l++) if (fin[l] != ((args[j].op == MS_AUX_PRODUCT && l == 0) ? 1u : 0u)) return MS_ERR_SHAPE;   // the argument does not hold
-  }
-  const u32 c1 = nargs * (u32)e;
-  if (nargs) {
-    if ((rc = ms_lde_commit_stage_coset(ctx, k, root))) return rc;
-    t.add_bytes(root, 32);
-  }
-  const ms_air* prog = pg.view();
-  std::vector<u64> r(e), z(e), gamma(e), alpha(e);
-  t.challenge_scalars(r.data(), e, p);
-  if ((rc = ms_mix_air_ext(ctx, r.data(), prog))) return rc;                 // MS_ERR_SHAPE: the trace violates the AIR
-  if ((u64)ms_validity_len(ctx) / N * e != sh.m) return MS_ERR_STATE;
-  if ((rc = ms_validity_commit_coset(ctx, k, root))) return rc;
-  t.add_bytes(root, 32);
-  draw_z(t, z.data(), e, p);
-  const std::vector<u64> pts = linked_points<F>(sh, z.data(), e);
-  const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  std::vector<u64> evals(sh.ne * e);
-  if ((rc = ms_deep_evals(ctx, &deep, evals.data()))) return rc;
-  t.add_scalars(evals.data(), evals.size());
-  t.challenge_scalars(gamma.data(), e, p);
-  if ((rc = ms_deep_compose(ctx, &deep, gamma.data()))) return rc;
-  if ((rc = ms_fri_begin_folded(ctx, sh.blowup, k, root))) return rc;
-  t.add_bytes(root, 32);
-  u64 nc = 0, D0 = 0;
-  if ((rc = ms_fri_round_info(ctx, 0, &nc, &D0))) return rc;
-  for (u32 i = 0; i + 1 < sh.R; i++) {
-    t.challenge_scalars(alpha.data(), e, p);
-    if ((rc = ms_fri_fold_folded(ctx, alpha.data(), root))) return rc;       // MS_ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
-    t.add_bytes(root, 32);
-  }
-  t.challenge_scalars(alpha.data(), e, p);
-  size_t nfinal = 0;
-  if ((rc = ms_fri_fold_final(ctx, alpha.data(), nullptr, 0, &nfinal))) return rc;
-  std::vector<u64> fin(nfinal * e + 1);
-  if ((rc = ms_fri_fold_final(ctx, alpha.data(), fin.data(), nfinal * e, &nfinal))) return rc;
-  t.add_scalars(fin.data(), nfinal * e);
-  if (sh.gb) {
-    u8 seed[32]; t.challenge_bytes(seed, 32);
-    u64 nonce = 0;
-    if ((rc = ms_grind(ctx, seed, sh.gb, 0, ~(u64)0, &nonce))) return rc;
     u8 le[8]; for (int b = 0; b < 8; b++) le[b] = (u8)(nonce >> (8 * b));
     t.add_bytes(le, 8);
   }
+  // the betas, the query phase in one call (asked for its size first), the header
   std::vector<u8> raw(8 * (size_t)sh.nq); t.challenge_bytes(raw.data(), raw.size());
   std::vector<u64> betas(sh.nq);
   memcpy(betas.data(), raw.data(), raw.size());
+  const auto query = kd.k ? ms_query_linked_folded : ms_query_linked;
   size_t lq = 0;
-  if ((rc = ms_query_linked_folded(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
+  if ((rc = query(ctx, betas.data(), (int)sh.nq, nullptr, 0, &lq))) return rc;
   const size_t la = t.prover_bytes.size();
-  if (la != arthur_len_folded(sh, e, nargs, nfinal)) return MS_ERR_STATE;
-  std::vector<u8> out(MSLP3_HEAD + la + lq);
-  const u32 h32[13] = {MSLP_MAGIC, 3, (u32)e, (u32)k, (u32)w, c1, sh.m, sh.npts, sh.R, sh.nq, sh.gb, nargs, nch};
-  const u64 h64[5] = {sh.N, sh.blowup, D0, (u64)la, (u64)lq};
-  memcpy(out.data(), h32, sizeof h32); memcpy(out.data() + sizeof h32, h64, sizeof h64);
-  memcpy(out.data() + MSLP3_HEAD, t.prover_bytes.data(), la);
-  if ((rc = ms_query_linked_folded(ctx, betas.data(), (int)sh.nq, out.data() + MSLP3_HEAD + la, lq, &lq))) return rc;
+  if (la != linked_arthur_len(sh, kd, e, nfinal)) return MS_ERR_STATE;
+  const std::vector<HeadWord> head = linked_header<E>(sh, kd, w);
+  std::vector<u64> h64 = {sh.N, sh.blowup};
+  if (kd.k) h64.push_back(D0);
+  h64.insert(h64.end(), {(u64)la, (u64)lq});
+  const size_t hb = linked_head_bytes(head, kd);
+  std::vector<u8> out(hb + la + lq);
+  for (size_t j = 0; j < head.size(); j++) memcpy(out.data() + 4 * j, &head[j].v, 4);
+  memcpy(out.data() + 4 * head.size(), h64.data(), 8 * h64.size());
+  memcpy(out.data() + hb, t.prover_bytes.data(), la);
+  if ((rc = query(ctx, betas.data(), (int)sh.nq, out.data() + hb + la, lq, &lq))) return rc;
   s.linked.swap(out);
   return MS_OK;
 }
 
-// the v3 verifier: nothing of the proof is trusted.  Order: header, transcript replay (both redraw rules, the challenge draw), proof of work, AIR identity, the folded
-// FRI on the MSFF, round 0's cosets against the coset-grouped trees
-template <class F, int E> static int verify_linked_folded(const StarkConfig& c, const ms_air* air, const msh_aux_arg* args, u32 nargs, u32 nch, size_t N, size_t w, int k, u32 fri_folds,
-                                                          const u8* data, size_t len, int zae, std::string* why) {
+// the replay of arthur: Arthur, with the rejection of a transcript that ends early written once
+struct Replay : Arthur {
+  std::string* why;
+  Replay(const Transcript& t0, const u8* d, size_t n, std::string* why_) : Arthur("", t0.digest, d, n), why(why_) { t = t0; }
+  bool bytes(u8* out, size_t n) { if (next_bytes(out, n)) return true; *why = "transcript: arthur ends early"; return false; }
+  bool scalars(u64* out, size_t n) { return bytes((u8*)out, n * 8); }
+};
+// the verifier: 1 accepted, 0 rejected (*why names the step), < 0 malformed arguments.  Nothing of the proof is trusted: every header field is the verifier's own.
+// Order: header, transcript replay (both redraw rules, the challenge draw), proof of work, AIR identity, FRI, round 0 against the row trees
+template <class F, int E> static int verify_linked(const StarkConfig& c, const ms_air* air, size_t N, size_t w, const LinkedKind& kd, const u8* data, size_t len, int zae, std::string* why) {
   typedef Verifier<F, E> V;
   const u64 p = c.p;
+  const LinkedText& tx = LINKED_TEXT[kd.version - 1];
   LinkedShape sh;
-  const int air_bytes = c.e != E ? MS_ERR_ARG : linked_shape_folded<F>(c, air, args, nargs, nch, N, w, k, fri_folds, &sh);
-  if (air_bytes < 0) { *why = "malformed arguments: the AIR program, the arguments, N, w, log_arity, the folds or the configuration"; return MS_ERR_ARG; }
-  const u32 c0 = (u32)w, c1 = nargs * (u32)E;
-  if (len < MSLP3_HEAD) { *why = "header: the proof is shorter than the MSLP v3 header"; return 0; }
-  u32 h32[13]; u64 h64[5];
-  memcpy(h32, data, sizeof h32); memcpy(h64, data + sizeof h32, sizeof h64);
-  if (h32[0] != MSLP_MAGIC) { *why = "header: magic is not the verifier's"; return 0; }
-  if (h32[1] != 3) { *why = "header: version is not 3"; return 0; }
-  const u32 want32[13] = {MSLP_MAGIC, 3, (u32)E, (u32)k, c0, c1, 0, 0, sh.R, sh.nq, sh.gb, nargs, nch};
-  static const char* const name32[13] = {"magic", "version", "E", "log_arity", "c0", "c1", "m", "npts", "R", "nq", "grinding bits", "nargs", "nch"};
-  for (int j = 2; j < 13; j++) if (j != 6 && j != 7 && h32[j] != want32[j]) { *why = std::string("header: ") + name32[j] + " is not the verifier's"; return 0; }
+  AirProg pg; std::vector<AuxInstance> inst;
+  if (c.e != E || linked_shape<F>(c, air, N, w, kd, &sh) || (kd.version == 1 && linked_combined<F, E>(air, nullptr, 0, nullptr, w, &pg, &inst, &sh))) {
+    *why = tx.bad_args; return MS_ERR_ARG;
+  }
+  const u32 c0 = (u32)w, c1 = kd.nargs * (u32)E;
+  // ---- header, first part: what the statement fixes without the challenges (v1: all of it); lengths exact
+  std::vector<HeadWord> head = linked_header<E>(sh, kd, w);
+  const size_t n64 = kd.k ? 5 : 4, hb = linked_head_bytes(head, kd);
+  if (len < hb) { *why = std::string("header: the proof is shorter than the ") + tx.head + " header"; return 0; }
+  if (!linked_header_ok(head, data, false, why)) return 0;
+  u64 h64[5]; memcpy(h64, data + 4 * head.size(), 8 * n64);
   if (h64[0] != sh.N) { *why = "header: N is not the verifier's"; return 0; }
   if (h64[1] != sh.blowup) { *why = "header: blowup is not the verifier's"; return 0; }
-  const u64 D0 = h64[2];
-  const unsigned kr = (unsigned)k * sh.R;
-  if (D0 < 1 || (D0 & (D0 - 1)) || D0 > sh.L || sh.L % D0 || kr >= 64 || (D0 >> kr) < sh.blowup) { *why = "header: D_0 is no power of two that divides L with arity^R * blowup <= D_0"; return 0; }
-  const u64 nfinal = (D0 >> kr) / sh.blowup;
-  if (h64[3] > len - MSLP3_HEAD || h64[4] != (u64)(len - MSLP3_HEAD) - h64[3]) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
-  const size_t la = (size_t)h64[3], lq = len - MSLP3_HEAD - la;
-  if (la < 64) { *why = "header: len(arthur) is not what the statement fixes"; return 0; }
-  // ---- transcript up to the challenges of the arguments; then the program and the rest of the header
-  Arthur a(c.domsep, c.digest, data + MSLP3_HEAD, la);
-  a.t = linked_transcript_folded(c, sh, (size_t)air_bytes);
+  u64 D0 = 0, nfinal = 0;
+  if (kd.k) {
+    D0 = h64[2];
+    const unsigned kr = (unsigned)kd.k * sh.R;
+    if (D0 < 1 || (D0 & (D0 - 1)) || D0 > sh.L || sh.L % D0 || kr >= 64 || (D0 >> kr) < sh.blowup) { *why = "header: D_0 is no power of two that divides L with arity^R * blowup <= D_0"; return 0; }
+    nfinal = (D0 >> kr) / sh.blowup;
+  }
+  const char* const bad_la = "header: len(arthur) is not what the statement fixes";
+  const u64 h_la = h64[n64 - 2], h_lq = h64[n64 - 1];
+  if (kd.version == 1 && h_la != (u64)linked_arthur_len(sh, kd, E, 0)) { *why = bad_la; return 0; }   // (v1 knows it here, and says so before it looks at the fit)
+  if (h_la > len - hb || h_lq != (u64)(len - hb) - h_la) { *why = "header: the lengths do not fit the proof exactly"; return 0; }
+  const size_t la = (size_t)h_la, lq = len - hb - la;
+  if (la < 64) { *why = bad_la; return 0; }
+  // ---- transcript up to the challenges of the arguments (la >= 64: the two roots are there); then the program and the rest of the header
+  Replay a(linked_transcript(c, sh, kd), data + hb, la, why);
   u8 troot[32], lroot[32], sroot[32], vroot[32];
-  const char* cut = "transcript: arthur ends early";
-  if (!a.next_bytes(troot, 32)) { *why = cut; return 0; }
+  if (!a.bytes(troot, 32)) return 0;
   const u64 shift = draw_shift<F>(a.t, sh.L);
-  if (!a.next_bytes(lroot, 32)) { *why = cut; return 0; }
-  std::vector<u64> ch((size_t)nch * E);
-  if (nargs) a.t.challenge_scalars(ch.data(), ch.size(), p);
-  AirProg pg; std::vector<AuxInstance> inst;
-  if (linked_program_folded<F, E>(air, args, nargs, ch.data(), w, &pg, &inst, &sh)) { *why = "malformed arguments: the program exceeds ms_mix_air's limits"; return MS_ERR_ARG; }
-  const ms_air* prog = pg.view();
-  if (h32[6] != sh.m) { *why = "header: m is not the verifier's"; return 0; }
-  if (h32[7] != sh.npts) { *why = "header: npts is not the verifier's"; return 0; }
-  if (la != arthur_len_folded(sh, E, nargs, nfinal)) { *why = "header: len(arthur) is not what the statement and D_0 fix"; return 0; }
-  std::vector<u64> q((lq + 7) / 8 + 5, 0);            // the MSLF blob, aligned for the section verifiers
-  memcpy(q.data(), data + MSLP3_HEAD + la, lq);
-  if (lq < 40 || q[0] != 0x464C534DULL) { *why = "header: no MSLF blob behind arthur"; return 0; }
-  const u64 l_msff = q[1], l_lde = q[2], l_stg = q[3], l_val = q[4];
-  if (l_msff > lq - 40 || l_lde > lq - 40 - l_msff || l_stg > lq - 40 - l_msff - l_lde || l_val != lq - 40 - l_msff - l_lde - l_stg) { *why = "header: the MSLF section lengths do not fit the blob exactly"; return 0; }
-  if ((l_msff | l_lde | l_stg | l_val) & 7) { *why = "header: an MSLF section length is no multiple of 8"; return 0; }
+  if (!a.bytes(lroot, 32)) return 0;
+  std::vector<u64> ch((size_t)kd.nch * E);
+  if (kd.nargs) a.t.challenge_scalars(ch.data(), ch.size(), p);
+  if (kd.version > 1 && linked_combined<F, E>(air, kd.args, kd.nargs, ch.data(), w, &pg, &inst, &sh)) { *why = tx.bad_program; return MS_ERR_ARG; }
+  head = linked_header<E>(sh, kd, w);
+  if (!linked_header_ok(head, data, true, why)) return 0;
+  if (la != linked_arthur_len(sh, kd, E, nfinal)) { *why = kd.k ? "header: len(arthur) is not what the statement and D_0 fix" : bad_la; return 0; }
+  // ---- the query blob behind arthur: its magic, its section lengths exact.  Sections: FRI, LDE, (staged,) validity
+  const std::string blob = tx.blob;
+  const size_t qh = 8 * (size_t)(1 + tx.nsec);
+  std::vector<u64> q((lq + 7) / 8 + 5, 0);            // aligned for the section verifiers
+  memcpy(q.data(), data + hb + la, lq);
+  if (lq < qh || q[0] != tx.magic) { *why = "header: no " + blob + " blob behind arthur"; return 0; }
+  const u64 l_fri = q[1], l_lde = q[2], l_stg = tx.nsec == 4 ? q[3] : 0, l_val = q[tx.nsec];
+  if (l_fri > lq - qh || l_lde > lq - qh - l_fri || l_stg > lq - qh - l_fri - l_lde || l_val != lq - qh - l_fri - l_lde - l_stg) {
+    *why = "header: the " + blob + " section lengths do not fit the blob exactly"; return 0;
+  }
+  if ((l_fri | l_lde | l_stg | l_val) & 7) { *why = "header: an " + blob + " section length is no multiple of 8"; return 0; }
   if (!c1 && l_stg) { *why = "header: a staged section in a proof without running columns"; return 0; }
-  const u8* msff = (const u8*)q.data() + 40; const u8* lde_open = msff + l_msff; const u8* stg_open = lde_open + l_lde; const u8* val_open = stg_open + l_stg;
-  if (l_msff < 56 + nfinal * E * 8 || q[5 + 5] != D0) { *why = "header: D_0 is not the MSFF's own"; return 0; }
+  const u8* fri = (const u8*)q.data() + qh; const u8* lde_open = fri + l_fri; const u8* stg_open = lde_open + l_lde; const u8* val_open = stg_open + l_stg;
+  if (kd.k && (l_fri < 56 + nfinal * E * 8 || q[qh / 8 + 5] != D0)) { *why = "header: D_0 is not the MSFF's own"; return 0; }
+  // ---- transcript, the rest: replayed from arthur, the redraw of z included
+  const size_t W = kd.k ? 0 : sh.R - 1;               // the windows of the plain FRI
   std::vector<u8> roots((size_t)sh.R * 32);
-  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), alphas((size_t)sh.R * E), fin((size_t)nfinal * E + 1), betas(sh.nq);
-  if (nargs && !a.next_bytes(sroot, 32)) { *why = cut; return 0; }
+  std::vector<u64> r(E), z(E), gamma(E), evals(sh.ne * E), zs(W * E), Bs(W * 2 * E), alphas((kd.k ? sh.R : W) * E), fin((size_t)nfinal * E + 1), betas(sh.nq);
+  if (kd.nargs && !a.bytes(sroot, 32)) return 0;
   a.t.challenge_scalars(r.data(), E, p);
-  if (!a.next_bytes(vroot, 32)) { *why = cut; return 0; }
+  if (!a.bytes(vroot, 32)) return 0;
   draw_z(a.t, z.data(), E, p);
-  if (!a.next_scalars(evals.data(), evals.size())) { *why = cut; return 0; }
+  if (!a.scalars(evals.data(), evals.size())) return 0;
   if (!V::canon(evals.data(), evals.size())) { *why = "transcript: a claimed evaluation is not canonical"; return 0; }
   a.t.challenge_scalars(gamma.data(), E, p);
-  if (!a.next_bytes(roots.data(), 32)) { *why = cut; return 0; }
-  for (u32 i = 0; i + 1 < sh.R; i++) {
-    a.t.challenge_scalars(alphas.data() + (size_t)i * E, E, p);
-    if (!a.next_bytes(roots.data() + (size_t)(i + 1) * 32, 32)) { *why = cut; return 0; }
+  if (!a.bytes(roots.data(), 32)) return 0;
+  if (!kd.k) {
+    for (u32 i = 1; i < sh.R; i++) {
+      a.t.challenge_scalars(zs.data() + (size_t)(i - 1) * E, E, p);
+      if (!a.scalars(Bs.data() + (size_t)(i - 1) * 2 * E, 2 * E)) return 0;
+      a.t.challenge_scalars(alphas.data() + (size_t)(i - 1) * E, E, p);
+      if (!a.bytes(roots.data() + (size_t)i * 32, 32)) return 0;
+    }
+    if (!V::canon(Bs.data(), Bs.size())) { *why = "transcript: a round's B is not canonical"; return 0; }
+  } else {
+    for (u32 i = 0; i + 1 < sh.R; i++) {
+      a.t.challenge_scalars(alphas.data() + (size_t)i * E, E, p);
+      if (!a.bytes(roots.data() + (size_t)(i + 1) * 32, 32)) return 0;
+    }
+    a.t.challenge_scalars(alphas.data() + (size_t)(sh.R - 1) * E, E, p);
+    if (!a.scalars(fin.data(), (size_t)nfinal * E)) return 0;
+    if (!V::canon(fin.data(), (size_t)nfinal * E)) { *why = "transcript: a coefficient of the final polynomial is not canonical"; return 0; }
+    if (memcmp(fin.data(), fri + 56, (size_t)nfinal * E * 8)) { *why = "transcript: the final polynomial in arthur is not the MSFF's"; return 0; }
   }
-  a.t.challenge_scalars(alphas.data() + (size_t)(sh.R - 1) * E, E, p);
-  if (!a.next_scalars(fin.data(), (size_t)nfinal * E)) { *why = cut; return 0; }
-  if (!V::canon(fin.data(), (size_t)nfinal * E)) { *why = "transcript: a coefficient of the final polynomial is not canonical"; return 0; }
-  if (memcmp(fin.data(), msff + 56, (size_t)nfinal * E * 8)) { *why = "transcript: the final polynomial in arthur is not the MSFF's"; return 0; }
   u8 seed[32] = {0}; u64 nonce = 0;
   if (sh.gb) {
     a.t.challenge_bytes(seed, 32);
     u8 le[8];
-    if (!a.next_bytes(le, 8)) { *why = cut; return 0; }
+    if (!a.bytes(le, 8)) return 0;
     for (int b = 0; b < 8; b++) nonce |= (u64)le[b] << (8 * b);
   }
   if (a.pos != la) { *why = "transcript: bytes left in arthur"; return 0; }
   { std::vector<u8> raw(8 * (size_t)sh.nq); a.t.challenge_bytes(raw.data(), raw.size()); memcpy(betas.data(), raw.data(), raw.size()); }
   // ---- 1. the proof of work
   if (sh.gb && !pow_ok(c.digest, seed, nonce, sh.gb)) { *why = "proof of work: the nonce does not give the digest its leading zero bits"; return 0; }
-  // ---- 2. the AIR identity at z
+  // ---- 2. the AIR identity at z: the program on the opened evaluations against V(z) from the chunk evaluations
   {
     std::vector<u64> opened((size_t)sh.npts * sh.c * E);
     for (u32 t = 0; t < sh.npts; t++) memcpy(opened.data() + (size_t)t * sh.c * E, evals.data() + (size_t)sh.pt_begin[t] * E, (size_t)sh.c * E * 8);
     u64 want[E], got[E];
-    const int rc = air_expected<F, E>(r.data(), *prog, N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
+    const int rc = air_expected<F, E>(r.data(), *pg.view(), N, z.data(), (int)sh.npts, sh.rows.data(), opened.data(), (size_t)sh.c * E, sh.c, want);
     if (rc) { *why = "malformed arguments: the AIR program cannot be evaluated at z"; return rc < 0 ? rc : MS_ERR_ARG; }
     validity_from_chunks<F, E>((u32)E, sh.m / E, N, z.data(), evals.data() + (size_t)sh.c * E, got);
     if (memcmp(want, got, sizeof want)) { *why = "AIR identity: the program on the opened evaluations is not V(z) of the chunk evaluations"; return 0; }
   }
-  // ---- 3. the folded FRI on the MSFF section, with the roots and challenges of the replay
+  // ---- 3. FRI on the blob's first section (MSFI, or MSFF for the folded FRI), with the roots and challenges of the replay
   std::string sub;
-  int rc = fri_folded_verify<F, E>(c.digest, zae, sh.blowup, k, roots.data(), sh.R, alphas.data(), betas.data(), sh.nq, msff, l_msff, &sub);
+  int rc = kd.k ? fri_folded_verify<F, E>(c.digest, zae, sh.blowup, kd.k, roots.data(), sh.R, alphas.data(), betas.data(), sh.nq, fri, l_fri, &sub)
+                : fri_index_verify<F, E>(c.digest, zae, sh.blowup, roots.data(), sh.R, zs.data(), Bs.data(), alphas.data(), betas.data(), sh.nq, fri, l_fri, &sub);
   if (rc != 1) { *why = "FRI: " + sub; return rc; }
-  // ---- 4. every slot of round 0's cosets against the coset-grouped trees
+  // ---- 4. round 0 against the row trees (every slot of its cosets against the coset-grouped trees)
   const std::vector<u64> pts = linked_points<F>(sh, z.data(), E);
   const ms_deep deep{sh.npts, pts.data(), sh.pt_begin.data(), sh.pt_poly.data()};
-  rc = deep_link_verify_folded<F, E>(c.digest, zae, N, sh.blowup, shift, k, c0, c1, sh.m, lroot, c1 ? sroot : nullptr, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, msff, l_msff,
-                                     lde_open, l_lde, stg_open, l_stg, val_open, l_val, &sub);
+  const u8* stg_root = c1 ? sroot : nullptr;
+  rc = kd.k ? deep_link_verify_folded<F, E>(c.digest, zae, N, sh.blowup, shift, kd.k, c0, c1, sh.m, lroot, stg_root, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, fri, l_fri,
+                                            lde_open, l_lde, stg_open, l_stg, val_open, l_val, &sub)
+            : deep_link_verify<F, E>(c.digest, zae, N, sh.blowup, shift, c0, c1, sh.m, lroot, stg_root, vroot, deep, evals.data(), gamma.data(), betas.data(), sh.nq, fri, l_fri, lde_open, l_lde,
+                                     stg_open, l_stg, val_open, l_val, &sub);
   if (rc != 1) { *why = sub; return rc; }
   return 1;
 }
@@ -2259,25 +1974,48 @@ int msh_deep_link_verify(int digest_id, int field, int zero_display_empty, u64 N
     return set_why(why, why_cap, w.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }
-// ---- linked proofs (MSLP v1)
-int msh_stark_prove_linked(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, uint32_t fri_rounds) {
+// ---- linked proofs (MSLP v1, v2, v3): every entry point checks its own arguments and names its kind; a proof that is refused or fails leaves an empty slot
+static int prove_linked_kind(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const LinkedKind& kd) {
   if (!h) return MS_ERR_ARG;
   try {
-    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked<GL>(h->s, trace_host, trace_dev, N, w, air, fri_rounds) : prove_linked<BB>(h->s, trace_host, trace_dev, N, w, air, fri_rounds);
-  } catch (...) { return MS_ERR_NOMEM; }
+    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked<GL, 2>(h->s, trace_host, trace_dev, N, w, air, kd) : prove_linked<BB, 4>(h->s, trace_host, trace_dev, N, w, air, kd);
+  } catch (...) { h->s.linked.clear(); return MS_ERR_NOMEM; }
+}
+static int verify_linked_kind(const msh_stark* h, const ms_air* air, size_t N, size_t w, const LinkedKind& kd, const u8* data, size_t len, int zae, char* why, size_t why_cap) {
+  try {
+    std::string msg;
+    const StarkConfig& c = h->s.cfg;
+    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked<GL, 2>(c, air, N, w, kd, data, len, zae, &msg) : verify_linked<BB, 4>(c, air, N, w, kd, data, len, zae, &msg);
+    return set_why(why, why_cap, msg.c_str(), rc);
+  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+}
+int msh_stark_prove_linked(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, uint32_t fri_rounds) {
+  return prove_linked_kind(h, trace_host, trace_dev, N, w, air, LinkedKind{1, 0, nullptr, 0, 0, fri_rounds});
 }
 size_t msh_linked_proof(const msh_stark* h, u8* out, size_t cap) { return h ? copy_out(h->s.linked.data(), h->s.linked.size(), out, cap) : 0; }
 int msh_stark_verify_linked(const msh_stark* h, const ms_air* air, size_t N, size_t w, uint32_t fri_rounds, const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
   if (!h || !data || !air) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
-  try {
-    std::string msg;
-    const StarkConfig& c = h->s.cfg;
-    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked<GL, 2>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg)
-                                                  : verify_linked<BB, 4>(c, air, N, w, fri_rounds, data, len, zero_display_empty, &msg);
-    return set_why(why, why_cap, msg.c_str(), rc);
-  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
+  return verify_linked_kind(h, air, N, w, LinkedKind{1, 0, nullptr, 0, 0, fri_rounds}, data, len, zero_display_empty, why, why_cap);
 }
-// ---- linked proofs with running columns (MSLP v2)
+int msh_stark_prove_linked_aux(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
+                               uint32_t nch, uint32_t fri_rounds) {
+  return prove_linked_kind(h, trace_host, trace_dev, N, w, air, LinkedKind{2, 0, args, nargs, nch, fri_rounds});
+}
+int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, uint32_t fri_rounds,
+                                const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
+  if (!h || !data || !air || !args) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
+  return verify_linked_kind(h, air, N, w, LinkedKind{2, 0, args, nargs, nch, fri_rounds}, data, len, zero_display_empty, why, why_cap);
+}
+int msh_stark_prove_linked_folded(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
+                                  uint32_t nch, int log_arity, uint32_t fri_folds) {
+  return prove_linked_kind(h, trace_host, trace_dev, N, w, air, LinkedKind{3, log_arity, args, nargs, nch, fri_folds});
+}
+int msh_stark_verify_linked_folded(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, int log_arity, uint32_t fri_folds,
+                                   const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
+  if (!h || !data || !air) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
+  return verify_linked_kind(h, air, N, w, LinkedKind{3, log_arity, args, nargs, nch, fri_folds}, data, len, zero_display_empty, why, why_cap);
+}
+// ---- running columns: the combined program and the encoding of the arguments
 struct msh_air_prog { AirProg p; };
 msh_air_prog* msh_air_prog_new(const ms_air* base) {
   try { std::unique_ptr<msh_air_prog> g(new msh_air_prog()); if (!g->p.load(base)) return nullptr; return g.release(); } catch (...) { return nullptr; }
@@ -2333,45 +2071,6 @@ int msh_deep_link_verify_folded(int digest_id, int field, int zero_display_empty
       ? deep_link_verify_folded<GL, 2>(digest_id, zero_display_empty, N, blowup, shift, log_arity, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msff, msff_len, lde_open, lde_len, stg_open, c1 ? stg_len : 0, val_open, val_len, &w)
       : deep_link_verify_folded<BB, 4>(digest_id, zero_display_empty, N, blowup, shift, log_arity, c0, c1, m, lde_root, stg_root, val_root, *deep, evals, gamma, betas, nq, msff, msff_len, lde_open, lde_len, stg_open, c1 ? stg_len : 0, val_open, val_len, &w);
     return set_why(why, why_cap, w.c_str(), rc);
-  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
-}
-int msh_stark_prove_linked_aux(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
-                               uint32_t nch, uint32_t fri_rounds) {
-  if (!h) return MS_ERR_ARG;
-  try {
-    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked_aux<GL, 2>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, fri_rounds)
-                                                 : prove_linked_aux<BB, 4>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, fri_rounds);
-  } catch (...) { h->s.linked.clear(); return MS_ERR_NOMEM; }
-}
-int msh_stark_verify_linked_aux(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, uint32_t fri_rounds,
-                                const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
-  if (!h || !data || !air || !args) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
-  try {
-    std::string msg;
-    const StarkConfig& c = h->s.cfg;
-    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked_aux<GL, 2>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg)
-                                                  : verify_linked_aux<BB, 4>(c, air, args, nargs, nch, N, w, fri_rounds, data, len, zero_display_empty, &msg);
-    return set_why(why, why_cap, msg.c_str(), rc);
-  } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
-}
-// ---- linked proofs over a folded FRI (MSLP v3)
-int msh_stark_prove_linked_folded(msh_stark* h, const u64* trace_host, const void* trace_dev, size_t N, size_t w, const ms_air* air, const msh_aux_arg* args, uint32_t nargs,
-                                  uint32_t nch, int log_arity, uint32_t fri_folds) {
-  if (!h) return MS_ERR_ARG;
-  try {
-    return h->s.cfg.field == MS_FIELD_GOLDILOCKS ? prove_linked_folded<GL, 2>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, log_arity, fri_folds)
-                                                 : prove_linked_folded<BB, 4>(h->s, trace_host, trace_dev, N, w, air, args, nargs, nch, log_arity, fri_folds);
-  } catch (...) { h->s.linked.clear(); return MS_ERR_NOMEM; }
-}
-int msh_stark_verify_linked_folded(const msh_stark* h, const ms_air* air, const msh_aux_arg* args, uint32_t nargs, uint32_t nch, size_t N, size_t w, int log_arity, uint32_t fri_folds,
-                                   const u8* data, size_t len, int zero_display_empty, char* why, size_t why_cap) {
-  if (!h || !data || !air) return set_why(why, why_cap, "null argument", MS_ERR_ARG);
-  try {
-    std::string msg;
-    const StarkConfig& c = h->s.cfg;
-    const int rc = c.field == MS_FIELD_GOLDILOCKS ? verify_linked_folded<GL, 2>(c, air, args, nargs, nch, N, w, log_arity, fri_folds, data, len, zero_display_empty, &msg)
-                                                  : verify_linked_folded<BB, 4>(c, air, args, nargs, nch, N, w, log_arity, fri_folds, data, len, zero_display_empty, &msg);
-    return set_why(why, why_cap, msg.c_str(), rc);
   } catch (...) { return set_why(why, why_cap, "out of memory / internal error while verifying", -1); }
 }
 size_t msh_air_encode(const ms_air* air, u8* out, size_t cap) {

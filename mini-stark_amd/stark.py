@@ -374,7 +374,7 @@ class Stark:
                           FriProof(blob or b"", device_resident=not read_fri_proof), roots)
 
 
-    # ---- linked proofs (build-defined; MSLP v1, transcript order and redraw rules: include/ministark_host.h) -----------------------
+    # ---- linked proofs (build-defined; MSLP v1, v2, v3; transcript order and redraw rules: include/ministark_host.h) ---------------
     def prove_air(self, trace, air, fri_rounds: int = 0, aux=None, forced_challenges=None, log_arity: int = 0, fri_folds: int = 0):
         """msh_stark_prove_linked driven from Python: the same stages, the same transcript, the same bytes.  trace: the N x w matrix; air: a flatten_air dict or the
         tuple (constraints, exempt, periodic, boundary).  The statement: there are w polynomials of degree < N, committed under the LDE root, that satisfy `air`.
@@ -382,22 +382,29 @@ class Stark:
         aux = (args, nch): a proof with running columns, MSLP v2 (msh_stark_prove_linked_aux) - args flatten_aux_arg dicts whose selectors name nch challenges;
         returns a LinkedProofV2.  forced_challenges (tests only): the columns are built from these instead of the transcript's.
         log_arity = k in 1..3: MSLP v3 (msh_stark_prove_linked_folded) - the folded FRI at arity 2^k over coset-grouped row trees, with or without aux; fri_folds = 0
-        means floor(log2 N / k) folds; returns a LinkedProofV3."""
-        if log_arity:
-            return self._prove_air_folded(trace, air, log_arity, fri_folds, aux[0] if aux else [], aux[1] if aux else 0)
-        if aux is not None:
-            return self._prove_air_aux(trace, air, fri_rounds, aux[0], aux[1], forced_challenges)
+        means floor(log2 N / k) folds; returns a LinkedProofV3.
+        One driver for the three versions: it branches where the table above prove_linked in host/stark_host.cpp says they differ, and nowhere else."""
         cfg, ctx = self.cfg, self.cfg.ctx
-        p, e = _MODULUS[ctx.field], ctx.e
+        field, p, e = ctx.field, _MODULUS[ctx.field], ctx.e
+        k, version = log_arity, 3 if log_arity else 1 if aux is None else 2
+        args, nch = aux if aux else ([], 0)
+        staged = version == 2 or bool(args)                       # running columns: challenges, a staged root, the combined program
         if not isinstance(air, dict):
             air = flatten_air(*air)
         data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
         N, w = data.shape
         blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
-        R, nq, gb = fri_rounds or cfg.rounds, cfg.fri_queries, cfg.grinding_bits
-        t = Transcript(cfg.domsep + "/linked/v1", ctx.digest)
-        t.add_bytes(struct.pack("<8Q", ctx.field, ctx.digest, N, w, blowup, R, nq, gb))
+        if k and (k not in (1, 2, 3) or (not args and nch)):
+            raise MsError(ERR_ARG, "prove_air: log_arity outside 1..3, or challenges without arguments")
+        R = (fri_folds or (N.bit_length() - 1) // k) if k else fri_rounds or cfg.rounds
+        nq, gb = cfg.fri_queries, cfg.grinding_bits
+        # the statement: its words, msh_air_encode(air), msh_aux_encode(args) where there are running columns
+        t = Transcript(cfg.domsep + "/linked/v%d" % version, ctx.digest)
+        words = [field, ctx.digest, N, w, blowup] + ([k] if k else []) + [R, nq, gb] + ([len(args), nch] if version > 1 else [])
+        t.add_bytes(struct.pack("<%dQ" % len(words), *words))
         t.add_bytes(encode_air(air))
+        if staged:
+            t.add_bytes(encode_aux(args, nch))
         t.prover_bytes = bytearray()                              # the statement is the verifier's own: it does not travel
         rc, root = ctx.trace_commit(data, w)                      # the raw-trace root: absorbed first, binds nothing
         ctx.check(rc)
@@ -406,187 +413,37 @@ class Stark:
         while shift == 0 or pow(shift, L, p) == 1:                # the coset must not meet the trace domain: part of the protocol on both sides
             (shift,) = t.challenge_scalars(1, p)
         ctx.check(ctx.interpolate())
-        rc, root = ctx.lde_commit(blowup, shift, w)
+        rc, root = ctx.lde_commit_coset(blowup, shift, k) if k else ctx.lde_commit(blowup, shift, w)
         ctx.check(rc)
         t.add_bytes(root)
-        r = t.challenge_scalars(e, p)
-        ctx.check(ctx.mix_air_ext(r, air))
-        m = e * ctx.validity_len() // N
-        rc, root = ctx.validity_commit(m)
-        ctx.check(rc)
-        t.add_bytes(root)
-        z = t.challenge_scalars(e, p)
-        while not any(z[1:]):                                     # z outside the base field
-            z = t.challenge_scalars(e, p)
-        rows = sorted({0} | {int(x) for x in np.asarray(air["fac_row"]).reshape(-1)})
-        if len(rows) > 8:
-            raise MsError(ERR_ARG, "prove_air: the program touches more than 8 row offsets")
-        omega = ctx.root_of_unity(N)
-        pts = [[v * pow(omega, row, p) % p for v in z] for row in rows]
-        lists = [list(range(w)) + (list(range(w, w + m)) if k == 0 else []) for k in range(len(rows))]
-        rc, ev = ctx.deep_evals(pts, lists)
-        ctx.check(rc)
-        t.add_scalars(ev.reshape(-1))
-        gamma = t.challenge_scalars(e, p)
-        ctx.check(ctx.deep_compose(pts, lists, gamma))
-        rc, root = ctx.fri_begin(blowup, R)
-        ctx.check(rc)
-        t.add_bytes(root)                                         # round 0's root is in the transcript
-        for _ in range(1, R):
-            zq = t.challenge_scalars(e, p)
-            rc, B = ctx.fri_deep(zq)
-            ctx.check(rc)
-            t.add_scalars(B)
-            alpha = t.challenge_scalars(e, p)
-            rc, root = ctx.fri_fold_commit(alpha)
-            ctx.check(rc)
-            t.add_bytes(root)
-        if gb:
-            rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
-            ctx.check(rc)
-            t.add_bytes(struct.pack("<Q", nonce))
-        raw = t.challenge_bytes(8 * nq)
-        betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
-        self.last_challenges = dict(shift=shift, r=r, z=z, gamma=gamma, betas=betas)
-        return LinkedProof(e, w, m, len(rows), R, nq, gb, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
-
-    def _prove_air_aux(self, trace, air, fri_rounds, args, nch, forced_challenges=None):
-        cfg, ctx = self.cfg, self.cfg.ctx
-        field, p, e = ctx.field, _MODULUS[ctx.field], ctx.e
-        if not isinstance(air, dict):
-            air = flatten_air(*air)
-        data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
-        N, w = data.shape
-        blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
-        R, nq, gb = fri_rounds or cfg.rounds, cfg.fri_queries, cfg.grinding_bits
-        t = Transcript(cfg.domsep + "/linked/v2", ctx.digest)
-        t.add_bytes(struct.pack("<10Q", field, ctx.digest, N, w, blowup, R, nq, gb, len(args), nch))
-        t.add_bytes(encode_air(air))
-        t.add_bytes(encode_aux(args, nch))
-        t.prover_bytes = bytearray()
-        rc, root = ctx.trace_commit(data, w)
-        ctx.check(rc)
-        t.add_bytes(root)
-        (shift,) = t.challenge_scalars(1, p)
-        while shift == 0 or pow(shift, L, p) == 1:
-            (shift,) = t.challenge_scalars(1, p)
-        ctx.check(ctx.interpolate())
-        rc, root = ctx.lde_commit(blowup, shift, w)
-        ctx.check(rc)
-        t.add_bytes(root)
-        flat = t.challenge_scalars(nch * e, p)                    # the arguments' challenges follow the commitment to the main columns
-        ch = [tuple(int(v) for v in flat[k * e:(k + 1) * e]) for k in range(nch)]
-        used = ch if forced_challenges is None else [tuple(c) for c in forced_challenges]
-        cons, exempt, periodic, boundary = unflatten_air(air)
-        for k, arg in enumerate(args):
-            inst = instantiate_aux(field, arg, used)              # (forced challenges: column AND constraints are the forger's, so the mix stage accepts them)
-            rc, final, _ = ctx.aux_running_staged(inst["op"], inst, e)
-            ctx.check(rc)                                         # ERR_SHAPE: a zero denominator
-            if tuple(final) != ((1 if inst["op"] == AUX_PRODUCT else 0),) + (0,) * (e - 1):
-                raise MsError(ERR_SHAPE, "prove_air: an argument does not hold (final is not the identity)")
-            c2, e2, b2 = aux_constraints(field, inst["op"], aux_fractions(inst), e, w + k * e)
-            cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
-        c1 = len(args) * e
-        c = w + c1
-        rc, root = ctx.lde_commit_stage(c1)
-        ctx.check(rc)
-        t.add_bytes(root)
-        prog = flatten_air(cons, exempt, periodic, boundary)
-        r = t.challenge_scalars(e, p)
-        ctx.check(ctx.mix_air_ext(r, prog))
-        m = e * ctx.validity_len() // N
-        rc, root = ctx.validity_commit(m)
-        ctx.check(rc)
-        t.add_bytes(root)
-        z = t.challenge_scalars(e, p)
-        while not any(z[1:]):
-            z = t.challenge_scalars(e, p)
-        rows = sorted({0} | {int(x) for x in np.asarray(prog["fac_row"]).reshape(-1)})
-        if len(rows) > 8:
-            raise MsError(ERR_ARG, "prove_air: the program touches more than 8 row offsets")
-        omega = ctx.root_of_unity(N)
-        pts = [[v * pow(omega, row, p) % p for v in z] for row in rows]
-        lists = [list(range(c)) + (list(range(c, c + m)) if k == 0 else []) for k in range(len(rows))]
-        rc, ev = ctx.deep_evals(pts, lists)
-        ctx.check(rc)
-        t.add_scalars(ev.reshape(-1))
-        gamma = t.challenge_scalars(e, p)
-        ctx.check(ctx.deep_compose(pts, lists, gamma))
-        rc, root = ctx.fri_begin(blowup, R)
-        ctx.check(rc)
-        t.add_bytes(root)
-        for _ in range(1, R):
-            zq = t.challenge_scalars(e, p)
-            rc, B = ctx.fri_deep(zq)
-            ctx.check(rc)
-            t.add_scalars(B)
-            alpha = t.challenge_scalars(e, p)
-            rc, root = ctx.fri_fold_commit(alpha)
-            ctx.check(rc)
-            t.add_bytes(root)
-        if gb:
-            rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
-            ctx.check(rc)
-            t.add_bytes(struct.pack("<Q", nonce))
-        raw = t.challenge_bytes(8 * nq)
-        betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
-        self.last_challenges = dict(shift=shift, ch=ch, r=r, z=z, gamma=gamma, betas=betas)
-        return LinkedProofV2(e, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, bytes(t.prover_bytes), ctx.query_linked(betas))
-
-    def _prove_air_folded(self, trace, air, k, fri_folds, args, nch):
-        cfg, ctx = self.cfg, self.cfg.ctx
-        field, p, e = ctx.field, _MODULUS[ctx.field], ctx.e
-        if not isinstance(air, dict):
-            air = flatten_air(*air)
-        data = np.ascontiguousarray(trace.data if isinstance(trace, TraceTable) else trace, dtype=np.uint64)
-        N, w = data.shape
-        blowup, L = cfg.blowup_factor, N * cfg.blowup_factor
-        if k not in (1, 2, 3) or (not args and nch):
-            raise MsError(ERR_ARG, "prove_air: log_arity outside 1..3, or challenges without arguments")
-        R, nq, gb = fri_folds or (N.bit_length() - 1) // k, cfg.fri_queries, cfg.grinding_bits
-        t = Transcript(cfg.domsep + "/linked/v3", ctx.digest)
-        t.add_bytes(struct.pack("<11Q", field, ctx.digest, N, w, blowup, k, R, nq, gb, len(args), nch))
-        t.add_bytes(encode_air(air))
-        if args:
-            t.add_bytes(encode_aux(args, nch))
-        t.prover_bytes = bytearray()
-        rc, root = ctx.trace_commit(data, w)
-        ctx.check(rc)
-        t.add_bytes(root)
-        (shift,) = t.challenge_scalars(1, p)
-        while shift == 0 or pow(shift, L, p) == 1:
-            (shift,) = t.challenge_scalars(1, p)
-        ctx.check(ctx.interpolate())
-        rc, root = ctx.lde_commit_coset(blowup, shift, k)
-        ctx.check(rc)
-        t.add_bytes(root)
-        cons, exempt, periodic, boundary = unflatten_air(air)
-        ch = []
-        if args:
+        ch, prog = [], air
+        if staged:
             flat = t.challenge_scalars(nch * e, p)                # the arguments' challenges follow the commitment to the main columns
             ch = [tuple(int(v) for v in flat[j * e:(j + 1) * e]) for j in range(nch)]
+            used = ch if forced_challenges is None or k else [tuple(c) for c in forced_challenges]   # (v2's tests force them; v3 never took them)
+            cons, exempt, periodic, boundary = unflatten_air(air)
             for j, arg in enumerate(args):
-                inst = instantiate_aux(field, arg, ch)
+                inst = instantiate_aux(field, arg, used)          # (forced challenges: column AND constraints are the forger's, so the mix stage accepts them)
                 rc, final, _ = ctx.aux_running_staged(inst["op"], inst, e)
-                ctx.check(rc)
+                ctx.check(rc)                                     # ERR_SHAPE: a zero denominator
                 if tuple(final) != ((1 if inst["op"] == AUX_PRODUCT else 0),) + (0,) * (e - 1):
                     raise MsError(ERR_SHAPE, "prove_air: an argument does not hold (final is not the identity)")
                 c2, e2, b2 = aux_constraints(field, inst["op"], aux_fractions(inst), e, w + j * e)
                 cons, exempt, boundary = cons + c2, exempt + e2, boundary + b2
-            rc, root = ctx.lde_commit_stage_coset(k)
+            rc, root = ctx.lde_commit_stage_coset(k) if k else ctx.lde_commit_stage(len(args) * e)
             ctx.check(rc)
             t.add_bytes(root)
+            prog = flatten_air(cons, exempt, periodic, boundary)
         c1 = len(args) * e
         c = w + c1
-        prog = flatten_air(cons, exempt, periodic, boundary) if args else air
         r = t.challenge_scalars(e, p)
         ctx.check(ctx.mix_air_ext(r, prog))
         m = e * ctx.validity_len() // N
-        rc, root = ctx.validity_commit_coset(k)
+        rc, root = ctx.validity_commit_coset(k) if k else ctx.validity_commit(m)
         ctx.check(rc)
         t.add_bytes(root)
         z = t.challenge_scalars(e, p)
-        while not any(z[1:]):
+        while not any(z[1:]):                                     # z outside the base field
             z = t.challenge_scalars(e, p)
         rows = sorted({0} | {int(x) for x in np.asarray(prog["fac_row"]).reshape(-1)})
         if len(rows) > 8:
@@ -599,25 +456,41 @@ class Stark:
         t.add_scalars(ev.reshape(-1))
         gamma = t.challenge_scalars(e, p)
         ctx.check(ctx.deep_compose(pts, lists, gamma))
-        rc, root = ctx.fri_begin_folded(blowup, k)
+        rc, root = ctx.fri_begin_folded(blowup, k) if k else ctx.fri_begin(blowup, R)
         ctx.check(rc)
-        t.add_bytes(root)
-        D0 = ctx.fri_round_info(0)[1]
-        for _ in range(R - 1):
-            rc, root = ctx.fri_fold_folded(t.challenge_scalars(e, p))
-            ctx.check(rc)                                         # ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
-            t.add_bytes(root)
-        rc, fin = ctx.fri_fold_final(t.challenge_scalars(e, p))
-        ctx.check(rc)
-        t.add_scalars(np.asarray(fin, dtype=np.uint64).reshape(-1))
+        t.add_bytes(root)                                         # round 0's root is in the transcript
+        if k:                                                     # the folded commit phase: R - 1 x (alpha, root), alpha, the final polynomial
+            D0 = ctx.fri_round_info(0)[1]
+            for _ in range(R - 1):
+                rc, root = ctx.fri_fold_folded(t.challenge_scalars(e, p))
+                ctx.check(rc)                                     # ERR_SHAPE: the DEEP polynomial is so short that R folds do not fit
+                t.add_bytes(root)
+            rc, fin = ctx.fri_fold_final(t.challenge_scalars(e, p))
+            ctx.check(rc)
+            t.add_scalars(np.asarray(fin, dtype=np.uint64).reshape(-1))
+        else:                                                     # the plain commit phase: R - 1 x (z, B, alpha, root)
+            for _ in range(1, R):
+                zq = t.challenge_scalars(e, p)
+                rc, B = ctx.fri_deep(zq)
+                ctx.check(rc)
+                t.add_scalars(B)
+                alpha = t.challenge_scalars(e, p)
+                rc, root = ctx.fri_fold_commit(alpha)
+                ctx.check(rc)
+                t.add_bytes(root)
         if gb:
             rc, nonce = ctx.grind(t.challenge_bytes(32), gb)
             ctx.check(rc)
             t.add_bytes(struct.pack("<Q", nonce))
         raw = t.challenge_bytes(8 * nq)
         betas = [int.from_bytes(raw[8 * i:8 * i + 8], "little") for i in range(nq)]
-        self.last_challenges = dict(shift=shift, ch=ch, r=r, z=z, gamma=gamma, betas=betas)
-        return LinkedProofV3(e, k, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, D0, bytes(t.prover_bytes), ctx.query_linked_folded(betas))
+        self.last_challenges = dict(shift=shift, r=r, z=z, gamma=gamma, betas=betas, **(dict(ch=ch) if version > 1 else {}))
+        arthur = bytes(t.prover_bytes)
+        if version == 1:
+            return LinkedProof(e, w, m, len(rows), R, nq, gb, N, blowup, arthur, ctx.query_linked(betas))
+        if version == 2:
+            return LinkedProofV2(e, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, arthur, ctx.query_linked(betas))
+        return LinkedProofV3(e, k, w, c1, m, len(rows), R, nq, gb, len(args), nch, N, blowup, D0, arthur, ctx.query_linked_folded(betas))
 
     def verify_air(self, data, air, N: int, w: int, fri_rounds: int = 0, zero_display_empty: bool = True, aux=None, log_arity: int = 0, fri_folds: int = 0) -> bool:
         """msh_stark_verify_linked on MSLP bytes (or a LinkedProof) under this configuration.  True / False, the reason of a rejection - naming the step - in

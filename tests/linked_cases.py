@@ -390,12 +390,10 @@ def apply_edits(base, cut, append, edits):
     return bytes(out)
 
 
-def tampered_fixture(make, field=0):
-    """(the proof's dict, [(name, cut, append, edits, rc, the beginning of why)]): truncated and tampered copies of one proof, as edits of it (apply_edits), with the
-    verdict msh_stark_verify_linked gives for each - what the sanitizer program (tests/asan) is fed"""
-    P = prove(make, SHA, field, "fib", N=8, R=3, gb=4)
-    data = P["data"]
-    m, rows, lists, ne, la = rl.shape(field, 8, P["w"], BLOWUP, 3, 4, P["air"])
+def tampered_edits(P):
+    """[(name, cut, append, edits)]: the truncated and tampered copies of the v1 proof P["data"], as edits of it (apply_edits)"""
+    data, field = P["data"], P["field"]
+    m, rows, lists, ne, la = rl.shape(field, P["N"], P["w"], BLOWUP, P["Rr"], P["gb"], P["air"])
     q0, n = HEAD + la, len(data)
     l_msfi, l_lde, l_val = struct.unpack_from("<3Q", data, q0 + 8)
     out = [("whole", n, 0, [])]
@@ -413,9 +411,16 @@ def tampered_fixture(make, field=0):
     for at in (nlev_lde, nlev_fri):
         for v in (big, 65, 64, 63, 0):
             out.append(("nlevels@%d=%d" % (at, v), n, 0, [(at, struct.pack("<Q", v))]))
+    return out
+
+
+def tampered_fixture(make, field=0):
+    """(the proof's dict, [(name, cut, append, edits, rc, the beginning of why)]): truncated and tampered copies of one proof, as edits of it (apply_edits), with the
+    verdict msh_stark_verify_linked gives for each - what the sanitizer program (tests/asan) is fed"""
+    P = prove(make, SHA, field, "fib", N=8, R=3, gb=4)
     cases = []
-    for name, cut, append, edits in out:
-        rc, why = P["hs"].verify_linked(apply_edits(data, cut, append, edits), P["air"], 8, P["w"], 3)
+    for name, cut, append, edits in tampered_edits(P):
+        rc, why = P["hs"].verify_linked(apply_edits(P["data"], cut, append, edits), P["air"], 8, P["w"], 3)
         cases.append((name, cut, append, edits, rc, why.split(":")[0]))
     return P, cases
 

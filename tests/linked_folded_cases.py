@@ -727,11 +727,9 @@ def case_v3_false_trace(make, d, field, which, k, N=16):
 
 
 # ---------------------------------------------------------------- 8. the fixture of the stand-alone sanitizer program of the v3 verifier (tests/asan_linked_v3)
-def v3_fixture(make, field=0, k=2, N=16, gb=4):
-    """(the proof's dict, [(name, cut, append, edits, rc, the beginning of why up to its first colon)]): truncated and tampered copies of one v3 proof with one
-    permutation argument, as edits of it, with the verdict msh_stark_verify_linked_folded gives for each"""
-    P = prove3(make, SHA, field, "permutation", k, N=N, gb=gb)
-    data, e = P["data"], EXT[field]
+def v3_edits(P):
+    """[(name, cut, append, edits)]: the truncated and tampered copies of the v3 proof P["data"], as edits of it (apply_edits)"""
+    data, e, k = P["data"], EXT[P["field"]], P["k"]
     n = len(data)
     hd = struct.unpack_from("<4s12I5Q", data, 0)
     la = hd[16]
@@ -756,9 +754,16 @@ def v3_fixture(make, field=0, k=2, N=16, gb=4):
     for at in (s_msff + 56 + nfinal * e * 8 + 8 + a * e * 8, s_lde + 8 + a * P["w"] * 8, s_stg + 8 + a * e * 8):   # nlevels words of the first path of three sections
         for v in (big, 65, 64, 63, 0):
             out.append(("nlevels@%d=%d" % (at, v), n, 0, [(at, struct.pack("<Q", v))]))
+    return out
+
+
+def v3_fixture(make, field=0, k=2, N=16, gb=4):
+    """(the proof's dict, [(name, cut, append, edits, rc, the beginning of why up to its first colon)]): truncated and tampered copies of one v3 proof with one
+    permutation argument, as edits of it, with the verdict msh_stark_verify_linked_folded gives for each"""
+    P = prove3(make, SHA, field, "permutation", k, N=N, gb=gb)
     cases = []
-    for name, cut, append, edits in out:
-        rc, why = P["hs"].verify_linked_folded(apply_edits(data, cut, append, edits), P["air"], N, P["w"], k, P["args"], P["nch"])
+    for name, cut, append, edits in v3_edits(P):
+        rc, why = P["hs"].verify_linked_folded(apply_edits(P["data"], cut, append, edits), P["air"], N, P["w"], k, P["args"], P["nch"])
         cases.append((name, cut, append, edits, rc, why.split(":")[0]))
     return P, cases
 
@@ -773,3 +778,79 @@ def v3_fixture_bytes(make):
         out += blob(name.encode()) + struct.pack("<3I", cut, append, len(edits)) + b"".join(struct.pack("<I", at) + blob(new) for at, new in edits)
         out += struct.pack("<i", rc) + blob(step.encode())
     return out, cases
+
+
+# ---------------------------------------------------------------- 9. the verdicts of the three linked verifiers on tampered proofs (tests/golden/linked_verdicts.json)
+def v2_edits(P):
+    """([(name, cut, append, edits)], the cuts of the truncation sweep) of the v2 proof P["data"]: every header word flipped, one flipped byte at the start of each
+    arthur region and of each MSLS section; every truncation length"""
+    data, e = P["data"], EXT[P["field"]]
+    n = len(data)
+    hd = struct.unpack_from("<4s11I4Q", data, 0)
+    c0, c1, m, npts, R, gb, la = hd[3], hd[4], hd[5], hd[6], hd[7], hd[9], hd[14]
+    a0, q0 = sc.HEAD2, sc.HEAD2 + la
+    l_msfi, l_lde, l_stg, l_val = struct.unpack_from("<4Q", data, q0 + 8)
+    fri0 = a0 + 128 + (npts * (c0 + c1) + m) * e * 8
+    regions = [a0, a0 + 32, a0 + 64, a0 + 96, a0 + 128, fri0]
+    for i in range(R - 1):
+        regions += [fri0 + 32 + i * (2 * e * 8 + 32), fri0 + 32 + i * (2 * e * 8 + 32) + 2 * e * 8]
+    if gb:
+        regions.append(q0 - 8)
+    assert regions[-1] < q0 and q0 + 40 + l_msfi + l_lde + l_stg + l_val == n
+    regions += [q0, q0 + 40, q0 + 40 + l_msfi, q0 + 40 + l_msfi + l_lde, q0 + 40 + l_msfi + l_lde + l_stg]
+    out = [("whole", n, 0, []), ("trailing", n, 8, [])]
+    out += [("flip %d" % at, n, 0, [(at, bytes([data[at] ^ 0x80]))]) for at in [4 * j for j in range(12)] + [48 + 8 * j for j in range(4)] + regions]
+    return out, range(n)
+
+
+def verdict_cases():
+    """(name, version, digest, field, which, k, gb): v1 and v2 at N = 8, R = 3, v3 at N = 16, on both fields at grinding bits 0 and 4 under SHA-256; one v3 case per
+    other digest"""
+    out = []
+    for field in (0, 1):
+        for gb in (0, 4):
+            out.append(("v1 fib field %d gb %d" % (field, gb), 1, SHA, field, None, 0, gb))
+            out.append(("v2 permutation field %d gb %d" % (field, gb), 2, SHA, field, "permutation", 0, gb))
+            for k in (1, 2, 3):
+                for which in (None, "permutation"):
+                    out.append(("v3 %s k %d field %d gb %d" % (which or "fib", k, field, gb), 3, SHA, field, which, k, gb))
+    for d in DIGESTS[1:]:
+        out.append(("v3 permutation k 2 field 0 gb 4 digest %d" % d, 3, d, 0, "permutation", 2, 4))
+    return out
+
+
+def linked_verdicts(make):
+    """tests/golden/linked_verdicts.json as a dict: per case the SHA-256 of the proof's bytes and, for every tampered copy in the order of the edit list, the index of
+    its (rc, why) in `table`; v2's truncation sweep as a SHA-256 over its verdicts, one 'rc|why' line per length"""
+    import hashlib
+    table, index, cases = [], {}, {}
+
+    def idx(rc, why):
+        if (rc, why) not in index:
+            index[(rc, why)] = len(table)
+            table.append([rc, why])
+        return index[(rc, why)]
+
+    for name, version, d, field, which, k, gb in verdict_cases():
+        sweep = ()
+        if version == 1:
+            P = lc.prove(make, d, field, "fib", N=8, R=3, gb=gb)
+            edits, verify = lc.tampered_edits(P), lambda b: P["hs"].verify_linked(b, P["air"], 8, P["w"], 3)   # noqa: E731
+        elif version == 2:
+            P = sc.prove2(make, d, field, which, N=8, R=3, gb=gb)
+            (edits, sweep), verify = v2_edits(P), lambda b: P["hs"].verify_linked_aux(b, P["air"], P["args"], P["nch"], 8, P["w"], 3)   # noqa: E731
+        else:
+            P = prove3(make, d, field, which, k, N=16, gb=gb)
+            edits, verify = v3_edits(P), lambda b: P["hs"].verify_linked_folded(b, P["air"], 16, P["w"], k, P["args"], P["nch"])   # noqa: E731
+        data = P["data"]
+        case = dict(sha256=hashlib.sha256(data).hexdigest(), verdicts=[idx(*verify(apply_edits(data, cut, append, ed))) for _n, cut, append, ed in edits])
+        if sweep:
+            case["truncations"] = hashlib.sha256("".join("%d|%s\n" % verify(data[:cut]) for cut in sweep).encode()).hexdigest()
+        cases[name] = case
+    return dict(table=table, cases=cases)
+
+
+def linked_verdicts_text(verdicts):
+    """the file's text for the dict of linked_verdicts"""
+    import json
+    return json.dumps(verdicts, indent=0, separators=(",", ":"), ensure_ascii=True) + "\n"

@@ -1,6 +1,7 @@
 """Coset-grouped row trees (ms_lde_commit_coset, ms_lde_commit_stage_coset, ms_validity_commit_coset) and ms_query_linked_folded on the emulation build of the kernel
 code (tests/emu, -DMS_EMU), against tests/pyref_linked_folded.py.  The same cases run on the HIP build in tests/test_linked_folded_gpu.py (-m gpu), which adds the
 2^13-row shape."""
+import json
 import os
 import subprocess
 
@@ -172,3 +173,20 @@ def test_v3_sanitizer_fixture_is_current(make):
     assert sum(1 for c in cases if c[4] == 1) == 1 and all(c[4] in (0, 1) for c in cases) and len(cases) > 400
     with open(os.path.join(HERE, "golden", "linked_v3_tampered.bin"), "rb") as fh:
         assert fh.read() == out
+
+
+def test_linked_verdicts_are_the_recorded_ones(make):
+    """tests/golden/linked_verdicts.json (tests/golden/gen_linked_verdicts.py) is what the drivers and verifiers of MSLP v1, v2 and v3 give today: per case the digest
+    of the proof's bytes, and the whole (rc, why) for every tampered copy - v1 and v2 at N = 8, v3 at N = 16 for k = 1, 2, 3 with and without the permutation argument,
+    both fields, 0 and 4 grinding bits, one v3 case per other digest.  The file was written by the three separate drivers the one driver replaced"""
+    with open(os.path.join(HERE, "golden", "linked_verdicts.json")) as fh:
+        text = fh.read()
+    want, got = json.loads(text), lf.linked_verdicts(make)
+    assert list(got["cases"]) == list(want["cases"]) and len(got["cases"]) == 36
+    for name, case in got["cases"].items():
+        rec = want["cases"][name]
+        assert case["sha256"] == rec["sha256"], name
+        assert [got["table"][i] for i in case["verdicts"]] == [want["table"][i] for i in rec["verdicts"]], name
+        assert case.get("truncations") == rec.get("truncations"), name
+        assert got["table"][case["verdicts"][0]] == [1, ""] and all(got["table"][i][0] in (0, 1) for i in case["verdicts"]), name   # the whole proof is accepted
+    assert lf.linked_verdicts_text(got) == text                                           # ... and the file as a whole, byte for byte
